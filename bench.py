@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- element-updates/s of one dynamics step (explicitSolve + update) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--mesh 2km|10km|40km] [--no-cpu-baseline]
+    python bench.py --gpus N --steps K --warmup W [--mesh 2km|10km|40km] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-aux] [--no-live-pmc]]
+
+A plain run sets up, warms up, times the K steps and prints the line (the roofline from the traffic model, the committed counter profile replayed).
+--full adds the secondary measurements: the live rocprofv3 counter passes (roofline.traffic), the CPU baseline, the aux_* legs (10 km, open water,
+partition floor, regrid, SpMV; at N > 1 the RCCL transport beside the kept one).  --dump-outputs DIR writes the state the last timed step left
+(get_state(): the arrays a caller of the path receives) as DIR/<name>.npy, float64, whole meshes gathered; a fixed, seeded sample of nodes and
+elements where the whole would exceed 64 MiB.
 
 N > 1 is launched by the driver as one rank per GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
@@ -24,9 +30,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# the host driver of this pool supports dmabuf IPC only: without this hipIpcGetMemHandle (the mailboxes of the device-direct halo transport, RCCL)
-# fails with "invalid argument"; it is exported on the GPU boxes already -- kept here for a launcher that builds its own environment
-os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 # Algorithmic HBM bytes per element-update of the sub-step loop (DESIGN.md "Roofline model"):
 # 172 B per element + 217 B per node per sub-step.
@@ -42,10 +45,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mesh", default="2km", help="2km (~1.5M triangles, default: the mesh north_star's target and "
                     "HBM roofline are quoted on), 10km (~60k), 40km, small")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the secondary 10 km measurement")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not measure roofline.traffic with two rocprofv3 --pmc child runs (replay the committed profile)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements (live counter passes, CPU baseline, aux_* legs); off: only what "
+                    "the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state the last timed step left as DIR/<name>.npy (float64, at most 64 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the aux_* legs")
+    ap.add_argument("--no-live-pmc", action="store_true", help="with --full: do not measure roofline.traffic with two rocprofv3 --pmc child runs (replay the committed profile)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 PMC_PROFILES = ("profiles/r04_pmc_traffic.json", "profiles/r03_pmc_traffic.json", "profiles/r02_pmc_traffic.json", "profiles/r01_v2_pmc_traffic.json")
@@ -146,7 +155,7 @@ def ice_cover(f):
     return {"ice_free_fraction": float((c == 0).mean()), "low_concentration_fraction": float(((c > 0) & (c <= 0.1)).mean())}
 
 
-def run_gpu(kind, args, rank, world, local_rank, dist, torch, unique_id_fn, state="arctic", own_device=False):
+def run_gpu(kind, args, rank, world, local_rank, dist, torch, unique_id_fn, state="arctic", own_device=False, keep_state=False):
     from nextsim_amd import dynamics
     gm, p, lm, f = build_case(kind, world, rank, state)
     fe = dynamics.FiniteElementDynamics(p, device=local_rank)
@@ -203,6 +212,7 @@ def run_gpu(kind, args, rank, world, local_rank, dist, torch, unique_id_fn, stat
     step_ms = fe.step_times()
     options_used = dict(getattr(fe, "_bench_options", {}))
     crash = fe.checkFieldsFast()
+    final = fe.get_state() if keep_state else None   # (after the timed region: what the last timed step left, rank-local)
     fe.close()
     phases = {k: tm[k] for k in ("prep_ms", "substeps_ms", "smoother_ms", "update_ms", "total_ms")}
     if world > 1:   # the slowest rank's figure for every phase (the line is rank 0's otherwise)
@@ -213,7 +223,7 @@ def run_gpu(kind, args, rank, world, local_rank, dist, torch, unique_id_fn, stat
     else:
         phases_max = dict(phases)
     return dict(gm=gm, p=p, lm=lm, f=f, dt=dt, timing=tm, crash=crash, transport=transport, halo=halo, phases_max=phases_max,  # (f: rank-local fields)
-                traffic=traffic, step_ms=step_ms, options=options_used)
+                traffic=traffic, step_ms=step_ms, options=options_used, final=final)
 
 
 def choose_halo_kernels(fe, f, rank, world, dist, torch, own_device):
@@ -825,7 +835,68 @@ def launch_ranks(nranks, worker_cmd, grace_s=20.0, poll_s=0.2):
     return (bad[0] if bad[0] > 0 else 1) if bad else 0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20240601
+
+
+def global_state(final, lm, gm, rank, world, dist):
+    """get_state()'s rank-local arrays as whole-mesh arrays (nodal: u of every node, then v; elemental: one entry per triangle), from the entries each
+    rank owns.  world > 1: collective, rank 0 receives them (None elsewhere)."""
+    import numpy as np
+    from nextsim_amd import _abi
+    No, Neo, Nl = lm.local_ndof, lm.local_nelements, lm.num_nodes
+    mine = (lm.node_gid[:No], lm.elem_gid[:Neo],
+            {k: (np.concatenate([v[:No], v[Nl:Nl + No]]) if k in _abi.STATE_NODAL else v[:Neo]) for k, v in final.items()})
+    parts = [mine]
+    if world > 1:
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(mine, parts, dst=0)
+        if rank != 0:
+            return None
+    Nn, Ne = gm.num_nodes, gm.num_elements
+    out = {k: np.full(2 * Nn if k in _abi.STATE_NODAL else Ne, np.nan) for k in final}
+    for nodes, elems, arrays in parts:
+        for k, v in arrays.items():
+            if k in _abi.STATE_NODAL:
+                out[k][nodes] = v[:nodes.size]
+                out[k][Nn + nodes] = v[nodes.size:]
+            else:
+                out[k][elems] = v
+    return out
+
+
+def dump_outputs(path, arrays, num_nodes, num_elements):
+    """Whole-mesh arrays (global_state) -> path/<name>.npy, float64.  Where all of them would exceed DUMP_LIMIT_BYTES, every array keeps the same fixed,
+    seeded sample of nodes (u, then v, of each) or of triangles: it depends on the mesh's size alone, so two builds' files compare entry for entry."""
+    import numpy as np
+    from nextsim_amd import _abi
+    os.makedirs(path, exist_ok=True)
+    total = sum(8 * a.size for a in arrays.values())
+    keep = min(1.0, 0.95 * DUMP_LIMIT_BYTES / total)   # (0.95: room for the .npy headers)
+    nodes, elems, sample = slice(None), slice(None), None
+    if keep < 1.0:
+        rng = np.random.default_rng(DUMP_SEED)
+        nodes = np.sort(rng.choice(num_nodes, int(keep * num_nodes), replace=False))
+        elems = np.sort(rng.choice(num_elements, int(keep * num_elements), replace=False))
+        sample = {"seed": DUMP_SEED, "nodes": int(nodes.size), "of_nodes": num_nodes, "elements": int(elems.size), "of_elements": num_elements,
+                  "how": "numpy.random.default_rng(seed): sorted choice without replacement of the nodes, then of the triangles"}
+    written = 0
+    for k, a in arrays.items():
+        a = np.asarray(a, np.float64)
+        v = a.reshape(2, num_nodes)[:, nodes].ravel() if k in _abi.STATE_NODAL else a[elems]
+        fn = os.path.join(path, k + ".npy")
+        np.save(fn, np.ascontiguousarray(v))
+        written += os.path.getsize(fn)
+    assert written <= DUMP_LIMIT_BYTES, written
+    return {"dir": os.path.abspath(path), "arrays": sorted(arrays), "dtype": "float64", "bytes": written, "sample": sample,
+            "what": "the state after the last timed step (get_state), gathered over the ranks"}
+
+
 def main():
+    # where the host driver supports dmabuf IPC only, hipIpcGetMemHandle (the mailboxes of the device-direct halo transport, RCCL) fails with "invalid
+    # argument" without this; set for a launcher that builds its own environment -- here, before the ranks are started and torch is imported, so
+    # that importing bench.py leaves the environment alone
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # called like the single-GPU bench (`python bench.py --gpus N ...`): be the launcher, before anything of torch / HIP is in this process
@@ -883,8 +954,14 @@ def main():
         devices = [None] * world
         dist.all_gather_object(devices, (os.environ.get("GROUP_RANK", "0"), local_rank))
     distinct_devices = len(set(devices))
-    res = run_gpu(args.mesh, args, rank, world, local_rank, dist, torch, unique_id_fn, own_device=distinct_devices == world)
+    res = run_gpu(args.mesh, args, rank, world, local_rank, dist, torch, unique_id_fn, own_device=distinct_devices == world, keep_state=bool(args.dump_outputs))
     gm, p, lm, tm = res["gm"], res["p"], res["lm"], res["timing"]
+    dumped = None
+    if args.dump_outputs:
+        arrays = global_state(res.pop("final"), lm, gm, rank, world, dist)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, arrays, gm.num_nodes, gm.num_elements)
+        del arrays
     S = p.substeps
     value = gm.num_elements * S * args.steps / res["dt"]
 
@@ -906,8 +983,9 @@ def main():
     # through the L2, not what crosses to memory.  unique <= counted always holds.)
     achieved = rate(tr["substep_unique_bytes"], launch_ms)
     want = [kernel_name.split(" ")[0]] + (["k_move_ring"] if tr["move_ring_slots"] else []) + {3: ["k_prep_fused"], 2: ["k_prep_elements", "k_prep_nodes"], 1: ["k_prep_elements", "k_prep_nodes"]}.get(tr["prep_kernel"], []) + ["k_update"]
-    if args.no_live_pmc or rank != 0:
-        counted, traffic_source = {}, "skipped (--no-live-pmc)" if args.no_live_pmc else "rank 0 measures"
+    if not args.full or args.no_live_pmc or rank != 0:
+        counted, traffic_source = {}, ("skipped (the live counter passes run with --full)" if not args.full else "skipped (--no-live-pmc)" if args.no_live_pmc else
+                                       "rank 0 measures")
     else:
         counted, traffic_source = pmc_traffic_live(args.mesh, world, rank, want, options=[f"{k}={v}" for k, v in res["options"].items()])
     traffic = counted.get(want[0])
@@ -1003,8 +1081,11 @@ def main():
         "phases_ms": res["phases_max"],   # (N > 1: the slowest rank's figure for every phase)
         "phases_ms_rank0": {k: tm[k] for k in ("prep_ms", "substeps_ms", "smoother_ms", "update_ms", "total_ms")},
         "fields_ok": res["crash"] == 0,
+        "full": args.full,
     }
-    if world > 1:   # north_star's named transport beside the kept one (collective: every rank takes part, rank 0 reports)
+    if dumped:
+        out["outputs"] = dumped
+    if world > 1 and args.full:   # north_star's named transport beside the kept one (collective: every rank takes part, rank 0 reports)
         try:
             if res["halo"].get("transport") == "rccl":
                 out["aux_rccl"] = {"status": "is the transport of the main line", "ms_per_step": out["ms_per_step"]}
@@ -1023,7 +1104,7 @@ def main():
                     os.close(saved)
         except Exception as e:  # noqa: BLE001 -- never lose the main line over it
             out["aux_rccl"] = {"status": "failed", "error": repr(e)[:300]}
-    if rank == 0 and not args.no_cpu_baseline:   # (at every N: rank 0's host is the same host)
+    if args.full and rank == 0 and not args.no_cpu_baseline:   # (at every N: rank 0's host is the same host)
         try:
             cb = cpu_baseline(args.mesh, 1, 2)
             out["cpu_baseline"] = {
@@ -1042,7 +1123,7 @@ def main():
             }
         except Exception as e:  # noqa: BLE001 -- the GPU line must survive a host-side failure of the baseline leg
             out["cpu_baseline"] = {"value": None, "unit": "element-updates/s", "cores": 0, "kind": "port", "sample": "failed: " + repr(e)}
-    if world == 1 and not args.no_aux and args.mesh != "10km":
+    if args.full and world == 1 and not args.no_aux and args.mesh != "10km":
         # (a 0.55 ms step is enqueued by the host as fast as the device runs it: 20 steps measure the host's mood and the device's clocks after half a minute of idling -- 0.55 to 0.80 ms in this round's records)
         aux_args = argparse.Namespace(**vars(args)); aux_args.steps = max(args.steps, 400); aux_args.warmup = max(args.warmup, 200)   # (the leg follows the CPU baseline: the device has idled for half a minute)
         try:
@@ -1054,7 +1135,7 @@ def main():
             }
         except Exception as e:  # noqa: BLE001 -- never lose the main line over a secondary measurement
             out["aux_10km"] = {"error": repr(e)}
-    if world == 1 and not args.no_aux and args.mesh == "2km":
+    if args.full and world == 1 and not args.no_aux and args.mesh == "2km":
         aux_args = argparse.Namespace(**vars(args)); aux_args.steps = min(args.steps, 10); aux_args.warmup = min(args.warmup, 2)
         try:   # the same mesh with 29 % of the triangles ice free and 4 % in the 0 < A <= 0.1 band: the open-water smoother (FE.cpp:10578-10611),
             # its tail and the skipped-element path do real work here

@@ -1,5 +1,5 @@
 # Round-3 profile of the hot path on the GPU box (through gpurun, from the repo root):   bash scripts/profile_round3.sh [tag]   -> gpurun_out/<tag>_*
-#   1. the bench line as the driver runs it (N = 1)                                  -> <tag>_bench.json
+#   1. the full bench line (bench.py --full, N = 1)                                  -> <tag>_bench.json
 #   2. rocprofv3 --kernel-trace --stats of the same command (no aux legs)            -> <tag>_prof/stats
 #   3. FETCH_SIZE / WRITE_SIZE passes (separate, counters only) over one 2 km step   -> <tag>_prof/pmc
 #   4. SQ counters (waves, VALU instructions, busy cycles; separate pass)            -> <tag>_prof/sq
@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${TAG}_prof
 mkdir -p $OUT
 run() { echo "== $1" >&2; shift; timeout -k 10 600 "$@"; rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "timed out: stopping"; exit 1; fi; return $rc; }
-run bench python3 bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 1
+run bench python3 bench.py --full --steps 20 --warmup 5 > $(dirname $OUT)/${TAG}_bench.json 2> $(dirname $OUT)/${TAG}_bench.err || exit 1
 run stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-aux --no-live-pmc > $OUT/bench_under_prof.json 2> $OUT/bench_under_prof.err || exit 1
 run fetch rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc/FETCH_SIZE -o f -- python3 scripts/run_steps.py --mesh 2km --steps 1 --graph 0 > $OUT/fetch.log 2>&1 || exit 1
 run write rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc/WRITE_SIZE -o w -- python3 scripts/run_steps.py --mesh 2km --steps 1 --graph 0 > $OUT/write.log 2>&1 || exit 1

@@ -69,7 +69,8 @@ int main(int argc, char **argv) {
         CHECK(T.handles() == 4);                                  // pid 999999 does not exist HERE, the entry stays: its owner lives in another namespace
         T.release(b);
         CHECK(!T.claim(b, 300, 512, true, &why) && why.find("of another process") != std::string::npos);
-        foreign.stamp = nxs_reg::boot_seconds() > nxs_reg::STALE_SECONDS + 5 ? nxs_reg::boot_seconds() - nxs_reg::STALE_SECONDS - 5 : 0; foreign.handle = 0x78;
+        // (unsigned: on a machine up for less than STALE_SECONDS + 5 the stamp wraps below zero, and the sweep's now > stamp + STALE_SECONDS wraps back the same way)
+        foreign.stamp = nxs_reg::boot_seconds() - nxs_reg::STALE_SECONDS - 5; foreign.handle = 0x78;
         T.plant(foreign);                                         // the same, untouched for more than STALE_SECONDS: dropped by the next sweep
         CHECK(T.handles() == 4);
         nxs_reg::Entry dead{}; dead.pid = 999998; dead.start = 1; dead.handle = 0x79; dead.wg = 100; dead.slots = 512; dead.pidns = nxs_reg::my_pid_namespace(); dead.stamp = nxs_reg::boot_seconds();

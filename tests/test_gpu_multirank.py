@@ -409,7 +409,7 @@ def test_resident_loop_in_the_build_with_all_its_registers(world, kind, over, tm
 
 
 def test_bench_line_of_a_two_rank_run_is_one_json_line_with_every_structured_field(tmp_path):
-    """bench.py as the driver launches it at N = 2 (torch.distributed.run, one rank per "GPU"; here both ranks share device 0, so the figures only
+    """bench.py --full as the driver launches it at N = 2 (torch.distributed.run, one rank per "GPU"; here both ranks share device 0, so the figures only
     bound the protocol): stdout is ONE JSON line (RCCL's and gloo's banners stay on stderr), it carries the contract's keys, the structured
     transport / variant report (config.halo), the slowest rank's phases, aux_rccl (RCCL refuses two ranks on one device: a recorded failure, not a
     lost line) and the CPU baseline of rank 0's host."""
@@ -420,7 +420,7 @@ def test_bench_line_of_a_two_rank_run_is_one_json_line_with_every_structured_fie
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541",
-           os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--mesh", "40km"]
+           os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--mesh", "40km", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
