@@ -72,6 +72,25 @@ using nxs_cut::HostPatches2;
 static_assert(NXS_CUT_BLOCK == BLOCK && NXS_CUT_T256_MAXP == NXS_T256_MAXP && NXS_CUT_RES_NBR == NXS_RES_NBR && NXS_CUT_RES_MAXNB == NXS_RES_MAXNB,
               "nxs_patchcut.hpp and nxs_dyn_kernels.inl disagree about a limit");
 
+// What one step launches: decided once per step (plan_step: wish_plan says which regime the options, sizes and transport want, the ensure_* functions
+// build its tables and may downgrade it), then read by the enqueue functions, the smoother and nxs_dyn_get_traffic_model.  Buffers are ring slots
+// (VTRing: slot 0 is M_VT, slot 1 its twin), so the plan holds no pointer and is decided before the ring exists.
+struct StepPlan {
+    int kernel = NXS_KERNEL_NONE;   // NXS_KERNEL_*: the family of the sub-step loop
+    int prep = NXS_PREP_NONE;       // NXS_PREP_*
+    int D = 1;                      // sub-steps per launch
+    int K = 1, R = 2;               // the mesh move is applied every K sub-steps from a ring of R = K + 1 velocity slots
+    bool deferred = false;          // K > 1: k_move_ring applies the move, not the sub-step kernel
+    bool move_in_pair = false;      // k_substep_pair applies the move of its two sub-steps itself (no k_move_ring)
+    bool halo_in_kernel = false;    // the exchange runs inside the sub-step kernels
+    bool capturable = false;        // no host work inside the loop (nor the smoother): replayed from a hipGraph
+    bool records_end_odd = false;   // the element records end in the second buffer (S4b): unpacked from there
+    int final_count = 0;            // sub-steps the step's last k_move_ring applies (launched behind the graph); 0: none
+    bool flush_to_vt = false;       // ... which also writes the newest velocity back into M_VT
+    int smooth_slot = -1;           // the ring slot that equals M_VT after the loop (the smoother's second buffer); -1: none, it copies
+    int launches = 0;               // kernel launches of the sub-step loop (nxs_dyn_timing::substep_launches)
+};
+
 struct nxs_dyn_handle {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
@@ -90,11 +109,11 @@ struct nxs_dyn_handle {
     int pair_nodes = 0;     // v3: own nodes per patch; 0 = auto
     int pair_depth = 0;     // v3: sub-steps per launch, 2..NXS_MAX_DEPTH; 0 = auto
     int pair_depth_built = 0;
-    int depth_now = 1;      // sub-steps per launch of the current step (choose_depth)
+    StepPlan plan{};        // what the last step launched (plan_step)
     bool pair_failed = false;   // the D-ring patches could not be built for this mesh: v2 instead
     DevPatches2 dpch2{};
     size_t pair_lds = 0;
-    int pair_threads = 512;
+    int pair_threads_chosen = 512;   // threads of a k_substep_pair / k_substep_multi workgroup as the planner CHOSE them for the patches in dpch2
     bool pair_ready = false;
     std::vector<void *> pair_allocs;
     int patch_nodes = 0;    // own nodes per patch; 0 = auto
@@ -116,15 +135,14 @@ struct nxs_dyn_handle {
     bool pair_kernel = false;              // the multi-sub-step patches were cut for k_substep_pair
     int pair_hilbert = 0;                  // option "pair_hilbert": 1 = the two-ring patches of a single rank are cut along a Hilbert curve even where the caller's numbering has locality
     int pair_move = -1;                    // option "pair_move": k_substep_pair on a single rank applies the mesh move of its two sub-steps itself (no ring of velocity slots, no
-                                           // k_move_ring): -1 = automatic, 0 = never (the move deferred to one flush per step), 1 = wherever that kernel runs on one rank
-    bool move_now = false, last_move_in_pair = false;                 // ... decided for the step being built (run_substeps), read by launch_multi
-    int pair_flow = -1;                    // option "pair_flow": the pairs of sub-steps of a step as ONE data-flow launch (k_substep_flow): -1 = wherever k_substep_pair runs on a
-                                           // single rank with 512 threads, 0 = never (one launch per pair), 1 = the same as -1
+                                           // k_move_ring): -1 = automatic (the same as 1), 0 = never (the move deferred to one flush per step), 1 = wherever that kernel runs on one rank
+    int pair_flow = -1;                    // option "pair_flow": the pairs of sub-steps of a step as ONE data-flow launch (k_substep_flow): 1 = wherever k_substep_pair runs on a
+                                           // single rank with 512 threads; anything else (0, and the default -1) = never (one launch per pair)
     bool flow_ready = false, flow_failed = false;
     PairFlow flow{};                       // its dependency lists, queues and counters (they go with the patches)
     size_t flow_words = 0;                 // ... the words zeroed before every launch
     int flow_grid = 0;
-    int pair_T = 512;                      // option "pair_threads": threads of a k_substep_pair workgroup on a single rank (512: two per CU; 256: four per CU, smaller patches)
+    int pair_threads_requested = 512;      // option "pair_threads": threads of a k_substep_pair workgroup on a single rank (512: two per CU; 256: four per CU, smaller patches)
     PairHalo pairh{};                      // several ranks: the patches' duties in the exchange inside k_substep_pair<HALO>, the ticket words
     bool pair_claim = false;               // ... and their claim on the device's workgroup slots (nxs_resident_registry.hpp)
     int pair_hint = 0;                     // the patch size the planner kept for the previous mesh (tried first after a regrid)
@@ -194,7 +212,6 @@ struct nxs_dyn_handle {
     double *d_vt3 = nullptr;
     double *d_icediag = nullptr;           // [Ne][NXS_ICE_DIAG_FIELDS] rows of nxs_dyn_ice_diagnostics (state pool: goes with the mesh)
     double *d_icediag_soa = nullptr;       // [NXS_ICE_DIAG_FIELDS][Ne] the same per field, made when the host asks for its vectors
-    double *smooth_second = nullptr;       // the ring slot that equals M_VT after the sub-step loop (the smoother's second buffer), or NULL
     int sig_loc = 0;                       // where M_sigma / M_damage are current: 0 = the state arrays, 1 = the records in S4a (left there by
                                            // the fused sub-step loop; k_update works on them, the arrays follow on demand: ensure_arrays)
     int trace_branches = 0;                // option "trace_branches": the per-loop kernels keep the branch trace of updateSigmaDamage (dw.trace)
@@ -239,11 +256,9 @@ struct nxs_dyn_handle {
     int sum_steps = 0;
     std::vector<float> step_ms;  // device time of every step since "timing_reset" (at most 4096 kept): nxs_dyn_get_step_times
     hipEvent_t *cur = nullptr;  // event set of the step being enqueued (nullptr: untimed)
-    // sums over the patch tables (filled where the tables are uploaded) and what the last step launched: nxs_dyn_get_traffic_model
+    // sums over the patch tables (filled where the tables are uploaded): nxs_dyn_get_traffic_model prices what the last step launched (plan) with them
     struct PatchSums { double nP = 0, M = 0, E = 0, O = 0, W = 0; } sums1;                       // DevPatches: staged nodes, elements, own nodes, written elements
     struct PatchSums2 { double nP = 0, W = 0, E1_second_round = 0; std::vector<double> N, E; } sums2;   // DevPatches2: nodes per level N_0..N_D, elements per level E_1..E_D; elements of E_1 beyond the first 512 of their patch
-    int last_kernel = 0, last_ring_count = 0, last_prep = 0;                                     // NXS_KERNEL_* / slots of the last k_move_ring / NXS_PREP_*
-    bool last_deferred = false, last_halo_in_kernel = false;
     nxs_dyn_timing timing{};
     int timing_enabled = 1;
     std::string err;
@@ -253,15 +268,6 @@ namespace {
 
 // the kernel family of this step: option "fused", except that the branch trace lives in the per-loop kernels
 inline int eff_fused(const nxs_dyn_handle *h) { return h->trace_branches ? 0 : h->fused; }
-int build_halo_fused(nxs_dyn_handle *h);  // (defined with the launch logic below)
-int build_resident(nxs_dyn_handle *h);
-void resident_registry_release(const nxs_dyn_handle *h, int kind);
-bool resident_registry_claim(const nxs_dyn_handle *h, int workgroups, int slots, std::string *why, int kind);
-void release_resident(nxs_dyn_handle *h);
-void release_graph(nxs_dyn_handle *h);
-bool multi_rank(const nxs_dyn_handle *h);
-void register_waiting_grid(nxs_dyn_handle *h, int blocks, int slots, bool reset = false);
-void register_smoother_grid(nxs_dyn_handle *h);
 
 int fail(nxs_dyn_handle *h, int code, const char *fmt, ...) {
     char buf[512];
@@ -409,13 +415,57 @@ int harvest(nxs_dyn_handle *h, int k) {
     return NXS_OK;
 }
 
-// option "pair_flow": 1 = on, 0 = off, -1 = automatic
+
+bool multi_rank(const nxs_dyn_handle *h) { return h->nranks > 1; }
+// the exchange runs on the device, without host work inside the loops (peer-mapped mailboxes, no callback of the caller's): graph-capturable ...
+inline bool device_halo(const nxs_dyn_handle *h) { return multi_rank(h) && h->have_halo && h->ipc_ready && !h->halo_fn; }
+// ... and may run inside the kernels (option "halo_fused")
+inline bool exchange_in_kernel_possible(const nxs_dyn_handle *h) { return device_halo(h) && h->halo_fused; }
+
+// option "pair_flow": 1 = on, anything else off
 bool flow_wanted(const nxs_dyn_handle *h) { return h->pair_flow == 1; }
-// option "pair_move" = -1: wherever k_substep_pair runs on a single rank (2 km: 5.27 -> 5.17 ms per step -- the launch grows by 2.8 us, the 0.27 ms flush goes)
-bool pair_move_default(const nxs_dyn_handle *) { return true; }
 // the data-flow build of k_substep_pair for this handle's parameters: one place for the occupancy query and the launch
 const void *flow_kernel(const nxs_dyn_handle *h) {
     return h->dp.ers_int == 4 ? (const void *)k_substep_flow<512, true, 3> : (const void *)k_substep_flow<512, false, 3>;
+}
+
+void release_graph(nxs_dyn_handle *h) {
+    if (h->substep_graph) { (void)hipGraphExecDestroy(h->substep_graph); h->substep_graph = nullptr; }
+    if (h->tail_graph) { (void)hipGraphExecDestroy(h->tail_graph); h->tail_graph = nullptr; }
+    h->graph_valid = false;
+    h->tail_graph_valid = false;
+}
+
+// The resident launch needs every workgroup of its grid on a CU at once, and its workgroups spin: a handle claims its workgroup slots in the device's
+// registry before it builds the loop and gives them back when its tables go; a claim that does not fit beside what is claimed already -- by handles
+// of this process or of any other process on the device, with headroom for the co-tenants' ordinary kernels where the device is shared -- is refused
+// up front and the step runs one kernel per sub-step (nxs_resident_registry.hpp has the rule and the evidence behind it).
+// (kind: nxs_reg::KIND_RESIDENT / KIND_PAIR -- one claim per handle, held by ONE of its two grids of waiting workgroups; a release names the grid that lets go,
+// so that the resident loop's tables going away do not take the pair patches' claim with them)
+void resident_registry_release(const nxs_dyn_handle *h, int kind) {
+    if (!h->reg_key.empty()) nxs_reg::table_for(h->reg_key).release((uint64_t)(uintptr_t)h, kind);
+}
+bool resident_registry_claim(const nxs_dyn_handle *h, int workgroups, int slots, std::string *why, int kind) {
+    if (h->reg_key.empty()) { if (why) *why = "the handle is not registered on its device"; return false; }
+    return nxs_reg::table_for(h->reg_key).claim((uint64_t)(uintptr_t)h, workgroups, slots, multi_rank(h), why, kind);
+}
+
+// The blocks of this handle's ORDINARY kernels that may spin for a neighbour rank (k_smooth_halo, k_halo_pull, the boundary patches of k_substep_fused<HALO>): the
+// largest such grid, as a fraction of the device, is registered -- other handles' claims leave it room (nxs_resident_registry.hpp).  reset: start from nothing.
+void register_waiting_grid(nxs_dyn_handle *h, int blocks, int slots, bool reset = false) {
+    if (h->reg_key.empty()) return;
+    if (reset) { h->ord_blocks = 0; h->ord_slots = 0; }
+    if (blocks > 0 && slots > 0 && (h->ord_blocks == 0 || (double)blocks / slots > (double)h->ord_blocks / h->ord_slots)) { h->ord_blocks = blocks; h->ord_slots = slots; }
+    nxs_reg::table_for(h->reg_key).set_ordinary((uint64_t)(uintptr_t)h, h->ord_blocks, h->ord_slots);
+}
+
+// the resident loop's tables and its claim on the device's workgroup slots
+void release_resident(nxs_dyn_handle *h) {
+    drop_pool(h, h->res_allocs);
+    h->res = DevResident{};
+    h->d_vt3 = nullptr;
+    h->res_ready = false; h->res_failed = false;
+    resident_registry_release(h, nxs_reg::KIND_RESIDENT);
 }
 
 #include "nxs_dyn_patches.inl"
@@ -533,21 +583,7 @@ void ensure_arrays(nxs_dyn_handle *h) {
     h->sig_loc = 0;
 }
 
-void release_graph(nxs_dyn_handle *h) {
-    if (h->substep_graph) { (void)hipGraphExecDestroy(h->substep_graph); h->substep_graph = nullptr; }
-    if (h->tail_graph) { (void)hipGraphExecDestroy(h->tail_graph); h->tail_graph = nullptr; }
-    h->graph_valid = false;
-    h->tail_graph_valid = false;
-}
 
-// the resident loop's tables and its claim on the device's workgroup slots
-void release_resident(nxs_dyn_handle *h) {
-    drop_pool(h, h->res_allocs);
-    h->res = DevResident{};
-    h->d_vt3 = nullptr;
-    h->res_ready = false; h->res_failed = false;
-    resident_registry_release(h, nxs_reg::KIND_RESIDENT);
-}
 
 // A resident launch that gave up (k_substep_resident's bounded waits) leaves a mixture of the step's start and its end behind (no patch writes after
 // it has seen the error, the ones that had finished before have written); whoever hands state to the host next says so.  Call with the stream synchronised.
@@ -578,6 +614,805 @@ int resident_error(nxs_dyn_handle *h) {
                                 : "unknown wait";
     return fail(h, NXS_ERR_HIP, "the resident sub-step launch gave up (code %d): %s; the step is lost and M_UM, M_UT, sigma and damage are undefined (patches that had finished "
                                 "before the time-out have written their result, the others have not): put the state again before going on; later steps run one kernel per sub-step", err, what);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the launches: which regime a step wants (wish_plan), the tables that regime needs (ensure_*: they may downgrade the plan), its enqueue (enqueue_*)
+
+#define LAUNCH(h, kern, n, ...)                                                              \
+    do {                                                                                      \
+        hipLaunchKernelGGL(kern, dim3(nblocks(n)), dim3(BLOCK), 0, (h)->stream, __VA_ARGS__); \
+    } while (0)
+
+int halo_exchange(nxs_dyn_handle *h, double *vec, double move_dt) {
+    // updateGhosts (FE.cpp:13963-13996): pack -> grouped send/recv -> unpack
+    const int ns = (int)h->send_procs.size(), nr = (int)h->recv_procs.size();
+    const int ts = h->send_offsets[ns], tr = h->recv_offsets[nr];
+    if (device_halo(h)) {
+        // device-direct: pack + peer stores + flags, then wait + unpack (+ ghost-node move); no host work
+        hipLaunchKernelGGL(k_halo_push, dim3(nblocks(ts)), dim3(BLOCK), 0, h->stream, (const double *)vec, h->dm.Nn, ts,
+                           h->d_send_index, h->d_send_seg, h->d_send_off, h->ipc, h->rank, 0);
+        hipLaunchKernelGGL(k_halo_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, vec, h->dm, h->ds, tr, h->d_recv_index,
+                           h->d_recv_seg, h->d_recv_off, h->ipc, move_dt, 0, h->d_recv_procs, 0);
+        return NXS_OK;
+    }
+    if (!h->comm && !h->halo_fn) return fail(h, NXS_ERR_STATE, "halo exchange needs nxs_dyn_comm_init, nxs_dyn_ipc_connect or nxs_dyn_set_halo_exchange_fn");
+    if (ts > 0) LAUNCH(h, k_halo_pack, ts, vec, h->dm.Nn, ts, h->d_send_index, h->d_send_seg, h->d_send_off, h->d_send_buf);
+    if (h->halo_fn) {
+        // host-staged: exactly the reference's M_comm.send / M_comm.recv of packed std::vector<double>
+        if (ts > 0) HIPCHK(h, hipMemcpyAsync(h->h_send, h->d_send_buf, 2 * (size_t)ts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        const int rc = h->halo_fn(h->halo_ctx, h->h_send, h->h_recv);
+        if (rc != 0) return fail(h, NXS_ERR_COMM, "halo exchange callback returned %d", rc);
+        if (tr > 0) {
+            HIPCHK(h, hipMemcpyAsync(h->d_recv_buf, h->h_recv, 2 * (size_t)tr * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            LAUNCH(h, k_halo_unpack, tr, vec, h->dm, h->ds, tr, h->d_recv_index, h->d_recv_seg, h->d_recv_off, h->d_recv_buf, move_dt);
+        }
+        return NXS_OK;
+    }
+    const int ncclDouble = 8;  // ncclFloat64
+    int e = h->rccl.GroupStart();
+    for (int k = 0; k < ns && e == 0; ++k)   // (a segment without nodes -- a direction set_halo added -- is no message: both ends know it is empty)
+        if (h->send_offsets[k + 1] > h->send_offsets[k])
+            e = h->rccl.Send(h->d_send_buf + 2 * (size_t)h->send_offsets[k], 2 * (size_t)(h->send_offsets[k + 1] - h->send_offsets[k]),
+                             ncclDouble, h->send_procs[k], h->comm, h->stream);
+    for (int k = 0; k < nr && e == 0; ++k)
+        if (h->recv_offsets[k + 1] > h->recv_offsets[k])
+            e = h->rccl.Recv(h->d_recv_buf + 2 * (size_t)h->recv_offsets[k], 2 * (size_t)(h->recv_offsets[k + 1] - h->recv_offsets[k]),
+                             ncclDouble, h->recv_procs[k], h->comm, h->stream);
+    int e2 = h->rccl.GroupEnd();
+    if (e == 0) e = e2;
+    if (e != 0) return fail(h, NXS_ERR_COMM, "halo send/recv: %s", h->rccl.GetErrorString(e));
+    if (tr > 0) LAUNCH(h, k_halo_unpack, tr, vec, h->dm, h->ds, tr, h->d_recv_index, h->d_recv_seg, h->d_recv_off, h->d_recv_buf, move_dt);
+    return NXS_OK;
+}
+
+PingPong pingpong(const nxs_dyn_handle *h, int parity) {
+    const DevState &s = h->ds;
+    PingPong b;
+    if (parity == 0) { b.VTc = s.VT; b.Sc = s.S4a; b.VTn = s.VT2; b.Sn = s.S4b; }
+    else { b.VTc = s.VT2; b.Sc = s.S4b; b.VTn = s.VT; b.Sn = s.S4a; }
+    return b;
+}
+
+// ---- one picker per kernel family: ONE place decides the instantiation, for the occupancy query and for the launch alike.  The launches go through
+// hipLaunchKernel; a launch the device refuses is reported by the hipGetLastError at the end of explicit_solve, like those of the <<<>>> launches beside them.
+
+template <int T, bool HALO>
+const void *fused_kernel_of(bool pow4, int nt_mask, bool pmem) {
+#define FUSED(PP, NN) (pmem ? (const void *)k_substep_fused<T, PP, NN, HALO, true> : (const void *)k_substep_fused<T, PP, NN, HALO, false>)
+    if (!pow4) return FUSED(false, 0);
+    if constexpr (HALO) return nt_mask ? FUSED(true, 3) : FUSED(true, 0);
+    else switch (nt_mask) {
+        case 0: return FUSED(true, 0);
+        case 1: return FUSED(true, 1);
+        case 3: return FUSED(true, 3);
+        case 4: return FUSED(true, 4);
+        case 5: return FUSED(true, 5);
+        default: return FUSED(true, 7);
+    }
+#undef FUSED
+}
+// k_substep_fused: 512 threads where a patch holds more than 256 can take (big); the exchange inside (halo); parameters from memory (pmem); streaming hints (nt_mask)
+const void *fused_kernel_fn(const nxs_dyn_handle *h, bool halo, bool pmem, int nt_mask, bool big) {
+    const bool p4 = h->dp.ers_int == 4;
+    if (halo) return big ? fused_kernel_of<512, true>(p4, nt_mask, pmem) : fused_kernel_of<256, true>(p4, nt_mask, pmem);
+    return big ? fused_kernel_of<512, false>(p4, nt_mask, pmem) : fused_kernel_of<256, false>(p4, nt_mask, pmem);
+}
+
+// k_substep_pair: both exchanges inside the launch (halo: several ranks), four small workgroups per CU (256 threads), or the mesh move of its two sub-steps inside (move)
+const void *pair_kernel_fn(const nxs_dyn_handle *h, bool halo, bool move) {
+    const bool p4 = h->dp.ers_int == 4;
+    if (halo) return p4 ? (const void *)k_substep_pair<512, true, 3, true> : (const void *)k_substep_pair<512, false, 3, true>;
+    if (h->pair_threads_chosen == 256) return p4 ? (const void *)k_substep_pair<256, true, 3> : (const void *)k_substep_pair<256, false, 3>;
+    if (move) return p4 ? (const void *)k_substep_pair<512, true, 3, false, true> : (const void *)k_substep_pair<512, false, 3, false, true>;
+    return p4 ? (const void *)k_substep_pair<512, true, 3> : (const void *)k_substep_pair<512, false, 3>;
+}
+
+// k_substep_multi, by the threads the planner chose for the patches
+// no non-temporal hints: this kernel runs where the mesh lives in the caches (58 k triangles: 0.768 ms/step with them, 0.750 without; 111 k: 0.927 / 0.90)
+const void *multi_kernel_fn(const nxs_dyn_handle *h) {
+    const bool p4 = h->dp.ers_int == 4;
+    if (h->pair_threads_chosen == 768) return p4 ? (const void *)k_substep_multi<768, true, 0> : (const void *)k_substep_multi<768, false, 0>;
+    if (h->pair_threads_chosen == 512) return p4 ? (const void *)k_substep_multi<512, true, 0> : (const void *)k_substep_multi<512, false, 0>;
+    return p4 ? (const void *)k_substep_multi<256, true, 0> : (const void *)k_substep_multi<256, false, 0>;
+}
+
+// The resident sub-step kernel of this handle: ONE place decides the instantiation, for the occupancy query and for the launch alike.
+// (WPE = 2: the several-rank build with all the registers it wants, BBM's default exponent only.)
+const void *resident_kernel(const nxs_dyn_handle *h, bool mr, bool ovl) {
+    const bool p4 = h->res_pow4;
+    if (h->res_big) {  // one large patch per CU, four elements and two own nodes per thread
+        if (mr && ovl) return p4 ? (const void *)k_substep_resident_big<true, true, true> : (const void *)k_substep_resident_big<false, true, true>;
+        if (mr) return p4 ? (const void *)k_substep_resident_big<true, true, false> : (const void *)k_substep_resident_big<false, true, false>;
+        if (ovl) return p4 ? (const void *)k_substep_resident_big<true, false, true> : (const void *)k_substep_resident_big<false, false, true>;
+        return p4 ? (const void *)k_substep_resident_big<true, false, false> : (const void *)k_substep_resident_big<false, false, false>;
+    }
+    if (mr && h->res_wpe == 2 && p4) return ovl ? (const void *)k_substep_resident<512, true, true, true, 2> : (const void *)k_substep_resident<512, true, true, false, 2>;
+    if (mr && ovl) return p4 ? (const void *)k_substep_resident<512, true, true, true> : (const void *)k_substep_resident<512, false, true, true>;
+    if (mr) return p4 ? (const void *)k_substep_resident<512, true, true> : (const void *)k_substep_resident<512, false, true>;
+    return p4 ? (const void *)k_substep_resident<512, true, false> : (const void *)k_substep_resident<512, false, false>;
+}
+
+// sub-step `sidx` of the fused path: sigma/damage ping-pong by parity; velocities move through the ring
+// (ring of 2 == ping-pong between VT and VT2 when the deferred mesh move is off)
+// halo: the sub-step also performs updateGhosts (HaloFused); from_mailbox = ghosts come from exchange x-1
+void launch_fused(nxs_dyn_handle *h, int sidx, double move_dt, bool halo = false, int from_mailbox = 0) {
+    PingPong b = pingpong(h, sidx & 1);
+    const int R = h->ring.R;
+    b.VTc = h->ring.slot[sidx % R];
+    b.VTn = h->ring.slot[(sidx + 1) % R];
+    const bool big = h->dpch.Pmax > NXS_T256_MAXP || h->dpch.Emax > 3 * 256;
+    // streaming hints keep the state from displacing the reusable arrays -- a gain only when a sub-step's ~210 B/triangle do not fit
+    // the 256 MiB Infinity Cache anyway: 1.46 M triangles 7.08 -> 6.96 ms/step with them, 730 k 3.75 -> 3.98, 367 k 2.20 -> 2.33, 182 k 1.27 -> 1.31
+    const int nt_mask = h->nt_mask >= 0 ? h->nt_mask : (h->dm.Ne >= 1000000 ? 3 : 0);
+    // parameters from memory (PMEM) where one round of resident workgroups covers the partition, by value where several rounds stream
+    const bool pmem = h->dpch.nP <= 5 * device_cus(h) / 2;  // 511 patches (182 k triangles): 1.375 -> 1.344 ms/step; 752 patches (263 k): 1.83 -> 1.91
+    const DevParams *pdev = h->d_dp;
+    const HaloFused *hfp = halo ? h->d_hf : nullptr;
+    int n_boundary = halo ? h->hf.n_boundary : 0;
+    void *args[] = {&h->dm, &h->dpch, &h->ds, &h->dw, &h->dp, &pdev, &b, &move_dt, &hfp, &n_boundary, &from_mailbox};
+    (void)hipLaunchKernel(fused_kernel_fn(h, halo, pmem, nt_mask, big), dim3(h->dpch.nP), dim3(big ? 512 : 256), args, h->fused_lds, h->stream);
+}
+
+// sub-steps sidx .. sidx+D-1 in one launch (k_substep_multi / k_substep_pair): sigma/damage ping-pong per LAUNCH, velocities through the ring
+void launch_pair(nxs_dyn_handle *h, const StepPlan &p, int sidx) {
+    const int D = p.D, R = h->ring.R;
+    PingPong b = pingpong(h, (sidx / D) & 1);
+    b.VTc = h->ring.slot[sidx % R];
+    b.VTn = nullptr;
+    VTOut vo{};
+    for (int k = 0; k < D; ++k) vo.slot[k] = h->ring.slot[(sidx + 1 + k) % R];
+    const dim3 grid(h->dpch2.nP), block(h->pair_threads_chosen);
+    if (p.kernel == NXS_KERNEL_MULTI) {
+        const DevParams *pdev = h->d_dp;
+        void *args[] = {&h->dm, &h->dpch2, &h->ds, &h->dw, &pdev, &b, &vo};
+        (void)hipLaunchKernel(multi_kernel_fn(h), grid, block, args, h->pair_lds, h->stream);
+        return;
+    }
+    // k_substep_pair (D == 2: upload_patches2 / upload_pair_patches_mr cut the patches for it)
+    const bool halo = p.halo_in_kernel;   // several ranks: both exchanges inside the launch; the first launch of a step finds its ghosts in the velocity buffer
+    PairHalo ph = halo ? h->pairh : PairHalo{};
+    if (halo) ph.from_mailbox = sidx > 0 ? 1 : 0;
+    const HaloFused *hfp = halo ? h->d_hf : nullptr;
+    // the mesh move of the two sub-steps inside the launch: the first velocity slot is not written; the LAST launch of a step whose final velocity lands in M_VT itself
+    // writes it a second time there instead: the smoother wants two equal buffers and would otherwise copy one
+    if (p.move_in_pair) vo.slot[0] = (sidx + D == h->dp.substeps && (h->dp.substeps % R) == 0) ? h->ring.slot[(sidx + 1) % R] : nullptr;
+    void *args[] = {&h->dm, &h->dpch2, &h->ds, &h->dw, &h->dp, &b, &vo, &hfp, &ph};
+    (void)hipLaunchKernel(pair_kernel_fn(h, halo, p.move_in_pair), grid, block, args, h->pair_lds, h->stream);
+}
+
+void launch_substep(nxs_dyn_handle *h, double move_dt) {
+    if (h->dp.dynamics_type == NXS_DYN_BBM) {
+        if (h->trace_branches) {
+            if (h->dp.ers_int == 4) LAUNCH(h, (k_sigma_bbm<true, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+            else LAUNCH(h, (k_sigma_bbm<false, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+        }
+        else if (h->dp.ers_int == 4) LAUNCH(h, k_sigma_bbm<true>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+        else LAUNCH(h, k_sigma_bbm<false>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+    }
+    else
+        LAUNCH(h, k_sigma_vp, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+    LAUNCH(h, k_solve_move, h->dm.No, h->dm, h->ds, h->dw, h->dp, move_dt);
+}
+
+// ---- which regime the step wants
+
+// One round of one k_substep_multi patch per CU covers the mesh (<= 256 own nodes per patch: 65 k nodes, 130 k triangles on 256 CUs); above, a mesh STREAMS from HBM
+inline bool fits_one_round(const nxs_dyn_handle *h) { return (long long)h->dm.Nn <= 256ll * 256; }
+// The resident loop (option fused = 4) can run here at all.  Several ranks: only with the exchange inside the kernels (device-direct mailboxes).
+inline bool resident_possible(const nxs_dyn_handle *h) {
+    return h->fused == 4 && h->dp.dynamics_type != NXS_DYN_MEVP && (!multi_rank(h) || exchange_in_kernel_possible(h));
+}
+
+// The regime of this step, from the handle's options, sizes and transport state alone: no HIP call, no table is built.  It assumes that the tables it asks for can
+// be built; an ensure_* function that finds otherwise records why in the handle (pair_failed, res_failed) and asks again.  resident_ok = false: as if fused were 1.
+StepPlan wish_plan(const nxs_dyn_handle *h, bool resident_ok = true) {
+    StepPlan p;
+    const int S = h->dp.substeps, family = eff_fused(h);
+    const bool fused = family != 0, mr = multi_rank(h), xk = exchange_in_kernel_possible(h);
+    const bool moves = h->dp.dynamics_type != NXS_DYN_MEVP;   // (mEVP: one mesh move, after the loop)
+    // ---- sub-steps per launch.  v3: D sub-steps per launch -- the deferred mesh move (ring of >= D+1 buffers).  It trades redundant arithmetic
+    // on the halo rings for less HBM traffic and fewer launches: a gain where the sub-step is latency-bound (10 km: 1.23 -> 0.97
+    // ms/step), a loss as soon as a CU hosts more than one patch (182 k triangles: 1.65 -> 1.90) and where the v2 kernel already
+    // runs at 5.5 TB/s with its VALUs half busy (2 km, D = 2: 7.4 -> 8.0).
+    const bool can_pair = moves && S >= 2 && !h->pair_failed, depth2_ok = h->pair_depth == 0 || h->pair_depth == 2;
+    bool pair_kernel = false;
+    if (mr) {
+        // several ranks: two sub-steps per launch with BOTH exchanges inside it (k_substep_pair<HALO>: device-direct mailboxes, the exchange inside the kernels) --
+        // automatically where the partition streams from HBM (more than 65 k nodes: a rank of two of the 2 km mesh; smaller partitions run the resident loop where
+        // they have a device to themselves), with option pair_regs = 1 at any size
+        if (xk && family == 3 && can_pair && S % 2 == 0 && depth2_ok && (h->pair_regs == 1 || (h->pair_regs < 0 && !fits_one_round(h)))) { p.D = 2; pair_kernel = true; }
+    } else if (can_pair && family == 3 && h->pair_regs != 0 && !fits_one_round(h) && S % 2 == 0 && depth2_ok) {
+        // on meshes that STREAM from HBM (fused == 3, every mesh too large for one k_substep_multi patch per CU, an even number of sub-steps) two sub-steps per launch
+        // with the stresses between them in registers and two workgroups per CU (k_substep_pair): 2 km 6.3 -> 5.7 ms of sub-steps
+        p.D = 2; pair_kernel = true;
+    } else if (can_pair && (family == 2 || (family == 3 && fits_one_round(h)))) {
+        // Automatic (fused == 3): only where ONE round of one patch per CU covers the mesh -- 111 k triangles: 1.47 (v2) -> 0.97 ms/step; 182 k triangles, two patches
+        // per CU: 1.65 -> 1.90-2.31.  The requested depth, else 4 (10 km: D = 2 / 3 / 4 / 5 / 6 / 8: 1.11 / 1.01 / 0.97 / 0.96 / 0.98 / 1.08 ms/step; the
+        // rings grow the arithmetic by x2.0 per sub-step at D = 4) -- lowered until it divides the number of sub-steps
+        p.D = std::min(h->pair_depth > 0 ? h->pair_depth : 4, std::min(S, NXS_MAX_DEPTH));
+        while (p.D > 1 && S % p.D != 0) --p.D;
+        pair_kernel = p.D == 2 && h->pair_regs == 1;   // (forced depth 2 with option pair_regs = 1: k_substep_pair at any size)
+    }
+    const int D = p.D;
+    const bool pair = D >= 2;   // (family 2 or 3: never with the branch trace)
+    // ---- the mesh move.  auto ring: one flush per step (up to 120 sub-steps) on meshes that stream from HBM -- the flush reads every slot once
+    // whatever its period, so a longer ring only saves UM/UT passes (2 km: 7.60 -> 7.49 ms/step from 16 to 120, 1.4 GB of
+    // slots); also whenever the halo exchange runs inside the sub-step kernel
+    const int want_ring = h->um_ring > 0 ? h->um_ring : ((h->dm.Ne >= 400000 || xk) ? 120 : 1);
+    int K = (fused && moves) ? std::max(1, std::min(want_ring, S)) : 1;
+    // k_substep_pair on a single rank can apply the mesh move of its two sub-steps itself (M_UM / M_UT in and out once per launch): no ring beyond the three
+    // buffers a launch reads and writes, no k_move_ring.  Option "pair_move" = -1: wherever that kernel runs with 512 threads (2 km: 5.27 -> 5.17 ms per step -- the
+    // launch grows by 2.8 us, the 0.27 ms flush goes).  (The threads are the planner's choice: for this kernel on a single rank it takes the requested number.)
+    p.move_in_pair = pair_kernel && !mr && h->pair_threads_requested == 512 && h->um_ring <= 0 && h->pair_move != 0 && !flow_wanted(h);
+    if (pair) {  // the ring is flushed between launches; by default once per step (a flush per launch costs 30 small launches at 10 km: 66 us of 0.88 ms)
+        if (h->um_ring <= 0) K = std::min(S, NXS_MAX_RING - 1);
+        K = std::max(D, K - K % D);
+        if (p.move_in_pair) K = D;
+    }
+    p.K = K; p.R = K + 1;
+    p.deferred = K > 1;   // (fused path, not mEVP)
+    // ---- the family.  v4: the resident sub-step loop (opt-in; which of its two kernels is known once its tables are built: plan_step)
+    const bool resident = resident_ok && resident_possible(h) && !h->trace_branches && !h->res_failed;
+    // single rank: all the pairs of a step in one data-flow launch (needs the whole step in the ring: one flush, behind the launch; whether its tables could be
+    // built is known after ensure_pair_patches)
+    const bool flow = pair_kernel && !mr && h->pair_threads_requested == 512 && flow_wanted(h) && !h->flow_failed && K == S;
+    p.kernel = resident ? NXS_KERNEL_RESIDENT : flow ? NXS_KERNEL_PAIR_FLOW : pair ? (pair_kernel ? NXS_KERNEL_PAIR : NXS_KERNEL_MULTI) : fused ? NXS_KERNEL_FUSED : NXS_KERNEL_PER_LOOP;
+    // the exchange inside the one-sub-step kernel: needs the deferred mesh move (ghost nodes are moved from the ring) or no move at all (mEVP)
+    const bool fused_halo = xk && fused && (p.deferred || !moves);
+    p.halo_in_kernel = fused_halo || (resident && mr) || (pair && mr);
+    p.capturable = h->use_graph && (!mr || device_halo(h));
+    p.records_end_odd = resident ? false : (pair ? ((S / D) & 1) : (S & 1));
+    // with the deferred mesh move the last flush of the step reads the newest velocity anyway and puts it back into M_VT itself; the
+    // ring slot it came from then equals M_VT and serves the smoother as its second buffer (no copy before the sweeps)
+    const bool flushes = p.deferred && !resident && !p.move_in_pair;
+    p.final_count = flushes ? S - K * ((S - 1) / K) : 0;
+    p.flush_to_vt = flushes && (S % p.R) != 0;
+    p.smooth_slot = p.flush_to_vt ? S % p.R : -1;
+    if (p.move_in_pair)   // the final velocity: in a ring slot that k_pingpong_copy_back copies into M_VT, or in M_VT itself with a second copy in the last launch's free slot
+        p.smooth_slot = (S % p.R) ? S % p.R : (S - D + 1) % p.R;
+    p.launches = (resident || flow) ? 1 : pair ? S / D : fused_halo ? S + (S + K - 1) / K : S * ((fused ? 1 : 2) + (mr ? 2 : 0));
+    // ---- the prep kernels.  The fused kernels read records only: the per-quantity work vectors (v1 kernels, debug door) are filled on request.  One launch over the
+    // sub-step kernel's patches (k_prep_fused), automatic: meshes that stream from HBM; on cache-resident ones the two small kernels are as fast: 10 km 24.7 vs 27.4 us
+    // (from 250 k triangles on a single rank; on a rank of several from 500 k -- measured on rank 0's partitions of the 2 km mesh, looped back: 730 k
+    // 0.108 -> 0.086 ms, 366 k in the resident loop's large patches 0.046 -> 0.053, 184 k 0.033 -> 0.043: gpurun_out/r5_prepmr_ab.log)
+    const bool prep_pays = h->prep_fused == 1 || (h->prep_fused < 0 && h->dm.Ne >= (mr ? 500000 : 250000));
+    p.prep = (!fused || h->work_arrays) ? NXS_PREP_FULL : (prep_pays && h->prep_lds > 0 && h->dpch.prow && h->dpch.nP > 0) ? NXS_PREP_FUSED : NXS_PREP_LEAN;
+    return p;
+}
+
+// ---- the tables the wish needs.  Everything here runs outside any stream capture; device memory let go of inside a step is parked (nxs_dyn_handle::retired).
+
+// (re)build the ring of velocity buffers of the fused path: slot 0 is M_VT itself, slot 1 is VT2
+int ensure_ring(nxs_dyn_handle *h, int K) {
+    const int R = K + 1;
+    if (h->ring.R == R) return NXS_OK;
+    // Buffers are only ever ADDED (they go with the mesh): a hipFree synchronises the whole device, and on a device that another handle of this
+    // process shares (the several-ranks-per-process tests and rehearsals) that other rank's kernels may be spinning for THIS rank's next launch --
+    // freeing here, inside a step, deadlocked such runs until the 10 s guard fired whenever a run switched from the long ring to the short one
+    // (round 3: found in the kernel statistics of a two-rank run, one k_halo_pull of 10 s).
+    h->ring.slot[0] = h->ds.VT;
+    h->ring.slot[1] = h->ds.VT2;
+    for (int i = 2; i < R; ++i) {
+        if (i - 2 < (int)h->ring_allocs.size()) { h->ring.slot[i] = static_cast<double *>(h->ring_allocs[i - 2]); continue; }
+        int rc = dev_alloc(h, h->ring_allocs, &h->ring.slot[i], 2 * (size_t)h->dm.Nn);
+        if (rc) return rc;
+    }
+    for (int i = R; i < NXS_MAX_RING; ++i) h->ring.slot[i] = nullptr;
+    h->ring.R = R;
+    return NXS_OK;
+}
+
+// ... the smoother's: k_smooth_persist runs at most 128 persistent workgroups that wait for each other and for the neighbour ranks; with option smooth_persist 0 every
+// block of k_smooth_halo (one per BLOCK own nodes) may spin for a neighbour's sweep; k_halo_pull's blocks (one per BLOCK ghosts) spin for its flags.  Called where the
+// halo lists are set and where the option changes.
+void register_smoother_grid(nxs_dyn_handle *h) {
+    if (!h->have_halo) return;
+    const int No = h->dm.No, tr = h->recv_offsets[h->recv_procs.size()];
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_smooth_halo, BLOCK, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
+    const int sweeps = h->smooth_persist != 0 ? std::min(nblocks(No), 128) : nblocks(No);
+    register_waiting_grid(h, h->nranks > 1 ? std::max(sweeps, nblocks(tr)) : 0, per_cu * device_cus(h), true);
+    if (h->hf_ready) register_waiting_grid(h, h->hf.n_boundary, 2 * device_cus(h));   // (the boundary patches of k_substep_fused<HALO>, as build_halo_fused registers them)
+}
+
+// tables of the halo exchange fused into the sub-step kernel (see HaloFused)
+int build_halo_fused(nxs_dyn_handle *h) {
+    drop_pool(h, h->hf_allocs);
+    h->hf = HaloFused{};
+    h->hf_ready = false;
+    const int Nn = h->dm.Nn, No = h->dm.No, nP = h->dpch.nP;
+    if (!h->hp || h->hp->nP != nP) return fail(h, NXS_ERR_STATE, "fused halo tables: patches / halo lists missing");
+    const nxs_cut::HaloLists hl{&h->send_offsets, &h->recv_offsets, &h->h_send_index, &h->h_recv_index, (int)h->send_procs.size(), (int)h->recv_procs.size()};
+    nxs_cut::HaloFusedPlan plan;
+    const std::string why = nxs_cut::plan_halo_fused(Nn, No, hl, *h->hp, plan);  // (host only: nxs_patchcut.hpp)
+    if (!why.empty()) return fail(h, NXS_ERR_STATE, "%s", why.c_str());
+    if (plan.reordered) {  // the patch arrays again, boundary patches first: the grid starts with them and "boundary" is blk < n_boundary
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        release_graph(h);
+        int rcu = upload_host_patches(h, *h->hp);
+        if (rcu) return rcu;
+    }
+    HaloFused &f = h->hf;
+    int rc;
+    if ((rc = dev_upload(h, h->hf_allocs, &f.send_ptr, plan.sptr))) return rc;
+    if ((rc = dev_upload(h, h->hf_allocs, &f.send_k, plan.sk))) return rc;
+    if ((rc = dev_upload(h, h->hf_allocs, &f.send_pos, plan.spos))) return rc;
+    if ((rc = dev_upload(h, h->hf_allocs, &f.ghost_off, plan.goff))) return rc;
+    if ((rc = dev_upload(h, h->hf_allocs, &f.ghost_srl, plan.gsrl))) return rc;
+    if ((rc = dev_upload(h, h->hf_allocs, &f.ghost_k, plan.gk))) return rc;
+    unsigned int *ctr = nullptr;
+    if ((rc = dev_alloc(h, h->hf_allocs, &ctr, 32 * 19))) return rc;   // [0] and [32 (g + 1)]: two-level tickets; [32 * 17]: the generation word of k_smooth_persist's barrier
+    HIPCHK(h, hipMemsetAsync(ctr, 0, 32 * 19 * sizeof(unsigned int), h->stream));
+    f.done_all = ctr;
+    if ((rc = dev_upload(h, h->hf_allocs, &f.send_block_rank, plan.send_block_rank))) return rc;  // k_smooth_halo: which blocks store into a mailbox
+    f.n_send_blocks = plan.n_send_blocks;
+    f.no_release = h->res_no_release;
+    f.send_off = h->d_send_off;
+    f.n_boundary = plan.n_boundary;
+    register_waiting_grid(h, plan.n_boundary, 2 * device_cus(h));   // (two 512-thread workgroups of the fused kernel per CU)
+    f.No = No;
+    {
+        unsigned long long *raw = nullptr;  // device copy of the struct itself (filled in by ensure_halo_device_copy once the mailboxes are connected)
+        if ((rc = dev_alloc(h, h->hf_allocs, &raw, (sizeof(HaloFused) + 7) / 8))) return rc;
+        h->d_hf = reinterpret_cast<HaloFused *>(raw);
+        h->d_hf_dirty = true;
+    }
+    h->hf_ready = true;
+    if (getenv("NXS_DEBUG_PATCHES")) {
+        fprintf(stderr, "[nxs] rank %d fused halo: %d of %d patches on the boundary, %d sent nodes, %d ghosts\n", h->rank, plan.n_boundary, nP, plan.sptr[No], Nn - No);
+        std::string sizes;   // own nodes / elements / of them sent, of the boundary patches (they lead the arrays now)
+        for (int q = 0; q < plan.n_boundary && q < 80; ++q) {
+            int sent = 0, ghosts = 0;
+            const int *nd = h->hp->pnodes.data() + (size_t)q * h->hp->Mmax;
+            for (int i = 0; i < h->hp->node_cnt[q]; ++i) { if (nd[i] >= No) ++ghosts; else if (i < h->hp->own_cnt[q] && plan.sptr[nd[i] + 1] > plan.sptr[nd[i]]) ++sent; }
+            char b[64]; snprintf(b, sizeof b, " %d/%d/s%d/g%d", h->hp->own_cnt[q], h->hp->elem_cnt[q], sent, ghosts); sizes += b;
+        }
+        fprintf(stderr, "[nxs] rank %d boundary patches (own nodes / elements / sent / ghosts staged):%s\n", h->rank, sizes.c_str());
+    }
+    return NXS_OK;
+}
+int ensure_halo_fused(nxs_dyn_handle *h) { return h->hf_ready ? NXS_OK : build_halo_fused(h); }
+
+// the device copy of the exchange's tables, with the mailbox addresses as they are connected now
+int ensure_halo_device_copy(nxs_dyn_handle *h) {
+    if (!h->d_hf_dirty) return NXS_OK;
+    HaloFused tmp = h->hf;
+    tmp.ipc = h->ipc;
+    HIPCHK(h, hipMemcpyAsync(h->d_hf, &tmp, sizeof tmp, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // tmp leaves scope
+    h->d_hf_dirty = false;
+    return NXS_OK;
+}
+
+// Tables of the resident sub-step kernel (nxs_cut::plan_resident), the counters, the exchange buffers.  NXS_OK with res_ready == false
+// means "not possible here" (the caller then runs one kernel per sub-step).  Everything lives in a pool of its own that is given back
+// before it is rebuilt (options fused / resident_wide / resident_overlap / resident_dryrun, a change of parameters, a timed-out launch).
+int build_resident(nxs_dyn_handle *h) {
+    h->res_ready = false;
+    drop_pool(h, h->res_allocs);
+    h->res = DevResident{};
+    h->d_vt3 = nullptr;
+    if (!h->hp || h->hp->nP != h->dpch.nP) return NXS_OK;
+    const HostPatches &hp = *h->hp;
+    const int nP = hp.nP, No = h->dm.No, Nn = h->dm.Nn, S = h->dp.substeps;
+    const bool mr = multi_rank(h);
+    const bool big = nxs_cut::resident_is_big(hp);
+    const bool ovl = big ? h->res_overlap != 0 : (mr && h->res_overlap == 1);
+    h->res_ovl = ovl;
+    auto refuse = [&](const char *why) {
+        if (getenv("NXS_DEBUG_PATCHES")) fprintf(stderr, "[nxs] rank %d resident kernel not possible: %s\n", h->rank, why);
+        h->res_failed = true;
+        return NXS_OK;
+    };
+    if (S > NXS_RES_MAXS) return refuse("more sub-steps than the kernel keeps counters for");
+    nxs_cut::ResidentPlan plan;
+    nxs_cut::plan_resident(hp, Nn, No, mr, (int)h->send_procs.size(), ovl, plan);
+    if (!plan.ok) return refuse(plan.why.c_str());
+    h->res_big = big;
+    h->res_lds = big ? nxs_cut::resident_big_lds_of(hp, mr) : nxs_cut::resident_lds_of(hp, mr);
+    if (h->res_lds > 160 * 1024) return refuse("a patch needs more LDS than a CU has");
+    // every workgroup must be resident at once
+    int per_cu = 0;
+    const int cus = device_cus(h);
+    const bool p4 = h->dp.ers_int == 4;
+    // one workgroup per CU is enough and the caller says the device is this handle's alone (option resident_wide): the several-rank build with all
+    // the registers it wants -- one such workgroup fills a CU, so ranks that share a device (the tests) would no longer fit side by side
+    h->res_wpe = (mr && p4 && h->res_wide && nP <= cus && !big) ? 2 : 4;
+    h->res_pow4 = p4;
+    const void *kern = resident_kernel(h, mr, ovl);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, h->res_lds);
+    if (e != hipSuccess || (long long)per_cu * cus < nP) {
+        (void)hipGetLastError();
+        char why[160];
+        snprintf(why, sizeof why, "%d patches, %d x %d workgroups fit (%zu B of LDS each)", nP, per_cu, cus, h->res_lds);
+        return refuse(why);
+    }
+    // the device's other resident grids (other handles of this process: the ranks a host drives from one process, the tests): all of them
+    // together must fit, or the spinning workgroups of one keep the other's from ever starting
+    {
+        std::string why;
+        if (!resident_registry_claim(h, nP, per_cu * cus, &why, nxs_reg::KIND_RESIDENT)) return refuse(why.c_str());
+        if (h->pair_claim) { h->pair_claim = false; h->pair_ready = false; }   // (a handle holds ONE claim: the pair patches' went with it and are cut -- and claimed -- again if they are wanted)
+    }
+    int rc;
+    DevResident &r = h->res;
+    if (ovl) {
+        if (getenv("NXS_DEBUG_PATCHES")) fprintf(stderr, "[nxs] rank %d resident kernel: %.1f %% of the patch elements computed under the exchange\n", h->rank, 100. * plan.early_fraction);
+        if ((rc = dev_upload(h, h->res_allocs, &r.pelem, plan.rpelem))) return rc;
+        if ((rc = dev_upload(h, h->res_allocs, &r.ptri, plan.rptri))) return rc;
+        if ((rc = dev_upload(h, h->res_allocs, &r.pfan, plan.rpfan))) return rc;
+        if ((rc = dev_upload(h, h->res_allocs, &r.ecut, plan.ecut))) return rc;
+    }
+    if ((rc = dev_upload(h, h->res_allocs, &r.pnbr, plan.nbr))) return rc;
+    if ((rc = dev_upload(h, h->res_allocs, &r.pnbr_cnt, plan.cnt))) return rc;
+    r.rank = h->rank;
+    if (mr) {  // the ghosts' ring: what arrived after every sub-step but the last (sized for THIS number of sub-steps: a change of parameters rebuilds the tables)
+        r.NG = Nn - No;
+        if ((rc = dev_alloc(h, h->res_allocs, &r.gring, std::max<size_t>((size_t)std::max(S - 1, 1) * 2 * (size_t)r.NG, 1)))) return rc;
+    }
+    h->res_substeps = S;
+    if ((rc = dev_alloc(h, h->res_allocs, &r.flag, 32 * (size_t)nP + NXS_RES_MAXS + 32))) return rc;  // counters behind the flags: one memset per launch
+    r.cnt = r.flag + 32 * (size_t)nP;
+    r.raised = r.cnt + NXS_RES_MAXS;
+    if ((rc = dev_alloc(h, h->res_allocs, &r.error, 1))) return rc;
+    HIPCHK(h, hipMemsetAsync(r.error, 0, sizeof(int), h->stream));
+    if ((rc = dev_alloc(h, h->res_allocs, &h->d_vt3, 2 * (size_t)Nn))) return rc;
+    r.X0 = h->ds.VT2; r.X1 = h->d_vt3;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (getenv("NXS_DEBUG_PATCHES")) fprintf(stderr, "[nxs] rank %d resident kernel: %d patches (%d x %d fit), %zu B of LDS each, up to %d neighbour patches, %d ghost nodes\n", h->rank, nP, per_cu, cus, h->res_lds, plan.max_nbr, mr ? Nn - No : 0);
+    h->res_ready = true;
+    return NXS_OK;
+}
+
+// The resident loop's tables, where they are neither there nor refused already.  Refused on a mesh that was cut into one large patch per CU for
+// k_substep_resident_big (the device's workgroup slots are taken, ...): the one-launch-per-sub-step kernel wants its own cut (two smaller workgroups per CU,
+// whole rounds), so the mesh is cut again and the exchange's tables follow.
+int ensure_resident(nxs_dyn_handle *h) {
+    if (h->res_ready || h->res_failed) return NXS_OK;
+    int rc = build_resident(h);
+    if (rc) return rc;
+    if (h->res_failed && h->cut_big && !h->no_big_cut) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        release_graph(h);
+        h->no_big_cut = true;
+        if ((rc = upload_patches(h))) return rc;
+        if (multi_rank(h) && (rc = ensure_halo_fused(h))) return rc;
+        h->res_failed = true;   // (after the rebuilds, which reset it: this cut exists because the resident loop cannot run)
+    }
+    return NXS_OK;
+}
+
+// The D-ring patches of k_substep_multi / k_substep_pair (several ranks: the exchange's tables first, the patches' duties in it refer to them).  Where nothing fits
+// (a numbering without any locality, huge fans; the device's workgroup slots taken) pair_failed is set and the step is planned again: one sub-step per launch.
+int ensure_pair_patches(nxs_dyn_handle *h, StepPlan &p) {
+    if (p.D < 2) return NXS_OK;
+    const bool for_pair_kernel = p.kernel != NXS_KERNEL_MULTI;
+    const bool stale = !h->pair_ready || h->pair_depth_built != p.D || h->pair_kernel != for_pair_kernel;
+    if (multi_rank(h)) {
+        if (ensure_halo_fused(h) != NXS_OK || (stale && upload_pair_patches_mr(h) != NXS_OK)) h->pair_failed = true;
+    } else if (stale && upload_patches2(h, p.D, eff_fused(h) == 3 && fits_one_round(h), for_pair_kernel) != NXS_OK) h->pair_failed = true;
+    if (h->pair_failed || !h->pair_ready) { h->pair_failed = true; p = wish_plan(h); return NXS_OK; }
+    // (the data-flow launch's queues go with the patches; refused there: one launch per pair)
+    if (p.kernel == NXS_KERNEL_PAIR_FLOW && !h->flow_ready) { p.kernel = NXS_KERNEL_PAIR; p.launches = h->dp.substeps / p.D; }
+    return NXS_OK;
+}
+
+// What this step launches (h->plan), with every table it needs built.  Called before the prep kernels: they need D and the prep kind.
+int plan_step(nxs_dyn_handle *h) {
+    StepPlan &p = h->plan;
+    p = wish_plan(h);
+    int rc;
+    if ((rc = ensure_pair_patches(h, p))) return rc;
+    if (p.kernel != NXS_KERNEL_PER_LOOP && (rc = ensure_ring(h, p.K))) return rc;
+    if (p.halo_in_kernel && (rc = ensure_halo_fused(h))) return rc;   // (re-uploads the patches boundary-first)
+    if (h->res_ready && (h->res_substeps != h->dp.substeps || h->res_pow4 != (h->dp.ers_int == 4))) {  // parameters changed since the tables were built:
+        h->res_ready = false;                                                                         // another kernel build (its residency unchecked), a ring of another length
+        release_graph(h);
+    }
+    if (p.kernel == NXS_KERNEL_RESIDENT) {
+        if ((rc = ensure_resident(h))) return rc;
+        if (h->res_ready && !h->res_failed) p.kernel = h->res_big ? NXS_KERNEL_RESIDENT_BIG : NXS_KERNEL_RESIDENT;   // (the cut decides which of the two)
+        else p = wish_plan(h, false);   // refused: one kernel per sub-step (on the mesh as ensure_resident left it)
+    }
+    if (p.halo_in_kernel && (rc = ensure_halo_device_copy(h))) return rc;
+    return NXS_OK;
+}
+
+// ---- the enqueue of a planned step: one function per family, the flushes of the ring shared
+
+// the newest ghosts into `vec`, for the move / the end of the step
+void pull_latest(nxs_dyn_handle *h, double *vec) {
+    const int tr = h->recv_offsets[h->recv_procs.size()];
+    hipLaunchKernelGGL(k_halo_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, vec, h->dm, h->ds, tr, h->d_recv_index,
+                       h->d_recv_seg, h->d_recv_off, h->ipc, 0., 0, h->d_recv_procs, 1);
+}
+
+// the mesh move of the `pending` sub-steps up to s, from the ring -- but for the LAST flush of the step, which is launched behind the graph (final_flush)
+void flush_ring(nxs_dyn_handle *h, const StepPlan &p, int s, int pending) {
+    if (s == h->dp.substeps - 1 && p.final_count > 0) return;
+    LAUNCH(h, k_move_ring, h->dm.Nn, h->dm, h->ds, h->ring, (s + 1 - (pending - 1)) % p.R, pending, h->dp.dte, (double *)nullptr);
+}
+
+// the LAST flush of the step: one plain launch per step behind the graph, so that its own events can bracket it
+int final_flush(nxs_dyn_handle *h, const StepPlan &p) {
+    if (p.final_count <= 0) return NXS_OK;
+    const int k = h->cur ? (int)((h->cur - &h->ev[0][0]) / 5) : -1;
+    if (k >= 0) HIPCHK(h, hipEventRecord(h->ev_flush[k][0], h->stream));
+    LAUNCH(h, k_move_ring, h->dm.Nn, h->dm, h->ds, h->ring, (h->dp.substeps - p.final_count + 1) % p.R, p.final_count, h->dp.dte, p.flush_to_vt ? h->ds.VT : (double *)nullptr);
+    if (k >= 0) { HIPCHK(h, hipEventRecord(h->ev_flush[k][1], h->stream)); h->flush_timed[k] = true; }
+    return NXS_OK;
+}
+
+// the end of every loop over the record buffers: the result back in the primary buffers
+void finish_records(nxs_dyn_handle *h, const StepPlan &p) {
+    const int S = h->dp.substeps;
+    // (with flush_to_vt the last ring flush brings the velocity back)
+    if ((S % p.R) && !p.flush_to_vt) LAUNCH(h, k_pingpong_copy_back, 2 * h->dm.Nn, h->dm, h->ds, (const double *)h->ring.slot[S % p.R]);
+    // the element state stays in its records when the loop ends in the first buffer (an even number of launches): update()
+    // works on them and the arrays follow when somebody asks (ensure_arrays); from the second buffer it is unpacked here
+    if (p.records_end_odd) LAUNCH(h, k_unpack_state, h->dm.Ne, h->dm, h->ds, h->dp.dynamics_type == NXS_DYN_BBM, (const double *)h->ds.S4b);
+}
+
+// the whole loop in one launch; the element state is read from and written back to S4a (each record by its one writer)
+int enqueue_resident(nxs_dyn_handle *h, const StepPlan &) {
+    const int S = h->dp.substeps;
+    const bool mr = multi_rank(h);
+    HIPCHK(h, hipMemsetAsync(h->res.flag, 0, (32 * (size_t)h->dpch.nP + NXS_RES_MAXS + 32) * sizeof(unsigned int), h->stream));
+    const DevParams *pdev = h->d_dp;
+    const double *Sc = h->ds.S4a;
+    double *Sn = h->ds.S4a;
+    double mdt = h->dp.dte;
+    const HaloFused *hfp = mr ? h->d_hf : nullptr;
+    int nb = mr ? h->hf.n_boundary : 0;
+    void *args[] = {&h->dm, &h->dpch, &h->ds, &h->dw, &pdev, &h->res, &Sc, &Sn, &mdt, &hfp, &nb};
+    HIPCHK(h, hipLaunchKernel(resident_kernel(h, mr, h->res_ovl), dim3(h->dpch.nP), dim3(512), args, h->res_lds, h->stream));
+    if (mr) {
+        // the ghosts' mesh moves of all sub-steps but the last, from the ring the launch filled ...
+        if (h->res.NG > 0 && S > 1)
+            hipLaunchKernelGGL(k_ghost_ring_move, dim3(nblocks(h->res.NG)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->res.gring, h->res.NG, S - 1, mdt, (const int *)h->res.error);
+        // ... and the exchange of the last sub-step: the ghosts land in M_VT and make their last move
+        const int tr = h->recv_offsets[h->recv_procs.size()];
+        hipLaunchKernelGGL(k_halo_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, h->ds.VT, h->dm, h->ds, tr, h->d_recv_index,
+                           h->d_recv_seg, h->d_recv_off, h->ipc, mdt, 0, h->d_recv_procs, 1);
+    }
+    return NXS_OK;
+}
+
+// every pair of sub-steps of the step in ONE data-flow launch over the patches of k_substep_pair; the ring is flushed behind it (final_flush)
+int enqueue_flow(nxs_dyn_handle *h, const StepPlan &p) {
+    HIPCHK(h, hipMemsetAsync(h->flow.queue, 0, h->flow_words * sizeof(unsigned int), h->stream));
+    PairFlow f = h->flow;
+    f.K = h->dp.substeps / 2;
+    f.S[0] = h->ds.S4a; f.S[1] = h->ds.S4b;
+    const DevParams *pdev = h->d_dp;   // (explicit_solve keeps the device copy current)
+    void *args[] = {&h->dm, &h->dpch2, &h->ds, &h->dw, &pdev, &h->ring, &f};
+    HIPCHK(h, hipLaunchKernel(flow_kernel(h), dim3(h->flow_grid), dim3(512), args, h->pair_lds, h->stream));
+    finish_records(h, p);   // (K == S: the velocity comes back with the flush)
+    return NXS_OK;
+}
+
+// D sub-steps per launch (k_substep_multi, k_substep_pair); several ranks: both exchanges inside the launches
+int enqueue_pair(nxs_dyn_handle *h, const StepPlan &p) {
+    const int S = h->dp.substeps, D = p.D;
+    int pending = 0;  // sub-steps whose velocity still has to be applied to UM/UT
+    for (int s = D - 1; s < S; s += D) {   // s: the last sub-step of the launch
+        launch_pair(h, p, s - (D - 1));
+        pending += D;
+        if (pending == p.K || s == S - 1) {
+            if (p.halo_in_kernel) pull_latest(h, h->ring.slot[(s + 1) % p.R]);
+            if (!p.move_in_pair) flush_ring(h, p, s, pending);   // (else the launches have moved the mesh)
+            pending = 0;
+        }
+    }
+    finish_records(h, p);
+    return NXS_OK;
+}
+
+// one sub-step per launch with the exchange inside it (k_substep_fused<HALO>); the ghosts of a sub-step come from the mailbox of the one before
+int enqueue_fused_halo(nxs_dyn_handle *h, const StepPlan &p) {
+    const int S = h->dp.substeps;
+    int pending = 0;
+    for (int s = 0; s < S; ++s) {
+        launch_fused(h, s, 0., true, s > 0);
+        if (p.deferred) ++pending;
+        const bool flush_now = p.deferred && (pending == p.K || s == S - 1);
+        if (flush_now || s == S - 1) pull_latest(h, h->ring.slot[(s + 1) % p.R]);
+        if (flush_now) { flush_ring(h, p, s, pending); pending = 0; }
+    }
+    finish_records(h, p);
+    return NXS_OK;
+}
+
+// one sub-step per launch (k_substep_fused, or the per-loop kernels) and, several ranks, a separate exchange behind each
+int enqueue_separate(nxs_dyn_handle *h, const StepPlan &p) {
+    const int S = h->dp.substeps;
+    const bool fused = p.kernel == NXS_KERNEL_FUSED, mr = multi_rank(h);
+    const double move_dt = h->dp.dynamics_type == NXS_DYN_MEVP ? 0. : h->dp.dte, in_kernel_dt = p.deferred ? 0. : move_dt;
+    int pending = 0;
+    for (int s = 0; s < S; ++s) {
+        if (fused) launch_fused(h, s, in_kernel_dt); else launch_substep(h, move_dt);
+        if (mr) {
+            // owned nodes were written to the buffer the next sub-step reads; ghosts must land there too
+            int rc = halo_exchange(h, fused ? h->ring.slot[(s + 1) % p.R] : h->ds.VT, in_kernel_dt);
+            if (rc) return rc;
+        }
+        if (p.deferred && (++pending == p.K || s == S - 1)) { flush_ring(h, p, s, pending); pending = 0; }
+    }
+    if (fused) finish_records(h, p);
+    return NXS_OK;
+}
+
+int enqueue_substeps(nxs_dyn_handle *h, const StepPlan &p) {
+    switch (p.kernel) {
+    case NXS_KERNEL_RESIDENT: case NXS_KERNEL_RESIDENT_BIG: return enqueue_resident(h, p);
+    case NXS_KERNEL_PAIR_FLOW: return enqueue_flow(h, p);
+    case NXS_KERNEL_PAIR: case NXS_KERNEL_MULTI: return enqueue_pair(h, p);
+    case NXS_KERNEL_FUSED: return p.halo_in_kernel ? enqueue_fused_halo(h, p) : enqueue_separate(h, p);
+    default: return enqueue_separate(h, p);   // (the per-loop kernels)
+    }
+}
+
+// Replays `exec`; captures it first from what `body` enqueues where it is not valid (the capture is ended on an error of the body too).
+template <typename Body>
+int capture_or_replay(nxs_dyn_handle *h, hipGraphExec_t &exec, bool &valid, const char *what, Body body) {
+    if (!valid) {
+        if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
+        hipGraph_t g = nullptr;
+        HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+        int rc = body();
+        if (rc) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(h->stream, &dead); if (dead) (void)hipGraphDestroy(dead); return rc; }
+        HIPCHK(h, hipStreamEndCapture(h->stream, &g));
+        hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        if (e != hipSuccess) return fail(h, NXS_ERR_HIP, "hipGraphInstantiate%s: %s", what, hipGetErrorString(e));
+        valid = true;
+    }
+    HIPCHK(h, hipGraphLaunch(exec, h->stream));
+    return NXS_OK;
+}
+
+int run_substeps(nxs_dyn_handle *h) {
+    const StepPlan &p = h->plan;
+    // (outside the graph: whether the records are current depends on what the caller did since the last step)
+    if (p.kernel == NXS_KERNEL_PER_LOOP) ensure_arrays(h);
+    else {
+        if (h->sig_loc == 0) LAUNCH(h, k_pack_state, h->dm.Ne, h->dm, h->ds, h->dp.dynamics_type == NXS_DYN_BBM, h->ds.S4a);
+        h->sig_loc = p.records_end_odd ? 0 : 1;
+    }
+    int rc;
+    if (!p.capturable) rc = enqueue_substeps(h, p);
+    else {
+        if (!h->graph_valid) release_graph(h);   // (the tail graph is captured again with it)
+        rc = capture_or_replay(h, h->substep_graph, h->graph_valid, "", [&] { return enqueue_substeps(h, p); });
+    }
+    return rc ? rc : final_flush(h, p);
+}
+
+int ready(nxs_dyn_handle *h) {
+    if (!h) return NXS_ERR_INVALID;
+    if (!h->have_mesh || !h->have_state || !h->have_forcing)
+        return fail(h, NXS_ERR_STATE, "step needs set_mesh, put_state and set_forcing first");
+    if (multi_rank(h) && !h->have_halo) return fail(h, NXS_ERR_STATE, "nranks>1 needs set_halo");
+    hipError_t e = hipSetDevice(h->device);
+    if (e != hipSuccess) return fail(h, NXS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    return NXS_OK;
+}
+
+// Q9: 50 sweeps, hard-coded (FE.cpp:10580); + open-water mesh move.  52+ small launches: replayed from
+// a second hipGraph whenever no host work is needed inside (single rank, or device-direct halo).
+int smooth_and_tail(nxs_dyn_handle *h) {
+    const DevMesh &m = h->dm;
+    const StepPlan &p = h->plan;
+    double *a = h->ds.VT, *b = p.smooth_slot >= 0 ? h->ring.slot[p.smooth_slot] : h->ds.VT2;
+    if (p.smooth_slot < 0) LAUNCH(h, k_copy_vt, 2 * m.Nn, 2 * m.Nn, a, b);  // both buffers equal: a sweep writes the ice-free nodes only
+    // single rank: D sweeps per launch on patches with D rings of nodes (k_smooth_multi) -- those of k_substep_multi where that
+    // kernel runs, else node-ring patches built for the smoother alone
+    const bool v3_patches = h->pair_ready && !h->pair_failed && h->dpch2.pnbr && eff_fused(h) >= 2 && p.D >= 2 && !h->sm_ready;  // (only where the smoother's own patches could not be built)
+    if (!multi_rank(h) && (v3_patches || h->sm_ready)) {
+        const DevPatches2 &pp = v3_patches ? h->dpch2 : h->dsm;
+        const size_t lds = v3_patches ? h->smooth_lds : h->sm_lds;
+        const int D = pp.D, L = (50 + D - 1) / D;
+        if (L & 1) std::swap(a, b);  // the buffers are equal now; end in ds.VT after L swaps
+        for (int nit = 0; nit < 50; nit += D) {
+            const int ks = std::min(D, 50 - nit);
+            if (pp.NSmax > 256) hipLaunchKernelGGL((k_smooth_multi<512>), dim3(pp.nP), dim3(512), lds, h->stream, m, pp, h->dw, (const double *)a, b, ks);
+            else hipLaunchKernelGGL((k_smooth_multi<256>), dim3(pp.nP), dim3(256), lds, h->stream, m, pp, h->dw, (const double *)a, b, ks);
+            std::swap(a, b);
+        }
+        LAUNCH(h, k_ow_tail, m.Nn, m, h->ds, h->dw, h->dp);
+        return NXS_OK;
+    }
+    const bool halo_in_kernel = exchange_in_kernel_possible(h) && h->hf_ready && m.No > 0;
+    if (halo_in_kernel) {  // which of my directions carry values the sweeps cannot change (they are sent once)
+        const int ts = h->send_offsets[h->send_procs.size()];
+        if (ts > 0) LAUNCH(h, k_smooth_static, ts, ts, h->d_send_index, h->d_send_seg, m, h->dw, h->ipc.my_static);
+    }
+    static_assert(NXS_SMOOTH_SWEEPS == 50, "Q9: FE.cpp:10580 hard-codes 50 sweeps");
+    if (halo_in_kernel && h->smooth_persist != 0) {   // all 50 sweeps in ONE launch of persistent workgroups (k_smooth_persist); the result is back in `a` (50 is even)
+        HaloFused hf = h->hf;
+        hf.ipc = h->ipc;
+        const int nblk = nblocks(m.No), G = std::min(nblk, 128);
+        hipLaunchKernelGGL(k_smooth_persist, dim3(G), dim3(BLOCK), 0, h->stream, m, h->dw, a, b, hf, nblk);
+        const int tr = h->recv_offsets[h->recv_procs.size()];
+        hipLaunchKernelGGL(k_smooth_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, a, m.Nn, tr, h->d_recv_index, h->d_recv_seg, h->d_recv_off, h->ipc);
+        LAUNCH(h, k_ow_tail, m.Nn, m, h->ds, h->dw, h->dp);
+        return NXS_OK;
+    }
+    for (int nit = 0; nit < 50; ++nit) {
+        if (halo_in_kernel) {  // updateGhosts inside the sweep; the ghosts land in the array once, after the last sweep
+            HaloFused hf = h->hf;
+            hf.ipc = h->ipc;
+            LAUNCH(h, k_smooth_halo, m.No, m, h->dw, (const double *)a, b, hf, nit);
+            if (nit == 49) {
+                const int tr = h->recv_offsets[h->recv_procs.size()];
+                hipLaunchKernelGGL(k_smooth_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, b, m.Nn, tr, h->d_recv_index,
+                                   h->d_recv_seg, h->d_recv_off, h->ipc);
+            }
+        } else {
+            LAUNCH(h, k_smooth, m.No, m, h->dw, a, b);
+            if (multi_rank(h)) { int r2 = halo_exchange(h, b, 0.); if (r2) return r2; }
+        }
+        std::swap(a, b);
+    }
+    // 50 is even: the result is back in ds.VT
+    LAUNCH(h, k_ow_tail, m.Nn, m, h->ds, h->dw, h->dp);
+    return NXS_OK;
+}
+
+int explicit_solve(nxs_dyn_handle *h) {
+    const bool timed = h->cur != nullptr;
+    // FE.cpp:10182-10643
+    const DevMesh &m = h->dm;
+    if (timed) HIPCHK(h, hipEventRecord(h->cur[0], h->stream));
+    int rc = plan_step(h);
+    if (rc) return rc;
+    const StepPlan &p = h->plan;
+    {
+        // (the per-step shape-coefficient records are read by k_substep_multi only: k_substep_pair rebuilds the coefficients from the staged coordinates)
+        double *want = (p.kernel == NXS_KERNEL_MULTI && h->shape_mem != 0) ? h->d_srec : nullptr;
+        if (want != h->dw.srec) { h->dw.srec = want; release_graph(h); }  // (kernel arguments are baked into the graphs)
+    }
+    if (h->dp_dirty) {  // (outside any stream capture)
+        if (!h->d_dp) HIPCHK(h, hipMalloc((void **)&h->d_dp, sizeof(DevParams)));
+        HIPCHK(h, hipMemcpyAsync(h->d_dp, &h->dp, sizeof(DevParams), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));  // h->dp may change right after
+        h->dp_dirty = false;
+    }
+    if (p.prep == NXS_PREP_FUSED) {
+        // one launch over the sub-step kernel's patches: the elements' values reach their nodes through LDS (k_prep_fused)
+        // (the open-water flags of the node blocks are lowered by the step before -- k_update's first threads, as the range flag -- and at allocation: no memset per step;
+        // a step that ended without update() leaves them raised, which only costs the smoother some blocks it could have skipped)
+        hipLaunchKernelGGL(k_prep_fused, dim3(h->dpch.nP), dim3(512), h->prep_lds, h->stream, m, h->dpch, h->ds, h->dw, h->dp);
+        if (m.Nn > m.No) LAUNCH(h, k_prep_ghost_nodes, m.Nn - m.No, m, h->ds, h->dw, h->dp);   // several ranks: the ghost nodes' share of the nodal loops
+        HIPCHK(h, hipGetLastError());
+    } else if (p.prep == NXS_PREP_LEAN) {
+        LAUNCH(h, k_prep_elements<true>, m.Ne, m, h->ds, h->dw, h->dp);
+        LAUNCH(h, k_prep_nodes<true>, m.Nn, m, h->ds, h->dw, h->dp);
+    } else {
+        LAUNCH(h, k_prep_elements<false>, m.Ne, m, h->ds, h->dw, h->dp);
+        LAUNCH(h, k_prep_nodes<false>, m.Nn, m, h->ds, h->dw, h->dp);
+    }
+    if (timed) HIPCHK(h, hipEventRecord(h->cur[1], h->stream));
+    rc = run_substeps(h);
+    if (rc) return rc;
+    if (!multi_rank(h) && !h->sm_ready && !h->sm_failed && eff_fused(h) != 0) {
+        // automatic: ten sweeps per launch (five launches; 10 km: smoother 43 -> 25 us per step) where ten rings fit the LDS, else five
+        if (h->sm_depth > 0) { if (build_smooth_patches(h, h->sm_depth) != NXS_OK) h->sm_failed = true; }  // the smoother then runs sweep by sweep
+        else if (build_smooth_patches(h, 10) != NXS_OK && build_smooth_patches(h, 5) != NXS_OK) h->sm_failed = true;
+        h->tail_graph_valid = false;
+    }
+    if (h->dp.dynamics_type == NXS_DYN_MEVP)  // FE.cpp:10559-10573
+        LAUNCH(h, k_move, m.Nn, m, h->ds, 0, m.Nn, h->dp.dtime_step);
+    if (timed) HIPCHK(h, hipEventRecord(h->cur[2], h->stream));
+    rc = p.capturable ? capture_or_replay(h, h->tail_graph, h->tail_graph_valid, "(tail)", [&] { return smooth_and_tail(h); }) : smooth_and_tail(h);
+    if (rc) return rc;
+    if (timed) HIPCHK(h, hipEventRecord(h->cur[3], h->stream));
+    // a refused launch (a launch configuration the device rejects, e.g. more dynamic LDS than a CU has) is reported here,
+    // at the step that issued it, not as a generic error at the next synchronize
+    HIPCHK(h, hipGetLastError());
+    return NXS_OK;
 }
 
 }  // namespace
@@ -775,7 +1610,7 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
         HIPCHK(h, hipSetDevice(h->device));
         h->res_ready = false; h->res_failed = false;
         int rc = NXS_OK;
-        if (multi_rank(h) && !h->hf_ready && (rc = build_halo_fused(h))) return rc;
+        if (multi_rank(h) && (rc = ensure_halo_fused(h))) return rc;
         if ((rc = build_resident(h))) return rc;
         if (!h->res_ready) return fail(h, NXS_ERR_INVALID, "the resident sub-step loop cannot run this partition (NXS_DEBUG_PATCHES=1 says why)");
         return NXS_OK;
@@ -788,20 +1623,9 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
         if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "prepare needs set_mesh");
         HIPCHK(h, hipSetDevice(h->device));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        const bool mr = multi_rank(h);
-        const bool device_halo = mr && h->have_halo && h->ipc_ready && !h->halo_fn;
         int rc = NXS_OK;
-        if (device_halo && h->halo_fused && !h->hf_ready && (rc = build_halo_fused(h))) return rc;
-        if (h->fused == 4 && (!mr || (device_halo && h->halo_fused)) && !h->res_ready && !h->res_failed && h->dp.dynamics_type != NXS_DYN_MEVP) {
-            if ((rc = build_resident(h))) return rc;
-            if (h->res_failed && h->cut_big && !h->no_big_cut) {
-                release_graph(h);
-                h->no_big_cut = true;
-                if ((rc = upload_patches(h))) return rc;
-                if (device_halo && h->halo_fused && !h->hf_ready && (rc = build_halo_fused(h))) return rc;
-                h->res_failed = true;   // (after the rebuilds: they give a fresh cut a fresh chance, this cut was made because the resident loop cannot run)
-            }
-        }
+        if (exchange_in_kernel_possible(h) && (rc = ensure_halo_fused(h))) return rc;
+        if (resident_possible(h) && (rc = ensure_resident(h))) return rc;
         return NXS_OK;
     }
     if (!std::strcmp(key, "resident_wide")) {
@@ -831,7 +1655,7 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
     }
     if (!std::strcmp(key, "pair_threads")) {
         if (value != 256 && value != 512) return fail(h, NXS_ERR_INVALID, "pair_threads must be 256 or 512");
-        h->pair_T = (int)value; h->pair_ready = false; h->pair_failed = false; h->pair_hint = 0; release_graph(h); return NXS_OK;
+        h->pair_threads_requested = (int)value; h->pair_ready = false; h->pair_failed = false; h->pair_hint = 0; release_graph(h); return NXS_OK;
     }
     if (!std::strcmp(key, "pair_hilbert")) { h->pair_hilbert = value != 0; h->pair_ready = false; h->pair_failed = false; h->pair_hint = 0; release_graph(h); return NXS_OK; }
     if (!std::strcmp(key, "pair_move")) { h->pair_move = value < 0 ? -1 : (value != 0); release_graph(h); return NXS_OK; }
@@ -1736,760 +2560,6 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
     return fail(h, NXS_ERR_INVALID, "unknown debug array '%s'", name);
 } catch (...) { return dyn_caught(h, "nxs_dyn_debug_array"); }
 
-// ------------------------------------------------------------------------------------------------
-// the launches
-
-namespace {
-
-#define LAUNCH(h, kern, n, ...)                                                              \
-    do {                                                                                      \
-        hipLaunchKernelGGL(kern, dim3(nblocks(n)), dim3(BLOCK), 0, (h)->stream, __VA_ARGS__); \
-    } while (0)
-
-int halo_exchange(nxs_dyn_handle *h, double *vec, double move_dt) {
-    // updateGhosts (FE.cpp:13963-13996): pack -> grouped send/recv -> unpack
-    const int ns = (int)h->send_procs.size(), nr = (int)h->recv_procs.size();
-    const int ts = h->send_offsets[ns], tr = h->recv_offsets[nr];
-    if (h->ipc_ready && !h->halo_fn) {
-        // device-direct: pack + peer stores + flags, then wait + unpack (+ ghost-node move); no host work
-        hipLaunchKernelGGL(k_halo_push, dim3(nblocks(ts)), dim3(BLOCK), 0, h->stream, (const double *)vec, h->dm.Nn, ts,
-                           h->d_send_index, h->d_send_seg, h->d_send_off, h->ipc, h->rank, 0);
-        hipLaunchKernelGGL(k_halo_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, vec, h->dm, h->ds, tr, h->d_recv_index,
-                           h->d_recv_seg, h->d_recv_off, h->ipc, move_dt, 0, h->d_recv_procs, 0);
-        return NXS_OK;
-    }
-    if (!h->comm && !h->halo_fn) return fail(h, NXS_ERR_STATE, "halo exchange needs nxs_dyn_comm_init, nxs_dyn_ipc_connect or nxs_dyn_set_halo_exchange_fn");
-    if (ts > 0) LAUNCH(h, k_halo_pack, ts, vec, h->dm.Nn, ts, h->d_send_index, h->d_send_seg, h->d_send_off, h->d_send_buf);
-    if (h->halo_fn) {
-        // host-staged: exactly the reference's M_comm.send / M_comm.recv of packed std::vector<double>
-        if (ts > 0) HIPCHK(h, hipMemcpyAsync(h->h_send, h->d_send_buf, 2 * (size_t)ts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        const int rc = h->halo_fn(h->halo_ctx, h->h_send, h->h_recv);
-        if (rc != 0) return fail(h, NXS_ERR_COMM, "halo exchange callback returned %d", rc);
-        if (tr > 0) {
-            HIPCHK(h, hipMemcpyAsync(h->d_recv_buf, h->h_recv, 2 * (size_t)tr * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            LAUNCH(h, k_halo_unpack, tr, vec, h->dm, h->ds, tr, h->d_recv_index, h->d_recv_seg, h->d_recv_off, h->d_recv_buf, move_dt);
-        }
-        return NXS_OK;
-    }
-    const int ncclDouble = 8;  // ncclFloat64
-    int e = h->rccl.GroupStart();
-    for (int k = 0; k < ns && e == 0; ++k)   // (a segment without nodes -- a direction set_halo added -- is no message: both ends know it is empty)
-        if (h->send_offsets[k + 1] > h->send_offsets[k])
-            e = h->rccl.Send(h->d_send_buf + 2 * (size_t)h->send_offsets[k], 2 * (size_t)(h->send_offsets[k + 1] - h->send_offsets[k]),
-                             ncclDouble, h->send_procs[k], h->comm, h->stream);
-    for (int k = 0; k < nr && e == 0; ++k)
-        if (h->recv_offsets[k + 1] > h->recv_offsets[k])
-            e = h->rccl.Recv(h->d_recv_buf + 2 * (size_t)h->recv_offsets[k], 2 * (size_t)(h->recv_offsets[k + 1] - h->recv_offsets[k]),
-                             ncclDouble, h->recv_procs[k], h->comm, h->stream);
-    int e2 = h->rccl.GroupEnd();
-    if (e == 0) e = e2;
-    if (e != 0) return fail(h, NXS_ERR_COMM, "halo send/recv: %s", h->rccl.GetErrorString(e));
-    if (tr > 0) LAUNCH(h, k_halo_unpack, tr, vec, h->dm, h->ds, tr, h->d_recv_index, h->d_recv_seg, h->d_recv_off, h->d_recv_buf, move_dt);
-    return NXS_OK;
-}
-
-bool multi_rank(const nxs_dyn_handle *h) { return h->nranks > 1; }
-
-PingPong pingpong(const nxs_dyn_handle *h, int parity) {
-    const DevState &s = h->ds;
-    PingPong b;
-    if (parity == 0) { b.VTc = s.VT; b.Sc = s.S4a; b.VTn = s.VT2; b.Sn = s.S4b; }
-    else { b.VTc = s.VT2; b.Sc = s.S4b; b.VTn = s.VT; b.Sn = s.S4a; }
-    return b;
-}
-
-// sub-step `sidx` of the fused path: sigma/damage ping-pong by parity; velocities move through the ring
-// (ring of 2 == ping-pong between VT and VT2 when the deferred mesh move is off)
-// halo != 0: the sub-step also performs updateGhosts (HaloFused); from_mailbox = ghosts come from exchange x-1
-void launch_fused(nxs_dyn_handle *h, int sidx, double move_dt, int halo = 0, int from_mailbox = 0) {
-    PingPong b = pingpong(h, sidx & 1);
-    const int R = h->ring.R;
-    b.VTc = h->ring.slot[sidx % R];
-    b.VTn = h->ring.slot[(sidx + 1) % R];
-    const dim3 grid(h->dpch.nP);
-    const bool big = h->dpch.Pmax > NXS_T256_MAXP || h->dpch.Emax > 3 * 256, pow4 = h->dp.ers_int == 4;
-    // streaming hints keep the state from displacing the reusable arrays -- a gain only when a sub-step's ~210 B/triangle do not fit
-    // the 256 MiB Infinity Cache anyway: 1.46 M triangles 7.08 -> 6.96 ms/step with them, 730 k 3.75 -> 3.98, 367 k 2.20 -> 2.33, 182 k 1.27 -> 1.31
-    const int nt_mask = h->nt_mask >= 0 ? h->nt_mask : (h->dm.Ne >= 1000000 ? 3 : 0);
-    // parameters from memory (PMEM) where one round of resident workgroups covers the partition, by value where several rounds stream
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-    const bool pmem = h->dpch.nP <= 5 * cus / 2;  // 511 patches (182 k triangles): 1.375 -> 1.344 ms/step; 752 patches (263 k): 1.83 -> 1.91
-#define FUSED_K(TT, PP, NN, HH, MM, HFP, NB, FM) hipLaunchKernelGGL((k_substep_fused<TT, PP, NN, HH, MM>), grid, dim3(TT), h->fused_lds, h->stream, h->dm, h->dpch, h->ds, h->dw, h->dp, (const DevParams *)h->d_dp, b, move_dt, HFP, NB, FM)
-    if (halo) {
-#define FUSED_H(TT, PP, NN) do { if (pmem) FUSED_K(TT, PP, NN, true, true, (const HaloFused *)h->d_hf, h->hf.n_boundary, from_mailbox); else FUSED_K(TT, PP, NN, true, false, (const HaloFused *)h->d_hf, h->hf.n_boundary, from_mailbox); } while (0)
-        if (big) { if (pow4) { if (nt_mask) FUSED_H(512, true, 3); else FUSED_H(512, true, 0); } else { FUSED_H(512, false, 0); } }
-        else { if (pow4) { if (nt_mask) FUSED_H(256, true, 3); else FUSED_H(256, true, 0); } else { FUSED_H(256, false, 0); } }
-#undef FUSED_H
-        return;
-    }
-#define FUSED(TT, PP, NN) do { if (pmem) FUSED_K(TT, PP, NN, false, true, (const HaloFused *)nullptr, 0, 0); else FUSED_K(TT, PP, NN, false, false, (const HaloFused *)nullptr, 0, 0); } while (0)
-#define FUSED_NT(TT, PP) switch (nt_mask) { case 0: FUSED(TT, PP, 0); break; case 1: FUSED(TT, PP, 1); break; case 3: FUSED(TT, PP, 3); break; case 4: FUSED(TT, PP, 4); break; case 5: FUSED(TT, PP, 5); break; default: FUSED(TT, PP, 7); break; }
-    if (big) { if (pow4) { FUSED_NT(512, true); } else { FUSED(512, false, 0); } }
-    else { if (pow4) { FUSED_NT(256, true); } else { FUSED(256, false, 0); } }
-#undef FUSED_NT
-#undef FUSED
-#undef FUSED_K
-}
-
-// sub-steps sidx .. sidx+D-1 in one launch (k_substep_multi): sigma/damage ping-pong per LAUNCH, velocities through the ring
-void launch_multi(nxs_dyn_handle *h, int sidx, int D, bool halo = false) {
-    PingPong b = pingpong(h, (sidx / D) & 1);
-    const int R = h->ring.R;
-    b.VTc = h->ring.slot[sidx % R];
-    b.VTn = nullptr;
-    VTOut vo{};
-    for (int k = 0; k < D; ++k) vo.slot[k] = h->ring.slot[(sidx + 1 + k) % R];
-    const dim3 grid(h->dpch2.nP);
-    const bool pow4 = h->dp.ers_int == 4;
-    if (h->pair_kernel) {  // (D == 2: upload_patches2 / upload_pair_patches_mr cut the patches for it)
-        if (halo) {        // several ranks: both exchanges inside the launch; the first launch of a step finds its ghosts in the velocity buffer
-            PairHalo ph = h->pairh;
-            ph.from_mailbox = sidx > 0 ? 1 : 0;
-            if (pow4) hipLaunchKernelGGL((k_substep_pair<512, true, 3, true>), grid, dim3(512), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, h->dp, b, vo, (const HaloFused *)h->d_hf, ph);
-            else hipLaunchKernelGGL((k_substep_pair<512, false, 3, true>), grid, dim3(512), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, h->dp, b, vo, (const HaloFused *)h->d_hf, ph);
-            return;
-        }
-        if (h->pair_threads == 256) {
-            if (pow4) hipLaunchKernelGGL((k_substep_pair<256, true, 3>), grid, dim3(256), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, h->dp, b, vo, (const HaloFused *)nullptr, PairHalo{});
-            else hipLaunchKernelGGL((k_substep_pair<256, false, 3>), grid, dim3(256), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, h->dp, b, vo, (const HaloFused *)nullptr, PairHalo{});
-            return;
-        }
-        if (h->move_now) {   // the mesh move of the two sub-steps inside the launch
-            // (the first velocity slot is not written; the LAST launch of a step whose final velocity lands in M_VT itself writes it a second time there instead: the
-            // smoother wants two equal buffers and would otherwise copy one)
-            vo.slot[0] = (sidx + D == h->dp.substeps && (h->dp.substeps % R) == 0) ? h->ring.slot[(sidx + 1) % R] : nullptr;
-            if (pow4) hipLaunchKernelGGL((k_substep_pair<512, true, 3, false, true>), grid, dim3(512), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, h->dp, b, vo, (const HaloFused *)nullptr, PairHalo{});
-            else hipLaunchKernelGGL((k_substep_pair<512, false, 3, false, true>), grid, dim3(512), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, h->dp, b, vo, (const HaloFused *)nullptr, PairHalo{});
-            return;
-        }
-        if (pow4) hipLaunchKernelGGL((k_substep_pair<512, true, 3>), grid, dim3(512), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, h->dp, b, vo, (const HaloFused *)nullptr, PairHalo{});
-        else hipLaunchKernelGGL((k_substep_pair<512, false, 3>), grid, dim3(512), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, h->dp, b, vo, (const HaloFused *)nullptr, PairHalo{});
-        return;
-    }
-#define MULTI(TT, PP, NN) hipLaunchKernelGGL((k_substep_multi<TT, PP, NN>), grid, dim3(TT), h->pair_lds, h->stream, h->dm, h->dpch2, h->ds, h->dw, (const DevParams *)h->d_dp, b, vo)
-// no non-temporal hints: this kernel runs where the mesh lives in the caches (58 k triangles: 0.768 ms/step with them, 0.750 without; 111 k: 0.927 / 0.90)
-#define MULTI_T(TT) do { if (pow4) MULTI(TT, true, 0); else MULTI(TT, false, 0); } while (0)
-    if (h->pair_threads == 768) MULTI_T(768); else if (h->pair_threads == 512) MULTI_T(512); else MULTI_T(256);
-#undef MULTI_T
-#undef MULTI
-}
-
-// (re)build the ring of velocity buffers of the fused path: slot 0 is M_VT itself, slot 1 is VT2
-int setup_ring(nxs_dyn_handle *h, int K) {
-    const int R = K + 1;
-    if (h->ring.R == R) return NXS_OK;
-    // Buffers are only ever ADDED (they go with the mesh): a hipFree synchronises the whole device, and on a device that another handle of this
-    // process shares (the several-ranks-per-process tests and rehearsals) that other rank's kernels may be spinning for THIS rank's next launch --
-    // freeing here, inside a step, deadlocked such runs until the 10 s guard fired whenever a run switched from the long ring to the short one
-    // (round 3: found in the kernel statistics of a two-rank run, one k_halo_pull of 10 s).
-    h->ring.slot[0] = h->ds.VT;
-    h->ring.slot[1] = h->ds.VT2;
-    for (int i = 2; i < R; ++i) {
-        if (i - 2 < (int)h->ring_allocs.size()) { h->ring.slot[i] = static_cast<double *>(h->ring_allocs[i - 2]); continue; }
-        int rc = dev_alloc(h, h->ring_allocs, &h->ring.slot[i], 2 * (size_t)h->dm.Nn);
-        if (rc) return rc;
-    }
-    for (int i = R; i < NXS_MAX_RING; ++i) h->ring.slot[i] = nullptr;
-    h->ring.R = R;
-    return NXS_OK;
-}
-
-// The resident sub-step kernel of this handle: ONE place decides the instantiation, for the occupancy query and for the launch alike.
-// (WPE = 2: the several-rank build with all the registers it wants, BBM's default exponent only.)
-const void *resident_kernel(const nxs_dyn_handle *h, bool mr, bool ovl) {
-    const bool p4 = h->res_pow4;
-    if (h->res_big) {  // one large patch per CU, four elements and two own nodes per thread
-        if (mr && ovl) return p4 ? (const void *)k_substep_resident_big<true, true, true> : (const void *)k_substep_resident_big<false, true, true>;
-        if (mr) return p4 ? (const void *)k_substep_resident_big<true, true, false> : (const void *)k_substep_resident_big<false, true, false>;
-        if (ovl) return p4 ? (const void *)k_substep_resident_big<true, false, true> : (const void *)k_substep_resident_big<false, false, true>;
-        return p4 ? (const void *)k_substep_resident_big<true, false, false> : (const void *)k_substep_resident_big<false, false, false>;
-    }
-    if (mr && h->res_wpe == 2 && p4) return ovl ? (const void *)k_substep_resident<512, true, true, true, 2> : (const void *)k_substep_resident<512, true, true, false, 2>;
-    if (mr && ovl) return p4 ? (const void *)k_substep_resident<512, true, true, true> : (const void *)k_substep_resident<512, false, true, true>;
-    if (mr) return p4 ? (const void *)k_substep_resident<512, true, true> : (const void *)k_substep_resident<512, false, true>;
-    return p4 ? (const void *)k_substep_resident<512, true, false> : (const void *)k_substep_resident<512, false, false>;
-}
-
-// The resident launch needs every workgroup of its grid on a CU at once, and its workgroups spin: a handle claims its workgroup slots in the device's
-// registry before it builds the loop and gives them back when its tables go; a claim that does not fit beside what is claimed already -- by handles
-// of this process or of any other process on the device, with headroom for the co-tenants' ordinary kernels where the device is shared -- is refused
-// up front and the step runs one kernel per sub-step (nxs_resident_registry.hpp has the rule and the evidence behind it).
-// (kind: nxs_reg::KIND_RESIDENT / KIND_PAIR -- one claim per handle, held by ONE of its two grids of waiting workgroups; a release names the grid that lets go,
-// so that the resident loop's tables going away do not take the pair patches' claim with them)
-void resident_registry_release(const nxs_dyn_handle *h, int kind) {
-    if (!h->reg_key.empty()) nxs_reg::table_for(h->reg_key).release((uint64_t)(uintptr_t)h, kind);
-}
-bool resident_registry_claim(const nxs_dyn_handle *h, int workgroups, int slots, std::string *why, int kind) {
-    if (h->reg_key.empty()) { if (why) *why = "the handle is not registered on its device"; return false; }
-    return nxs_reg::table_for(h->reg_key).claim((uint64_t)(uintptr_t)h, workgroups, slots, multi_rank(h), why, kind);
-}
-
-// The blocks of this handle's ORDINARY kernels that may spin for a neighbour rank (k_smooth_halo, k_halo_pull, the boundary patches of k_substep_fused<HALO>): the
-// largest such grid, as a fraction of the device, is registered -- other handles' claims leave it room (nxs_resident_registry.hpp).  reset: start from nothing.
-void register_waiting_grid(nxs_dyn_handle *h, int blocks, int slots, bool reset) {
-    if (h->reg_key.empty()) return;
-    if (reset) { h->ord_blocks = 0; h->ord_slots = 0; }
-    if (blocks > 0 && slots > 0 && (h->ord_blocks == 0 || (double)blocks / slots > (double)h->ord_blocks / h->ord_slots)) { h->ord_blocks = blocks; h->ord_slots = slots; }
-    nxs_reg::table_for(h->reg_key).set_ordinary((uint64_t)(uintptr_t)h, h->ord_blocks, h->ord_slots);
-}
-
-// ... the smoother's: k_smooth_persist runs at most 128 persistent workgroups that wait for each other and for the neighbour ranks; with option smooth_persist 0 every
-// block of k_smooth_halo (one per BLOCK own nodes) may spin for a neighbour's sweep; k_halo_pull's blocks (one per BLOCK ghosts) spin for its flags.  Called where the
-// halo lists are set and where the option changes.
-void register_smoother_grid(nxs_dyn_handle *h) {
-    if (!h->have_halo) return;
-    const int No = h->dm.No, tr = h->recv_offsets[h->recv_procs.size()];
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_smooth_halo, BLOCK, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 1; }
-    const int sweeps = h->smooth_persist != 0 ? std::min(nblocks(No), 128) : nblocks(No);
-    register_waiting_grid(h, h->nranks > 1 ? std::max(sweeps, nblocks(tr)) : 0, per_cu * device_cus(h), true);
-    if (h->hf_ready) register_waiting_grid(h, h->hf.n_boundary, 2 * device_cus(h));   // (the boundary patches of k_substep_fused<HALO>, as build_halo_fused registers them)
-}
-
-// tables of the halo exchange fused into the sub-step kernel (see HaloFused)
-int build_halo_fused(nxs_dyn_handle *h) {
-    drop_pool(h, h->hf_allocs);
-    h->hf = HaloFused{};
-    h->hf_ready = false;
-    const int Nn = h->dm.Nn, No = h->dm.No, nP = h->dpch.nP;
-    if (!h->hp || h->hp->nP != nP) return fail(h, NXS_ERR_STATE, "fused halo tables: patches / halo lists missing");
-    const nxs_cut::HaloLists hl{&h->send_offsets, &h->recv_offsets, &h->h_send_index, &h->h_recv_index, (int)h->send_procs.size(), (int)h->recv_procs.size()};
-    nxs_cut::HaloFusedPlan plan;
-    const std::string why = nxs_cut::plan_halo_fused(Nn, No, hl, *h->hp, plan);  // (host only: nxs_patchcut.hpp)
-    if (!why.empty()) return fail(h, NXS_ERR_STATE, "%s", why.c_str());
-    if (plan.reordered) {  // the patch arrays again, boundary patches first: the grid starts with them and "boundary" is blk < n_boundary
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        release_graph(h);
-        int rcu = upload_host_patches(h, *h->hp);
-        if (rcu) return rcu;
-    }
-    HaloFused &f = h->hf;
-    int rc;
-    if ((rc = dev_upload(h, h->hf_allocs, &f.send_ptr, plan.sptr))) return rc;
-    if ((rc = dev_upload(h, h->hf_allocs, &f.send_k, plan.sk))) return rc;
-    if ((rc = dev_upload(h, h->hf_allocs, &f.send_pos, plan.spos))) return rc;
-    if ((rc = dev_upload(h, h->hf_allocs, &f.ghost_off, plan.goff))) return rc;
-    if ((rc = dev_upload(h, h->hf_allocs, &f.ghost_srl, plan.gsrl))) return rc;
-    if ((rc = dev_upload(h, h->hf_allocs, &f.ghost_k, plan.gk))) return rc;
-    unsigned int *ctr = nullptr;
-    if ((rc = dev_alloc(h, h->hf_allocs, &ctr, 32 * 19))) return rc;   // [0] and [32 (g + 1)]: two-level tickets; [32 * 17]: the generation word of k_smooth_persist's barrier
-    HIPCHK(h, hipMemsetAsync(ctr, 0, 32 * 19 * sizeof(unsigned int), h->stream));
-    f.done_all = ctr;
-    if ((rc = dev_upload(h, h->hf_allocs, &f.send_block_rank, plan.send_block_rank))) return rc;  // k_smooth_halo: which blocks store into a mailbox
-    f.n_send_blocks = plan.n_send_blocks;
-    f.no_release = h->res_no_release;
-    f.send_off = h->d_send_off;
-    f.n_boundary = plan.n_boundary;
-    register_waiting_grid(h, plan.n_boundary, 2 * device_cus(h));   // (two 512-thread workgroups of the fused kernel per CU)
-    f.No = No;
-    {
-        unsigned long long *raw = nullptr;  // device copy of the struct itself (filled in by run_substeps once the mailboxes are connected)
-        if ((rc = dev_alloc(h, h->hf_allocs, &raw, (sizeof(HaloFused) + 7) / 8))) return rc;
-        h->d_hf = reinterpret_cast<HaloFused *>(raw);
-        h->d_hf_dirty = true;
-    }
-    h->hf_ready = true;
-    if (getenv("NXS_DEBUG_PATCHES")) {
-        fprintf(stderr, "[nxs] rank %d fused halo: %d of %d patches on the boundary, %d sent nodes, %d ghosts\n", h->rank, plan.n_boundary, nP, plan.sptr[No], Nn - No);
-        std::string sizes;   // own nodes / elements / of them sent, of the boundary patches (they lead the arrays now)
-        for (int q = 0; q < plan.n_boundary && q < 80; ++q) {
-            int sent = 0, ghosts = 0;
-            const int *nd = h->hp->pnodes.data() + (size_t)q * h->hp->Mmax;
-            for (int i = 0; i < h->hp->node_cnt[q]; ++i) { if (nd[i] >= No) ++ghosts; else if (i < h->hp->own_cnt[q] && plan.sptr[nd[i] + 1] > plan.sptr[nd[i]]) ++sent; }
-            char b[64]; snprintf(b, sizeof b, " %d/%d/s%d/g%d", h->hp->own_cnt[q], h->hp->elem_cnt[q], sent, ghosts); sizes += b;
-        }
-        fprintf(stderr, "[nxs] rank %d boundary patches (own nodes / elements / sent / ghosts staged):%s\n", h->rank, sizes.c_str());
-    }
-    return NXS_OK;
-}
-
-// Tables of the resident sub-step kernel (nxs_cut::plan_resident), the counters, the exchange buffers.  NXS_OK with res_ready == false
-// means "not possible here" (the caller then runs one kernel per sub-step).  Everything lives in a pool of its own that is given back
-// before it is rebuilt (options fused / resident_wide / resident_overlap / resident_dryrun, a change of parameters, a timed-out launch).
-int build_resident(nxs_dyn_handle *h) {
-    h->res_ready = false;
-    drop_pool(h, h->res_allocs);
-    h->res = DevResident{};
-    h->d_vt3 = nullptr;
-    if (!h->hp || h->hp->nP != h->dpch.nP) return NXS_OK;
-    const HostPatches &hp = *h->hp;
-    const int nP = hp.nP, No = h->dm.No, Nn = h->dm.Nn, S = h->dp.substeps;
-    const bool mr = multi_rank(h);
-    const bool big = nxs_cut::resident_is_big(hp);
-    const bool ovl = big ? h->res_overlap != 0 : (mr && h->res_overlap == 1);
-    h->res_ovl = ovl;
-    auto refuse = [&](const char *why) {
-        if (getenv("NXS_DEBUG_PATCHES")) fprintf(stderr, "[nxs] rank %d resident kernel not possible: %s\n", h->rank, why);
-        h->res_failed = true;
-        return NXS_OK;
-    };
-    if (S > NXS_RES_MAXS) return refuse("more sub-steps than the kernel keeps counters for");
-    nxs_cut::ResidentPlan plan;
-    nxs_cut::plan_resident(hp, Nn, No, mr, (int)h->send_procs.size(), ovl, plan);
-    if (!plan.ok) return refuse(plan.why.c_str());
-    h->res_big = big;
-    h->res_lds = big ? nxs_cut::resident_big_lds_of(hp, mr) : nxs_cut::resident_lds_of(hp, mr);
-    if (h->res_lds > 160 * 1024) return refuse("a patch needs more LDS than a CU has");
-    // every workgroup must be resident at once
-    int per_cu = 0;
-    const int cus = device_cus(h);
-    const bool p4 = h->dp.ers_int == 4;
-    // one workgroup per CU is enough and the caller says the device is this handle's alone (option resident_wide): the several-rank build with all
-    // the registers it wants -- one such workgroup fills a CU, so ranks that share a device (the tests) would no longer fit side by side
-    h->res_wpe = (mr && p4 && h->res_wide && nP <= cus && !big) ? 2 : 4;
-    h->res_pow4 = p4;
-    const void *kern = resident_kernel(h, mr, ovl);
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, h->res_lds);
-    if (e != hipSuccess || (long long)per_cu * cus < nP) {
-        (void)hipGetLastError();
-        char why[160];
-        snprintf(why, sizeof why, "%d patches, %d x %d workgroups fit (%zu B of LDS each)", nP, per_cu, cus, h->res_lds);
-        return refuse(why);
-    }
-    // the device's other resident grids (other handles of this process: the ranks a host drives from one process, the tests): all of them
-    // together must fit, or the spinning workgroups of one keep the other's from ever starting
-    {
-        std::string why;
-        if (!resident_registry_claim(h, nP, per_cu * cus, &why, nxs_reg::KIND_RESIDENT)) return refuse(why.c_str());
-        if (h->pair_claim) { h->pair_claim = false; h->pair_ready = false; }   // (a handle holds ONE claim: the pair patches' went with it and are cut -- and claimed -- again if they are wanted)
-    }
-    int rc;
-    DevResident &r = h->res;
-    if (ovl) {
-        if (getenv("NXS_DEBUG_PATCHES")) fprintf(stderr, "[nxs] rank %d resident kernel: %.1f %% of the patch elements computed under the exchange\n", h->rank, 100. * plan.early_fraction);
-        if ((rc = dev_upload(h, h->res_allocs, &r.pelem, plan.rpelem))) return rc;
-        if ((rc = dev_upload(h, h->res_allocs, &r.ptri, plan.rptri))) return rc;
-        if ((rc = dev_upload(h, h->res_allocs, &r.pfan, plan.rpfan))) return rc;
-        if ((rc = dev_upload(h, h->res_allocs, &r.ecut, plan.ecut))) return rc;
-    }
-    if ((rc = dev_upload(h, h->res_allocs, &r.pnbr, plan.nbr))) return rc;
-    if ((rc = dev_upload(h, h->res_allocs, &r.pnbr_cnt, plan.cnt))) return rc;
-    r.rank = h->rank;
-    if (mr) {  // the ghosts' ring: what arrived after every sub-step but the last (sized for THIS number of sub-steps: a change of parameters rebuilds the tables)
-        r.NG = Nn - No;
-        if ((rc = dev_alloc(h, h->res_allocs, &r.gring, std::max<size_t>((size_t)std::max(S - 1, 1) * 2 * (size_t)r.NG, 1)))) return rc;
-    }
-    h->res_substeps = S;
-    if ((rc = dev_alloc(h, h->res_allocs, &r.flag, 32 * (size_t)nP + NXS_RES_MAXS + 32))) return rc;  // counters behind the flags: one memset per launch
-    r.cnt = r.flag + 32 * (size_t)nP;
-    r.raised = r.cnt + NXS_RES_MAXS;
-    if ((rc = dev_alloc(h, h->res_allocs, &r.error, 1))) return rc;
-    HIPCHK(h, hipMemsetAsync(r.error, 0, sizeof(int), h->stream));
-    if ((rc = dev_alloc(h, h->res_allocs, &h->d_vt3, 2 * (size_t)Nn))) return rc;
-    r.X0 = h->ds.VT2; r.X1 = h->d_vt3;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (getenv("NXS_DEBUG_PATCHES")) fprintf(stderr, "[nxs] rank %d resident kernel: %d patches (%d x %d fit), %zu B of LDS each, up to %d neighbour patches, %d ghost nodes\n", h->rank, nP, per_cu, cus, h->res_lds, plan.max_nbr, mr ? Nn - No : 0);
-    h->res_ready = true;
-    return NXS_OK;
-}
-
-void launch_substep(nxs_dyn_handle *h, double move_dt) {
-    if (h->dp.dynamics_type == NXS_DYN_BBM) {
-        if (h->trace_branches) {
-            if (h->dp.ers_int == 4) LAUNCH(h, (k_sigma_bbm<true, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
-            else LAUNCH(h, (k_sigma_bbm<false, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
-        }
-        else if (h->dp.ers_int == 4) LAUNCH(h, k_sigma_bbm<true>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
-        else LAUNCH(h, k_sigma_bbm<false>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
-    }
-    else
-        LAUNCH(h, k_sigma_vp, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
-    LAUNCH(h, k_solve_move, h->dm.No, h->dm, h->ds, h->dw, h->dp, move_dt);
-}
-
-// sub-steps per launch of this step (1 = the v2 / v1 kernels); builds the D-ring patches when they are needed
-int choose_depth(nxs_dyn_handle *h) {
-    const int S = h->dp.substeps;
-    const double move_dt = (h->dp.dynamics_type == NXS_DYN_MEVP) ? 0. : h->dp.dte;
-    int D = 1;
-    // Automatic (fused == 3): only where ONE round of one patch per CU covers the mesh (<= 256 own nodes per patch: 65 k nodes, 130 k
-    // triangles on 256 CUs) -- 111 k triangles: 1.47 (v2) -> 0.97 ms/step; 182 k triangles, two patches per CU: 1.65 -> 1.90-2.31.
-    // ... and on meshes that STREAM from HBM (fused == 3, >= 400 k triangles, an even number of sub-steps) two sub-steps per launch with the
-    // stresses between them in registers and two workgroups per CU (k_substep_pair): 2 km 6.3 -> 5.7 ms of sub-steps.
-    const bool single = !multi_rank(h) && move_dt != 0. && S >= 2 && !h->pair_failed;
-    // several ranks: two sub-steps per launch with BOTH exchanges inside it (k_substep_pair<HALO>: device-direct mailboxes, the exchange inside the kernels) --
-    // automatically where the partition streams from HBM (more than 65 k nodes: a rank of two of the 2 km mesh; smaller partitions run the resident loop where
-    // they have a device to themselves), with option pair_regs = 1 at any size
-    const bool mr_pair = multi_rank(h) && h->have_halo && h->ipc_ready && !h->halo_fn && h->halo_fused && eff_fused(h) == 3 && move_dt != 0. && S >= 2 && S % 2 == 0 &&
-                         !h->pair_failed && (h->pair_regs == 1 || (h->pair_regs < 0 && (long long)h->dm.Nn > 256ll * 256)) && (h->pair_depth == 0 || h->pair_depth == 2);
-    if (mr_pair) {
-        if (!h->hf_ready && build_halo_fused(h) != NXS_OK) { h->pair_failed = true; h->depth_now = 1; return 1; }
-        if ((!h->pair_ready || h->pair_depth_built != 2 || !h->pair_kernel) && upload_pair_patches_mr(h) != NXS_OK) h->pair_failed = true;
-        h->depth_now = (h->pair_ready && !h->pair_failed) ? 2 : 1;
-        return h->depth_now;
-    }
-    // (automatic: every mesh too large for one k_substep_multi patch per CU, i.e. above 65 k nodes)
-    const bool streaming_pair = single && eff_fused(h) == 3 && h->pair_regs != 0 && (long long)h->dm.Nn > 256ll * 256 && S % 2 == 0 && (h->pair_depth == 0 || h->pair_depth == 2);
-    if (streaming_pair) {
-        D = 2;
-        if ((!h->pair_ready || h->pair_depth_built != 2 || !h->pair_kernel) && upload_patches2(h, 2, false, true) != NXS_OK) {
-            h->pair_failed = true;  // (a numbering without any locality, huge fans): one sub-step per launch
-            D = 1;
-        }
-    } else if ((eff_fused(h) == 2 || (eff_fused(h) == 3 && (long long)h->dm.Nn <= 256ll * 256)) && single) {
-        D = std::min(h->pair_depth > 0 ? h->pair_depth : 4, std::min(S, NXS_MAX_DEPTH));
-        while (D > 1 && S % D != 0) --D;
-        const bool want_pair = D == 2 && h->pair_regs == 1;   // (forced depth 2 with option pair_regs = 1: k_substep_pair at any size)
-        if (D >= 2 && (!h->pair_ready || h->pair_depth_built != D || h->pair_kernel != want_pair) && upload_patches2(h, D, eff_fused(h) == 3, want_pair) != NXS_OK) {
-            h->pair_failed = true;  // no patch size fits (a numbering without any locality, huge fans): one sub-step per launch
-            D = 1;
-        }
-    }
-    h->depth_now = D;
-    return D;
-}
-
-int run_substeps(nxs_dyn_handle *h) {
-    const int S = h->dp.substeps;
-    const double move_dt = (h->dp.dynamics_type == NXS_DYN_MEVP) ? 0. : h->dp.dte;
-    const bool fused = eff_fused(h) != 0;
-    const int bbm = h->dp.dynamics_type == NXS_DYN_BBM;
-    const bool mr = multi_rank(h);
-    // deferred mesh move (fused path, not mEVP whose single move comes after the loop)
-    const bool device_halo = mr && h->ipc_ready && !h->halo_fn;  // no host work inside the loop: graph-capturable
-    // auto ring: one flush per step (up to 120 sub-steps) on meshes that stream from HBM -- the flush reads every slot once
-    // whatever its period, so a longer ring only saves UM/UT passes (2 km: 7.60 -> 7.49 ms/step from 16 to 120, 1.4 GB of
-    // slots); also whenever the halo exchange runs inside the sub-step kernel
-    const int want_ring = h->um_ring > 0 ? h->um_ring : ((h->dm.Ne >= 400000 || (device_halo && h->halo_fused)) ? 120 : 1);
-    // v3: D sub-steps per launch -- single rank, the deferred mesh move (ring of >= D+1 buffers).  It trades redundant arithmetic
-    // on the halo rings for less HBM traffic and fewer launches: a gain where the sub-step is latency-bound (10 km: 1.23 -> 0.97
-    // ms/step), a loss as soon as a CU hosts more than one patch (182 k triangles: 1.65 -> 1.90) and where the v2 kernel already
-    // runs at 5.5 TB/s with its VALUs half busy (2 km, D = 2: 7.4 -> 8.0).
-    // D sub-steps per launch: the requested depth, else (auto) 4 (10 km: D = 2 / 3 / 4 / 5 / 6 / 8: 1.11 / 1.01 / 0.97 / 0.96 / 0.98 / 1.08 ms/step; the
-    // rings grow the arithmetic by x2.0 per sub-step at D = 4) -- lowered until it divides the number of sub-steps
-    const int D = h->depth_now;  // decided by choose_depth() before the prep kernels (they fill the records the multi kernel reads)
-    const bool pair = D >= 2;
-    int K = (fused && move_dt != 0.) ? std::max(1, std::min(want_ring, S)) : 1;
-    // k_substep_pair on a single rank can apply the mesh move of its two sub-steps itself (M_UM / M_UT in and out once per launch): no ring beyond the three
-    // buffers a launch reads and writes, no k_move_ring
-    const bool move_in_pair = pair && !mr && D == 2 && h->pair_kernel && h->pair_threads == 512 && move_dt != 0. && !h->trace_branches && h->um_ring <= 0 &&
-                              (h->pair_move == 1 || (h->pair_move < 0 && pair_move_default(h))) && !flow_wanted(h);
-    h->move_now = move_in_pair;
-    if (pair) {  // the ring is flushed between launches; by default once per step (a flush per launch costs 30 small launches at 10 km: 66 us of 0.88 ms)
-        if (h->um_ring <= 0) K = std::min(S, NXS_MAX_RING - 1);
-        K = std::max(D, K - K % D);
-        if (move_in_pair) K = D;
-    }
-    const bool deferred = K > 1;
-    if (fused) { int rc = setup_ring(h, K); if (rc) return rc; }
-    const int R = h->ring.R;
-    // the exchange inside the sub-step kernel: needs the deferred mesh move (ghost nodes are moved from the ring)
-    // or no move at all (mEVP)
-    const bool halo_in_kernel = device_halo && fused && h->halo_fused && (deferred || move_dt == 0.);
-    if (halo_in_kernel && !h->hf_ready) { int rc = build_halo_fused(h); if (rc) return rc; }
-    // v4: resident sub-step loop (opt-in).  Several ranks: only with the exchange inside the kernels (device-direct mailboxes).
-    const bool res_wanted = h->fused == 4 && !h->trace_branches && !pair && move_dt != 0. && (!mr || (device_halo && h->halo_fused));
-    if (res_wanted && mr && !h->hf_ready) { int rc = build_halo_fused(h); if (rc) return rc; }  // (re-uploads the patches boundary-first)
-    if (h->res_ready && (h->res_substeps != S || h->res_pow4 != (h->dp.ers_int == 4))) {  // parameters changed since the tables were built:
-        h->res_ready = false;                                                           // another kernel build (its residency unchecked), a ring of another length
-        release_graph(h);
-    }
-    if (res_wanted && !h->res_ready && !h->res_failed) {  // (outside any capture)
-        int rcr = build_resident(h);
-        if (rcr) return rcr;
-        if (h->res_failed && h->cut_big && !h->no_big_cut) {
-            // the mesh was cut into one large patch per CU for k_substep_resident_big and that launch is not possible after all (the device's
-            // workgroup slots are taken, ...): the one-launch-per-sub-step kernel wants its own cut (two smaller workgroups per CU, whole rounds)
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            release_graph(h);
-            h->no_big_cut = true;
-            int rcu = upload_patches(h);
-            if (rcu) return rcu;
-            if (mr && !h->hf_ready) { int rc = build_halo_fused(h); if (rc) return rc; }
-            h->res_failed = true;   // (after the rebuilds, which reset it: this cut exists because the resident loop cannot run)
-        }
-    }
-    const bool resident = res_wanted && h->res_ready && !h->res_failed;
-    const bool pair_halo = pair && mr;   // (choose_depth built the tables: device-direct mailboxes, the exchange inside the kernels)
-    // ... single rank: all the pairs of a step in one data-flow launch (needs the whole step in the ring: one flush, behind the launch)
-    const bool flow = pair && !mr && D == 2 && h->pair_kernel && h->flow_ready && !h->flow_failed && flow_wanted(h) && !h->trace_branches && deferred && K == S && S % 2 == 0;
-    if ((halo_in_kernel || (resident && mr) || pair_halo) && h->d_hf_dirty) {  // (outside any stream capture)
-        HaloFused tmp = h->hf;
-        tmp.ipc = h->ipc;
-        HIPCHK(h, hipMemcpyAsync(h->d_hf, &tmp, sizeof tmp, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));  // tmp leaves scope
-        h->d_hf_dirty = false;
-    }
-    const bool records_end_odd = resident ? false : (pair ? ((S / D) & 1) : (S & 1));
-    // with the deferred mesh move the last flush of the step reads the newest velocity anyway and puts it back into M_VT itself; the
-    // ring slot it came from then equals M_VT and serves the smoother as its second buffer (no copy before the sweeps)
-    double *const vt_back = (deferred && !resident && !move_in_pair && (S % R) != 0) ? h->ds.VT : nullptr;
-    h->smooth_second = vt_back ? h->ring.slot[S % R] : nullptr;
-    if (move_in_pair)   // the final velocity: in a ring slot that k_pingpong_copy_back copies into M_VT, or in M_VT itself with a second copy in the last launch's free slot
-        h->smooth_second = (S % R) ? h->ring.slot[S % R] : h->ring.slot[(S - D + 1) % R];
-    auto pull_latest = [&](double *vec) {
-        const int tr = h->recv_offsets[h->recv_procs.size()];
-        hipLaunchKernelGGL(k_halo_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, vec, h->dm, h->ds, tr, h->d_recv_index,
-                           h->d_recv_seg, h->d_recv_off, h->ipc, 0., 0, h->d_recv_procs, 1);
-    };
-    // the LAST flush of the step is launched behind the graph (one plain launch per step) so that its own events can bracket it
-    const int final_count = (deferred && !resident && !move_in_pair) ? S - K * ((S - 1) / K) : 0;
-    auto flush = [&](int s, int pending) {
-        if (move_in_pair) return;                    // (the launches have moved the mesh)
-        if (s == S - 1 && final_count > 0) return;   // (launched below)
-        LAUNCH(h, k_move_ring, h->dm.Nn, h->dm, h->ds, h->ring, (s + 1 - (pending - 1)) % R, pending, move_dt, (double *)nullptr);
-    };
-    auto final_flush = [&]() -> int {
-        if (final_count <= 0) return NXS_OK;
-        const int k = h->cur ? (int)((h->cur - &h->ev[0][0]) / 5) : -1;
-        if (k >= 0) HIPCHK(h, hipEventRecord(h->ev_flush[k][0], h->stream));
-        LAUNCH(h, k_move_ring, h->dm.Nn, h->dm, h->ds, h->ring, (S - final_count + 1) % R, final_count, move_dt, vt_back);
-        if (k >= 0) { HIPCHK(h, hipEventRecord(h->ev_flush[k][1], h->stream)); h->flush_timed[k] = true; }
-        return NXS_OK;
-    };
-    auto loop = [&]() -> int {
-        if (resident) {  // the whole loop in one launch; the element state is read from and written back to S4a (each record by its one writer)
-            HIPCHK(h, hipMemsetAsync(h->res.flag, 0, (32 * (size_t)h->dpch.nP + NXS_RES_MAXS + 32) * sizeof(unsigned int), h->stream));
-            {
-                const DevParams *pdev = h->d_dp;
-                const double *Sc = h->ds.S4a;
-                double *Sn = h->ds.S4a;
-                double mdt = move_dt;
-                const HaloFused *hfp = mr ? h->d_hf : nullptr;
-                int nb = mr ? h->hf.n_boundary : 0;
-                void *args[] = {&h->dm, &h->dpch, &h->ds, &h->dw, &pdev, &h->res, &Sc, &Sn, &mdt, &hfp, &nb};
-                HIPCHK(h, hipLaunchKernel(resident_kernel(h, mr, h->res_ovl), dim3(h->dpch.nP), dim3(512), args, h->res_lds, h->stream));
-            }
-            if (mr) {
-                // the ghosts' mesh moves of all sub-steps but the last, from the ring the launch filled ...
-                if (move_dt != 0. && h->res.NG > 0 && S > 1)
-                    hipLaunchKernelGGL(k_ghost_ring_move, dim3(nblocks(h->res.NG)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->res.gring, h->res.NG, S - 1, move_dt, (const int *)h->res.error);
-                // ... and the exchange of the last sub-step: the ghosts land in M_VT and make their last move
-                const int tr = h->recv_offsets[h->recv_procs.size()];
-                hipLaunchKernelGGL(k_halo_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, h->ds.VT, h->dm, h->ds, tr, h->d_recv_index,
-                                   h->d_recv_seg, h->d_recv_off, h->ipc, move_dt, 0, h->d_recv_procs, 1);
-            }
-            return NXS_OK;
-        }
-        if (flow) {   // every pair of sub-steps of the step in ONE data-flow launch over the patches of k_substep_pair; the ring is flushed behind it (final_flush)
-            HIPCHK(h, hipMemsetAsync(h->flow.queue, 0, h->flow_words * sizeof(unsigned int), h->stream));
-            PairFlow f = h->flow;
-            f.K = S / 2;
-            f.S[0] = h->ds.S4a; f.S[1] = h->ds.S4b;
-            const DevParams *pdev = h->d_dp;   // (explicit_solve keeps the device copy current)
-            void *args[] = {&h->dm, &h->dpch2, &h->ds, &h->dw, &pdev, &h->ring, &f};
-            HIPCHK(h, hipLaunchKernel(flow_kernel(h), dim3(h->flow_grid), dim3(512), args, h->pair_lds, h->stream));
-            if (records_end_odd) LAUNCH(h, k_unpack_state, h->dm.Ne, h->dm, h->ds, bbm, (const double *)h->ds.S4b);
-            return NXS_OK;
-        }
-        int pending = 0;  // sub-steps whose velocity still has to be applied to UM/UT
-        for (int s = 0; s < S; ++s) {
-            if (pair) {
-                launch_multi(h, s, D, pair_halo);
-                s += D - 1;
-                pending += D;
-                if (pending == K || s == S - 1) {
-                    if (pair_halo) pull_latest(h->ring.slot[(s + 1) % R]);  // the newest ghosts, for the move / the end of the step
-                    flush(s, pending);
-                    pending = 0;
-                }
-                continue;
-            }
-            if (halo_in_kernel) {
-                launch_fused(h, s, 0., 1, s > 0);
-                const bool flush_now = deferred && (pending + 1 == K || s == S - 1);
-                if (flush_now || s == S - 1) pull_latest(h->ring.slot[(s + 1) % R]);  // the newest ghosts, for the move / the end of the step
-                if (flush_now) {
-                    ++pending;
-                    flush(s, pending);
-                    pending = 0;
-                } else if (deferred) ++pending;
-                continue;
-            }
-            if (fused) launch_fused(h, s, deferred ? 0. : move_dt); else launch_substep(h, move_dt);
-            if (mr) {
-                // owned nodes were written to the buffer the next sub-step reads; ghosts must land there too
-                double *vec = fused ? h->ring.slot[(s + 1) % R] : h->ds.VT;
-                int rc = halo_exchange(h, vec, deferred ? 0. : move_dt);
-                if (rc) return rc;
-            }
-            if (deferred && (++pending == K || s == S - 1)) {
-                flush(s, pending);
-                pending = 0;
-            }
-        }
-        if (fused) {  // bring the result back to the primary buffers
-            const double *vt_src = (S % R) ? h->ring.slot[S % R] : nullptr;
-            if (vt_src && !vt_back) LAUNCH(h, k_pingpong_copy_back, 2 * h->dm.Nn, h->dm, h->ds, vt_src);  // (else the last ring flush has done it)
-            // the element state stays in its records when the loop ends in the first buffer (an even number of launches): update()
-            // works on them and the arrays follow when somebody asks (ensure_arrays); from the second buffer it is unpacked here
-            if (records_end_odd) LAUNCH(h, k_unpack_state, h->dm.Ne, h->dm, h->ds, bbm, (const double *)h->ds.S4b);
-        }
-        return NXS_OK;
-    };
-    // (outside the graph: whether the records are current depends on what the caller did since the last step)
-    if (fused && h->sig_loc == 0) LAUNCH(h, k_pack_state, h->dm.Ne, h->dm, h->ds, bbm, h->ds.S4a);
-    if (!fused) ensure_arrays(h);
-    if (fused) h->sig_loc = records_end_odd ? 0 : 1;
-    h->timing.substep_launches = (resident || flow) ? 1 : pair ? S / D : halo_in_kernel ? S + (S + K - 1) / K : S * ((fused ? 1 : 2) + (mr ? 2 : 0));
-    h->last_kernel = resident ? (h->res_big ? NXS_KERNEL_RESIDENT_BIG : NXS_KERNEL_RESIDENT) : flow ? NXS_KERNEL_PAIR_FLOW : pair ? (h->pair_kernel ? NXS_KERNEL_PAIR : NXS_KERNEL_MULTI) : fused ? NXS_KERNEL_FUSED : NXS_KERNEL_PER_LOOP;
-    h->last_deferred = deferred; h->last_halo_in_kernel = halo_in_kernel || (resident && mr) || pair_halo;
-    h->last_ring_count = (deferred && !resident && !move_in_pair) ? K : 0;
-    h->last_move_in_pair = move_in_pair;
-    if (!h->use_graph || (mr && !device_halo)) { int lrc = loop(); return lrc ? lrc : final_flush(); }
-    if (!h->graph_valid) {
-        release_graph(h);
-        hipGraph_t g = nullptr;
-        HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-        int lrc = loop();
-        if (lrc) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(h->stream, &dead); if (dead) (void)hipGraphDestroy(dead); return lrc; }
-        HIPCHK(h, hipStreamEndCapture(h->stream, &g));
-        hipError_t e = hipGraphInstantiate(&h->substep_graph, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) return fail(h, NXS_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-        h->graph_valid = true;
-    }
-    HIPCHK(h, hipGraphLaunch(h->substep_graph, h->stream));
-    return final_flush();
-}
-
-int ready(nxs_dyn_handle *h) {
-    if (!h) return NXS_ERR_INVALID;
-    if (!h->have_mesh || !h->have_state || !h->have_forcing)
-        return fail(h, NXS_ERR_STATE, "step needs set_mesh, put_state and set_forcing first");
-    if (multi_rank(h) && !h->have_halo) return fail(h, NXS_ERR_STATE, "nranks>1 needs set_halo");
-    hipError_t e = hipSetDevice(h->device);
-    if (e != hipSuccess) return fail(h, NXS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-    return NXS_OK;
-}
-
-int explicit_solve(nxs_dyn_handle *h) {
-    const bool timed = h->cur != nullptr;
-    // FE.cpp:10182-10643
-    const DevMesh &m = h->dm;
-    if (timed) HIPCHK(h, hipEventRecord(h->cur[0], h->stream));
-    {
-        // (the per-step shape-coefficient records are read by k_substep_multi only: k_substep_pair rebuilds the coefficients from the staged coordinates)
-        double *want = (choose_depth(h) >= 2 && !h->pair_kernel && h->shape_mem != 0) ? h->d_srec : nullptr;
-        if (want != h->dw.srec) { h->dw.srec = want; release_graph(h); }  // (kernel arguments are baked into the graphs)
-    }
-    if (h->dp_dirty) {  // (outside any stream capture)
-        if (!h->d_dp) HIPCHK(h, hipMalloc((void **)&h->d_dp, sizeof(DevParams)));
-        HIPCHK(h, hipMemcpyAsync(h->d_dp, &h->dp, sizeof(DevParams), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));  // h->dp may change right after
-        h->dp_dirty = false;
-    }
-    // the fused kernels read records only: the per-quantity work vectors (v1 kernels, debug door) are filled on request
-    // (automatic: meshes that stream from HBM; on cache-resident ones the two small kernels are as fast: 10 km 24.7 vs 27.4 us)
-    // (automatic: from 250 k triangles on a single rank; on a rank of several from 500 k -- measured on rank 0's partitions of the 2 km mesh, looped back: 730 k
-    // 0.108 -> 0.086 ms, 366 k in the resident loop's large patches 0.046 -> 0.053, 184 k 0.033 -> 0.043: gpurun_out/r5_prepmr_ab.log)
-    if (eff_fused(h) != 0 && !h->work_arrays && (h->prep_fused == 1 || (h->prep_fused < 0 && m.Ne >= (multi_rank(h) ? 500000 : 250000))) && h->prep_lds > 0 && h->dpch.prow && h->dpch.nP > 0) {
-        // one launch over the sub-step kernel's patches: the elements' values reach their nodes through LDS (k_prep_fused)
-        // (the open-water flags of the node blocks are lowered by the step before -- k_update's first threads, as the range flag -- and at allocation: no memset per step;
-        // a step that ended without update() leaves them raised, which only costs the smoother some blocks it could have skipped)
-        hipLaunchKernelGGL(k_prep_fused, dim3(h->dpch.nP), dim3(512), h->prep_lds, h->stream, m, h->dpch, h->ds, h->dw, h->dp);
-        if (m.Nn > m.No) LAUNCH(h, k_prep_ghost_nodes, m.Nn - m.No, m, h->ds, h->dw, h->dp);   // several ranks: the ghost nodes' share of the nodal loops
-        HIPCHK(h, hipGetLastError());
-        h->last_prep = NXS_PREP_FUSED;
-    } else if (eff_fused(h) != 0 && !h->work_arrays) {
-        LAUNCH(h, k_prep_elements<true>, m.Ne, m, h->ds, h->dw, h->dp);
-        LAUNCH(h, k_prep_nodes<true>, m.Nn, m, h->ds, h->dw, h->dp);
-        h->last_prep = NXS_PREP_LEAN;
-    } else {
-        h->last_prep = NXS_PREP_FULL;
-        LAUNCH(h, k_prep_elements<false>, m.Ne, m, h->ds, h->dw, h->dp);
-        LAUNCH(h, k_prep_nodes<false>, m.Nn, m, h->ds, h->dw, h->dp);
-    }
-    if (timed) HIPCHK(h, hipEventRecord(h->cur[1], h->stream));
-    int rc = run_substeps(h);
-    if (rc) return rc;
-    if (!multi_rank(h) && !h->sm_ready && !h->sm_failed && eff_fused(h) != 0) {
-        // automatic: ten sweeps per launch (five launches; 10 km: smoother 43 -> 25 us per step) where ten rings fit the LDS, else five
-        if (h->sm_depth > 0) { if (build_smooth_patches(h, h->sm_depth) != NXS_OK) h->sm_failed = true; }  // the smoother then runs sweep by sweep
-        else if (build_smooth_patches(h, 10) != NXS_OK && build_smooth_patches(h, 5) != NXS_OK) h->sm_failed = true;
-        h->tail_graph_valid = false;
-    }
-    if (h->dp.dynamics_type == NXS_DYN_MEVP)  // FE.cpp:10559-10573
-        LAUNCH(h, k_move, m.Nn, m, h->ds, 0, m.Nn, h->dp.dtime_step);
-    if (timed) HIPCHK(h, hipEventRecord(h->cur[2], h->stream));
-    // Q9: 50 sweeps, hard-coded (FE.cpp:10580); + open-water mesh move.  52+ small launches: replayed from
-    // a second hipGraph whenever no host work is needed inside (single rank, or device-direct halo).
-    auto smooth_and_tail = [&]() -> int {
-        double *a = h->ds.VT, *b = h->smooth_second ? h->smooth_second : h->ds.VT2;
-        if (!h->smooth_second) LAUNCH(h, k_copy_vt, 2 * m.Nn, 2 * m.Nn, a, b);  // both buffers equal: a sweep writes the ice-free nodes only
-        // single rank: D sweeps per launch on patches with D rings of nodes (k_smooth_multi) -- those of k_substep_multi where that
-        // kernel runs, else node-ring patches built for the smoother alone
-        const bool v3_patches = h->pair_ready && !h->pair_failed && h->dpch2.pnbr && eff_fused(h) >= 2 && h->depth_now >= 2 && !h->sm_ready;  // (only where the smoother's own patches could not be built)
-        if (!multi_rank(h) && (v3_patches || h->sm_ready)) {
-            const DevPatches2 &pp = v3_patches ? h->dpch2 : h->dsm;
-            const size_t lds = v3_patches ? h->smooth_lds : h->sm_lds;
-            const int D = pp.D, L = (50 + D - 1) / D;
-            if (L & 1) std::swap(a, b);  // the buffers are equal now; end in ds.VT after L swaps
-            for (int nit = 0; nit < 50; nit += D) {
-                const int ks = std::min(D, 50 - nit);
-                if (pp.NSmax > 256) hipLaunchKernelGGL((k_smooth_multi<512>), dim3(pp.nP), dim3(512), lds, h->stream, m, pp, h->dw, (const double *)a, b, ks);
-                else hipLaunchKernelGGL((k_smooth_multi<256>), dim3(pp.nP), dim3(256), lds, h->stream, m, pp, h->dw, (const double *)a, b, ks);
-                std::swap(a, b);
-            }
-            LAUNCH(h, k_ow_tail, m.Nn, m, h->ds, h->dw, h->dp);
-            return NXS_OK;
-        }
-        const bool halo_in_kernel = multi_rank(h) && h->ipc_ready && !h->halo_fn && h->halo_fused && h->hf_ready && m.No > 0;
-        if (halo_in_kernel) {  // which of my directions carry values the sweeps cannot change (they are sent once)
-            const int ts = h->send_offsets[h->send_procs.size()];
-            if (ts > 0) LAUNCH(h, k_smooth_static, ts, ts, h->d_send_index, h->d_send_seg, m, h->dw, h->ipc.my_static);
-        }
-        static_assert(NXS_SMOOTH_SWEEPS == 50, "Q9: FE.cpp:10580 hard-codes 50 sweeps");
-        if (halo_in_kernel && h->smooth_persist != 0) {   // all 50 sweeps in ONE launch of persistent workgroups (k_smooth_persist); the result is back in `a` (50 is even)
-            HaloFused hf = h->hf;
-            hf.ipc = h->ipc;
-            const int nblk = nblocks(m.No), G = std::min(nblk, 128);
-            hipLaunchKernelGGL(k_smooth_persist, dim3(G), dim3(BLOCK), 0, h->stream, m, h->dw, a, b, hf, nblk);
-            const int tr = h->recv_offsets[h->recv_procs.size()];
-            hipLaunchKernelGGL(k_smooth_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, a, m.Nn, tr, h->d_recv_index, h->d_recv_seg, h->d_recv_off, h->ipc);
-            LAUNCH(h, k_ow_tail, m.Nn, m, h->ds, h->dw, h->dp);
-            return NXS_OK;
-        }
-        for (int nit = 0; nit < 50; ++nit) {
-            if (halo_in_kernel) {  // updateGhosts inside the sweep; the ghosts land in the array once, after the last sweep
-                HaloFused hf = h->hf;
-                hf.ipc = h->ipc;
-                LAUNCH(h, k_smooth_halo, m.No, m, h->dw, (const double *)a, b, hf, nit);
-                if (nit == 49) {
-                    const int tr = h->recv_offsets[h->recv_procs.size()];
-                    hipLaunchKernelGGL(k_smooth_pull, dim3(nblocks(tr)), dim3(BLOCK), 0, h->stream, b, m.Nn, tr, h->d_recv_index,
-                                       h->d_recv_seg, h->d_recv_off, h->ipc);
-                }
-            } else {
-                LAUNCH(h, k_smooth, m.No, m, h->dw, a, b);
-                if (multi_rank(h)) { int r2 = halo_exchange(h, b, 0.); if (r2) return r2; }
-            }
-            std::swap(a, b);
-        }
-        // 50 is even: the result is back in ds.VT
-        LAUNCH(h, k_ow_tail, m.Nn, m, h->ds, h->dw, h->dp);
-        return NXS_OK;
-    };
-    const bool tail_capturable = h->use_graph && (!multi_rank(h) || (h->ipc_ready && !h->halo_fn));
-    if (!tail_capturable) {
-        rc = smooth_and_tail();
-        if (rc) return rc;
-    } else {
-        if (!h->tail_graph_valid) {
-            if (h->tail_graph) { (void)hipGraphExecDestroy(h->tail_graph); h->tail_graph = nullptr; }
-            hipGraph_t g = nullptr;
-            HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-            rc = smooth_and_tail();
-            if (rc) { hipGraph_t dead = nullptr; (void)hipStreamEndCapture(h->stream, &dead); if (dead) (void)hipGraphDestroy(dead); return rc; }
-            HIPCHK(h, hipStreamEndCapture(h->stream, &g));
-            hipError_t e = hipGraphInstantiate(&h->tail_graph, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (e != hipSuccess) return fail(h, NXS_ERR_HIP, "hipGraphInstantiate(tail): %s", hipGetErrorString(e));
-            h->tail_graph_valid = true;
-        }
-        HIPCHK(h, hipGraphLaunch(h->tail_graph, h->stream));
-    }
-    if (timed) HIPCHK(h, hipEventRecord(h->cur[3], h->stream));
-    // a refused launch (a launch configuration the device rejects, e.g. more dynamic LDS than a CU has) is reported here,
-    // at the step that issued it, not as a generic error at the next synchronize
-    HIPCHK(h, hipGetLastError());
-    return NXS_OK;
-}
-
-}  // namespace
-
 int nxs_dyn_explicit_solve(nxs_dyn_handle *h) try {
     int rc = ready(h);
     if (rc) return rc;
@@ -2569,6 +2639,7 @@ int nxs_dyn_get_timing(nxs_dyn_handle *h, nxs_dyn_timing *t) try {
     h->timing.total_ms = (h->sum_ms[0] + h->sum_ms[1] + h->sum_ms[2] + h->sum_ms[3]) / n;
     h->timing.ring_flush_ms = h->sum_flush_ms / n;
     h->timing.steps_averaged = h->sum_steps;
+    h->timing.substep_launches = h->plan.launches;
     *t = h->timing;
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_get_timing"); }
@@ -2591,13 +2662,13 @@ int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t) try {
     std::memset(t, 0, sizeof *t);
     const double Ne = h->dm.Ne, Nn = h->dm.Nn, S = h->dp.substeps;
     const bool young = h->dp.young_cat != 0, bbm = h->dp.dynamics_type == NXS_DYN_BBM;
-    t->substep_kernel = h->last_kernel;
-    t->halo_in_kernel = h->last_halo_in_kernel ? 1 : 0;
-    t->prep_kernel = h->last_prep;
+    t->substep_kernel = h->plan.kernel;
+    t->halo_in_kernel = h->plan.halo_in_kernel ? 1 : 0;
+    t->prep_kernel = h->plan.prep;
     const double node_in = 1. /*nflags*/ + 80. /*nrec*/;
     const auto &s1 = h->sums1;
     const auto &s2 = h->sums2;
-    switch (h->last_kernel) {
+    switch (h->plan.kernel) {
     case NXS_KERNEL_PAIR: case NXS_KERNEL_PAIR_FLOW: if (s2.N.size() == 3 && s2.E.size() == 2) {
         const double fanw = 16.;   // (four words of ready-made LDS indices per solved node: DevPatches2::pfan8)
         const double N0 = s2.N[0], N1 = s2.N[1], N2 = s2.N[2], E2 = s2.E[1];
@@ -2605,13 +2676,13 @@ int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t) try {
         t->substep_scheme_bytes = s2.nP * 20. /*ncnt, ecnt*/ + N2 * (4. /*pnodes*/ + 16. /*VT*/ + 16. /*xy*/) + E2 * (8. /*pet*/ + 32. /*S in*/ + 48. /*erec*/)
                                   + N1 * (node_in + fanw) + s2.W * 32. /*S out*/ + N0 * 2. * 16. /*two velocity slots*/;
         t->substep_reread_bytes = s2.E1_second_round * 48. /*the constants of sub-step 1's second round, read again 3-6 us after the first time (the first round's stay in registers)*/
-                                  + ((h->last_halo_in_kernel || h->last_kernel == NXS_KERNEL_PAIR_FLOW) ? N0 * (node_in + fanw) : 0.) /*(the single-rank launch keeps the own nodes' inputs in registers between its two solves)*/;
+                                  + ((h->plan.halo_in_kernel || h->plan.kernel == NXS_KERNEL_PAIR_FLOW) ? N0 * (node_in + fanw) : 0.) /*(the single-rank launch keeps the own nodes' inputs in registers between its two solves)*/;
         t->substep_unique_bytes = Ne * (8. + 32. + 48. + 32.) + Nn * (4. + 16. + 16. + node_in + fanw + 32.);
-        if (h->last_move_in_pair) {   // M_UM, M_UT in and out, no first velocity slot
+        if (h->plan.move_in_pair) {   // M_UM, M_UT in and out, no first velocity slot
             t->substep_scheme_bytes += N0 * (64. - 16.);
             t->substep_unique_bytes += Nn * (64. - 16.);
         }
-        if (h->last_kernel == NXS_KERNEL_PAIR_FLOW) {   // ONE launch runs every pair of sub-steps of the step over the same tables
+        if (h->plan.kernel == NXS_KERNEL_PAIR_FLOW) {   // ONE launch runs every pair of sub-steps of the step over the same tables
             const double pairs = std::floor(S / 2.);
             t->substeps_per_launch = (int)S;
             t->substep_scheme_bytes *= pairs; t->substep_reread_bytes *= pairs; t->substep_unique_bytes *= pairs;
@@ -2627,7 +2698,7 @@ int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t) try {
         t->substep_unique_bytes = Ne * (12. + 32. + 48. + shape + 32.) + Nn * (4. + 16. + xy + node_in + fanw + D * 16.);
     } break;
     case NXS_KERNEL_FUSED: {
-        const double fanw = 2. * std::min(h->dpch.Wp, 8), move = h->last_deferred || h->dp.dynamics_type == NXS_DYN_MEVP ? 0. : 64. /*M_UM, M_UT read and written*/;
+        const double fanw = 2. * std::min(h->dpch.Wp, 8), move = h->plan.deferred || h->dp.dynamics_type == NXS_DYN_MEVP ? 0. : 64. /*M_UM, M_UT read and written*/;
         t->substeps_per_launch = 1;
         t->substep_scheme_bytes = s1.nP * 12. + s1.M * (4. + 16. + 16.) + s1.E * (8. /*pet*/ + 32. + 48.) + s1.O * (node_in + fanw + 16. /*VT out*/ + move) + s1.W * 32.;
         t->substep_unique_bytes = Ne * (8. + 32. + 48. + 32.) + Nn * (4. + 16. + 16.) + (double)h->dm.No * (node_in + fanw + 16. + move);
@@ -2636,7 +2707,7 @@ int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t) try {
         // once per step: indices, state in and out, element constants, nodal inputs, coordinates, M_UM / M_UT; per sub-step: the own nodes' velocity to the
         // exchange buffer and the halo nodes' velocity back (the big kernel also re-reads the element constants and nodal inputs every sub-step, from L2)
         const double fanw = 2. * std::min(h->dpch.Wp, 8);
-        const bool big = h->last_kernel == NXS_KERNEL_RESIDENT_BIG;
+        const bool big = h->plan.kernel == NXS_KERNEL_RESIDENT_BIG;
         t->substeps_per_launch = (int)S;
         t->substep_scheme_bytes = s1.M * (4. + 16. + 16.) + s1.E * (12. + 32. + 48.) + s1.O * (node_in + fanw + 64.) + s1.W * 32. + S * (s1.O * 16. + (s1.M - s1.O) * 16.);
         t->substep_reread_bytes = big ? (S - 1.) * (s1.E * 48. + s1.O * 80.) : 0.;
@@ -2649,20 +2720,20 @@ int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t) try {
     default: break;
     }
     t->survey_model_bytes = (172. * Ne + 217. * Nn) * std::max(t->substeps_per_launch, 1);
-    t->move_ring_slots = h->last_ring_count;
-    if (h->last_ring_count > 0) t->move_ring_bytes = Nn * (1. /*nflags*/ + 32. /*UM, UT in*/ + 32. /*out*/ + 16. * h->last_ring_count /*the slots*/ + 16. /*M_VT back, last flush*/);
+    t->move_ring_slots = h->plan.final_count > 0 ? h->plan.K : 0;   // (the slots of a k_move_ring launch)
+    if (t->move_ring_slots > 0) t->move_ring_bytes = Nn * (1. /*nflags*/ + 32. /*UM, UT in*/ + 32. /*out*/ + 16. * t->move_ring_slots /*the slots*/ + 16. /*M_VT back, last flush*/);
     {   // prep: per element 9 state fields (5 without the young category) + cohesion and healing time by the writer, out: delta_x, surface, 48-byte record;
         // per node x0, y0, UM, ssh in; VT, wind, ocean, lat, flags in; xy, tau_a, node_mass, VTM, 80-byte record out
         const double efields = (young ? 9. : 5.) * 8., ewrite = 16. + (bbm ? 16. : 8.) + 48. + (h->dw.srec ? 48. : 0.);
         const double nstage = 4. + 40., nin = 1. + 16. + 16. + 8. + 16., nout = 16. + 16. + 8. + 16. + 80.;
-        if (h->last_prep == NXS_PREP_FUSED) {
+        if (h->plan.prep == NXS_PREP_FUSED) {
             const double rows = 2. * (std::min(h->dpch.Wp, 8) + std::min(h->dpch.W1, 10));
             t->prep_scheme_bytes = s1.M * nstage + s1.E * (12. + efields) + s1.W * ewrite + s1.O * (rows + nin + nout);
             t->prep_unique_bytes = Nn * (nstage + rows + nin + nout) + Ne * (12. + efields + ewrite);
-        } else if (h->last_prep == NXS_PREP_LEAN || h->last_prep == NXS_PREP_FULL) {
+        } else if (h->plan.prep == NXS_PREP_LEAN || h->plan.prep == NXS_PREP_FULL) {
             // two kernels: the elements gather their corners' x0, y0, UM, ssh (40 B per node, once in the unique count, three times in the scheme) and leave a
             // 64-byte record + drag x area per element that every corner node gathers again
-            const double full = h->last_prep == NXS_PREP_FULL ? 104. + 48. : 0.;
+            const double full = h->plan.prep == NXS_PREP_FULL ? 104. + 48. : 0.;
             t->prep_scheme_bytes = Ne * (13. + 3. * 40. + efields + ewrite + 64. + 8. + full) + Nn * (4. * (h->dm.W + h->dm.W1) + nin + nout + 32.) + Ne * 3. * (64. + 8.);
             t->prep_unique_bytes = Ne * (13. + efields + ewrite + 64. + 8. + full + 64. + 8.) + Nn * (40. + 4. * (h->dm.W + h->dm.W1) + nin + nout + 32.);
         }

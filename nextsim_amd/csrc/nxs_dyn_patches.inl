@@ -22,11 +22,11 @@ int upload_patches2(nxs_dyn_handle *h, int D, bool single_round_only, bool for_p
     const DevMesh &m = h->dm;
     nxs_cut::Patch2Plan plan;
     const std::string why = nxs_cut::plan_patches2(mesh_view(h), (h->hp && h->hp->used_hilbert) || h->pair_hilbert == 1, h->pair_nodes, D, single_round_only, device_cus(h),
-                                                   h->h_n2n, h->h_n2n_cnt, m.W2, plan, for_pair_kernel, h->pair_hint, h->pair_T);
+                                                   h->h_n2n, h->h_n2n_cnt, m.W2, plan, for_pair_kernel, h->pair_hint, h->pair_threads_requested);
     if (!why.empty()) return fail(h, m.No != m.Nn ? NXS_ERR_STATE : NXS_ERR_INVALID, "%s", why.c_str());
     const HostPatches2 &hp = plan.hp;
     h->pair_lds = plan.lds;
-    h->pair_threads = plan.threads;
+    h->pair_threads_chosen = plan.threads;
     h->pair_kernel = plan.pair_kernel;
     if (plan.pair_kernel && h->pair_nodes == 0) h->pair_hint = plan.P_fit;
     h->pair_own_max = 0;
@@ -148,7 +148,7 @@ int upload_pair_patches_mr(nxs_dyn_handle *h) {
         h->pair_claim = plan.nG > 0;
     }
     if (h->pair_nodes == 0) h->pair_hint = plan.P;
-    h->pair_lds = plan.lds; h->pair_threads = 512; h->pair_kernel = true;
+    h->pair_lds = plan.lds; h->pair_threads_chosen = 512; h->pair_kernel = true;
     h->pair_own_max = 0;
     for (int q = 0; q < hp.nP; ++q) h->pair_own_max = std::max(h->pair_own_max, hp.ncnt[(size_t)q * 3]);
     {
