@@ -22,6 +22,8 @@
  *   checkRegridding()                           nxs_dyn_check_regridding(FE.cpp:8298-8309)
  *   checkFieldsFast()                           nxs_dyn_check_fields_fast (FE.cpp:14536-14655)
  *   M_surface, D_tau_a, D_tau_w, ...            nxs_dyn_get_diag
+ *   #ifdef OASIS: M_tau_wi in explicitSolve()   nxs_dyn_set_wave_stress (FE.cpp:10353-10354, 10408-10414, 10509-10518)
+ *   #ifdef OASIS: M_cum_damage, M_conc_fsd      nxs_dyn_put_coupled / nxs_dyn_get_coupled (FE.cpp:4233-4238, 3991-3994)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -163,6 +165,17 @@ typedef struct nxs_dyn_forcing {
     const double *ssh;           /* [Nn]   M_ssh */
     const double *element_depth; /* [Ne]   M_element_depth */
 } nxs_dyn_forcing;
+
+/* The element variables of the coupled build (#ifdef OASIS: a wave- or ocean-coupled neXtSIM) that the loops of this path touch:
+ *   M_cum_damage[cpt] += del_damage   inside the damage branch of every BBM sub-step (updateSigmaDamage, FE.cpp:4233-4238)
+ *   M_conc_fsd[k][cpt] *= surf_ratio  for every floe-size bin, where update() scales the other element variables (FE.cpp:3991-3994)
+ * The FSD redistribution / welding / lateral melt (FE.cpp:4268-4876) and the second M_cum_damage += of FE.cpp:4470 stay with the host. */
+typedef struct nxs_dyn_coupled {
+    double *cum_damage;      /* [Ne] M_cum_damage; NULL = not carried */
+    double *conc_fsd;        /* [num_fsd_bins][Ne], bin-major like M_conc_fsd[k][cpt]; NULL = none */
+    int32_t num_fsd_bins;    /* M_num_fsd_bins; 0 with conc_fsd == NULL */
+    int32_t reserved0;
+} nxs_dyn_coupled;
 
 /* Side outputs other parts of the model consume (moorings, coupler, exporter). NULL = skip. */
 typedef struct nxs_dyn_diag {
@@ -329,6 +342,26 @@ NXS_API int nxs_dyn_set_forcing(nxs_dyn_handle *h, const nxs_dyn_forcing *f);
  *   M_factor*(fcoeff[0]*d0[i] + fcoeff[1]*d1[i]) + M_bias_correction      -- the reference's expression, same bits. */
 NXS_API int nxs_dyn_set_forcing_pair(nxs_dyn_handle *h, const nxs_dyn_forcing *f0, const nxs_dyn_forcing *f1);
 NXS_API int nxs_dyn_set_forcing_time(nxs_dyn_handle *h, double fcoeff0, double fcoeff1, const double factor[3], const double bias[3]);
+/* The coupled build's terms.  NOTHING ATTACHED (the state after nxs_dyn_set_mesh) = the library without them, bit for bit and byte for byte: the kernels that
+ * carry a term are builds of their own, picked per launch while it is attached.
+ *   nxs_dyn_set_wave_stress   M_tau_wi.getVector(), [u | v] like every nodal vector: the wave radiation stress of the momentum equation,
+ *                  tau_x = D_tau_a[u] + tau_wi[u] + c_prime * (...) (FE.cpp:10509-10518; the sum associates left, and so does the library's).  Copied to the device and
+ *                  ATTACHED until tau_wi == NULL detaches it; NULL is the expression of the build without OASIS, a vector of zeros the coupled build that received
+ *                  no wave stress.  D_tau_a of nxs_dyn_get_diag stays drag * wind.  Values on a rank's ghost nodes are never used (only owned nodes are solved,
+ *                  FE.cpp:10472).  nxs_dyn_check_fields_fast raises crash_local when tau_wi[i] + tau_wi[i + Nn] is NaN for a node (FE.cpp:14631-14643).
+ *   nxs_dyn_put_coupled       host -> device, and ATTACHES: a non-NULL member is copied and carried by the following steps, a NULL member is detached (both NULL:
+ *                  the library without them).  A num_fsd_bins larger than any put before takes a new buffer of that size; the smaller one is kept until
+ *                  nxs_dyn_set_mesh / nxs_dyn_destroy (no device memory is freed between two steps), so a caller that grows the number step by step holds them all.
+ *   nxs_dyn_get_coupled       device -> host; a NULL member is not wanted; num_fsd_bins must be the attached number when conc_fsd is wanted.
+ * nxs_dyn_set_mesh detaches all three (the sizes change: the caller interpolates the element variables through nxs_interp like every other and puts them again).
+ * Errors: NXS_ERR_STATE before nxs_dyn_set_mesh; NXS_ERR_INVALID for num_fsd_bins < 0, bins without an array, an array without bins, and a get of a member that
+ * is not attached.
+ * EVP / mEVP: cum_damage is carried unchanged (there is no damage update).  Free drift / no motion: nothing is touched (step() skips update(), FE.cpp:8197-8214).
+ * With cum_damage attached the sub-step loop runs on a kernel family that accumulates it (option "fused" below).  nxs_dyn_step_host keeps its signature: a coupled
+ * host calls put_coupled / get_coupled beside it. */
+NXS_API int nxs_dyn_set_wave_stress(nxs_dyn_handle *h, const double *tau_wi /* [2*Nn] M_tau_wi, NULL = off */);
+NXS_API int nxs_dyn_put_coupled(nxs_dyn_handle *h, const nxs_dyn_coupled *c);
+NXS_API int nxs_dyn_get_coupled(nxs_dyn_handle *h, nxs_dyn_coupled *c);
 NXS_API int nxs_dyn_get_diag(nxs_dyn_handle *h, nxs_dyn_diag *d);
 /* updateIceDiagnostics() on the device-resident state.  d (may be NULL): host arrays to fill.  device_rows (may be NULL): receives a DEVICE
  * pointer to the same diagnostics as [Ne][NXS_ICE_DIAG_FIELDS] interleaved rows (library-owned, valid until the next call on this handle
@@ -347,7 +380,7 @@ NXS_API int nxs_dyn_step_host(nxs_dyn_handle *h, nxs_dyn_state *s, const nxs_dyn
 /* checkRegridding(): local minimum angle [deg] and flip test; the cross-rank reduction
  * (FE.cpp:8306, 1812) is left to the caller's communicator. */
 NXS_API int nxs_dyn_check_regridding(nxs_dyn_handle *h, double *min_angle, int32_t *flip, int32_t *regrid_local);
-/* checkFieldsFast(): crash_local != 0 when a field is out of range / NaN (FE.cpp:14541-14629). */
+/* checkFieldsFast(): crash_local != 0 when a field is out of range / NaN (FE.cpp:14541-14629) -- with a wave stress attached also its NaN test (FE.cpp:14631-14643). */
 NXS_API int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local);
 
 NXS_API int nxs_dyn_get_timing(nxs_dyn_handle *h, nxs_dyn_timing *t);
@@ -401,6 +434,10 @@ NXS_API int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t);
  *                  workgroups per CU with one element per thread (a rank of eight of a 1.5 M-triangle mesh: 0.85 instead of 1.3 ms per step),
  *                  partitions of 200 k - 400 k ONE workgroup per CU with four elements and two nodes per thread (a rank of four: 1.3 instead of
  *                  2.2 ms).  The option decides how the mesh is cut: setting or clearing it on a live mesh cuts the mesh again (same bits)
+ *                  WITH cum_damage ATTACHED (nxs_dyn_put_coupled, BBM) the accumulation lives in the one-kernel-per-loop family, k_substep_fused and
+ *                  k_substep_pair; where the settings would run k_substep_multi (several sub-steps per launch on small meshes), k_substep_flow ("pair_flow") or
+ *                  the resident loop (4), the step runs k_substep_pair where it applies and one patch kernel per sub-step (as 1) otherwise -- the same bits;
+ *                  nxs_dyn_get_traffic_model().substep_kernel names what ran.  No setting fails or skips the accumulation
  *   "resident_dryrun"  (an action, not a setting) builds the tables of the resident loop for the mesh and halo lists set so far -- no transport,
  *                  no neighbours needed -- and fails with NXS_ERR_INVALID when this partition cannot run it (a patch with more elements than
  *                  threads, more than one round of workgroups, LDS, > 24 neighbouring patches): a partition can be checked on its own

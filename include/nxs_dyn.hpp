@@ -34,6 +34,10 @@ public:
     }
     void setOption(const char *key, long long value) { check(nxs_dyn_set_option(h_, key, value), "set_option"); }
     void getDiag(nxs_dyn_diag &d) { check(nxs_dyn_get_diag(h_, &d), "get_diag"); }
+    // the coupled build's terms (#ifdef OASIS): M_tau_wi into explicitSolve(), M_cum_damage / M_conc_fsd through the sub-steps and update()
+    void setWaveStress(const double *tau_wi) { check(nxs_dyn_set_wave_stress(h_, tau_wi), "set_wave_stress"); }
+    void putCoupled(const nxs_dyn_coupled &c) { check(nxs_dyn_put_coupled(h_, &c), "put_coupled"); }
+    void getCoupled(nxs_dyn_coupled &c) { check(nxs_dyn_get_coupled(h_, &c), "get_coupled"); }
 
     void explicitSolve() { check(nxs_dyn_explicit_solve(h_), "explicitSolve"); }               // FE.cpp:10182-10643
     void update() { check(nxs_dyn_update(h_), "update"); }                                     // FE.cpp:3919-4132

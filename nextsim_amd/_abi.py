@@ -130,6 +130,10 @@ class Diag(C.Structure):
                 ("D_tau_w", c_double_p), ("D_del_ci_ridge_myi", c_double_p)]
 
 
+class Coupled(C.Structure):   # nxs_dyn_coupled
+    _fields_ = [("cum_damage", c_double_p), ("conc_fsd", c_double_p), ("num_fsd_bins", C.c_int32), ("reserved0", C.c_int32)]
+
+
 ICE_DIAG = ("D_conc", "D_thick", "D_snow_thick", "D_sigma0", "D_sigma1", "D_divergence")
 
 

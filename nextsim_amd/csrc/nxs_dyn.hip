@@ -194,6 +194,11 @@ struct nxs_dyn_handle {
     double *f_snap[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // wind0, wind1, ocean0, ocean1, ssh0, ssh1 (forcing pair)
     bool have_pair = false;
     std::vector<void *> forcing_allocs;
+    // the coupled build's arrays (nxs_dyn_set_wave_stress / nxs_dyn_put_coupled): buffers that go with the mesh.  ATTACHED is what h->dw says (tau_wi, cum_damage,
+    // conc_fsd non-NULL); a detached buffer is kept for the next attach (no hipFree between two steps: it would wait for the whole device, see `retired`)
+    double *d_tau_wi = nullptr, *d_tau_sum = nullptr, *d_cum = nullptr, *d_fsd = nullptr;
+    size_t fsd_capacity = 0;               // doubles d_fsd has room for
+    std::vector<void *> coupled_allocs;
     // v4: the whole sub-step loop in one resident launch (option "fused" = 4; see k_substep_resident)
     DevResident res{};
     std::vector<void *> res_allocs;  // its tables, exchange buffer and ghost ring (a pool of their own: rebuilt whenever an option of the loop changes)
@@ -268,6 +273,9 @@ namespace {
 
 // the kernel family of this step: option "fused", except that the branch trace lives in the per-loop kernels
 inline int eff_fused(const nxs_dyn_handle *h) { return h->trace_branches ? 0 : h->fused; }
+// the coupled build's terms (include/nxs_dyn.h, nxs_dyn_coupled).  M_cum_damage only moves where updateSigmaDamage runs: BBM
+inline bool cum_attached(const nxs_dyn_handle *h) { return h->dw.cum_damage != nullptr && h->dp.dynamics_type == NXS_DYN_BBM; }
+inline bool wave_attached(const nxs_dyn_handle *h) { return h->dw.tau_wi != nullptr; }
 
 int fail(nxs_dyn_handle *h, int code, const char *fmt, ...) {
     char buf[512];
@@ -679,7 +687,13 @@ PingPong pingpong(const nxs_dyn_handle *h, int parity) {
 // hipLaunchKernel; a launch the device refuses is reported by the hipGetLastError at the end of explicit_solve, like those of the <<<>>> launches beside them.
 
 template <int T, bool HALO>
-const void *fused_kernel_of(bool pow4, int nt_mask, bool pmem) {
+const void *fused_kernel_of(bool pow4, int nt_mask, bool pmem, bool cum) {
+    if (cum) {   // M_cum_damage attached: the builds that carry it (the streaming hints as with the exchange inside: all or none)
+#define FUSEDC(PP, NN) (pmem ? (const void *)k_substep_fused<T, PP, NN, HALO, true, true> : (const void *)k_substep_fused<T, PP, NN, HALO, false, true>)
+        if (!pow4) return FUSEDC(false, 0);
+        return nt_mask ? FUSEDC(true, 3) : FUSEDC(true, 0);
+#undef FUSEDC
+    }
 #define FUSED(PP, NN) (pmem ? (const void *)k_substep_fused<T, PP, NN, HALO, true> : (const void *)k_substep_fused<T, PP, NN, HALO, false>)
     if (!pow4) return FUSED(false, 0);
     if constexpr (HALO) return nt_mask ? FUSED(true, 3) : FUSED(true, 0);
@@ -695,14 +709,20 @@ const void *fused_kernel_of(bool pow4, int nt_mask, bool pmem) {
 }
 // k_substep_fused: 512 threads where a patch holds more than 256 can take (big); the exchange inside (halo); parameters from memory (pmem); streaming hints (nt_mask)
 const void *fused_kernel_fn(const nxs_dyn_handle *h, bool halo, bool pmem, int nt_mask, bool big) {
-    const bool p4 = h->dp.ers_int == 4;
-    if (halo) return big ? fused_kernel_of<512, true>(p4, nt_mask, pmem) : fused_kernel_of<256, true>(p4, nt_mask, pmem);
-    return big ? fused_kernel_of<512, false>(p4, nt_mask, pmem) : fused_kernel_of<256, false>(p4, nt_mask, pmem);
+    const bool p4 = h->dp.ers_int == 4, cum = cum_attached(h);
+    if (halo) return big ? fused_kernel_of<512, true>(p4, nt_mask, pmem, cum) : fused_kernel_of<256, true>(p4, nt_mask, pmem, cum);
+    return big ? fused_kernel_of<512, false>(p4, nt_mask, pmem, cum) : fused_kernel_of<256, false>(p4, nt_mask, pmem, cum);
 }
 
 // k_substep_pair: both exchanges inside the launch (halo: several ranks), four small workgroups per CU (256 threads), or the mesh move of its two sub-steps inside (move)
 const void *pair_kernel_fn(const nxs_dyn_handle *h, bool halo, bool move) {
     const bool p4 = h->dp.ers_int == 4;
+    if (cum_attached(h)) {   // M_cum_damage attached: the same four builds with the accumulation at write-back (pair_body<.., CUM>)
+        if (halo) return p4 ? (const void *)k_substep_pair<512, true, 3, true, false, true> : (const void *)k_substep_pair<512, false, 3, true, false, true>;
+        if (h->pair_threads_chosen == 256) return p4 ? (const void *)k_substep_pair<256, true, 3, false, false, true> : (const void *)k_substep_pair<256, false, 3, false, false, true>;
+        if (move) return p4 ? (const void *)k_substep_pair<512, true, 3, false, true, true> : (const void *)k_substep_pair<512, false, 3, false, true, true>;
+        return p4 ? (const void *)k_substep_pair<512, true, 3, false, false, true> : (const void *)k_substep_pair<512, false, 3, false, false, true>;
+    }
     if (halo) return p4 ? (const void *)k_substep_pair<512, true, 3, true> : (const void *)k_substep_pair<512, false, 3, true>;
     if (h->pair_threads_chosen == 256) return p4 ? (const void *)k_substep_pair<256, true, 3> : (const void *)k_substep_pair<256, false, 3>;
     if (move) return p4 ? (const void *)k_substep_pair<512, true, 3, false, true> : (const void *)k_substep_pair<512, false, 3, false, true>;
@@ -784,7 +804,12 @@ void launch_pair(nxs_dyn_handle *h, const StepPlan &p, int sidx) {
 
 void launch_substep(nxs_dyn_handle *h, double move_dt) {
     if (h->dp.dynamics_type == NXS_DYN_BBM) {
-        if (h->trace_branches) {
+        if (cum_attached(h)) {
+            const bool p4 = h->dp.ers_int == 4;
+            if (h->trace_branches) { if (p4) LAUNCH(h, (k_sigma_bbm<true, true, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp); else LAUNCH(h, (k_sigma_bbm<false, true, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp); }
+            else { if (p4) LAUNCH(h, (k_sigma_bbm<true, false, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp); else LAUNCH(h, (k_sigma_bbm<false, false, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp); }
+        }
+        else if (h->trace_branches) {
             if (h->dp.ers_int == 4) LAUNCH(h, (k_sigma_bbm<true, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
             else LAUNCH(h, (k_sigma_bbm<false, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
         }
@@ -793,7 +818,12 @@ void launch_substep(nxs_dyn_handle *h, double move_dt) {
     }
     else
         LAUNCH(h, k_sigma_vp, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
-    LAUNCH(h, k_solve_move, h->dm.No, h->dm, h->ds, h->dw, h->dp, move_dt);
+    if (wave_attached(h)) {   // the solve's wind stress is D_tau_a + M_tau_wi, left-associated (FE.cpp:10509-10518): the prep kernel left that sum in an array of its own
+        DevWork w = h->dw;
+        w.D_tau_a = h->dw.tau_sum;
+        LAUNCH(h, k_solve_move, h->dm.No, h->dm, h->ds, w, h->dp, move_dt);
+    }
+    else LAUNCH(h, k_solve_move, h->dm.No, h->dm, h->ds, h->dw, h->dp, move_dt);
 }
 
 // ---- which regime the step wants
@@ -811,6 +841,9 @@ StepPlan wish_plan(const nxs_dyn_handle *h, bool resident_ok = true) {
     StepPlan p;
     const int S = h->dp.substeps, family = eff_fused(h);
     const bool fused = family != 0, mr = multi_rank(h), xk = exchange_in_kernel_possible(h);
+    // M_cum_damage attached (BBM): the families that accumulate it are the per-loop kernels, k_substep_fused and k_substep_pair; where the options ask for
+    // k_substep_multi, k_substep_flow or the resident loop the step runs the nearest family that has it (nxs_dyn_get_traffic_model names it)
+    const bool cum = cum_attached(h);
     const bool moves = h->dp.dynamics_type != NXS_DYN_MEVP;   // (mEVP: one mesh move, after the loop)
     // ---- sub-steps per launch.  v3: D sub-steps per launch -- the deferred mesh move (ring of >= D+1 buffers).  It trades redundant arithmetic
     // on the halo rings for less HBM traffic and fewer launches: a gain where the sub-step is latency-bound (10 km: 1.23 -> 0.97
@@ -834,6 +867,9 @@ StepPlan wish_plan(const nxs_dyn_handle *h, bool resident_ok = true) {
         p.D = std::min(h->pair_depth > 0 ? h->pair_depth : 4, std::min(S, NXS_MAX_DEPTH));
         while (p.D > 1 && S % p.D != 0) --p.D;
         pair_kernel = p.D == 2 && h->pair_regs == 1;   // (forced depth 2 with option pair_regs = 1: k_substep_pair at any size)
+        // M_cum_damage attached: k_substep_multi does not carry it (its intermediate damage lives in LDS, the increments of D sub-steps would have to wait beside
+        // it) -- the step runs one patch kernel per sub-step instead, which does
+        if (cum && !pair_kernel) p.D = 1;
     }
     const int D = p.D;
     const bool pair = D >= 2;   // (family 2 or 3: never with the branch trace)
@@ -845,7 +881,7 @@ StepPlan wish_plan(const nxs_dyn_handle *h, bool resident_ok = true) {
     // k_substep_pair on a single rank can apply the mesh move of its two sub-steps itself (M_UM / M_UT in and out once per launch): no ring beyond the three
     // buffers a launch reads and writes, no k_move_ring.  Option "pair_move" = -1: wherever that kernel runs with 512 threads (2 km: 5.27 -> 5.17 ms per step -- the
     // launch grows by 2.8 us, the 0.27 ms flush goes).  (The threads are the planner's choice: for this kernel on a single rank it takes the requested number.)
-    p.move_in_pair = pair_kernel && !mr && h->pair_threads_requested == 512 && h->um_ring <= 0 && h->pair_move != 0 && !flow_wanted(h);
+    p.move_in_pair = pair_kernel && !mr && h->pair_threads_requested == 512 && h->um_ring <= 0 && h->pair_move != 0 && !(flow_wanted(h) && !cum);
     if (pair) {  // the ring is flushed between launches; by default once per step (a flush per launch costs 30 small launches at 10 km: 66 us of 0.88 ms)
         if (h->um_ring <= 0) K = std::min(S, NXS_MAX_RING - 1);
         K = std::max(D, K - K % D);
@@ -854,10 +890,10 @@ StepPlan wish_plan(const nxs_dyn_handle *h, bool resident_ok = true) {
     p.K = K; p.R = K + 1;
     p.deferred = K > 1;   // (fused path, not mEVP)
     // ---- the family.  v4: the resident sub-step loop (opt-in; which of its two kernels is known once its tables are built: plan_step)
-    const bool resident = resident_ok && resident_possible(h) && !h->trace_branches && !h->res_failed;
+    const bool resident = resident_ok && resident_possible(h) && !h->trace_branches && !h->res_failed && !cum;
     // single rank: all the pairs of a step in one data-flow launch (needs the whole step in the ring: one flush, behind the launch; whether its tables could be
     // built is known after ensure_pair_patches)
-    const bool flow = pair_kernel && !mr && h->pair_threads_requested == 512 && flow_wanted(h) && !h->flow_failed && K == S;
+    const bool flow = pair_kernel && !mr && h->pair_threads_requested == 512 && flow_wanted(h) && !h->flow_failed && K == S && !cum;
     p.kernel = resident ? NXS_KERNEL_RESIDENT : flow ? NXS_KERNEL_PAIR_FLOW : pair ? (pair_kernel ? NXS_KERNEL_PAIR : NXS_KERNEL_MULTI) : fused ? NXS_KERNEL_FUSED : NXS_KERNEL_PER_LOOP;
     // the exchange inside the one-sub-step kernel: needs the deferred mesh move (ghost nodes are moved from the ring) or no move at all (mEVP)
     const bool fused_halo = xk && fused && (p.deferred || !moves);
@@ -1290,6 +1326,17 @@ int run_substeps(nxs_dyn_handle *h) {
     return rc ? rc : final_flush(h, p);
 }
 
+// update(), FE.cpp:3919-4132 (with the floe-size bins attached: the build that scales them too)
+void launch_update(nxs_dyn_handle *h) {
+    if (h->dw.conc_fsd) {
+        if (h->sig_loc) LAUNCH(h, (k_update<true, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+        else LAUNCH(h, (k_update<false, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+        return;
+    }
+    if (h->sig_loc) LAUNCH(h, k_update<true>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+    else LAUNCH(h, k_update<false>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+}
+
 int ready(nxs_dyn_handle *h) {
     if (!h) return NXS_ERR_INVALID;
     if (!h->have_mesh || !h->have_state || !h->have_forcing)
@@ -1380,19 +1427,31 @@ int explicit_solve(nxs_dyn_handle *h) {
         HIPCHK(h, hipStreamSynchronize(h->stream));  // h->dp may change right after
         h->dp_dirty = false;
     }
+    const bool wave = wave_attached(h);   // (launch-uniform: the builds with the wave radiation stress in the nodal records)
+    if (wave && p.prep == NXS_PREP_FULL && !h->dw.tau_sum) {   // only the full prep writes the sum and only k_solve_move / the work arrays' readers want it: 16 B per node, on first use
+        if (!h->d_tau_sum && (rc = dev_alloc(h, h->coupled_allocs, &h->d_tau_sum, 2 * (size_t)m.Nn))) return rc;
+        h->dw.tau_sum = h->d_tau_sum;
+        release_graph(h);   // (kernel arguments are baked into the graphs)
+    }
     if (p.prep == NXS_PREP_FUSED) {
         // one launch over the sub-step kernel's patches: the elements' values reach their nodes through LDS (k_prep_fused)
         // (the open-water flags of the node blocks are lowered by the step before -- k_update's first threads, as the range flag -- and at allocation: no memset per step;
         // a step that ended without update() leaves them raised, which only costs the smoother some blocks it could have skipped)
-        hipLaunchKernelGGL(k_prep_fused, dim3(h->dpch.nP), dim3(512), h->prep_lds, h->stream, m, h->dpch, h->ds, h->dw, h->dp);
-        if (m.Nn > m.No) LAUNCH(h, k_prep_ghost_nodes, m.Nn - m.No, m, h->ds, h->dw, h->dp);   // several ranks: the ghost nodes' share of the nodal loops
+        if (wave) hipLaunchKernelGGL(k_prep_fused<true>, dim3(h->dpch.nP), dim3(512), h->prep_lds, h->stream, m, h->dpch, h->ds, h->dw, h->dp);
+        else hipLaunchKernelGGL(k_prep_fused<false>, dim3(h->dpch.nP), dim3(512), h->prep_lds, h->stream, m, h->dpch, h->ds, h->dw, h->dp);
+        if (m.Nn > m.No) {   // several ranks: the ghost nodes' share of the nodal loops
+            if (wave) LAUNCH(h, k_prep_ghost_nodes<true>, m.Nn - m.No, m, h->ds, h->dw, h->dp);
+            else LAUNCH(h, k_prep_ghost_nodes<false>, m.Nn - m.No, m, h->ds, h->dw, h->dp);
+        }
         HIPCHK(h, hipGetLastError());
     } else if (p.prep == NXS_PREP_LEAN) {
         LAUNCH(h, k_prep_elements<true>, m.Ne, m, h->ds, h->dw, h->dp);
-        LAUNCH(h, k_prep_nodes<true>, m.Nn, m, h->ds, h->dw, h->dp);
+        if (wave) LAUNCH(h, (k_prep_nodes<true, true>), m.Nn, m, h->ds, h->dw, h->dp);
+        else LAUNCH(h, k_prep_nodes<true>, m.Nn, m, h->ds, h->dw, h->dp);
     } else {
         LAUNCH(h, k_prep_elements<false>, m.Ne, m, h->ds, h->dw, h->dp);
-        LAUNCH(h, k_prep_nodes<false>, m.Nn, m, h->ds, h->dw, h->dp);
+        if (wave) LAUNCH(h, (k_prep_nodes<false, true>), m.Nn, m, h->ds, h->dw, h->dp);
+        else LAUNCH(h, k_prep_nodes<false>, m.Nn, m, h->ds, h->dw, h->dp);
     }
     if (timed) HIPCHK(h, hipEventRecord(h->cur[1], h->stream));
     rc = run_substeps(h);
@@ -1536,6 +1595,8 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     free_pool(h->hf_allocs);
     h->hf_ready = false;
     free_pool(h->forcing_allocs);
+    free_pool(h->coupled_allocs);   // (set_mesh: h->dw is reset below, which detaches the three)
+    h->d_tau_wi = h->d_tau_sum = h->d_cum = h->d_fsd = nullptr; h->fsd_capacity = 0;
     for (auto &q : h->f_snap) q = nullptr;
     h->have_pair = false;
     unpin_all(h);
@@ -1741,6 +1802,8 @@ int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
     free_pool(h->hf_allocs);
     h->hf_ready = false;
     free_pool(h->forcing_allocs);
+    free_pool(h->coupled_allocs);   // (set_mesh: h->dw is reset below, which detaches the three)
+    h->d_tau_wi = h->d_tau_sum = h->d_cum = h->d_fsd = nullptr; h->fsd_capacity = 0;
     for (auto &q : h->f_snap) q = nullptr;
     h->have_pair = false;
     unpin_all(h);
@@ -2447,6 +2510,73 @@ int nxs_dyn_set_forcing_time(nxs_dyn_handle *h, double fcoeff0, double fcoeff1, 
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_set_forcing_time"); }
 
+// ---- the coupled build's terms (#ifdef OASIS in the reference): see include/nxs_dyn.h
+int nxs_dyn_set_wave_stress(nxs_dyn_handle *h, const double *tau_wi) try {   // M_tau_wi, FE.cpp:10353-10354, 10408-10414, 10509-10518
+    if (!h) return NXS_ERR_INVALID;
+    if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "set_wave_stress before set_mesh");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t n2 = 2 * (size_t)h->dm.Nn;
+    const bool was = wave_attached(h);
+    if (!tau_wi) {
+        h->dw.tau_wi = nullptr; h->dw.tau_sum = nullptr;
+        if (was) release_graph(h);   // (kernel arguments are baked into the graphs)
+        return NXS_OK;
+    }
+    int rc;
+    if (!h->d_tau_wi && (rc = dev_alloc(h, h->coupled_allocs, &h->d_tau_wi, n2))) return rc;   // (tau_sum: by the first step that runs the full prep, explicit_solve)
+    pin_host_buffer(h, tau_wi, n2 * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(h->d_tau_wi, tau_wi, n2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->dw.tau_wi = h->d_tau_wi; h->dw.tau_sum = h->d_tau_sum;
+    if (!was) release_graph(h);
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_set_wave_stress"); }
+
+int nxs_dyn_put_coupled(nxs_dyn_handle *h, const nxs_dyn_coupled *c) try {   // M_cum_damage (FE.cpp:4233-4238), M_conc_fsd (FE.cpp:3991-3994)
+    if (!h || !c) return NXS_ERR_INVALID;
+    if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "put_coupled before set_mesh");
+    if (c->num_fsd_bins < 0) return fail(h, NXS_ERR_INVALID, "put_coupled: num_fsd_bins = %d", c->num_fsd_bins);
+    if ((c->num_fsd_bins > 0) != (c->conc_fsd != nullptr)) return fail(h, NXS_ERR_INVALID, "put_coupled: %s", c->conc_fsd ? "conc_fsd without bins" : "bins without conc_fsd");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t Ne = h->dm.Ne, nf = (size_t)c->num_fsd_bins * Ne;
+    const bool had_cum = h->dw.cum_damage != nullptr, had_fsd = h->dw.conc_fsd != nullptr;
+    int rc;
+    if (c->cum_damage) {
+        if (!h->d_cum && (rc = dev_alloc(h, h->coupled_allocs, &h->d_cum, Ne))) return rc;
+        pin_host_buffer(h, c->cum_damage, Ne * sizeof(double));
+        HIPCHK(h, hipMemcpyAsync(h->d_cum, c->cum_damage, Ne * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    if (c->conc_fsd) {
+        if (nf > h->fsd_capacity) {   // another number of bins: a buffer of that size (the smaller one goes with the mesh)
+            if ((rc = dev_alloc(h, h->coupled_allocs, &h->d_fsd, nf))) return rc;
+            h->fsd_capacity = nf;
+        }
+        pin_host_buffer(h, c->conc_fsd, nf * sizeof(double));
+        HIPCHK(h, hipMemcpyAsync(h->d_fsd, c->conc_fsd, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->dw.cum_damage = c->cum_damage ? h->d_cum : nullptr;
+    h->dw.conc_fsd = c->conc_fsd ? h->d_fsd : nullptr;
+    h->dw.nbins = c->num_fsd_bins;
+    if (had_cum != (h->dw.cum_damage != nullptr) || had_fsd != (h->dw.conc_fsd != nullptr)) release_graph(h);   // (another family may run; kernel arguments are baked into the graphs)
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_put_coupled"); }
+
+int nxs_dyn_get_coupled(nxs_dyn_handle *h, nxs_dyn_coupled *c) try {
+    if (!h || !c) return NXS_ERR_INVALID;
+    if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "get_coupled before set_mesh");
+    if (c->cum_damage && !h->dw.cum_damage) return fail(h, NXS_ERR_INVALID, "get_coupled: cum_damage is not attached");
+    if (c->conc_fsd && !h->dw.conc_fsd) return fail(h, NXS_ERR_INVALID, "get_coupled: conc_fsd is not attached");
+    if (c->conc_fsd && c->num_fsd_bins != h->dw.nbins) return fail(h, NXS_ERR_INVALID, "get_coupled: %d bins asked for, %d attached", c->num_fsd_bins, h->dw.nbins);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    const size_t Ne = h->dm.Ne, nf = (size_t)h->dw.nbins * Ne;
+    if (c->cum_damage) { pin_host_buffer(h, c->cum_damage, Ne * sizeof(double)); HIPCHK(h, hipMemcpyAsync(c->cum_damage, h->dw.cum_damage, Ne * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
+    if (c->conc_fsd) { pin_host_buffer(h, c->conc_fsd, nf * sizeof(double)); HIPCHK(h, hipMemcpyAsync(c->conc_fsd, h->dw.conc_fsd, nf * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_get_coupled"); }
+
 int nxs_dyn_get_diag(nxs_dyn_handle *h, nxs_dyn_diag *dg) try {
     if (!h || !dg) return NXS_ERR_INVALID;
     if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "get_diag before set_mesh");
@@ -2571,8 +2701,7 @@ int nxs_dyn_explicit_solve(nxs_dyn_handle *h) try {
 int nxs_dyn_update(nxs_dyn_handle *h) try {
     int rc = ready(h);
     if (rc) return rc;
-    if (h->sig_loc) LAUNCH(h, k_update<true>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
-    else LAUNCH(h, k_update<false>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+    launch_update(h);
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_update"); }
 
@@ -2599,8 +2728,7 @@ int nxs_dyn_step(nxs_dyn_handle *h) try {  // FE.cpp:8197-8214
     }
     rc = explicit_solve(h);
     if (rc) { h->cur = nullptr; return rc; }
-    if (h->sig_loc) LAUNCH(h, k_update<true>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
-    else LAUNCH(h, k_update<false>, h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
+    launch_update(h);
     HIPCHK(h, hipGetLastError());
     if (k >= 0) {
         HIPCHK(h, hipEventRecord(h->cur[4], h->stream));
@@ -2719,6 +2847,11 @@ int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t) try {
         break;
     default: break;
     }
+    if (cum_attached(h)) {   // M_cum_damage in and out, by the element's writer, once per launch
+        const double written = h->plan.kernel == NXS_KERNEL_PAIR ? s2.W : h->plan.kernel == NXS_KERNEL_FUSED ? s1.W : h->plan.kernel == NXS_KERNEL_PER_LOOP ? Ne : 0.;
+        t->substep_scheme_bytes += 16. * written;
+        if (h->plan.kernel == NXS_KERNEL_PAIR || h->plan.kernel == NXS_KERNEL_FUSED || h->plan.kernel == NXS_KERNEL_PER_LOOP) t->substep_unique_bytes += 16. * Ne;
+    }
     t->survey_model_bytes = (172. * Ne + 217. * Nn) * std::max(t->substeps_per_launch, 1);
     t->move_ring_slots = h->plan.final_count > 0 ? h->plan.K : 0;   // (the slots of a k_move_ring launch)
     if (t->move_ring_slots > 0) t->move_ring_bytes = Nn * (1. /*nflags*/ + 32. /*UM, UT in*/ + 32. /*out*/ + 16. * t->move_ring_slots /*the slots*/ + 16. /*M_VT back, last flush*/);
@@ -2738,8 +2871,14 @@ int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t) try {
             t->prep_unique_bytes = Ne * (13. + efields + ewrite + 64. + 8. + full + 64. + 8.) + Nn * (40. + 4. * (h->dm.W + h->dm.W1) + nin + nout + 32.);
         }
     }
+    if (wave_attached(h) && h->plan.prep != NXS_PREP_NONE) {   // M_tau_wi in, per node (the full prep also leaves the sum for k_solve_move: 16 B out)
+        const double per_node = 16. + (h->plan.prep == NXS_PREP_FULL ? 16. : 0.);
+        t->prep_scheme_bytes += per_node * Nn;
+        t->prep_unique_bytes += per_node * Nn;
+    }
     // update(): flags, corners, area in and out, six fields (+ three young) in and out, the stress record in and out, D_del out; the corners' x0, y0, UM gathered
     t->update_bytes = Ne * (1. + 12. + 16. + (young ? 9. : 6.) * 16. + 64. + 8.) + Nn * 32.;
+    if (h->dw.conc_fsd) t->update_bytes += 16. * h->dw.nbins * Ne;   // every bin in and out
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_get_traffic_model"); }
 
@@ -2812,6 +2951,7 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipMemsetAsync(h->d_crash, 0, sizeof(int), h->stream));
     LAUNCH(h, k_check_fields, std::max(h->dm.Ne, h->dm.Nn), h->dm, h->ds, h->dp, h->d_crash, (h->sig_loc && h->dp.dynamics_type == NXS_DYN_BBM) ? 1 : 0);
+    if (wave_attached(h)) LAUNCH(h, k_check_wave_stress, h->dm.Nn, h->dm.Nn, h->dw.tau_wi, h->d_crash);   // FE.cpp:14631-14643
     int c = 0;
     HIPCHK(h, hipMemcpyAsync(&c, h->d_crash, sizeof c, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

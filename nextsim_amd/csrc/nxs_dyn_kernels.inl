@@ -121,6 +121,13 @@ struct DevWork {
     double *xy;       // [Nn][2] node coordinates (x, y) on the displaced mesh at step start (frozen over the sub-steps, Q4)
     double *D_tau_a, *D_tau_w, *D_del;
     unsigned long long *trace;  // [Ne][4] branch trace of updateSigmaDamage (option "trace_branches"; layout of ref_work.trace in oracle/dyn_ref.h), else NULL
+    // the coupled build's terms (#ifdef OASIS in the reference; include/nxs_dyn.h, nxs_dyn_coupled): NULL = not attached.  Only the kernel instantiations that
+    // the host picks while one is attached (template parameters WAVE, CUM, FSD) read these members; the others never load them from the argument block
+    const double *tau_wi;       // [2Nn] M_tau_wi: added to the wind stress of the nodal records (FE.cpp:10408-10414, 10509-10518)
+    double *tau_sum;            // [2Nn] D_tau_a + M_tau_wi for the one-kernel-per-loop family, whose k_solve_move reads an array, not the records
+    double *cum_damage;         // [Ne] M_cum_damage (FE.cpp:4233-4238)
+    double *conc_fsd;           // [nbins][Ne] M_conc_fsd[k][cpt] (FE.cpp:3991-3994)
+    int nbins;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -415,7 +422,9 @@ __global__ void __launch_bounds__(BLOCK) k_prep_elements(DevMesh m, DevState s, 
 
 // ------------------------------------------------------------------------------------------------
 // K1b + K2  the nodal side of prep elements (as a gather) and prep nodes, FE.cpp:10309-10416
-template <bool LEAN>
+// WAVE: the wave radiation stress M_tau_wi is attached.  The reference's sum associates left, tau_x = (D_tau_a + tau_wi) + c_prime * (...) (FE.cpp:10509-10518), and
+// neither term changes during the sub-steps: the record's slots 6, 7 carry the sum, D_tau_a itself (the diagnostic) stays drag * wind
+template <bool LEAN, bool WAVE = false>
 __global__ void __launch_bounds__(BLOCK) k_prep_nodes(DevMesh m, DevState s, DevWork w, DevParams p) {
     // blocks are dealt round-robin over the 8 XCDs: give each XCD a contiguous range of nodes, so that the element records two rows of
     // nodes share are found in that XCD's L2 (each record is gathered by its three corner nodes)
@@ -476,6 +485,8 @@ __global__ void __launch_bounds__(BLOCK) k_prep_nodes(DevMesh m, DevState s, Dev
     const double tax = drag * wu, tay = drag * wv;
     w.D_tau_a[n] = tax;
     w.D_tau_a[n + Nn] = tay;
+    const double tsx = WAVE ? tax + w.tau_wi[n] : tax, tsy = WAVE ? tay + w.tau_wi[n + Nn] : tay;
+    if (WAVE && !LEAN) { w.tau_sum[n] = tsx; w.tau_sum[n + Nn] = tsy; }
 
     const double fc = 2 * NXS_OMEGA * sin(m.lat[n] * NXS_PI / 180.);
     if (!LEAN) w.fcor[n] = fc;
@@ -492,7 +503,7 @@ __global__ void __launch_bounds__(BLOCK) k_prep_nodes(DevMesh m, DevState s, Dev
     {   // the nodal inputs of the sub-step solve once more, as one 80-byte record per node (what the fused sub-step kernels read: one
         // base pointer, five 16-byte loads), staged through LDS so that the records leave the block as one contiguous stream
         double *r = rec + 10 * threadIdx.x;
-        r[0] = record_dte_over_mass(p, nm); r[1] = gu; r[2] = gv; r[3] = rl; r[4] = cb; r[5] = fc; r[6] = tax; r[7] = tay; r[8] = s.ocean[n]; r[9] = s.ocean[n + Nn];
+        r[0] = record_dte_over_mass(p, nm); r[1] = gu; r[2] = gv; r[3] = rl; r[4] = cb; r[5] = fc; r[6] = tsx; r[7] = tsy; r[8] = s.ocean[n]; r[9] = s.ocean[n + Nn];
     }
     __syncthreads();
     {
@@ -518,6 +529,7 @@ __device__ long long g_phase_p[8 * 8192];
 #else
 #define PSTAMP(k) do { } while (0)
 #endif
+template <bool WAVE = false>   // (WAVE: see k_prep_nodes)
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) k_prep_fused(DevMesh m, DevPatches pp, DevState s, DevWork w, DevParams p) {
     constexpr int T = 512;
     typedef double d2 __attribute__((ext_vector_type(2)));
@@ -747,7 +759,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
         w.VTM[n] = vu;
         w.VTM[n + Nn] = vv;
         d2 *r = reinterpret_cast<d2 *>(w.nrec) + 5 * (size_t)n;
-        r[0] = d2{record_dte_over_mass(p, nm), gu}; r[1] = d2{gv, rl}; r[2] = d2{cb, fc}; r[3] = d2{tax, tay}; r[4] = d2{ocu, ocv};
+        r[0] = d2{record_dte_over_mass(p, nm), gu}; r[1] = d2{gv, rl}; r[2] = d2{cb, fc}; r[3] = WAVE ? d2{tax + w.tau_wi[n], tay + w.tau_wi[n + Nn]} : d2{tax, tay}; r[4] = d2{ocu, ocv};
     }
     PSTAMP(4);
 }
@@ -757,6 +769,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
 // kernels, their M_VT is zeroed where their local mass is, D_tau_a of all nodes goes to the coupler.  This pass does them: one thread per ghost node, the values of
 // the few elements around it formed again with k_prep_elements' expressions (a rank of eight of the 2 km mesh has 793 ghosts).  Operand for operand k_prep_nodes
 // on a ghost node: its grad_ssh sums stay zero (every corner a ghost holds is flagged ghostNodes[i], FE.cpp:10328).
+template <bool WAVE = false>   // (WAVE: see k_prep_nodes; a ghost's record is never solved from, FE.cpp:10472 -- it is written like every other)
 __global__ void __launch_bounds__(BLOCK) k_prep_ghost_nodes(DevMesh m, DevState s, DevWork w, DevParams p) {
     const int n = m.No + blockIdx.x * BLOCK + (int)threadIdx.x;
     if (n >= m.Nn) return;
@@ -843,7 +856,7 @@ __global__ void __launch_bounds__(BLOCK) k_prep_ghost_nodes(DevMesh m, DevState 
     w.VTM[n] = vu;
     w.VTM[n + Nn] = vv;
     d2 *r = reinterpret_cast<d2 *>(w.nrec) + 5 * (size_t)n;
-    r[0] = d2{record_dte_over_mass(p, nm), gu}; r[1] = d2{gv, rl}; r[2] = d2{cb, fc}; r[3] = d2{tax, tay}; r[4] = d2{s.ocean[n], s.ocean[n + Nn]};
+    r[0] = d2{record_dte_over_mass(p, nm), gu}; r[1] = d2{gv, rl}; r[2] = d2{cb, fc}; r[3] = WAVE ? d2{tax + w.tau_wi[n], tay + w.tau_wi[n + Nn]} : d2{tax, tay}; r[4] = d2{s.ocean[n], s.ocean[n + Nn]};
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -910,7 +923,7 @@ __device__ __forceinline__ void elastic_stress_increment(double sig[3], const do
 template <bool POW4>
 __device__ __forceinline__ void bbm_stress(const DevParams &p, const double dxN[6], const double u[3], const double v[3],
                                            double sig[3], double &damage, const double expC, const double Pmax,
-                                           const double heal, const double dxs, const double cohesion, double *dcrit_out = nullptr) {
+                                           const double heal, const double dxs, const double cohesion, double *dcrit_out = nullptr, double *del_out = nullptr) {
     const double dt = p.dte;
     double eps[3];
     strain_rates<NXS_ZERO_TERMS>(dxN, u, v, eps);
@@ -951,6 +964,9 @@ __device__ __forceinline__ void bbm_stress(const DevParams &p, const double dxN[
         const double rtd = sqrt(elasticity) / dxs;
         const double del_damage = (1.0 - damage) * (1.0 - dcrit) * dt * rtd;
         damage += del_damage;
+        // M_cum_damage[cpt] += del_damage (FE.cpp:4233-4238, the coupled build): the caller adds it.  It hands in -0., the one value x + (-0.) == x holds
+        // for bit for bit whatever x is, so a sub-step that does not damage adds without changing a bit and needs no flag
+        if (del_out) *del_out = del_damage;
 #pragma unroll
         for (int i = 0; i < 3; ++i) sig[i] -= sig[i] * (1. - dcrit) * dt * rtd;
     }
@@ -1035,7 +1051,8 @@ __device__ __forceinline__ void trace_branch(unsigned long long *t, int code, do
     t[3]++;
 }
 
-template <bool POW4, bool TRACE = false>
+// CUM: M_cum_damage is attached (one load - add - store per element and sub-step, the reference's own sequence)
+template <bool POW4, bool TRACE = false, bool CUM = false>
 __global__ void __launch_bounds__(BLOCK) k_sigma_bbm(DevMesh m, DevState s, DevWork w, DevParams p) {
     const int e = blockIdx.x * BLOCK + threadIdx.x;
     if (e >= m.Ne) return;
@@ -1055,14 +1072,16 @@ __global__ void __launch_bounds__(BLOCK) k_sigma_bbm(DevMesh m, DevState s, DevW
         for (int j = 0; j < 3; ++j) { u[j] = s.VT[n[j]]; v[j] = s.VT[n[j] + Nn]; }
         sig[0] = s.s0[e]; sig[1] = s.s1[e]; sig[2] = s.s2[e];
         double damage = s.damage[e];
+        double del = -0.;
         if (TRACE) {
             double dcrit;
-            bbm_stress<POW4>(p, dxN, u, v, sig, damage, w.expC[e], w.pmax[e], w.heal[e], w.dxs[e], s.cohesion[e], &dcrit);
+            bbm_stress<POW4>(p, dxN, u, v, sig, damage, w.expC[e], w.pmax[e], w.heal[e], w.dxs[e], s.cohesion[e], &dcrit, CUM ? &del : nullptr);
             trace_branch(w.trace + 4 * (size_t)e, ((0. < dcrit) && (dcrit < 1.)) ? 1 : 0, dcrit, s.conc[e]);
         } else {
-            bbm_stress<POW4>(p, dxN, u, v, sig, damage, w.expC[e], w.pmax[e], w.heal[e], w.dxs[e], s.cohesion[e]);
+            bbm_stress<POW4>(p, dxN, u, v, sig, damage, w.expC[e], w.pmax[e], w.heal[e], w.dxs[e], s.cohesion[e], nullptr, CUM ? &del : nullptr);
         }
         s.damage[e] = damage;
+        if (CUM) w.cum_damage[e] += del;
     }
     s.s0[e] = sig[0]; s.s1[e] = sig[1]; s.s2[e] = sig[2];
     double F[6];
@@ -1281,7 +1300,7 @@ template <bool NT> __device__ __forceinline__ void stg(double *p, double v) { if
 // lets each own node subtract the forces of its fan (ascending element order, as the serial scatter)
 // and solve.  sigma, damage and VT are ping-pong buffered: a neighbouring patch may still be reading
 // the old values of a shared element / node while this one writes the new ones.
-template <int T, bool POW4, int NTM, bool HALO, bool PMEM>
+template <int T, bool POW4, int NTM, bool HALO, bool PMEM, bool CUM = false>   // CUM: M_cum_damage attached -- the element's writer loads, adds and stores it
 __global__ void __launch_bounds__(T) k_substep_fused(DevMesh m, DevPatches pp, DevState s, DevWork w, DevParams pval, const DevParams *__restrict__ pdev,
                                                      PingPong b, double move_dt, const HaloFused *__restrict__ hfp, int n_boundary, int from_mailbox) {
     // PMEM: the parameters are read from device memory, per phase (the element phase and the node phase need disjoint halves of them);
@@ -1441,7 +1460,11 @@ __global__ void __launch_bounds__(T) k_substep_fused(DevMesh m, DevPatches pp, D
             } else {
                 const double u[3] = {lu[tr.x], lu[tr.y], lu[tr.z]};
                 const double v[3] = {lv[tr.x], lv[tr.y], lv[tr.z]};
-                if (bbm) bbm_stress<POW4>(p, dxN, u, v, sig, damage, c_expC, c_pmax, c_heal, c_dxs, c_coh);
+                if (bbm) {
+                    double del = -0.;
+                    bbm_stress<POW4>(p, dxN, u, v, sig, damage, c_expC, c_pmax, c_heal, c_dxs, c_coh, nullptr, CUM ? &del : nullptr);
+                    if (CUM && writer) w.cum_damage[e] += del;   // (ring elements are computed by several patches and written by one)
+                }
                 else vp_stress(p, dxN, u, v, sig, c_expC);
             }
             if (writer) {
@@ -1800,7 +1823,9 @@ struct PairHalo {
 // slots: no k_move_ring, no first velocity slot (nobody reads the first sub-step's velocity after the launch).
 // KEEPN (the single-rank launch): the inputs of a thread's own node (25 registers) stay in registers from the first solve to the second -- no second read of the
 // 97 bytes per own node; the several-rank and the data-flow builds, short of registers, read them again ahead of the second sub-step's last element round.
-template <int T, bool POW4, int NTM, bool HALO, bool FLOW = false, bool MOVE = false, bool KEEPN = false>
+// CUM: M_cum_damage is attached.  The two damage increments of an E_1 element wait in registers (kd: the first across the exchange, -0. where none was made) and the
+// element's writer does load - add - add - store behind the second: the reference's additions in the reference's order, nothing loaded early.
+template <int T, bool POW4, int NTM, bool HALO, bool FLOW = false, bool MOVE = false, bool KEEPN = false, bool CUM = false>
 __device__ __forceinline__ void pair_body(const DevMesh &m, const DevPatches2 &pp, const DevState &s, const DevWork &w, const DevParams &p, const PingPong &b, const VTOut &vout,
                                           const HaloFused *__restrict__ hfp, const PairHalo &ph, const int blk, const unsigned flg, const int t_in = 0) {
     typedef double d2 __attribute__((ext_vector_type(2)));
@@ -1904,7 +1929,7 @@ __device__ __forceinline__ void pair_body(const DevMesh &m, const DevPatches2 &p
     for (int r = 0; r < 2; ++r) ks[r][0] = ks[r][1] = ks[r][2] = ks[r][3] = 0.;
 
     // one element update (FE.cpp:4137-4260 / 10649-10726 + the element half of 10445-10467) from the staged velocities
-    auto update_element = [&](const int l, const ushort4 trl, double sig[3], double &damage, const d2 r0, const d2 r1, const d2 r2) {
+    auto update_element = [&](const int l, const ushort4 trl, double sig[3], double &damage, const d2 r0, const d2 r1, const d2 r2, double *del) {
         const double c_expC = r0.x, volume = r0.y, c_pmax = r1.x, c_heal = r1.y, c_coh = r2.x;
         const int dxi = (int)(__double_as_longlong(r2.y) & 0xffffffffll);
         bool skip = bbm ? dxi < 0 : (__double_as_longlong(r2.y) >> 32) != 0;
@@ -1930,7 +1955,7 @@ __device__ __forceinline__ void pair_body(const DevMesh &m, const DevPatches2 &p
         } else {
             const double u[3] = {lu[trl.x], lu[trl.y], lu[trl.z]};
             const double v[3] = {lv[trl.x], lv[trl.y], lv[trl.z]};
-            if (bbm) bbm_stress<POW4>(p, dxN, u, v, sig, damage, c_expC, c_pmax, c_heal, c_dxs, c_coh);
+            if (bbm) bbm_stress<POW4>(p, dxN, u, v, sig, damage, c_expC, c_pmax, c_heal, c_dxs, c_coh, nullptr, CUM ? del : nullptr);
             else vp_stress(p, dxN, u, v, sig, c_expC);
         }
         double F[6];
@@ -1938,6 +1963,7 @@ __device__ __forceinline__ void pair_body(const DevMesh &m, const DevPatches2 &p
 #pragma unroll
         for (int k = 0; k < 3; ++k) lF2[(size_t)k * EDm + l] = d2{F[k], F[k + 3]};
     };
+    double kd[2] = {-0., -0.};   // (CUM) the first sub-step's damage increments of this thread's E_1 elements
     // one node (FE.cpp:10472-10529): its loads, then (behind the barrier) the fan gather in ascending element order and the 2x2 solve
     struct NodeIn { unsigned char nf; d2 r[5]; unsigned fw[4]; };
     auto load_node = [&](const int i, const int n) {
@@ -2008,7 +2034,9 @@ __device__ __forceinline__ void pair_body(const DevMesh &m, const DevPatches2 &p
         }
         if (active) {
             double sig[3] = {a.x, a.y, c2.x}, damage = c2.y;
-            update_element(l, tr[r], sig, damage, r0, r1, r2);
+            double del0 = -0.;
+            update_element(l, tr[r], sig, damage, r0, r1, r2, &del0);
+            if (CUM && r < 2) kd[r] = del0;
             if (r < 2) { ks[r][0] = sig[0]; ks[r][1] = sig[1]; ks[r][2] = sig[2]; ks[r][3] = damage; }
         }
         if (r == 0) { kc0[0] = r0; kc0[1] = r1; kc0[2] = r2; }
@@ -2079,7 +2107,14 @@ __device__ __forceinline__ void pair_body(const DevMesh &m, const DevPatches2 &p
         const bool writer = eraw[r] >= 0;
         const int e = writer ? eraw[r] : ~eraw[r];
         double sig[3] = {ks[r][0], ks[r][1], ks[r][2]}, damage = ks[r][3];
-        update_element(l, tr[r], sig, damage, r == 0 ? kc0[0] : kc1[0], r == 0 ? kc0[1] : kc1[1], r == 0 ? kc0[2] : kc1[2]);
+        double del1 = -0.;
+        update_element(l, tr[r], sig, damage, r == 0 ? kc0[0] : kc1[0], r == 0 ? kc0[1] : kc1[1], r == 0 ? kc0[2] : kc1[2], &del1);
+        if (CUM && writer && bbm) {   // FE.cpp:4233-4238, twice
+            double c = w.cum_damage[e];
+            c += kd[r];
+            c += del1;
+            w.cum_damage[e] = c;
+        }
         if (writer) {
             d2 *S = reinterpret_cast<d2 *>(b.Sn) + 2 * (size_t)e;
             const d2 a = {sig[0], sig[1]}, c2 = {sig[2], damage};
@@ -2143,7 +2178,7 @@ __device__ __forceinline__ void pair_body(const DevMesh &m, const DevPatches2 &p
 
 // the kernel: which patch, and -- several ranks -- whether it takes part in the exchange: the patches that do not (all but the few along the partition boundary)
 // run the single-rank body, so the exchange's tables and tickets cost them no register (the resident kernels branch the same way)
-template <int T, bool POW4, int NTM, bool HALO = false, bool MOVE = false>
+template <int T, bool POW4, int NTM, bool HALO = false, bool MOVE = false, bool CUM = false>
 __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) k_substep_pair(DevMesh m, DevPatches2 pp, DevState s, DevWork w, DevParams p, PingPong b, VTOut vout,
                                                                                                 const HaloFused *__restrict__ hfp, PairHalo ph) {
     int blk;
@@ -2155,11 +2190,11 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) 
     }
     if (HALO) {
         const unsigned flg = ph.pflags[blk];   // this patch's duties in the exchange (uniform over the workgroup)
-        if (flg & 1u) { pair_body<T, POW4, NTM, true>(m, pp, s, w, p, b, vout, hfp, ph, blk, flg); return; }
+        if (flg & 1u) { pair_body<T, POW4, NTM, true, false, false, false, CUM>(m, pp, s, w, p, b, vout, hfp, ph, blk, flg); return; }
         // a rank whose mesh holds no ghost (no G patch: nobody runs the exchange's body, nobody reads the sequence): the sequence still counts the two exchanges
         if (ph.nG == 0 && blockIdx.x == 0 && threadIdx.x == 0) *hfp->ipc.seq_push += 2ull;
     }
-    pair_body<T, POW4, NTM, false, false, MOVE, !HALO>(m, pp, s, w, p, b, vout, hfp, ph, blk, 0u);
+    pair_body<T, POW4, NTM, false, false, MOVE, !HALO, CUM>(m, pp, s, w, p, b, vout, hfp, ph, blk, 0u);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3803,7 +3838,8 @@ __global__ void __launch_bounds__(BLOCK) k_ow_tail(DevMesh m, DevState s, DevWor
 // ------------------------------------------------------------------------------------------------
 // K10 update(), FE.cpp:3946-4131
 // REC: M_sigma lives in the records the sub-step loop left in S4a (see k_pack_state); the arrays are brought up to date on demand
-template <bool REC>
+// FSD: the floe-size bins M_conc_fsd are attached: every bin of the element times the surf_ratio formed here, under the same condition (FE.cpp:3991-3994)
+template <bool REC, bool FSD = false>
 __global__ void __launch_bounds__(BLOCK) k_update(DevMesh m, DevState s, DevWork w, DevParams p) {
     const int e = blockIdx.x * BLOCK + threadIdx.x;
     if (e >= m.Ne) return;
@@ -3835,6 +3871,8 @@ __global__ void __launch_bounds__(BLOCK) k_update(DevMesh m, DevState s, DevWork
         }
         ridge = 1. - (1. - ridge) * STD_MIN(1., conc) / (old_conc * surf_ratio);
         if (p.young_cat) { hy *= surf_ratio; cy *= surf_ratio; hsy *= surf_ratio; }
+        if (FSD)
+            for (int k = 0; k < w.nbins; ++k) w.conc_fsd[(size_t)k * m.Ne + e] *= surf_ratio;   // bin-major: a wave reads and writes whole lines
         if (p.equal_ridging) {
             const double conc_ratio = STD_MIN(1., conc) / old_conc;
             cmyi *= conc_ratio;
@@ -4015,6 +4053,13 @@ __global__ void __launch_bounds__(BLOCK) k_check_fields(DevMesh m, DevState s, D
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(crash, 1);
 }
 
+
+// checkFieldsFast of the coupled build, FE.cpp:14631-14643: the NaN test of M_tau_wi
+__global__ void __launch_bounds__(BLOCK) k_check_wave_stress(int Nn, const double *__restrict__ tau_wi, int *crash) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    const bool bad = i < Nn && isnan(tau_wi[i] + tau_wi[i + Nn]);
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(crash, 1);
+}
 
 // ExternalData::get for a dataset that is interpolated linearly in time (model/externaldata.cpp:360-401):
 //   value = M_factor*(fcoeff[0]*interpolated_data[0][i] + fcoeff[1]*interpolated_data[1][i]) + M_bias_correction

@@ -198,6 +198,8 @@ int upload_pair_patches_mr(nxs_dyn_handle *h) {
     h->pairh.nG = plan.nG; h->pairh.nBand = plan.nBand; h->pairh.from_mailbox = 0;
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_substep_pair<512, true, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->pair_lds));
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_substep_pair<512, false, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->pair_lds));
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_substep_pair<512, true, 3, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->pair_lds));   // (with M_cum_damage attached)
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_substep_pair<512, false, 3, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->pair_lds));
     h->pair_ready = true;
     h->pair_depth_built = 2;
     return NXS_OK;
@@ -241,7 +243,8 @@ int upload_host_patches(nxs_dyn_handle *h, const HostPatches &hp) {
         if (nxs_cut::build_prep_rows(hp, h->h_n2e.data(), h->dm.W1, h->dm.Nn, rows)) {
             if ((rc = dev_upload(h, h->patch_allocs, &d.prow, rows))) return rc;
             h->prep_lds = nxs_cut::prep_fused_lds_of(hp);
-            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_prep_fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->prep_lds));
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_prep_fused<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->prep_lds));
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_prep_fused<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->prep_lds));   // (with M_tau_wi attached)
         }
     }
     return NXS_OK;

@@ -72,6 +72,9 @@ def load_library():
     L.nxs_dyn_get_state.argtypes = [H, P(_abi.State)]
     L.nxs_dyn_set_forcing.argtypes = [H, P(_abi.Forcing)]
     L.nxs_dyn_get_diag.argtypes = [H, P(_abi.Diag)]
+    L.nxs_dyn_set_wave_stress.argtypes = [H, _abi.c_double_p]
+    L.nxs_dyn_put_coupled.argtypes = [H, P(_abi.Coupled)]
+    L.nxs_dyn_get_coupled.argtypes = [H, P(_abi.Coupled)]
     L.nxs_dyn_ice_diagnostics.argtypes = [H, P(_abi.IceDiag), P(C.c_void_p)]
     L.nxs_dyn_step.argtypes = [H]
     L.nxs_dyn_explicit_solve.argtypes = [H]
@@ -117,6 +120,7 @@ EXPORTS = (
     "nxs_dyn_set_params", "nxs_dyn_set_mesh", "nxs_dyn_set_halo", "nxs_dyn_comm_unique_id", "nxs_dyn_comm_init", "nxs_dyn_comm_selftest",
     "nxs_dyn_put_state", "nxs_dyn_get_state", "nxs_dyn_set_forcing", "nxs_dyn_set_forcing_pair", "nxs_dyn_set_forcing_time",
     "nxs_dyn_get_diag", "nxs_dyn_ice_diagnostics", "nxs_dyn_step",
+    "nxs_dyn_set_wave_stress", "nxs_dyn_put_coupled", "nxs_dyn_get_coupled",
     "nxs_dyn_explicit_solve", "nxs_dyn_update", "nxs_dyn_synchronize", "nxs_dyn_step_host",
     "nxs_dyn_check_regridding", "nxs_dyn_check_fields_fast", "nxs_dyn_get_timing", "nxs_dyn_get_step_times", "nxs_dyn_get_traffic_model", "nxs_dyn_set_option",
     "nxs_dyn_debug_array", "nxs_dyn_get_branch_trace", "nxs_mesh_connectivity", "nxs_mesh_element_connectivity", "nxs_calc_cohesion",
@@ -367,6 +371,50 @@ class FiniteElementDynamics:
         fa = (C.c_double * 3)(*factor) if factor is not None else None
         bi = (C.c_double * 3)(*bias) if bias is not None else None
         self._chk(self.L.nxs_dyn_set_forcing_time(self.h, float(fcoeff0), float(fcoeff1), fa, bi))
+
+    # ---- the coupled build's terms (#ifdef OASIS in the reference) ----
+    def set_wave_stress(self, tau_wi):
+        """M_tau_wi ([2*Nn], u then v): the wave radiation stress explicitSolve() adds to the wind stress (FE.cpp:10509-10518).  None detaches it."""
+        if tau_wi is None:
+            self._chk(self.L.nxs_dyn_set_wave_stress(self.h, None))
+            return
+        a = np.ascontiguousarray(tau_wi, np.float64)
+        if a.shape != (2 * self.lm.num_nodes,):
+            raise ValueError(f"tau_wi has shape {a.shape}, expected ({2 * self.lm.num_nodes},)")
+        self._chk(self.L.nxs_dyn_set_wave_stress(self.h, _abi.dptr(a)))
+
+    def put_coupled(self, cum_damage=None, conc_fsd=None):
+        """M_cum_damage ([Ne]) and M_conc_fsd ([num_fsd_bins, Ne], bin-major) to the device; what is given is carried by the following steps
+        (FE.cpp:4233-4238, 3991-3994), what is None is detached."""
+        c = _abi.Coupled()
+        Ne = self.lm.num_elements
+        if cum_damage is not None:
+            cd = np.ascontiguousarray(cum_damage, np.float64)
+            if cd.shape != (Ne,):
+                raise ValueError(f"cum_damage has shape {cd.shape}, expected ({Ne},)")
+            c.cum_damage = _abi.dptr(cd)
+        if conc_fsd is not None:
+            cf = np.ascontiguousarray(conc_fsd, np.float64)
+            if cf.ndim != 2 or cf.shape[1] != Ne:
+                raise ValueError(f"conc_fsd has shape {cf.shape}, expected (num_fsd_bins, {Ne})")
+            c.conc_fsd = _abi.dptr(cf)
+            c.num_fsd_bins = cf.shape[0]
+        self._chk(self.L.nxs_dyn_put_coupled(self.h, C.byref(c)))
+
+    def get_coupled(self, cum_damage: bool = True, num_fsd_bins: int = 0) -> dict:
+        """{'cum_damage': [Ne]} and / or {'conc_fsd': [num_fsd_bins, Ne]} from the device; asking for a member that is not attached is an error."""
+        c = _abi.Coupled()
+        out = {}
+        Ne = self.lm.num_elements
+        if cum_damage:
+            out["cum_damage"] = np.empty(Ne)
+            c.cum_damage = _abi.dptr(out["cum_damage"])
+        if num_fsd_bins > 0:
+            out["conc_fsd"] = np.empty((num_fsd_bins, Ne))
+            c.conc_fsd = _abi.dptr(out["conc_fsd"])
+            c.num_fsd_bins = num_fsd_bins
+        self._chk(self.L.nxs_dyn_get_coupled(self.h, C.byref(c)))
+        return out
 
     def get_state(self) -> dict:
         Nn, Ne = self.lm.num_nodes, self.lm.num_elements

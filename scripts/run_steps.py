@@ -8,6 +8,7 @@ ap.add_argument("--opt", action="append", default=[], help="key=value for set_op
 ap.add_argument("--torch-first", action="store_true"); ap.add_argument("--graph", type=int, default=1)
 ap.add_argument("--fused", type=int, default=3); ap.add_argument("--patch-nodes", type=int, default=0); ap.add_argument("--nt", type=int, default=-1); ap.add_argument("--ring", type=int, default=0); ap.add_argument("--pair-nodes", type=int, default=0); ap.add_argument("--depth", type=int, default=0); ap.add_argument("--shape-mem", type=int, default=-1); ap.add_argument("--compare-fused", type=int, default=-1, help="also run with this value of option fused and compare the states bit for bit")
 ap.add_argument("--nparts", type=int, default=1, help="partitions of the mesh (with --rank and --loopback: one rank's partition stepped alone, for counter collection)")
+ap.add_argument("--coupled", type=int, default=0, help="N > 0: the coupled build's terms attached -- M_cum_damage, a wave stress of 0.1 N m-2 and N floe-size bins (the issue's measurement: 12)")
 ap.add_argument("--rank", type=int, default=0); ap.add_argument("--loopback", action="store_true", help="several partitions: this rank's mailboxes connected to themselves (dynamics.ipc_loopback)")
 a = ap.parse_args()
 if a.torch_first:
@@ -31,11 +32,14 @@ if a.nparts > 1:
     for kv in a.opt: fe.set_option(kv.split("=")[0], int(kv.split("=")[1]))   # (fused / halo_fused again: set_mesh and the transport are in place now)
     fe.set_option("prepare", 1)
 fe.put_state(f); fe.set_forcing(f)
+if a.coupled > 0:
+    import numpy as np
+    fe.put_coupled(cum_damage=np.zeros(lm.num_elements), conc_fsd=np.full((a.coupled, lm.num_elements), 0.05)); fe.set_wave_stress(np.full(2 * lm.num_nodes, 0.1))
 fe.step(); fe.synchronize(); fe.set_option("timing_reset", 1)
 t = time.perf_counter()
 for _ in range(a.steps): fe.step()
 fe.synchronize(); dt = time.perf_counter() - t
-print(f"shape_mem={a.shape_mem} ring={a.ring} nt={a.nt} fused={a.fused} patch_nodes={a.patch_nodes} {a.mesh}: {lm.num_elements} triangles, {a.steps} steps, {dt/a.steps*1e3:.3f} ms/step, {lm.num_elements*120*a.steps/dt:.4e} element-updates/s, timing {fe.timing()}, crash {fe.checkFieldsFast()}", flush=True)
+print(f"shape_mem={a.shape_mem} ring={a.ring} nt={a.nt} fused={a.fused} patch_nodes={a.patch_nodes} {a.mesh}: {lm.num_elements} triangles, {a.steps} steps, {dt/a.steps*1e3:.3f} ms/step, {lm.num_elements*120*a.steps/dt:.4e} element-updates/s, timing {fe.timing()}, crash {fe.checkFieldsFast()}, coupled {a.coupled}, traffic {fe.traffic_model()}", flush=True)
 if a.compare_fused >= 0:
     import numpy as np
     fe2 = dynamics.FiniteElementDynamics(p); fe2.set_option("fused", a.compare_fused); fe2.set_mesh(lm); fe2.put_state(f); fe2.set_forcing(f)
