@@ -24,6 +24,7 @@
  *   M_surface, D_tau_a, D_tau_w, ...            nxs_dyn_get_diag
  *   #ifdef OASIS: M_tau_wi in explicitSolve()   nxs_dyn_set_wave_stress (FE.cpp:10353-10354, 10408-10414, 10509-10518)
  *   #ifdef OASIS: M_cum_damage, M_conc_fsd      nxs_dyn_put_coupled / nxs_dyn_get_coupled (FE.cpp:4233-4238, 3991-3994)
+ *   updateMeans(M_moorings, time_factor)        nxs_dyn_means_update    (FE.cpp:8518-9024; configure / get / to_grid / reset beside it)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -368,6 +369,97 @@ NXS_API int nxs_dyn_get_diag(nxs_dyn_handle *h, nxs_dyn_diag *d);
  * or nxs_dyn_set_mesh) -- the layout nxs_interp_mesh_to_grid_device samples, so a Moorings record needs no round trip of the state. */
 NXS_API int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *d, const double **device_rows);
 
+/* ---- Moorings time means on the device: updateMeans() (FE.cpp:8518-9024), GridOutput::updateGridMean() on the regular grid (model/gridoutput.cpp:387-550),
+ * resetMeshMean().  checkOutputs() calls updateIceDiagnostics() and updateMoorings() after EVERY step (FE.cpp:8316-8327, 9403-9408); with moorings.snapshot=false
+ * that is updateMeans(M_moorings, mooring_time_factor): data_mesh[i] += field[i] * time_factor into one mesh accumulator per output variable.  The accumulators
+ * live here as interleaved rows ([Ne][n_el] and [Nn][n_nod], the layout nxs_interp_mesh_to_grid_device samples), one launch per kind and step updates them, and
+ * nxs_dyn_means_to_grid samples them at output time -- the state never crosses PCIe for a time-mean Moorings file.
+ * The identifiers are named after GridOutput::variableID (model/gridoutput.hpp) and cover the variables whose sources the handle holds.
+ * OUT OF SCOPE (the host keeps summing those itself): variables whose sources never reach the handle -- thermodynamic fields, fluxes, atmosphere and ocean forcing
+ * other than the wind, age, melt ponds, the *_rplnt_* / *_mlt_* multi-year-ice terms --, loaded (non-regular) grids, ConservativeRemappingMeshToGrid,
+ * rotateVectors, the land-sea mask, and the coupler's means (M_cpl_out). */
+enum nxs_means_var {
+    /* elemental: accumulated over the owned elements i < M_local_nelements, the rows of ghost elements stay 0 (FE.cpp:8527) */
+    NXS_MEANS_CONC = 0,           /* FE.cpp:8526  D_conc */
+    NXS_MEANS_THICK = 1,          /* FE.cpp:8531  D_thick */
+    NXS_MEANS_SNOW = 2,           /* FE.cpp:8546  D_snow_thick */
+    NXS_MEANS_CONC_CONS = 3,      /* FE.cpp:8586  M_conc */
+    NXS_MEANS_DAMAGE = 4,         /* FE.cpp:8536  M_damage */
+    NXS_MEANS_RIDGE_RATIO = 5,    /* FE.cpp:8541  M_ridge_ratio */
+    NXS_MEANS_CONC_YOUNG = 6,     /* FE.cpp:8581  M_conc_young */
+    NXS_MEANS_H_YOUNG = 7,        /* FE.cpp:8591  M_h_young */
+    NXS_MEANS_HS_YOUNG = 8,       /* FE.cpp:8596  M_hs_young */
+    NXS_MEANS_CONC_MYI = 9,       /* FE.cpp:8632  M_conc_myi */
+    NXS_MEANS_THICK_MYI = 10,     /* FE.cpp:8636  M_thick_myi */
+    NXS_MEANS_DCI_RIDGE_MYI = 11, /* FE.cpp:8660  D_del_ci_ridge_myi */
+    NXS_MEANS_SIGMA_11 = 12,      /* FE.cpp:8682  M_sigma[0] */
+    NXS_MEANS_SIGMA_22 = 13,      /* FE.cpp:8686  M_sigma[1] */
+    NXS_MEANS_SIGMA_12 = 14,      /* FE.cpp:8691  M_sigma[2] */
+    NXS_MEANS_SIGMA_N = 15,       /* FE.cpp:8741  D_sigma[0] */
+    NXS_MEANS_SIGMA_S = 16,       /* FE.cpp:8746  D_sigma[1] */
+    NXS_MEANS_DIVERGENCE = 17,    /* FE.cpp:8751  D_divergence */
+    NXS_MEANS_DRAG_UI = 18,       /* FE.cpp:8756-8766  M_drag_ui, concentration-weighted with M_drag_ui_young in the young-ice category */
+    NXS_MEANS_ICE_MASK = 19,      /* FE.cpp:8912-8920  += 1 where M_thick (+ M_h_young) > 0 -- NOT multiplied by time_factor */
+    NXS_MEANS_ELEMENTAL_END = 20,
+    /* nodal: accumulated over all M_num_nodes, ghosts included */
+    NXS_MEANS_VT_X = 64,          /* FE.cpp:8931  M_VT[i] */
+    NXS_MEANS_VT_Y = 65,          /* FE.cpp:8936  M_VT[i + M_num_nodes] */
+    NXS_MEANS_WIND_X = 66,        /* FE.cpp:8941  M_wind[i] */
+    NXS_MEANS_WIND_Y = 67,        /* FE.cpp:8946 */
+    NXS_MEANS_TAU_AX = 68,        /* FE.cpp:8951  D_tau_a[i] */
+    NXS_MEANS_TAU_AY = 69,        /* FE.cpp:8956 */
+    NXS_MEANS_TAUWIX = 70,        /* FE.cpp:8962  M_tau_wi[i]: needs a wave stress attached (nxs_dyn_set_wave_stress) */
+    NXS_MEANS_TAUWIY = 71,        /* FE.cpp:8966 */
+    NXS_MEANS_TAUX = 72,          /* FE.cpp:8974-9020  D_tau_w and the area-weighted means of D_tau_ow and M_conc over NodalElementConnectivity: */
+    NXS_MEANS_TAUY = 73,          /*                   needs nxs_dyn_means_set_tau_ow */
+    NXS_MEANS_TAUMOD = 74,
+    NXS_MEANS_NODAL_END = 75
+};
+#define NXS_MEANS_NODAL_BEGIN 64
+#define NXS_MEANS_MAX_VARS 24   /* entries per list (the list travels to the kernel by value; a workgroup stages 256 rows of it in LDS) */
+
+typedef struct nxs_dyn_means_config {
+    int32_t num_elemental;          /* M_elemental_variables.size(), <= NXS_MEANS_MAX_VARS; 0 in both lists = the feature off, buffers freed */
+    int32_t num_nodal;              /* M_nodal_variables.size() */
+    const int32_t *elemental_ids;   /* [num_elemental] NXS_MEANS_* : the column order of the elemental rows */
+    const uint8_t *elemental_mask;  /* [num_elemental] Variable::mask (NULL = none): zeroed on the grid where ice_mask <= 0 (gridoutput.cpp:404-414) */
+    const int32_t *nodal_ids;       /* [num_nodal] */
+    const uint8_t *nodal_mask;      /* [num_nodal] */
+} nxs_dyn_means_config;
+
+/* the regular grid of GridOutput (gridoutput.cpp:496-504): M_xmin, M_ymax, M_mooring_spacing, M_ncols (along x), M_nrows (along y), M_miss_val */
+typedef struct nxs_dyn_means_grid {
+    double xmin, ymax, mooring_spacing;
+    double miss_val;
+    int32_t ncols, nrows;
+} nxs_dyn_means_grid;
+
+/*   nxs_dyn_means_configure  the two lists (copied).  The configuration survives nxs_dyn_set_mesh: the accumulators are re-sized and zeroed there, which is
+ *                  resetMeshMean(bamgmesh, regrid = true, ...).  NXS_ERR_INVALID: an unknown id, an elemental id in the nodal list or the reverse, more than
+ *                  NXS_MEANS_MAX_VARS entries, a mask flag without NXS_MEANS_ICE_MASK among the elemental ids.  A refused configuration leaves the previous one.
+ *   nxs_dyn_means_set_tau_ow  D_tau_ow ([Ne], written by the thermodynamics): the one input of taux / tauy / taumod that is not the handle's; uploaded like
+ *                  a forcing member, NULL detaches.  nxs_dyn_set_mesh detaches it (the size changes).
+ *   nxs_dyn_means_update   updateMeans(means, time_factor): one launch over the owned elements, one over the nodes; asynchronous on the handle's stream.  It
+ *                  includes the part of updateIceDiagnostics() the configured ids need (no nxs_dyn_ice_diagnostics call first) and only READS state and
+ *                  diagnostics.  NXS_ERR_STATE: before nxs_dyn_set_mesh / nxs_dyn_put_state, nothing configured, tauwix / tauwiy without a wave stress
+ *                  attached, taux / tauy / taumod without tau_ow attached.
+ *   nxs_dyn_means_get      synchronised on return.  elemental [Ne][num_elemental], nodal [Nn][num_nodal] host arrays (either may be NULL);
+ *                  *elemental_dev / *nodal_dev (either may be NULL) receive the DEVICE pointers of the same interleaved rows (library-owned, valid until
+ *                  nxs_dyn_means_configure / nxs_dyn_set_mesh; NULL for an empty list).
+ *   nxs_dyn_means_to_grid  updateGridMean() on the regular grid: the coordinates displaced by the device's M_UM; with nodal variables the reference's setProcMask
+ *                  (one elemental column, 1 on owned elements, 0 on ghosts, sampled with default 0); both row sets sampled with InterpFromMeshToGridx
+ *                  semantics (nxs_interp_mesh_to_grid_device, default value 0); transposed as gridoutput.cpp:526-537 (grid_ind = i + ncols * j) and ADDED to
+ *                  the caller's grid_elemental [num_elemental][ncols * nrows] / grid_nodal [num_nodal][ncols * nrows] (nodal values times the proc mask);
+ *                  then the ice-mask rule on the variables with `mask`.  Summing the ranks' grids (boost::mpi::reduce, FE.cpp:9476-9487) stays with the caller.
+ *   nxs_dyn_means_reset    resetMeshMean(bamgmesh): zeroes both accumulators on the stream. */
+NXS_API int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c);
+NXS_API int nxs_dyn_means_set_tau_ow(nxs_dyn_handle *h, const double *tau_ow /* [Ne] D_tau_ow, NULL = detach */);
+NXS_API int nxs_dyn_means_update(nxs_dyn_handle *h, double time_factor);
+NXS_API int nxs_dyn_means_get(nxs_dyn_handle *h, double *elemental /* [Ne][n_el] */, double *nodal /* [Nn][n_nod] */, const double **elemental_dev,
+                              const double **nodal_dev);
+NXS_API int nxs_dyn_means_to_grid(nxs_dyn_handle *h, const nxs_dyn_means_grid *g, double *grid_elemental, double *grid_nodal);
+NXS_API int nxs_dyn_means_reset(nxs_dyn_handle *h);
+
 /* One dynamics step on the device-resident state: FE.cpp:8197-8214.  Asynchronous on the
  * handle's stream; nxs_dyn_synchronize() waits for it. */
 NXS_API int nxs_dyn_step(nxs_dyn_handle *h);
@@ -508,6 +600,11 @@ NXS_API int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t);
  *                  bits.  -1 (default) / 1 = on, 0 = one launch per sweep
  *   "ipc_pad"      before nxs_dyn_ipc_export: the mailbox gets room for at least this many received nodes (profiling aid: a rank whose mailbox is connected
  *                  to itself stores its own, possibly longer, send segments into it)
+ *   "means_stage"  the read-modify-write of the Moorings accumulators (nxs_dyn_means_update): 1 (default) = a workgroup's rows staged through LDS and
+ *                  added as one contiguous stream of 16-byte accesses; 0 = every thread walks its own row in 16-byte accesses (rows of an even number of
+ *                  variables; 8-byte otherwise).  The same bits; scripts/time_means.py times both
+ *   "means_timing" 1 = nxs_dyn_means_update records events around its two launches; nxs_dyn_debug_array "means_update_ms" returns their device times
+ *                  [elemental, nodal] in ms.  Default 0
  *   "ipc_delay", "halo_one_directional"   test doors of the exchange protocols, see NXS_DELAY_* above */
 NXS_API int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value);
 

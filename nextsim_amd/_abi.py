@@ -134,6 +134,26 @@ class Coupled(C.Structure):   # nxs_dyn_coupled
     _fields_ = [("cum_damage", c_double_p), ("conc_fsd", c_double_p), ("num_fsd_bins", C.c_int32), ("reserved0", C.c_int32)]
 
 
+# enum nxs_means_var: the Moorings variables nxs_dyn_means_* accumulates, named after GridOutput::variableID
+MEANS_ELEMENTAL = ("conc", "thick", "snow", "conc_cons", "damage", "ridge_ratio", "conc_young", "h_young", "hs_young", "conc_myi", "thick_myi",
+                   "dci_ridge_myi", "sigma_11", "sigma_22", "sigma_12", "sigma_n", "sigma_s", "divergence", "drag_ui", "ice_mask")
+MEANS_NODAL = ("VT_x", "VT_y", "wind_x", "wind_y", "tau_ax", "tau_ay", "tauwix", "tauwiy", "taux", "tauy", "taumod")
+NXS_MEANS_NODAL_BEGIN = 64
+NXS_MEANS_MAX_VARS = 24
+MEANS_ID = {k: i for i, k in enumerate(MEANS_ELEMENTAL)}
+MEANS_ID.update({k: NXS_MEANS_NODAL_BEGIN + i for i, k in enumerate(MEANS_NODAL)})
+
+
+class MeansConfig(C.Structure):   # nxs_dyn_means_config
+    _fields_ = [("num_elemental", C.c_int32), ("num_nodal", C.c_int32), ("elemental_ids", c_int32_p), ("elemental_mask", c_uint8_p),
+                ("nodal_ids", c_int32_p), ("nodal_mask", c_uint8_p)]
+
+
+class MeansGrid(C.Structure):   # nxs_dyn_means_grid
+    _fields_ = [("xmin", C.c_double), ("ymax", C.c_double), ("mooring_spacing", C.c_double), ("miss_val", C.c_double),
+                ("ncols", C.c_int32), ("nrows", C.c_int32)]
+
+
 ICE_DIAG = ("D_conc", "D_thick", "D_snow_thick", "D_sigma0", "D_sigma1", "D_divergence")
 
 

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "nxs_dyn.h"
+#include "nxs_interp.h"
 #include "nxs_guard.hpp"
 #include "nxs_patchcut.hpp"
 #include "nxs_resident_registry.hpp"
@@ -217,6 +218,19 @@ struct nxs_dyn_handle {
     double *d_vt3 = nullptr;
     double *d_icediag = nullptr;           // [Ne][NXS_ICE_DIAG_FIELDS] rows of nxs_dyn_ice_diagnostics (state pool: goes with the mesh)
     double *d_icediag_soa = nullptr;       // [NXS_ICE_DIAG_FIELDS][Ne] the same per field, made when the host asks for its vectors
+    // the Moorings time means (nxs_dyn_means_*): the configuration is the handle's and survives set_mesh; the buffers are in the state pool and go with the mesh
+    std::vector<int> means_ids[2];                 // [0] elemental, [1] nodal: NXS_MEANS_* in column order
+    std::vector<unsigned char> means_mask[2];      // Variable::mask per column
+    int means_ice_mask_col = -1;                   // the elemental column that holds NXS_MEANS_ICE_MASK (M_ice_mask_indx); -1: none
+    MeansTable means_tab[2] = {};                  // what the two kernels receive by value
+    double *d_means[2] = {nullptr, nullptr};       // [Ne][n_el], [Nn][n_nod] interleaved accumulators
+    double *d_means_pm = nullptr;                  // [Ne] setProcMask's column: 1 on owned elements, 0 on ghosts
+    double *d_tau_ow = nullptr;                    // [Ne] D_tau_ow as nxs_dyn_means_set_tau_ow uploaded it
+    bool tau_ow_attached = false;
+    int means_timing = 0;                          // option "means_timing": events around the two launches of nxs_dyn_means_update (nxs_dyn_debug_array "means_update_ms")
+    hipEvent_t means_ev[3] = {nullptr, nullptr, nullptr};
+    bool means_timed = false;
+    int means_stage = 1;                           // option "means_stage": the rows' read-modify-write staged through LDS (1) or walked by each thread (0)
     int sig_loc = 0;                       // where M_sigma / M_damage are current: 0 = the state arrays, 1 = the records in S4a (left there by
                                            // the fused sub-step loop; k_update works on them, the arrays follow on demand: ensure_arrays)
     int trace_branches = 0;                // option "trace_branches": the per-loop kernels keep the branch trace of updateSigmaDamage (dw.trace)
@@ -1477,6 +1491,67 @@ int explicit_solve(nxs_dyn_handle *h) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
+// ---- the Moorings time means (include/nxs_dyn.h, nxs_dyn_means_*)
+// one buffer out of a pool (nxs_dyn_means_configure re-sizes the accumulators between two meshes; a set-up call like set_option: frees are allowed there)
+static void pool_free_one(std::vector<void *> &pool, void *p) {
+    if (!p) return;
+    auto it = std::find(pool.begin(), pool.end(), p);
+    if (it != pool.end()) pool.erase(it);
+    (void)hipFree(p);
+}
+static void means_drop_buffers(nxs_dyn_handle *h) {
+    for (double *&q : h->d_means) { pool_free_one(h->state_allocs, q); q = nullptr; }
+    pool_free_one(h->state_allocs, h->d_means_pm); h->d_means_pm = nullptr;
+}
+// the accumulators of the current configuration at the current mesh's sizes, zeroed; the proc-mask column when there are nodal variables (gridoutput.cpp:391-395)
+static int means_make_buffers(nxs_dyn_handle *h) {
+    const size_t len[2] = {(size_t)h->dm.Ne, (size_t)h->dm.Nn};
+    for (int k = 0; k < 2; ++k) {
+        const size_t n = h->means_ids[k].size();
+        if (!n) continue;
+        int rc = dev_alloc(h, h->state_allocs, &h->d_means[k], len[k] * n);
+        if (rc) return rc;
+        HIPCHK(h, hipMemsetAsync(h->d_means[k], 0, len[k] * n * sizeof(double), h->stream));
+    }
+    if (!h->means_ids[1].empty()) {
+        int rc = dev_alloc(h, h->state_allocs, &h->d_means_pm, len[0]);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_means_proc_mask, dim3(nblocks(h->dm.Ne)), dim3(BLOCK), 0, h->stream, h->dm.Ne, h->dm.Neo, h->d_means_pm);
+        HIPCHK(h, hipGetLastError());
+    }
+    return NXS_OK;
+}
+// the source fields an elemental / a nodal list needs (MS_* / MN_*): each is loaded once per element / node
+static unsigned means_sources(int kind, const std::vector<int> &ids, bool young_cat) {
+    unsigned src = 0;
+    for (int id : ids) {
+        if (kind == 0) switch (id) {
+            case NXS_MEANS_CONC: src |= MS_CONC | (young_cat ? MS_CYOUNG : 0); break;
+            case NXS_MEANS_THICK: src |= MS_THICK | (young_cat ? MS_HYOUNG : 0); break;
+            case NXS_MEANS_SNOW: src |= MS_SNOW | (young_cat ? MS_HSYOUNG : 0); break;
+            case NXS_MEANS_CONC_CONS: src |= MS_CONC; break;
+            case NXS_MEANS_DAMAGE: src |= MS_DAMAGE; break;
+            case NXS_MEANS_RIDGE_RATIO: src |= MS_RIDGE; break;
+            case NXS_MEANS_CONC_YOUNG: src |= MS_CYOUNG; break;
+            case NXS_MEANS_H_YOUNG: src |= MS_HYOUNG; break;
+            case NXS_MEANS_HS_YOUNG: src |= MS_HSYOUNG; break;
+            case NXS_MEANS_CONC_MYI: src |= MS_CMYI; break;
+            case NXS_MEANS_THICK_MYI: src |= MS_TMYI; break;
+            case NXS_MEANS_DCI_RIDGE_MYI: src |= MS_DEL; break;
+            case NXS_MEANS_SIGMA_11: case NXS_MEANS_SIGMA_22: case NXS_MEANS_SIGMA_12: case NXS_MEANS_SIGMA_N: case NXS_MEANS_SIGMA_S: src |= MS_SIGMA; break;
+            case NXS_MEANS_DIVERGENCE: src |= MS_DIV; break;
+            case NXS_MEANS_DRAG_UI: src |= MS_DRAG | (young_cat ? MS_DRAGY | MS_CONC | MS_CYOUNG : 0); break;
+            case NXS_MEANS_ICE_MASK: src |= MS_THICK | (young_cat ? MS_HYOUNG : 0); break;
+        } else switch (id) {
+            case NXS_MEANS_VT_X: case NXS_MEANS_VT_Y: src |= MN_VT; break;
+            case NXS_MEANS_WIND_X: case NXS_MEANS_WIND_Y: src |= MN_WIND; break;
+            case NXS_MEANS_TAU_AX: case NXS_MEANS_TAU_AY: src |= MN_TAUA; break;
+            case NXS_MEANS_TAUWIX: case NXS_MEANS_TAUWIY: src |= MN_TAUWI; break;
+            case NXS_MEANS_TAUX: case NXS_MEANS_TAUY: case NXS_MEANS_TAUMOD: src |= MN_WIND | MN_TAUW | MN_GATHER; break;
+        }
+    }
+    return src;
+}
 extern "C" {
 
 int nxs_dyn_abi_version(void) { return NXS_DYN_ABI_VERSION; }
@@ -1608,6 +1683,7 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     if (h->d_dp) (void)hipFree(h->d_dp);
     for (auto &set : h->ev) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
     for (auto &set : h->ev_flush) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : h->means_ev) if (ev) (void)hipEventDestroy(ev);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return NXS_OK;
@@ -1744,6 +1820,12 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
         h->ipc_pad = (int)value; return NXS_OK;
     }
     if (!std::strcmp(key, "pin_host")) { h->pin_host = value != 0; if (!h->pin_host) unpin_all(h); return NXS_OK; }
+    if (!std::strcmp(key, "means_stage")) { h->means_stage = value != 0; return NXS_OK; }
+    if (!std::strcmp(key, "means_timing")) {
+        h->means_timing = value != 0; h->means_timed = false;
+        if (h->means_timing) { HIPCHK(h, hipSetDevice(h->device)); for (auto &ev : h->means_ev) if (!ev) HIPCHK(h, hipEventCreate(&ev)); }
+        return NXS_OK;
+    }
     if (!std::strcmp(key, "halo_fused")) { h->halo_fused = value != 0; release_graph(h); return NXS_OK; }
     if (!std::strcmp(key, "patch_nodes")) {
         if (value != 0 && (value < 64 || value > 1024)) return fail(h, NXS_ERR_INVALID, "patch_nodes must be 0 (auto) or in [64,1024]");
@@ -1914,6 +1996,7 @@ int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
     DevWork &w = h->dw;
     s = DevState{}; w = DevWork{};
     h->d_icediag = nullptr; h->d_icediag_soa = nullptr;
+    h->d_means[0] = h->d_means[1] = h->d_means_pm = h->d_tau_ow = nullptr; h->tau_ow_attached = false;   // (freed with the state pool above)
     auto &P = h->state_allocs;
     const size_t n2 = 2 * (size_t)Nn, ne = Ne;
 #define A(ptr, cnt) if ((rc = dev_alloc(h, P, &(ptr), (cnt)))) return rc
@@ -1945,6 +2028,7 @@ int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
     HIPCHK(h, hipMalloc((void **)&h->d_partials, sizeof(RegridPartial) * h->n_partials));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if ((rc = upload_patches(h))) return rc;
+    if ((rc = means_make_buffers(h))) return rc;   // resetMeshMean(bamgmesh, regrid = true, ...): the configured accumulators at the new sizes, zeroed
     h->have_mesh = true;
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_set_mesh"); }
@@ -2617,6 +2701,196 @@ int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *dg, const doubl
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_ice_diagnostics"); }
 
+// ---- the Moorings time means: updateMeans (FE.cpp:8518-9024), updateGridMean on the regular grid (gridoutput.cpp:387-550), resetMeshMean
+int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) try {
+    if (!h || !c) return NXS_ERR_INVALID;
+    if (c->num_elemental < 0 || c->num_nodal < 0 || c->num_elemental > NXS_MEANS_MAX_VARS || c->num_nodal > NXS_MEANS_MAX_VARS)
+        return fail(h, NXS_ERR_INVALID, "means_configure: %d elemental and %d nodal variables (0..%d each)", c->num_elemental, c->num_nodal, NXS_MEANS_MAX_VARS);
+    if ((c->num_elemental > 0 && !c->elemental_ids) || (c->num_nodal > 0 && !c->nodal_ids)) return fail(h, NXS_ERR_INVALID, "means_configure: an id list is NULL");
+    std::vector<int> ids[2] = {std::vector<int>(c->elemental_ids, c->elemental_ids + c->num_elemental), std::vector<int>(c->nodal_ids, c->nodal_ids + c->num_nodal)};
+    std::vector<unsigned char> mask[2] = {std::vector<unsigned char>(ids[0].size(), 0), std::vector<unsigned char>(ids[1].size(), 0)};
+    if (c->elemental_mask) for (size_t k = 0; k < ids[0].size(); ++k) mask[0][k] = c->elemental_mask[k] ? 1 : 0;
+    if (c->nodal_mask) for (size_t k = 0; k < ids[1].size(); ++k) mask[1][k] = c->nodal_mask[k] ? 1 : 0;
+    int ice_col = -1;
+    bool any_mask = false;
+    for (size_t k = 0; k < ids[0].size(); ++k) {
+        if (ids[0][k] < 0 || ids[0][k] >= NXS_MEANS_ELEMENTAL_END)
+            return fail(h, NXS_ERR_INVALID, "means_configure: elemental_ids[%d] = %d is not an elemental NXS_MEANS_* id", (int)k, ids[0][k]);
+        if (ids[0][k] == NXS_MEANS_ICE_MASK && ice_col < 0) ice_col = (int)k;
+        any_mask = any_mask || mask[0][k];
+    }
+    for (size_t k = 0; k < ids[1].size(); ++k) {
+        if (ids[1][k] < NXS_MEANS_NODAL_BEGIN || ids[1][k] >= NXS_MEANS_NODAL_END)
+            return fail(h, NXS_ERR_INVALID, "means_configure: nodal_ids[%d] = %d is not a nodal NXS_MEANS_* id", (int)k, ids[1][k]);
+        any_mask = any_mask || mask[1][k];
+    }
+    if (any_mask && ice_col < 0) return fail(h, NXS_ERR_INVALID, "means_configure: a variable has `mask` set but NXS_MEANS_ICE_MASK is not among the elemental ids");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));
+    means_drop_buffers(h);
+    for (int k = 0; k < 2; ++k) { h->means_ids[k] = ids[k]; h->means_mask[k] = mask[k]; }
+    h->means_ice_mask_col = ice_col;
+    if (h->have_mesh) { int rc = means_make_buffers(h); if (rc) return rc; }
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_means_configure"); }
+
+int nxs_dyn_means_set_tau_ow(nxs_dyn_handle *h, const double *tau_ow) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "means_set_tau_ow before set_mesh");
+    if (!tau_ow) { h->tau_ow_attached = false; return NXS_OK; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t Ne = h->dm.Ne;
+    int rc;
+    if (!h->d_tau_ow && (rc = dev_alloc(h, h->state_allocs, &h->d_tau_ow, Ne))) return rc;
+    pin_host_buffer(h, tau_ow, Ne * sizeof(double));
+    HIPCHK(h, hipMemcpyAsync(h->d_tau_ow, tau_ow, Ne * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->tau_ow_attached = true;
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_means_set_tau_ow"); }
+
+int nxs_dyn_means_update(nxs_dyn_handle *h, double time_factor) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "means_update needs set_mesh and put_state");
+    if (h->means_ids[0].empty() && h->means_ids[1].empty()) return fail(h, NXS_ERR_STATE, "means_update: no variable is configured (nxs_dyn_means_configure)");
+    for (int id : h->means_ids[1]) {
+        if ((id == NXS_MEANS_TAUWIX || id == NXS_MEANS_TAUWIY) && !wave_attached(h))
+            return fail(h, NXS_ERR_STATE, "means_update: tauwix / tauwiy are configured but no wave stress is attached (nxs_dyn_set_wave_stress)");
+        if ((id == NXS_MEANS_TAUX || id == NXS_MEANS_TAUY || id == NXS_MEANS_TAUMOD) && !h->tau_ow_attached)
+            return fail(h, NXS_ERR_STATE, "means_update: taux / tauy / taumod are configured but no D_tau_ow is attached (nxs_dyn_means_set_tau_ow)");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    // (the opt-in one-launch loops can give up half-way: never a mean of a half-made step without an error -- as nxs_dyn_ice_diagnostics; the default path stays asynchronous)
+    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    const int young = h->dp.young_cat ? 1 : 0;
+    for (int k = 0; k < 2; ++k) {
+        MeansTable &t = h->means_tab[k];
+        t = MeansTable{};
+        t.n = (int)h->means_ids[k].size();
+        t.src = means_sources(k, h->means_ids[k], young != 0);
+        for (int q = 0; q < t.n; ++q) t.id[q] = (unsigned char)(h->means_ids[k][q] - (k ? NXS_MEANS_NODAL_BEGIN : 0));
+    }
+    const bool stage = h->means_stage != 0;
+    if (h->means_timing) HIPCHK(h, hipEventRecord(h->means_ev[0], h->stream));
+    if (h->means_tab[0].n > 0 && h->dm.Neo > 0) {
+        const MeansTable &t = h->means_tab[0];
+        const double *S4 = h->sig_loc ? (const double *)h->ds.S4a : (const double *)nullptr;
+        if (stage) hipLaunchKernelGGL(k_means_elements<true>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), (size_t)BLOCK * t.n * sizeof(double), h->stream, h->dm, h->ds,
+                                      (const double *)h->dw.D_del, young, S4, t, time_factor, h->d_means[0]);
+        else hipLaunchKernelGGL(k_means_elements<false>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->dw.D_del, young, S4, t,
+                                time_factor, h->d_means[0]);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (h->means_timing) HIPCHK(h, hipEventRecord(h->means_ev[1], h->stream));
+    if (h->means_tab[1].n > 0) {
+        const MeansTable &t = h->means_tab[1];
+        if (stage) hipLaunchKernelGGL(k_means_nodes<true>, dim3(nblocks(h->dm.Nn)), dim3(BLOCK), (size_t)BLOCK * t.n * sizeof(double), h->stream, h->dm, h->ds,
+                                      (const double *)h->dw.D_tau_a, (const double *)h->dw.D_tau_w, h->dw.tau_wi, (const double *)h->d_tau_ow,
+                                      (const double *)h->dw.surface, t, time_factor, h->d_means[1]);
+        else hipLaunchKernelGGL(k_means_nodes<false>, dim3(nblocks(h->dm.Nn)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->dw.D_tau_a,
+                                (const double *)h->dw.D_tau_w, h->dw.tau_wi, (const double *)h->d_tau_ow, (const double *)h->dw.surface, t, time_factor, h->d_means[1]);
+        HIPCHK(h, hipGetLastError());
+    }
+    if (h->means_timing) { HIPCHK(h, hipEventRecord(h->means_ev[2], h->stream)); h->means_timed = true; }
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_means_update"); }
+
+int nxs_dyn_means_get(nxs_dyn_handle *h, double *elemental, double *nodal, const double **elemental_dev, const double **nodal_dev) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "means_get before set_mesh");
+    if (h->means_ids[0].empty() && h->means_ids[1].empty()) return fail(h, NXS_ERR_STATE, "means_get: no variable is configured (nxs_dyn_means_configure)");
+    HIPCHK(h, hipSetDevice(h->device));
+    double *dst[2] = {elemental, nodal};
+    const size_t len[2] = {(size_t)h->dm.Ne, (size_t)h->dm.Nn};
+    for (int k = 0; k < 2; ++k) {
+        const size_t bytes = len[k] * h->means_ids[k].size() * sizeof(double);
+        if (dst[k] && bytes) { pin_host_buffer(h, dst[k], bytes); HIPCHK(h, hipMemcpyAsync(dst[k], h->d_means[k], bytes, hipMemcpyDeviceToHost, h->stream)); }
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (elemental_dev) *elemental_dev = h->d_means[0];
+    if (nodal_dev) *nodal_dev = h->d_means[1];
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_means_get"); }
+
+int nxs_dyn_means_reset(nxs_dyn_handle *h) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "means_reset before set_mesh");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t len[2] = {(size_t)h->dm.Ne, (size_t)h->dm.Nn};
+    for (int k = 0; k < 2; ++k)
+        if (h->d_means[k]) HIPCHK(h, hipMemsetAsync(h->d_means[k], 0, len[k] * h->means_ids[k].size() * sizeof(double), h->stream));
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_means_reset"); }
+
+int nxs_dyn_means_to_grid(nxs_dyn_handle *h, const nxs_dyn_means_grid *g, double *grid_elemental, double *grid_nodal) try {
+    if (!h || !g) return NXS_ERR_INVALID;
+    if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "means_to_grid needs set_mesh and put_state");
+    const int n_el = (int)h->means_ids[0].size(), n_nod = (int)h->means_ids[1].size();
+    if (!n_el && !n_nod) return fail(h, NXS_ERR_STATE, "means_to_grid: no variable is configured (nxs_dyn_means_configure)");
+    if (g->ncols <= 0 || g->nrows <= 0 || !(g->mooring_spacing > 0.)) return fail(h, NXS_ERR_INVALID, "means_to_grid: ncols, nrows and mooring_spacing must be positive (gridoutput.cpp:488)");
+    if ((n_el && !grid_elemental) || (n_nod && !grid_nodal)) return fail(h, NXS_ERR_INVALID, "means_to_grid: a grid array is NULL for a configured list");
+    HIPCHK(h, hipSetDevice(h->device));
+    const int Nn = h->dm.Nn, Ne = h->dm.Ne;
+    // 1. the displaced coordinates, from the device's M_UM (gridoutput.cpp:442-447)
+    std::vector<double> um(2 * (size_t)Nn), x(Nn), y(Nn);
+    HIPCHK(h, hipMemcpyAsync(um.data(), h->ds.UM, um.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (also: the accumulators are complete before the sampling, which runs on the interpolation's own stream)
+    if (h->res_ready || h->flow_ready) { int rc = resident_error(h); if (rc) return rc; }
+    for (int i = 0; i < Nn; ++i) { x[i] = h->h_x0[i] + um[i]; y[i] = h->h_y0[i] + um[(size_t)i + Nn]; }
+    std::vector<int32_t> index(3 * (size_t)Ne);
+    for (int e = 0; e < Ne; ++e) for (int k = 0; k < 3; ++k) index[3 * (size_t)e + k] = h->h_t[k][e] + 1;
+    const size_t G = (size_t)g->ncols * g->nrows;
+    // InterpFromMeshToGridx(..., M_xmin, M_ymax, M_mooring_spacing, M_mooring_spacing, M_ncols, M_nrows, 0.) (gridoutput.cpp:496-504): bamg's "lines" run along x
+    auto sample = [&](const double *rows, int length, int nvar, std::vector<double> &out) -> int {
+        out.resize(G * nvar);
+        int rc = nxs_interp_mesh_to_grid_device(out.data(), index.data(), x.data(), y.data(), Nn, Ne, rows, length, nvar, g->xmin, g->ymax, g->mooring_spacing,
+                                                g->mooring_spacing, g->ncols, g->nrows, 0., h->device, nullptr);
+        if (rc) return fail(h, rc, "means_to_grid: %s", nxs_interp_last_error());
+        return NXS_OK;
+    };
+    std::vector<double> out, pm;
+    // 2. setProcMask (gridoutput.cpp:360-378), whenever there are nodal variables: M_proc_mask[grid_ind] = 0 + interp_out[bamg_ind]
+    if (n_nod) {
+        int rc = sample(h->d_means_pm, Ne, 1, out);
+        if (rc) return rc;
+        pm.assign(G, 0.);
+        size_t bamg_ind = 0;
+        for (int i = 0; i < g->ncols; ++i) for (int j = 0; j < g->nrows; ++j) { pm[i + (size_t)g->ncols * j] += out[bamg_ind]; ++bamg_ind; }
+    }
+    // 3.-5. sample, transpose (gridoutput.cpp:526-537) and add
+    if (n_el) {
+        int rc = sample(h->d_means[0], Ne, n_el, out);
+        if (rc) return rc;
+        for (int nv = 0; nv < n_el; ++nv) {
+            size_t bamg_ind = 0;
+            for (int i = 0; i < g->ncols; ++i) for (int j = 0; j < g->nrows; ++j) { grid_elemental[nv * G + i + (size_t)g->ncols * j] += out[n_el * bamg_ind + nv]; ++bamg_ind; }
+        }
+    }
+    if (n_nod) {
+        int rc = sample(h->d_means[1], Nn, n_nod, out);
+        if (rc) return rc;
+        for (int nv = 0; nv < n_nod; ++nv) {
+            size_t bamg_ind = 0;
+            for (int i = 0; i < g->ncols; ++i) for (int j = 0; j < g->nrows; ++j) {
+                const size_t grid_ind = i + (size_t)g->ncols * j;
+                grid_nodal[nv * G + grid_ind] += out[n_nod * bamg_ind + nv] * pm[grid_ind];
+                ++bamg_ind;
+            }
+        }
+    }
+    // 6. the ice mask (gridoutput.cpp:404-414): nodal variables first, then the elemental ones in their order
+    if (h->means_ice_mask_col >= 0) {
+        const double *ice = grid_elemental + (size_t)h->means_ice_mask_col * G;
+        for (int nv = 0; nv < n_nod; ++nv)
+            if (h->means_mask[1][nv])
+                for (size_t i = 0; i < G; ++i) if (ice[i] <= 0. && grid_nodal[nv * G + i] != g->miss_val) grid_nodal[nv * G + i] = 0.;
+        for (int nv = 0; nv < n_el; ++nv)
+            if (h->means_mask[0][nv])
+                for (size_t i = 0; i < G; ++i) if (ice[i] <= 0. && grid_elemental[nv * G + i] != g->miss_val) grid_elemental[nv * G + i] = 0.;
+    }
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_means_to_grid"); }
+
 // test door: the branch trace of updateSigmaDamage (option "trace_branches"), 4 words per element
 int nxs_dyn_get_branch_trace(nxs_dyn_handle *h, uint64_t *out, int64_t num_words) try {
     if (!h || !out) return NXS_ERR_INVALID;
@@ -2662,6 +2936,13 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
                 HIPCHK(h, hipStreamSynchronize(h->stream));
                 return NXS_OK;
             }
+    }
+    if (!std::strcmp(name, "means_update_ms")) {   // [2] device time of the last nxs_dyn_means_update with option "means_timing" 1: the elemental launch, the nodal launch
+        if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array means_update_ms has 2 entries");
+        if (!h->means_timed) return fail(h, NXS_ERR_STATE, "debug_array means_update_ms: no timed nxs_dyn_means_update (option means_timing)");
+        HIPCHK(h, hipEventSynchronize(h->means_ev[2]));
+        for (int k = 0; k < 2; ++k) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->means_ev[k], h->means_ev[k + 1])); out[k] = ms; }
+        return NXS_OK;
     }
     if (!std::strcmp(name, "shape_range")) {   // [1] the per-step range flag of the shared-reciprocal shape coefficients (raised by the prep kernels, lowered by k_update)
         if (n != 1) return fail(h, NXS_ERR_INVALID, "debug_array shape_range has 1 entry");

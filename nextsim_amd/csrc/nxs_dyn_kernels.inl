@@ -3193,17 +3193,13 @@ __global__ void __launch_bounds__(BLOCK) k_ghost_ring_move(DevMesh m, DevState s
     s.UT[n] = utu; s.UT[n + Nn] = utv;
 }
 
-// K14  updateIceDiagnostics(), FE.cpp:7860-7905: totals over the ice categories, principal stresses, divergence of M_VT on the mesh displaced by
-// M_UM (shapeCoeff, FE.cpp:1951-1964).  One [Ne][6] row per element (D_conc, D_thick, D_snow_thick, D_sigma0, D_sigma1, D_divergence), staged through
-// LDS so that the rows leave as one stream.  S4 != NULL: sigma lives in the records the sub-step loop left behind (k_pack_state's layout).
-__global__ void __launch_bounds__(BLOCK) k_ice_diagnostics(DevMesh m, DevState s, int young_cat, const double *__restrict__ S4, double *__restrict__ out) {
-    const int e = min(blockIdx.x * BLOCK + (int)threadIdx.x, m.Ne - 1);  // (threads past the end redo the last element: every thread reaches the barrier)
-    __shared__ double rows[BLOCK * 6];
-    double dc = s.conc[e], dt = s.thick[e], ds = s.snow[e];
-    if (young_cat) { dc += s.cyoung[e]; dt += s.hyoung[e]; ds += s.hsyoung[e]; }
-    double s0, s1, s2;
-    if (S4) { s0 = S4[4 * (size_t)e]; s1 = S4[4 * (size_t)e + 1]; s2 = S4[4 * (size_t)e + 2]; }
-    else { s0 = s.s0[e]; s1 = s.s1[e]; s2 = s.s2[e]; }
+// The arithmetic of updateIceDiagnostics() (FE.cpp:7860-7905) that k_ice_diagnostics and the Moorings means (k_means_elements) share -- one statement of it,
+// so that the two give the same bits: the principal stresses, and the divergence of M_VT on the mesh displaced by M_UM (shapeCoeff, FE.cpp:1951-1964).
+__device__ __forceinline__ void ice_diag_sigma(double s0, double s1, double s2, double &sigma_n, double &sigma_s) {
+    sigma_n = (s0 + s1) / 2.;
+    sigma_s = hypot((s0 - s1) / 2., s2);
+}
+__device__ __forceinline__ double ice_diag_divergence(const DevMesh &m, const DevState &s, int e) {
     double vx[3], vy[3];
     load_vertices(m, s.UM, e, vx, vy);
     const double jac = jacobian(vx, vy);
@@ -3215,12 +3211,236 @@ __global__ void __launch_bounds__(BLOCK) k_ice_diagnostics(DevMesh m, DevState s
         const double dxN = (vy[kp1] - vy[kp2]) / jac, dyN = (vx[kp2] - vx[kp1]) / jac;
         div += dxN * s.VT[n[j]] + dyN * s.VT[n[j] + m.Nn];
     }
+    return div;
+}
+
+// K14  updateIceDiagnostics(), FE.cpp:7860-7905: totals over the ice categories, principal stresses, divergence of M_VT on the mesh displaced by
+// M_UM (shapeCoeff, FE.cpp:1951-1964).  One [Ne][6] row per element (D_conc, D_thick, D_snow_thick, D_sigma0, D_sigma1, D_divergence), staged through
+// LDS so that the rows leave as one stream.  S4 != NULL: sigma lives in the records the sub-step loop left behind (k_pack_state's layout).
+__global__ void __launch_bounds__(BLOCK) k_ice_diagnostics(DevMesh m, DevState s, int young_cat, const double *__restrict__ S4, double *__restrict__ out) {
+    const int e = min(blockIdx.x * BLOCK + (int)threadIdx.x, m.Ne - 1);  // (threads past the end redo the last element: every thread reaches the barrier)
+    __shared__ double rows[BLOCK * 6];
+    double dc = s.conc[e], dt = s.thick[e], ds = s.snow[e];
+    if (young_cat) { dc += s.cyoung[e]; dt += s.hyoung[e]; ds += s.hsyoung[e]; }
+    double s0, s1, s2;
+    if (S4) { s0 = S4[4 * (size_t)e]; s1 = S4[4 * (size_t)e + 1]; s2 = S4[4 * (size_t)e + 2]; }
+    else { s0 = s.s0[e]; s1 = s.s1[e]; s2 = s.s2[e]; }
+    const double div = ice_diag_divergence(m, s, e);
+    double sn, ss;
+    ice_diag_sigma(s0, s1, s2, sn, ss);
     double *r = rows + 6 * threadIdx.x;
-    r[0] = dc; r[1] = dt; r[2] = ds; r[3] = (s0 + s1) / 2.; r[4] = hypot((s0 - s1) / 2., s2); r[5] = div;
+    r[0] = dc; r[1] = dt; r[2] = ds; r[3] = sn; r[4] = ss; r[5] = div;
     __syncthreads();
     const size_t base = (size_t)blockIdx.x * BLOCK * 6;
     const int count = min(BLOCK, m.Ne - (int)blockIdx.x * BLOCK) * 6;
     for (int i = threadIdx.x; i < count; i += BLOCK) out[base + i] = rows[i];
+}
+
+// ------------------------------------------------------------------------------------------------
+// The Moorings time means: updateMeans(means, time_factor), FE.cpp:8518-9024 -- data_mesh[i] += field[i] * time_factor for every configured variable, into
+// interleaved rows ([Ne][n] / [Nn][n]: what k_mesh_to_grid samples at output time).  The variable list travels by value; every branch on it is wave-uniform.
+// `src` is the set of source fields the list needs, computed by the host: a field is loaded once per element however many variables use it.
+// -ffp-contract=off: acc += x * tf is a rounded product and a rounded sum, as in the reference.
+struct MeansTable {
+    int n;                                    // variables = row length
+    unsigned src;                             // MS_* / MN_* bits
+    unsigned char id[NXS_MEANS_MAX_VARS];     // NXS_MEANS_* (nodal ids minus NXS_MEANS_NODAL_BEGIN)
+};
+enum { MS_CONC = 1, MS_THICK = 2, MS_SNOW = 4, MS_SIGMA = 8 /* + damage when it lives in the records */, MS_DAMAGE = 16, MS_RIDGE = 32, MS_CYOUNG = 64, MS_HYOUNG = 128,
+       MS_HSYOUNG = 256, MS_CMYI = 512, MS_TMYI = 1024, MS_DEL = 2048, MS_DRAG = 4096, MS_DRAGY = 8192, MS_DIV = 16384 };
+enum { MN_VT = 1, MN_WIND = 2, MN_TAUA = 4, MN_TAUW = 8, MN_TAUWI = 16, MN_GATHER = 32 };
+
+struct MeansElem { double conc, thick, snow, damage, ridge, s0, s1, s2, cy, hy, hsy, cmyi, tmyi, del, drag, dragy, div, sn, ss; };
+
+// the increment of one elemental variable (already multiplied by time_factor where the reference multiplies)
+__device__ __forceinline__ double means_elem_value(int id, const MeansElem &f, int young_cat, double tf) {
+    switch (id) {
+        case NXS_MEANS_CONC: return (young_cat ? f.conc + f.cy : f.conc) * tf;          // D_conc as k_ice_diagnostics forms it (FE.cpp:7866-7884)
+        case NXS_MEANS_THICK: return (young_cat ? f.thick + f.hy : f.thick) * tf;
+        case NXS_MEANS_SNOW: return (young_cat ? f.snow + f.hsy : f.snow) * tf;
+        case NXS_MEANS_CONC_CONS: return f.conc * tf;
+        case NXS_MEANS_DAMAGE: return f.damage * tf;
+        case NXS_MEANS_RIDGE_RATIO: return f.ridge * tf;
+        case NXS_MEANS_CONC_YOUNG: return f.cy * tf;
+        case NXS_MEANS_H_YOUNG: return f.hy * tf;
+        case NXS_MEANS_HS_YOUNG: return f.hsy * tf;
+        case NXS_MEANS_CONC_MYI: return f.cmyi * tf;
+        case NXS_MEANS_THICK_MYI: return f.tmyi * tf;
+        case NXS_MEANS_DCI_RIDGE_MYI: return f.del * tf;
+        case NXS_MEANS_SIGMA_11: return f.s0 * tf;
+        case NXS_MEANS_SIGMA_22: return f.s1 * tf;
+        case NXS_MEANS_SIGMA_12: return f.s2 * tf;
+        case NXS_MEANS_SIGMA_N: return f.sn * tf;
+        case NXS_MEANS_SIGMA_S: return f.ss * tf;
+        case NXS_MEANS_DIVERGENCE: return f.div * tf;
+        case NXS_MEANS_DRAG_UI: {                                                        // FE.cpp:8756-8766
+            double drag = f.drag;
+            if (young_cat) drag = (f.drag * f.conc + f.dragy * f.cy) / (f.conc + f.cy);
+            return drag * tf;
+        }
+        default: /* NXS_MEANS_ICE_MASK, FE.cpp:8912-8920: no time_factor */
+            return ((young_cat ? f.thick + f.hy : f.thick) > 0.) ? 1. : 0.;
+    }
+}
+
+// acc[base .. base + count) += stage[0 .. count): a workgroup's rows as ONE contiguous stream, 16 bytes per lane (base is even: a multiple of BLOCK)
+__device__ __forceinline__ void means_add_staged(double *__restrict__ acc, size_t base, const double *stage, int count) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    d2 *a2 = reinterpret_cast<d2 *>(acc + base);
+    const d2 *s2 = reinterpret_cast<const d2 *>(stage);
+    for (int i = threadIdx.x; i < count / 2; i += BLOCK) { d2 a = a2[i]; const d2 v = s2[i]; a.x += v.x; a.y += v.y; a2[i] = a; }
+    if ((count & 1) && threadIdx.x == 0) acc[base + count - 1] += stage[count - 1];
+}
+
+// Elemental pass: one thread per OWNED element (ghost rows are not touched: FE.cpp:8527 loops i < M_local_nelements).
+// STAGE: the increments of a workgroup go to LDS ([BLOCK][n], dynamic) and are added to the rows as one stream; else every thread walks its own row.
+template <bool STAGE>
+__global__ void __launch_bounds__(BLOCK) k_means_elements(DevMesh m, DevState s, const double *__restrict__ D_del, int young_cat, const double *__restrict__ S4,
+                                                          MeansTable t, double tf, double *__restrict__ acc) {
+    extern __shared__ double means_stage[];
+    const int e = min(blockIdx.x * BLOCK + (int)threadIdx.x, m.Neo - 1);  // (threads past the end redo the last owned element: every thread reaches the barrier)
+    const bool live = blockIdx.x * BLOCK + (int)threadIdx.x < m.Neo;
+    const unsigned src = t.src;
+    MeansElem f = {};
+    if (src & MS_CONC) f.conc = s.conc[e];
+    if (src & MS_THICK) f.thick = s.thick[e];
+    if (src & MS_SNOW) f.snow = s.snow[e];
+    if (src & MS_RIDGE) f.ridge = s.ridge[e];
+    if (src & MS_CYOUNG) f.cy = s.cyoung[e];
+    if (src & MS_HYOUNG) f.hy = s.hyoung[e];
+    if (src & MS_HSYOUNG) f.hsy = s.hsyoung[e];
+    if (src & MS_CMYI) f.cmyi = s.cmyi[e];
+    if (src & MS_TMYI) f.tmyi = s.tmyi[e];
+    if (src & MS_DEL) f.del = D_del[e];
+    if (src & MS_DRAG) f.drag = s.drag_ui[e];
+    if (src & MS_DRAGY) f.dragy = s.drag_ui_young[e];
+    if (S4) {   // sigma and damage live in the records the sub-step loop left behind (k_pack_state's layout): two 16-byte loads
+        if (src & (MS_SIGMA | MS_DAMAGE)) {
+            typedef double d2 __attribute__((ext_vector_type(2)));
+            const d2 a = reinterpret_cast<const d2 *>(S4)[2 * (size_t)e], b = reinterpret_cast<const d2 *>(S4)[2 * (size_t)e + 1];
+            f.s0 = a.x; f.s1 = a.y; f.s2 = b.x; f.damage = b.y;
+        }
+    } else {
+        if (src & MS_SIGMA) { f.s0 = s.s0[e]; f.s1 = s.s1[e]; f.s2 = s.s2[e]; }
+        if (src & MS_DAMAGE) f.damage = s.damage[e];
+    }
+    if (src & MS_SIGMA) ice_diag_sigma(f.s0, f.s1, f.s2, f.sn, f.ss);
+    if (src & MS_DIV) f.div = ice_diag_divergence(m, s, e);
+    const int n = t.n;
+    if (STAGE) {
+        double *r = means_stage + (size_t)threadIdx.x * n;
+        for (int k = 0; k < n; ++k) r[k] = means_elem_value(t.id[k], f, young_cat, tf);
+        __syncthreads();
+        means_add_staged(acc, (size_t)blockIdx.x * BLOCK * n, means_stage, min(BLOCK, m.Neo - (int)blockIdx.x * BLOCK) * n);
+    } else if (live) {
+        double *row = acc + (size_t)e * n;
+        if (n & 1) {
+            for (int k = 0; k < n; ++k) row[k] += means_elem_value(t.id[k], f, young_cat, tf);
+        } else {
+            typedef double d2 __attribute__((ext_vector_type(2)));
+            d2 *row2 = reinterpret_cast<d2 *>(row);
+            for (int k = 0; k < n; k += 2) {
+                d2 a = row2[k / 2];
+                a.x += means_elem_value(t.id[k], f, young_cat, tf); a.y += means_elem_value(t.id[k + 1], f, young_cat, tf);
+                row2[k / 2] = a;
+            }
+        }
+    }
+}
+
+// hypot for the Moorings stresses (FE.cpp:8980, 8996).  The reference calls the host C library's, which rounds correctly in all but rare cases; OCML's is allowed a
+// unit in the last place, and taumod squares the wind speed: one such unit becomes two in the mean.  This is the compensated form of C. F. Borges, "An improved
+// algorithm for hypot(a, b)" (2019), Algorithm 4 -- sqrt of the fused sum of squares, then one Newton correction with the residual x^2 + y^2 - h^2 formed exactly by
+// FMAs -- for operands whose squares neither overflow nor lose bits to underflow; anything else (zero, huge, tiny, inf, NaN) goes to OCML's hypot.
+__device__ __forceinline__ double means_hypot(double a, double b) {
+    double x = fabs(a), y = fabs(b);
+    if (x < y) { const double t = x; x = y; y = t; }
+    if (!(x < 1e150) || !(y > 1e-130)) return hypot(a, b);
+    double h = sqrt(__builtin_fma(x, x, y * y));
+    const double h_sq = h * h, x_sq = x * x;
+    const double t = __builtin_fma(-y, y, h_sq - x_sq) + __builtin_fma(h, h, -h_sq) - __builtin_fma(x, x, -x_sq);
+    h -= t / (2. * h);
+    return h;
+}
+
+struct MeansNode { double vtx, vty, wx, wy, tax, tay, twx, twy, wix, wiy, gconc, gtau; };
+
+__device__ __forceinline__ double means_node_value(int id, const MeansNode &f, double tf) {
+    switch (id + NXS_MEANS_NODAL_BEGIN) {
+        case NXS_MEANS_VT_X: return f.vtx * tf;
+        case NXS_MEANS_VT_Y: return f.vty * tf;
+        case NXS_MEANS_WIND_X: return f.wx * tf;
+        case NXS_MEANS_WIND_Y: return f.wy * tf;
+        case NXS_MEANS_TAU_AX: return f.tax * tf;
+        case NXS_MEANS_TAU_AY: return f.tay * tf;
+        case NXS_MEANS_TAUWIX: return f.wix * tf;
+        case NXS_MEANS_TAUWIY: return f.wiy * tf;
+        default: {   // taux, tauy, taumod: FE.cpp:8974-9020
+            double tau_i, wind2 = means_hypot(f.wx, f.wy);
+            if (id + NXS_MEANS_NODAL_BEGIN == NXS_MEANS_TAUX) { tau_i = f.twx; wind2 *= f.wx; }
+            else if (id + NXS_MEANS_NODAL_BEGIN == NXS_MEANS_TAUY) { tau_i = f.twy; wind2 *= f.wy; }
+            else { tau_i = means_hypot(f.twx, f.twy); wind2 *= wind2; }
+            return (tau_i * f.gconc + f.gtau * wind2 * (1. - f.gconc)) * tf;
+        }
+    }
+}
+
+// Nodal pass: one thread per node, ghosts included (FE.cpp:8932 loops i < M_num_nodes).  The stress variables gather D_tau_ow * M_surface and M_conc * M_surface
+// over the node's row of NodalElementConnectivity in the reference's order of j (n2e: bamg's row order, -1 where the reference skips a negative entry); a list
+// without them never reads the connectivity.
+template <bool STAGE>
+__global__ void __launch_bounds__(BLOCK) k_means_nodes(DevMesh m, DevState s, const double *__restrict__ D_tau_a, const double *__restrict__ D_tau_w,
+                                                       const double *__restrict__ tau_wi, const double *__restrict__ tau_ow, const double *__restrict__ surface,
+                                                       MeansTable t, double tf, double *__restrict__ acc) {
+    extern __shared__ double means_stage[];
+    const int Nn = m.Nn;
+    const int i = min(blockIdx.x * BLOCK + (int)threadIdx.x, Nn - 1);
+    const bool live = blockIdx.x * BLOCK + (int)threadIdx.x < Nn;
+    const unsigned src = t.src;
+    MeansNode f = {};
+    if (src & MN_VT) { f.vtx = s.VT[i]; f.vty = s.VT[i + Nn]; }
+    if (src & MN_WIND) { f.wx = s.wind[i]; f.wy = s.wind[i + Nn]; }
+    if (src & MN_TAUA) { f.tax = D_tau_a[i]; f.tay = D_tau_a[i + Nn]; }
+    if (src & MN_TAUW) { f.twx = D_tau_w[i]; f.twy = D_tau_w[i + Nn]; }
+    if (src & MN_TAUWI) { f.wix = tau_wi[i]; f.wiy = tau_wi[i + Nn]; }
+    if (src & MN_GATHER) {
+        double tau_a = 0., conc = 0., surf = 0.;
+        for (int j = 0; j < m.W1; ++j) {
+            const int el = m.n2e[(size_t)j * Nn + i];
+            if (el < 0) continue;
+            const double a = surface[el];
+            tau_a += tau_ow[el] * a;
+            conc += s.conc[el] * a;
+            surf += a;
+        }
+        f.gtau = tau_a / surf; f.gconc = conc / surf;
+    }
+    const int n = t.n;
+    if (STAGE) {
+        double *r = means_stage + (size_t)threadIdx.x * n;
+        for (int k = 0; k < n; ++k) r[k] = means_node_value(t.id[k], f, tf);
+        __syncthreads();
+        means_add_staged(acc, (size_t)blockIdx.x * BLOCK * n, means_stage, min(BLOCK, Nn - (int)blockIdx.x * BLOCK) * n);
+    } else if (live) {
+        double *row = acc + (size_t)i * n;
+        if (n & 1) {
+            for (int k = 0; k < n; ++k) row[k] += means_node_value(t.id[k], f, tf);
+        } else {
+            typedef double d2 __attribute__((ext_vector_type(2)));
+            d2 *row2 = reinterpret_cast<d2 *>(row);
+            for (int k = 0; k < n; k += 2) {
+                d2 a = row2[k / 2];
+                a.x += means_node_value(t.id[k], f, tf); a.y += means_node_value(t.id[k + 1], f, tf);
+                row2[k / 2] = a;
+            }
+        }
+    }
+}
+
+// setProcMask's elemental column (gridoutput.cpp:372-373): 1 on owned elements, 0 on ghosts
+__global__ void __launch_bounds__(BLOCK) k_means_proc_mask(int Ne, int Neo, double *__restrict__ out) {
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e < Ne) out[e] = e < Neo ? 1. : 0.;
 }
 
 // Deferred mesh move of the fused path: the fused kernel leaves every sub-step's velocity in a ring of

@@ -76,6 +76,12 @@ def load_library():
     L.nxs_dyn_put_coupled.argtypes = [H, P(_abi.Coupled)]
     L.nxs_dyn_get_coupled.argtypes = [H, P(_abi.Coupled)]
     L.nxs_dyn_ice_diagnostics.argtypes = [H, P(_abi.IceDiag), P(C.c_void_p)]
+    L.nxs_dyn_means_configure.argtypes = [H, P(_abi.MeansConfig)]
+    L.nxs_dyn_means_set_tau_ow.argtypes = [H, _abi.c_double_p]
+    L.nxs_dyn_means_update.argtypes = [H, C.c_double]
+    L.nxs_dyn_means_get.argtypes = [H, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
+    L.nxs_dyn_means_to_grid.argtypes = [H, P(_abi.MeansGrid), _abi.c_double_p, _abi.c_double_p]
+    L.nxs_dyn_means_reset.argtypes = [H]
     L.nxs_dyn_step.argtypes = [H]
     L.nxs_dyn_explicit_solve.argtypes = [H]
     L.nxs_dyn_update.argtypes = [H]
@@ -121,6 +127,7 @@ EXPORTS = (
     "nxs_dyn_put_state", "nxs_dyn_get_state", "nxs_dyn_set_forcing", "nxs_dyn_set_forcing_pair", "nxs_dyn_set_forcing_time",
     "nxs_dyn_get_diag", "nxs_dyn_ice_diagnostics", "nxs_dyn_step",
     "nxs_dyn_set_wave_stress", "nxs_dyn_put_coupled", "nxs_dyn_get_coupled",
+    "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
     "nxs_dyn_explicit_solve", "nxs_dyn_update", "nxs_dyn_synchronize", "nxs_dyn_step_host",
     "nxs_dyn_check_regridding", "nxs_dyn_check_fields_fast", "nxs_dyn_get_timing", "nxs_dyn_get_step_times", "nxs_dyn_get_traffic_model", "nxs_dyn_set_option",
     "nxs_dyn_debug_array", "nxs_dyn_get_branch_trace", "nxs_mesh_connectivity", "nxs_mesh_element_connectivity", "nxs_calc_cohesion",
@@ -455,6 +462,75 @@ class FiniteElementDynamics:
         self._chk(self.L.nxs_dyn_ice_diagnostics(self.h, C.byref(d) if d is not None else None, C.byref(dev)))
         return out, dev.value
 
+    # ---- the Moorings time means: updateMeans / updateGridMean / resetMeshMean (FE.cpp:8518-9024, gridoutput.cpp:387-550) ----
+    @staticmethod
+    def _means_list(variables, first, last):
+        """[(name or id, mask)] or [name or id] -> (ids, masks) as int32 / uint8 arrays"""
+        ids, masks = [], []
+        for v in variables or ():
+            name, mask = v if isinstance(v, (tuple, list)) else (v, False)
+            ids.append(_abi.MEANS_ID[name] if isinstance(name, str) else int(name))
+            masks.append(1 if mask else 0)
+        return np.asarray(ids, np.int32), np.asarray(masks, np.uint8)
+
+    def means_configure(self, elemental=(), nodal=()):
+        """The output variables of the Moorings (GridOutput's M_elemental_variables / M_nodal_variables): names of _abi.MEANS_ELEMENTAL / MEANS_NODAL (or
+        NXS_MEANS_* numbers), each optionally as (name, mask) for Variable::mask.  Two empty lists switch the feature off.  Survives set_mesh."""
+        ei, em = self._means_list(elemental, 0, len(_abi.MEANS_ELEMENTAL))
+        ni, nm = self._means_list(nodal, _abi.NXS_MEANS_NODAL_BEGIN, _abi.NXS_MEANS_NODAL_BEGIN + len(_abi.MEANS_NODAL))
+        c = _abi.MeansConfig()
+        c.num_elemental, c.num_nodal = ei.size, ni.size
+        if ei.size:
+            c.elemental_ids, c.elemental_mask = _abi.iptr(ei), _abi.bptr(em)
+        if ni.size:
+            c.nodal_ids, c.nodal_mask = _abi.iptr(ni), _abi.bptr(nm)
+        self._chk(self.L.nxs_dyn_means_configure(self.h, C.byref(c)))
+        self._means_n = (int(ei.size), int(ni.size))
+
+    def means_set_tau_ow(self, tau_ow):
+        """D_tau_ow ([Ne], written by the thermodynamics): the input of taux / tauy / taumod that is not the handle's.  None detaches it."""
+        if tau_ow is None:
+            self._chk(self.L.nxs_dyn_means_set_tau_ow(self.h, None))
+            return
+        a = np.ascontiguousarray(tau_ow, np.float64)
+        if a.shape != (self.lm.num_elements,):
+            raise ValueError(f"tau_ow has shape {a.shape}, expected ({self.lm.num_elements},)")
+        self._chk(self.L.nxs_dyn_means_set_tau_ow(self.h, _abi.dptr(a)))
+
+    def means_update(self, time_factor: float):
+        """updateMeans(means, time_factor) on the device-resident state; asynchronous on the handle's stream."""
+        self._chk(self.L.nxs_dyn_means_update(self.h, float(time_factor)))
+
+    def means_get(self, want_host: bool = True):
+        """(elemental [Ne, n_el] or None, nodal [Nn, n_nod] or None, device pointer of the elemental rows, of the nodal rows)."""
+        n_el, n_nod = getattr(self, "_means_n", (0, 0))
+        el = np.empty((self.lm.num_elements, n_el)) if want_host and n_el else None
+        nod = np.empty((self.lm.num_nodes, n_nod)) if want_host and n_nod else None
+        de, dn = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.nxs_dyn_means_get(self.h, _abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None,
+                                           C.byref(de), C.byref(dn)))
+        return el, nod, de.value, dn.value
+
+    def means_to_grid(self, xmin, ymax, mooring_spacing, ncols, nrows, miss_val=-1e14, grid_elemental=None, grid_nodal=None):
+        """updateGridMean() on the regular grid: samples the accumulators and ADDS them to grid_elemental [n_el, ncols * nrows] / grid_nodal
+        [n_nod, ncols * nrows] (made of zeros when None); returns the two arrays (None for an empty list)."""
+        n_el, n_nod = getattr(self, "_means_n", (0, 0))
+        G = int(ncols) * int(nrows)
+        if grid_elemental is None and n_el:
+            grid_elemental = np.zeros((n_el, G))
+        if grid_nodal is None and n_nod:
+            grid_nodal = np.zeros((n_nod, G))
+        for a, n in ((grid_elemental, n_el), (grid_nodal, n_nod)):
+            if n and a.shape != (n, G):
+                raise ValueError(f"grid array has shape {a.shape}, expected ({n}, {G})")
+        g = _abi.MeansGrid(float(xmin), float(ymax), float(mooring_spacing), float(miss_val), int(ncols), int(nrows))
+        self._chk(self.L.nxs_dyn_means_to_grid(self.h, C.byref(g), _abi.dptr(grid_elemental) if n_el else None, _abi.dptr(grid_nodal) if n_nod else None))
+        return (grid_elemental if n_el else None), (grid_nodal if n_nod else None)
+
+    def means_reset(self):
+        """resetMeshMean(bamgmesh): both accumulators to zero, on the stream."""
+        self._chk(self.L.nxs_dyn_means_reset(self.h))
+
     def branch_trace(self) -> dict:
         """The record option "trace_branches" keeps (include/nxs_dyn.h): {'hash', 'damage_substeps', 'flags', 'substeps'}."""
         t = np.zeros((self.lm.num_elements, 4), np.uint64)
@@ -466,7 +542,7 @@ class FiniteElementDynamics:
         n = {"rlmass": Nn, "node_mass": Nn, "C_bu": Nn, "grad_ssh": 2 * Nn, "fcor": Nn, "VTM": 2 * Nn,
              "shape": 6 * Ne, "emass": Ne, "ecbu": Ne, "force": 6 * Ne, "volume": Ne, "expC": Ne,
              "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn,
-             "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1}[name]
+             "means_update_ms": 2, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1}[name]
         out = np.empty(n)
         self._chk(self.L.nxs_dyn_debug_array(self.h, name.encode(), _abi.dptr(out), n))
         return out
@@ -520,3 +596,6 @@ class FiniteElementDynamics:
         d["substep_kernel_name"] = self.KERNEL_NAMES.get(t.substep_kernel, "?")
         d["prep_kernel_name"] = self.PREP_NAMES.get(t.prep_kernel, "?")
         return d
+
+
+Dynamics = FiniteElementDynamics

@@ -200,3 +200,15 @@ def moorings_append(path, timestamp, fields, averaging_period=0.0):
     keep = [np.ascontiguousarray(f, np.float32) for f in fields]
     ptrs = (C.POINTER(C.c_float) * len(keep))(*[k.ctypes.data_as(C.POINTER(C.c_float)) for k in keep])
     _chk(L, L.nxs_moorings_append(path.encode(), float(timestamp), float(averaging_period), len(keep), ptrs))
+
+
+def moorings_append_means(path, timestamp, fe, xmin, ymax, mooring_spacing, ncols, nrows, miss_val=-1e14, averaging_period=0.0, reset=True):
+    """One time-mean record from the device-resident accumulators of `fe` (a dynamics.FiniteElementDynamics with means configured): updateGridMean on the
+    regular grid, the record appended in the order elemental variables, nodal variables -- the order `variables` of moorings_create must have --, then
+    resetMeshMean.  Single rank: with several, sum the ranks' grids (boost::mpi::reduce, FE.cpp:9476-9487) between means_to_grid and moorings_append."""
+    ge, gn = fe.means_to_grid(xmin, ymax, mooring_spacing, ncols, nrows, miss_val)
+    fields = [g.reshape(nrows, ncols) for grid in (ge, gn) if grid is not None for g in grid]
+    moorings_append(path, timestamp, fields, averaging_period)
+    if reset:
+        fe.means_reset()
+    return ge, gn
