@@ -460,6 +460,41 @@ NXS_API int nxs_dyn_means_get(nxs_dyn_handle *h, double *elemental /* [Ne][n_el]
 NXS_API int nxs_dyn_means_to_grid(nxs_dyn_handle *h, const nxs_dyn_means_grid *g, double *grid_elemental, double *grid_nodal);
 NXS_API int nxs_dyn_means_reset(nxs_dyn_handle *h);
 
+/* ---- The drifters on the device: the three statements of checkUpdateDrifters() (FE.cpp:8403-8437) that touch the handle's arrays -- Drifters::move with
+ * M_UT and the reset of M_UT (checkMoveDrifters, FE.cpp:8375-8397), Drifters::updateConc on the mesh displaced by M_UM, Drifters::maskXY.  drifters.cpp's file
+ * input and output, its timing logic and initFromSpacing's grid stay with the host.  A handle holds up to NXS_DRIFTER_SETS sets (M_drifters is a vector of
+ * Drifters), each with x, y, id (M_X, M_Y, M_i) and conc on the device.  The sets are the handle's: they survive nxs_dyn_set_mesh (positions do not depend on the
+ * mesh), so a host that regrids calls nxs_dyn_drifters_move BEFORE it replaces the mesh, as regrid() does (FE.cpp:3609).  Both interpolations locate the drifters
+ * with bamg's integer predicates (include/nxs_interp.h), isdefault = true and default 0.: inside the mesh the bits are InterpFromMeshToMesh2dx's.
+ *   bbox           NULL, or xmin, xmax, ymin, ymax of the mesh whose integer plane (Mesh::SetIntCoor) and isdefault box (InterpFromMeshToMesh2dx.cpp:92) are to be
+ *                  used.  One rank: NULL.  Several ranks: every rank passes the box of the GLOBAL mesh -- the ranks' nxs_dyn_drifters_mesh_bbox results reduced
+ *                  with min / max -- so that a shared node has the same integer coordinates on every rank and the rank that finds a drifter computes what the
+ *                  reference's root computes on the gathered mesh.  Every rank holds the full sets; nothing is exchanged between handles.
+ *   found          per drifter, from the last move or conc: 0 = in no triangle of this handle's mesh, 1 = in an owned element, 2 = in a ghost element.  move
+ *                  displaces the drifters with found == 1 only; the host takes each drifter from the rank that reports 1 and sets the merged positions again.
+ *   nxs_dyn_drifters_set    replaces set `set` (initFromSpacing / initFromTextFile / initFromNetCDF / a restart: drifters.cpp:27-71, 100-330); n == 0 is legal:
+ *                  the set then exists and is empty
+ *   nxs_dyn_drifters_clear  removes it (Drifters::reset, drifters.cpp:456-459)
+ *   nxs_dyn_drifters_mesh_bbox  xmin, xmax, ymin, ymax of this handle's nodes, of coord_x / coord_y (displaced == 0) or displaced by M_UM (!= 0): a device reduction
+ *   nxs_dyn_drifters_move   checkMoveDrifters(): with no set nothing happens and M_UT is left alone (FE.cpp:8383-8384); otherwise M_UT is interpolated at the
+ *                  drifters of every set in the UNDISPLACED mesh (drifters.cpp:490-496), x += du, y += dv (drifters.cpp:499-503), then M_UT = 0 on every
+ *                  node of the handle, ghosts included (FE.cpp:8390).  Asynchronous on the handle's stream
+ *   nxs_dyn_drifters_conc   Drifters::updateConc (drifters.cpp:512-542): M_conc of the element that holds the drifter in the mesh displaced by M_UM
+ *                  (FE.cpp:8433-8434), default 0., then std::max(0., std::min(1., v)); kept in the set, and copied to conc_host [n] unless that is NULL
+ *   nxs_dyn_drifters_mask   Drifters::maskXY (drifters.cpp:548-579): drifter i stays iff conc[i] > conc_lim and id[i] occurs in keepers [n_keepers]; keepers
+ *                  NULL keeps every id (the one-argument overload, drifters.hpp:231-237).  The survivors keep their order; *n_left = how many
+ *   nxs_dyn_drifters_get    the set as it is now: *n and x, y, id, conc, found [n]; any output may be NULL
+ * Errors: NXS_ERR_INVALID for a set outside 0 .. NXS_DRIFTER_SETS - 1 or a NaN coordinate in the mesh, NXS_ERR_STATE before set_mesh / put_state and for conc,
+ * mask or get on a set that does not exist.  conc and move on an empty set succeed and do nothing (drifters.cpp:476-477, 518-519). */
+#define NXS_DRIFTER_SETS 8
+NXS_API int nxs_dyn_drifters_set(nxs_dyn_handle *h, int32_t set, int32_t n, const double *x, const double *y, const int32_t *id);
+NXS_API int nxs_dyn_drifters_clear(nxs_dyn_handle *h, int32_t set);
+NXS_API int nxs_dyn_drifters_mesh_bbox(nxs_dyn_handle *h, int32_t displaced, double *out /* [4] */);
+NXS_API int nxs_dyn_drifters_move(nxs_dyn_handle *h, const double *bbox /* [4] or NULL */);
+NXS_API int nxs_dyn_drifters_conc(nxs_dyn_handle *h, int32_t set, const double *bbox /* [4] or NULL */, double *conc_host /* [n] or NULL */);
+NXS_API int nxs_dyn_drifters_mask(nxs_dyn_handle *h, int32_t set, double conc_lim, const int32_t *keepers, int32_t n_keepers, int32_t *n_left);
+NXS_API int nxs_dyn_drifters_get(nxs_dyn_handle *h, int32_t set, int32_t *n, double *x, double *y, int32_t *id, double *conc, int32_t *found);
+
 /* One dynamics step on the device-resident state: FE.cpp:8197-8214.  Asynchronous on the
  * handle's stream; nxs_dyn_synchronize() waits for it. */
 NXS_API int nxs_dyn_step(nxs_dyn_handle *h);
@@ -605,6 +640,8 @@ NXS_API int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t);
  *                  variables; 8-byte otherwise).  The same bits; scripts/time_means.py times both
  *   "means_timing" 1 = nxs_dyn_means_update records events around its two launches; nxs_dyn_debug_array "means_update_ms" returns their device times
  *                  [elemental, nodal] in ms.  Default 0
+ *   "drifters_timing" 1 = the nxs_dyn_drifters_* calls record events around their launches and wait for them; nxs_dyn_debug_array "drifters_ms" returns the device
+ *                  times [locator build, move kernels, conc kernel, mask kernels] of the last of each in ms.  Default 0
  *   "ipc_delay", "halo_one_directional"   test doors of the exchange protocols, see NXS_DELAY_* above */
 NXS_API int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value);
 

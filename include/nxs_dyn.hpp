@@ -62,6 +62,23 @@ public:
         check(nxs_dyn_ice_diagnostics(h_, d, &rows), "updateIceDiagnostics");
         return rows;
     }
+    // The drifters (checkMoveDrifters / checkUpdateDrifters, FE.cpp:8375-8437; Drifters::move / updateConc / maskXY, drifters.cpp:468-579) on the device-resident
+    // arrays.  bbox: NULL on one rank, the min / max-reduced driftersMeshBbox of all ranks otherwise.
+    void driftersSet(int set, int n, const double *x, const double *y, const int32_t *id) { check(nxs_dyn_drifters_set(h_, set, n, x, y, id), "drifters_set"); }
+    void driftersClear(int set) { check(nxs_dyn_drifters_clear(h_, set), "drifters_clear"); }                               // drifters.cpp:456-459
+    void driftersMeshBbox(bool displaced, double out[4]) { check(nxs_dyn_drifters_mesh_bbox(h_, displaced ? 1 : 0, out), "drifters_mesh_bbox"); }
+    void checkMoveDrifters(const double *bbox = nullptr) { check(nxs_dyn_drifters_move(h_, bbox), "checkMoveDrifters"); }   // FE.cpp:8375-8397, M_UT = 0 included
+    void driftersUpdateConc(int set, const double *bbox = nullptr, double *conc_host = nullptr) { check(nxs_dyn_drifters_conc(h_, set, bbox, conc_host), "drifters_conc"); }
+    int driftersMaskXY(int set, double conc_lim, const int32_t *keepers = nullptr, int n_keepers = 0) {                    // drifters.cpp:548-579; returns how many are left
+        int32_t left = 0;
+        check(nxs_dyn_drifters_mask(h_, set, conc_lim, keepers, n_keepers, &left), "drifters_mask");
+        return left;
+    }
+    int driftersGet(int set, double *x = nullptr, double *y = nullptr, int32_t *id = nullptr, double *conc = nullptr, int32_t *found = nullptr) {
+        int32_t n = 0;
+        check(nxs_dyn_drifters_get(h_, set, &n, x, y, id, conc, found), "drifters_get");
+        return n;
+    }
     nxs_dyn_handle *handle() { return h_; }
 
 private:

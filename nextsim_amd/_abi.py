@@ -154,6 +154,8 @@ class MeansGrid(C.Structure):   # nxs_dyn_means_grid
                 ("ncols", C.c_int32), ("nrows", C.c_int32)]
 
 
+NXS_DRIFTER_SETS = 8   # include/nxs_dyn.h: drifter sets per handle (nxs_dyn_drifters_*)
+
 ICE_DIAG = ("D_conc", "D_thick", "D_snow_thick", "D_sigma0", "D_sigma1", "D_divergence")
 
 

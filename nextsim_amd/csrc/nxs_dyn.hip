@@ -39,6 +39,7 @@
 #include "nxs_dyn.h"
 #include "nxs_interp.h"
 #include "nxs_guard.hpp"
+#include "nxs_drifters.hpp"
 #include "nxs_patchcut.hpp"
 #include "nxs_resident_registry.hpp"
 
@@ -231,6 +232,8 @@ struct nxs_dyn_handle {
     hipEvent_t means_ev[3] = {nullptr, nullptr, nullptr};
     bool means_timed = false;
     int means_stage = 1;                           // option "means_stage": the rows' read-modify-write staged through LDS (1) or walked by each thread (0)
+    // the drifters (nxs_dyn_drifters_*): the sets are the handle's and survive set_mesh; the two locators go with the mesh / with M_UM (nxs_drifters.hpp)
+    nxs_drifters::State *drift = nullptr;          // made by the first nxs_dyn_drifters_set
     int sig_loc = 0;                       // where M_sigma / M_damage are current: 0 = the state arrays, 1 = the records in S4a (left there by
                                            // the fused sub-step loop; k_update works on them, the arrays follow on demand: ensure_arrays)
     int trace_branches = 0;                // option "trace_branches": the per-loop kernels keep the branch trace of updateSigmaDamage (dw.trace)
@@ -1358,6 +1361,7 @@ int ready(nxs_dyn_handle *h) {
     if (multi_rank(h) && !h->have_halo) return fail(h, NXS_ERR_STATE, "nranks>1 needs set_halo");
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return fail(h, NXS_ERR_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (h->drift) nxs_drifters::state_changed(h->drift);   // M_UM is about to move: the drifters' displaced locator is stale
     return NXS_OK;
 }
 
@@ -1684,6 +1688,7 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     for (auto &set : h->ev) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
     for (auto &set : h->ev_flush) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : h->means_ev) if (ev) (void)hipEventDestroy(ev);
+    nxs_drifters::destroy(h->drift); h->drift = nullptr;
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return NXS_OK;
@@ -1821,6 +1826,11 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
     }
     if (!std::strcmp(key, "pin_host")) { h->pin_host = value != 0; if (!h->pin_host) unpin_all(h); return NXS_OK; }
     if (!std::strcmp(key, "means_stage")) { h->means_stage = value != 0; return NXS_OK; }
+    if (!std::strcmp(key, "drifters_timing")) {
+        if (!h->drift) h->drift = nxs_drifters::create();
+        nxs_drifters::set_timing(h->drift, value != 0);
+        return NXS_OK;
+    }
     if (!std::strcmp(key, "means_timing")) {
         h->means_timing = value != 0; h->means_timed = false;
         if (h->means_timing) { HIPCHK(h, hipSetDevice(h->device)); for (auto &ev : h->means_ev) if (!ev) HIPCHK(h, hipEventCreate(&ev)); }
@@ -1872,6 +1882,7 @@ int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
     free_pool(h->state_allocs);
     free_pool(h->halo_allocs);
     free_pool(h->patch_allocs);
+    if (h->drift) nxs_drifters::mesh_changed(h->drift);   // (the sets stay: positions do not depend on the mesh)
     release_resident(h);
     if (h->pair_claim) { resident_registry_release(h, nxs_reg::KIND_PAIR); h->pair_claim = false; }
     free_pool(h->pair_allocs);
@@ -2524,6 +2535,7 @@ int nxs_dyn_put_state(nxs_dyn_handle *h, const nxs_dyn_state *s) try {
     for (auto &c : cp) if (c.src) HIPCHK(h, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_state = true;
+    if (h->drift) nxs_drifters::state_changed(h->drift);
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_put_state"); }
 
@@ -2892,6 +2904,80 @@ int nxs_dyn_means_to_grid(nxs_dyn_handle *h, const nxs_dyn_means_grid *g, double
 } catch (...) { return dyn_caught(h, "nxs_dyn_means_to_grid"); }
 
 // test door: the branch trace of updateSigmaDamage (option "trace_branches"), 4 words per element
+// ---- the drifters: checkMoveDrifters / checkUpdateDrifters (FE.cpp:8375-8437), Drifters::move / updateConc / maskXY (drifters.cpp:468-579); the kernels live next to
+// the exact point locator (nxs_drifters.inl), this file hands them the handle's own device arrays
+static nxs_drifters::MeshView drift_view(const nxs_dyn_handle *h) {
+    nxs_drifters::MeshView m;
+    m.Nn = h->dm.Nn; m.Ne = h->dm.Ne; m.Neo = h->dm.Neo;
+    m.t0 = h->dm.t0; m.t1 = h->dm.t1; m.t2 = h->dm.t2; m.x0 = h->dm.x0; m.y0 = h->dm.y0;
+    return m;
+}
+static int drift_rc(nxs_dyn_handle *h, int rc, const char *entry, const std::string &err) { return rc ? fail(h, rc, "%s: %s", entry, err.c_str()) : NXS_OK; }
+
+int nxs_dyn_drifters_set(nxs_dyn_handle *h, int32_t set, int32_t n, const double *x, const double *y, const int32_t *id) try {
+    if (!h) return NXS_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->drift) h->drift = nxs_drifters::create();
+    std::string err;
+    return drift_rc(h, nxs_drifters::set(h->drift, h->stream, set, n, x, y, id, err), "drifters_set", err);
+} catch (...) { return dyn_caught(h, "nxs_dyn_drifters_set"); }
+
+int nxs_dyn_drifters_clear(nxs_dyn_handle *h, int32_t set) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (set < 0 || set >= NXS_DRIFTER_SETS) return fail(h, NXS_ERR_INVALID, "drifters_clear: set %d out of range (0..%d)", set, NXS_DRIFTER_SETS - 1);
+    return h->drift ? nxs_drifters::clear(h->drift, set) : NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_drifters_clear"); }
+
+int nxs_dyn_drifters_mesh_bbox(nxs_dyn_handle *h, int32_t displaced, double *out) try {
+    if (!h || !out) return NXS_ERR_INVALID;
+    if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "drifters_mesh_bbox before set_mesh");
+    if (displaced && !h->have_state) return fail(h, NXS_ERR_STATE, "drifters_mesh_bbox of the displaced mesh before put_state");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->drift) h->drift = nxs_drifters::create();
+    std::string err;
+    return drift_rc(h, nxs_drifters::mesh_bbox(h->drift, h->stream, drift_view(h), displaced ? h->ds.UM : nullptr, out, err), "drifters_mesh_bbox", err);
+} catch (...) { return dyn_caught(h, "nxs_dyn_drifters_mesh_bbox"); }
+
+int nxs_dyn_drifters_move(nxs_dyn_handle *h, const double *bbox) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (!h->drift || !nxs_drifters::any_set(h->drift)) return NXS_OK;   // FE.cpp:8383-8384: no active drifters, M_UT is left alone
+    if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "drifters_move needs set_mesh and put_state");
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    int rc = nxs_drifters::move(h->drift, h->stream, drift_view(h), h->ds.UT, bbox, err);
+    if (rc) return drift_rc(h, rc, "drifters_move", err);
+    HIPCHK(h, hipMemsetAsync(h->ds.UT, 0, 2 * (size_t)h->dm.Nn * sizeof(double), h->stream));   // FE.cpp:8390
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_drifters_move"); }
+
+int nxs_dyn_drifters_conc(nxs_dyn_handle *h, int32_t set, const double *bbox, double *conc_host) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (set < 0 || set >= NXS_DRIFTER_SETS) return fail(h, NXS_ERR_INVALID, "drifters_conc: set %d out of range (0..%d)", set, NXS_DRIFTER_SETS - 1);
+    if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "drifters_conc needs set_mesh and put_state");
+    if (!h->drift || !nxs_drifters::has_set(h->drift, set)) return fail(h, NXS_ERR_STATE, "drifters_conc: set %d does not exist (nxs_dyn_drifters_set)", set);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    return drift_rc(h, nxs_drifters::conc(h->drift, h->stream, drift_view(h), h->ds.UM, h->ds.conc, set, bbox, conc_host, err), "drifters_conc", err);
+} catch (...) { return dyn_caught(h, "nxs_dyn_drifters_conc"); }
+
+int nxs_dyn_drifters_mask(nxs_dyn_handle *h, int32_t set, double conc_lim, const int32_t *keepers, int32_t n_keepers, int32_t *n_left) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (set < 0 || set >= NXS_DRIFTER_SETS) return fail(h, NXS_ERR_INVALID, "drifters_mask: set %d out of range (0..%d)", set, NXS_DRIFTER_SETS - 1);
+    if (!h->drift || !nxs_drifters::has_set(h->drift, set)) return fail(h, NXS_ERR_STATE, "drifters_mask: set %d does not exist (nxs_dyn_drifters_set)", set);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    return drift_rc(h, nxs_drifters::mask(h->drift, h->stream, set, conc_lim, keepers, n_keepers, n_left, err), "drifters_mask", err);
+} catch (...) { return dyn_caught(h, "nxs_dyn_drifters_mask"); }
+
+int nxs_dyn_drifters_get(nxs_dyn_handle *h, int32_t set, int32_t *n, double *x, double *y, int32_t *id, double *conc, int32_t *found) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (set < 0 || set >= NXS_DRIFTER_SETS) return fail(h, NXS_ERR_INVALID, "drifters_get: set %d out of range (0..%d)", set, NXS_DRIFTER_SETS - 1);
+    if (!h->drift || !nxs_drifters::has_set(h->drift, set)) return fail(h, NXS_ERR_STATE, "drifters_get: set %d does not exist (nxs_dyn_drifters_set)", set);
+    HIPCHK(h, hipSetDevice(h->device));
+    std::string err;
+    return drift_rc(h, nxs_drifters::get(h->drift, h->stream, set, n, x, y, id, conc, found, err), "drifters_get", err);
+} catch (...) { return dyn_caught(h, "nxs_dyn_drifters_get"); }
+
 int nxs_dyn_get_branch_trace(nxs_dyn_handle *h, uint64_t *out, int64_t num_words) try {
     if (!h || !out) return NXS_ERR_INVALID;
     if (!h->have_mesh || !h->dw.trace) return fail(h, NXS_ERR_STATE, "get_branch_trace: set option trace_branches = 1 first");
@@ -2936,6 +3022,11 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
                 HIPCHK(h, hipStreamSynchronize(h->stream));
                 return NXS_OK;
             }
+    }
+    if (!std::strcmp(name, "drifters_ms")) {   // [4] device time of the last locator build, move kernels, conc kernel, mask kernels with option "drifters_timing" 1
+        if (n != 4) return fail(h, NXS_ERR_INVALID, "debug_array drifters_ms has 4 entries");
+        if (!h->drift || !nxs_drifters::timing(h->drift, out)) return fail(h, NXS_ERR_STATE, "debug_array drifters_ms: no timed nxs_dyn_drifters_* call (option drifters_timing)");
+        return NXS_OK;
     }
     if (!std::strcmp(name, "means_update_ms")) {   // [2] device time of the last nxs_dyn_means_update with option "means_timing" 1: the elemental launch, the nodal launch
         if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array means_update_ms has 2 entries");

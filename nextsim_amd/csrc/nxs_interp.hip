@@ -29,6 +29,7 @@
 #include "nxs_guard.hpp"
 #include "nxs_interp.h"
 #include "nxs_hull.inl"
+#include "nxs_drifters.hpp"
 
 namespace {
 
@@ -1196,3 +1197,8 @@ extern "C" int nxs_interp_grid_to_mesh(double *data_mesh, const double *x_in, in
     if (copy_sync(data_mesh, dout.p, (size_t)nods * N_data * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
     return NXS_OK;
 } catch (...) { return entry_caught("nxs_interp_grid_to_mesh"); }
+
+// ---------------------------------------------------------------------------------------------------------
+// The drifters of a dynamics handle (nxs_dyn_drifters_*): kernels that share locate() with k_interp, and the locator built from device coordinates
+// ---------------------------------------------------------------------------------------------------------
+#include "nxs_drifters.inl"

@@ -82,6 +82,13 @@ def load_library():
     L.nxs_dyn_means_get.argtypes = [H, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
     L.nxs_dyn_means_to_grid.argtypes = [H, P(_abi.MeansGrid), _abi.c_double_p, _abi.c_double_p]
     L.nxs_dyn_means_reset.argtypes = [H]
+    L.nxs_dyn_drifters_set.argtypes = [H, C.c_int32, C.c_int32, _abi.c_double_p, _abi.c_double_p, _abi.c_int32_p]
+    L.nxs_dyn_drifters_clear.argtypes = [H, C.c_int32]
+    L.nxs_dyn_drifters_mesh_bbox.argtypes = [H, C.c_int32, _abi.c_double_p]
+    L.nxs_dyn_drifters_move.argtypes = [H, _abi.c_double_p]
+    L.nxs_dyn_drifters_conc.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p]
+    L.nxs_dyn_drifters_mask.argtypes = [H, C.c_int32, C.c_double, _abi.c_int32_p, C.c_int32, P(C.c_int32)]
+    L.nxs_dyn_drifters_get.argtypes = [H, C.c_int32, P(C.c_int32), _abi.c_double_p, _abi.c_double_p, _abi.c_int32_p, _abi.c_double_p, _abi.c_int32_p]
     L.nxs_dyn_step.argtypes = [H]
     L.nxs_dyn_explicit_solve.argtypes = [H]
     L.nxs_dyn_update.argtypes = [H]
@@ -128,6 +135,8 @@ EXPORTS = (
     "nxs_dyn_get_diag", "nxs_dyn_ice_diagnostics", "nxs_dyn_step",
     "nxs_dyn_set_wave_stress", "nxs_dyn_put_coupled", "nxs_dyn_get_coupled",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
+    "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
+    "nxs_dyn_drifters_get",
     "nxs_dyn_explicit_solve", "nxs_dyn_update", "nxs_dyn_synchronize", "nxs_dyn_step_host",
     "nxs_dyn_check_regridding", "nxs_dyn_check_fields_fast", "nxs_dyn_get_timing", "nxs_dyn_get_step_times", "nxs_dyn_get_traffic_model", "nxs_dyn_set_option",
     "nxs_dyn_debug_array", "nxs_dyn_get_branch_trace", "nxs_mesh_connectivity", "nxs_mesh_element_connectivity", "nxs_calc_cohesion",
@@ -531,6 +540,73 @@ class FiniteElementDynamics:
         """resetMeshMean(bamgmesh): both accumulators to zero, on the stream."""
         self._chk(self.L.nxs_dyn_means_reset(self.h))
 
+    # ---- the drifters: checkMoveDrifters / checkUpdateDrifters (FE.cpp:8375-8437), Drifters::move / updateConc / maskXY (drifters.cpp:468-579) ----
+    @staticmethod
+    def _bbox(bbox):
+        if bbox is None:
+            return None, None
+        b = np.ascontiguousarray(bbox, np.float64)
+        if b.shape != (4,):
+            raise ValueError("bbox is xmin, xmax, ymin, ymax")
+        return b, _abi.dptr(b)
+
+    def drifters_set(self, set: int, x, y, id):
+        """Replace drifter set `set` (0 .. NXS_DRIFTER_SETS - 1) by the positions x, y and ids (M_X, M_Y, M_i); empty arrays make an empty set."""
+        x = np.ascontiguousarray(x, np.float64); y = np.ascontiguousarray(y, np.float64); id = np.ascontiguousarray(id, np.int32)
+        if not (x.ndim == y.ndim == id.ndim == 1 and x.size == y.size == id.size):
+            raise ValueError("x, y and id must be vectors of one length")
+        self._chk(self.L.nxs_dyn_drifters_set(self.h, int(set), int(x.size), _abi.dptr(x), _abi.dptr(y), _abi.iptr(id)))
+
+    def drifters_clear(self, set: int):
+        self._chk(self.L.nxs_dyn_drifters_clear(self.h, int(set)))
+
+    def drifters_mesh_bbox(self, displaced: bool = False) -> np.ndarray:
+        """xmin, xmax, ymin, ymax of this handle's nodes (displaced by M_UM when asked): several ranks reduce it with min / max and pass the result as `bbox`."""
+        out = np.empty(4)
+        self._chk(self.L.nxs_dyn_drifters_mesh_bbox(self.h, int(bool(displaced)), _abi.dptr(out)))
+        return out
+
+    def drifters_move(self, bbox=None):
+        """checkMoveDrifters(): every set moved by M_UT interpolated in the undisplaced mesh, then M_UT = 0; nothing at all without a set.  Asynchronous."""
+        keep, ptr = self._bbox(bbox)
+        self._chk(self.L.nxs_dyn_drifters_move(self.h, ptr))
+
+    def drifters_conc(self, set: int, bbox=None, want_host: bool = True):
+        """Drifters::updateConc on the mesh displaced by M_UM; returns the concentrations (None when want_host is False: they stay in the set)."""
+        keep, ptr = self._bbox(bbox)
+        out = None
+        if want_host:
+            out = np.empty(self.drifters_count(set))
+        self._chk(self.L.nxs_dyn_drifters_conc(self.h, int(set), ptr, _abi.dptr(out) if out is not None else None))
+        return out
+
+    def drifters_mask(self, set: int, conc_lim: float, keepers=None) -> int:
+        """Drifters::maskXY: keeps the drifters with conc > conc_lim whose id is among `keepers` (None: every id), in their order; returns how many are left."""
+        left = C.c_int32(-1)
+        k = None if keepers is None else np.ascontiguousarray(keepers, np.int32)
+        self._chk(self.L.nxs_dyn_drifters_mask(self.h, int(set), float(conc_lim), _abi.iptr(k) if k is not None else None, 0 if k is None else int(k.size), C.byref(left)))
+        return left.value
+
+    def drifters_count(self, set: int) -> int:
+        n = C.c_int32(-1)
+        self._chk(self.L.nxs_dyn_drifters_get(self.h, int(set), C.byref(n), None, None, None, None, None))
+        return n.value
+
+    def drifters_get(self, set: int) -> dict:
+        """The set as it is now: x, y, id, conc, found (0 = in no triangle at the last move / conc, 1 = in an owned element, 2 = in a ghost element)."""
+        n = self.drifters_count(set)
+        out = {"x": np.empty(n), "y": np.empty(n), "id": np.empty(n, np.int32), "conc": np.empty(n), "found": np.empty(n, np.int32)}
+        m = C.c_int32(-1)
+        self._chk(self.L.nxs_dyn_drifters_get(self.h, int(set), C.byref(m), _abi.dptr(out["x"]), _abi.dptr(out["y"]), _abi.iptr(out["id"]), _abi.dptr(out["conc"]),
+                                              _abi.iptr(out["found"])))
+        assert m.value == n
+        return out
+
+    def drifters_update(self, set: int, conc_lim: float, keepers=None, bbox=None) -> int:
+        """updateConc + maskXY, as Drifters::updateDrifters chains them at an output time; returns how many drifters are left."""
+        self.drifters_conc(set, bbox, want_host=False)
+        return self.drifters_mask(set, conc_lim, keepers)
+
     def branch_trace(self) -> dict:
         """The record option "trace_branches" keeps (include/nxs_dyn.h): {'hash', 'damage_substeps', 'flags', 'substeps'}."""
         t = np.zeros((self.lm.num_elements, 4), np.uint64)
@@ -542,7 +618,7 @@ class FiniteElementDynamics:
         n = {"rlmass": Nn, "node_mass": Nn, "C_bu": Nn, "grad_ssh": 2 * Nn, "fcor": Nn, "VTM": 2 * Nn,
              "shape": 6 * Ne, "emass": Ne, "ecbu": Ne, "force": 6 * Ne, "volume": Ne, "expC": Ne,
              "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn,
-             "means_update_ms": 2, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1}[name]
+             "means_update_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1}[name]
         out = np.empty(n)
         self._chk(self.L.nxs_dyn_debug_array(self.h, name.encode(), _abi.dptr(out), n))
         return out
