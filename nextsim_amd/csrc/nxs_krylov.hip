@@ -50,6 +50,32 @@ int entry_caught(const char *entry) noexcept {
         if (e_ != hipSuccess) return fail(NXS_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_));          \
     } while (0)
 
+// after every kernel launch: a refused launch (too much LDS, a bad grid) is an error of its own, not a wrong result later
+#define KLAUNCHED(kernel)                                                                                \
+    do {                                                                                                 \
+        hipError_t e_ = hipGetLastError();                                                               \
+        if (e_ != hipSuccess) return fail(NXS_ERR_HIP, "launch of %s: %s", kernel, hipGetErrorString(e_)); \
+    } while (0)
+
+// before the first launch of an entry point: an error another library of the process left unread on this thread is not ours
+inline void drop_stale_error() { (void)hipGetLastError(); }
+
+// the two timing events of an entry point; destroyed on every way out of it, the error returns of KCHK / KLAUNCHED included
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t create() {
+        const hipError_t e = hipEventCreate(&e0);
+        return e != hipSuccess ? e : hipEventCreate(&e1);
+    }
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    EventPair() = default;
+    EventPair(const EventPair &) = delete;
+    EventPair &operator=(const EventPair &) = delete;
+};
+
 // (never the legacy default stream: another handle of this process may be capturing a graph on its own thread)
 inline hipError_t copy_on(hipStream_t st, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
     const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
@@ -64,6 +90,12 @@ constexpr int BS = 256;     // threads per block = 4 slices
 constexpr int SL = 64;      // rows per slice
 constexpr int MAXG = 2048;  // most blocks of a reducing kernel (= partial sums per value)
 constexpr unsigned int NGRP = 16, CSTRIDE = 32;  // ticket counters: [0] global, [CSTRIDE (g+1)] group g (128 B apart)
+
+// a / b of two reduced scalars, 0 where b == 0.  The host looks at the residual every check_every iterations only; once the
+// iteration has converged EXACTLY (r == 0: a diagonal or 1 x 1 system, the identity) every dot is 0 from then on, and 0 / 0
+// would turn x into NaN before the host sees rr == 0.  With the quotients 0 the remaining iterations leave x and r as they are.
+// The operands are uniform (read from scal): no divergence; a quotient with b != 0 keeps its bits.
+__device__ __forceinline__ double quot(double a, double b) { return b != 0. ? a / b : 0.; }
 
 // scalar slots (device array of 16 doubles).  A pair that is all-reduced together is adjacent.
 //   CG:       [0] rz (even iterations) [1] rr   [2] rz (odd) [3] rr   [4] pAp   [5] bb
@@ -187,7 +219,7 @@ __global__ void __launch_bounds__(BS) k_cg_init(int n, const double *__restrict_
 __global__ void __launch_bounds__(BS) k_cg_xr(int n, int par, const double *__restrict__ p, const double *__restrict__ Ap, const double *__restrict__ dinv,
                                               double *__restrict__ x, double *__restrict__ r, double *__restrict__ z, double *__restrict__ partial,
                                               unsigned int *__restrict__ counter, double *__restrict__ scal) {
-    const double alpha = scal[2 * par] / scal[S_PAP];
+    const double alpha = quot(scal[2 * par], scal[S_PAP]);
     double acc[2] = {0., 0.};
     for (int i = blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
         x[i] += alpha * p[i];
@@ -199,7 +231,7 @@ __global__ void __launch_bounds__(BS) k_cg_xr(int n, int par, const double *__re
     grid_sum<2>(acc, partial, counter, scal, 2 * (par ^ 1));
 }
 __global__ void __launch_bounds__(BS) k_cg_p(int n, int par, const double *__restrict__ scal, const double *__restrict__ z, double *__restrict__ p) {
-    const double beta = scal[2 * (par ^ 1)] / scal[2 * par];
+    const double beta = quot(scal[2 * (par ^ 1)], scal[2 * par]);
     for (int i = blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) p[i] = z[i] + beta * p[i];
 }
 
@@ -219,8 +251,8 @@ __global__ void __launch_bounds__(BS) k_bicg_init(int n, const double *__restric
 __global__ void __launch_bounds__(BS) k_bicg_p(int n, int par, const double *__restrict__ scal, const double *__restrict__ r, const double *__restrict__ v,
                                                const double *__restrict__ dinv, double *__restrict__ p, double *__restrict__ y) {
     const double rho = scal[2 * par], rho_old = scal[2 * (par ^ 1)];
-    const double alpha_prev = rho_old / scal[S_PAP], omega_prev = scal[S_TS + 1] != 0. ? scal[S_TS] / scal[S_TS + 1] : 0.;
-    const double beta = (rho / rho_old) * (alpha_prev / omega_prev);
+    const double alpha_prev = quot(rho_old, scal[S_PAP]), omega_prev = quot(scal[S_TS], scal[S_TS + 1]);
+    const double beta = rho_old != 0. && omega_prev != 0. ? (rho / rho_old) * (alpha_prev / omega_prev) : 0.;  // 0: p restarts from r
     for (int i = blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
         const double pi = r[i] + beta * (p[i] - omega_prev * v[i]);
         p[i] = pi;
@@ -229,7 +261,7 @@ __global__ void __launch_bounds__(BS) k_bicg_p(int n, int par, const double *__r
 }
 __global__ void __launch_bounds__(BS) k_bicg_s(int n, int par, const double *__restrict__ scal, const double *__restrict__ r, const double *__restrict__ v,
                                                const double *__restrict__ dinv, double *__restrict__ sv, double *__restrict__ z) {
-    const double alpha = scal[2 * par] / scal[S_PAP];
+    const double alpha = quot(scal[2 * par], scal[S_PAP]);
     for (int i = blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
         const double si = r[i] - alpha * v[i];
         sv[i] = si;
@@ -239,8 +271,8 @@ __global__ void __launch_bounds__(BS) k_bicg_s(int n, int par, const double *__r
 __global__ void __launch_bounds__(BS) k_bicg_x(int n, int par, const double *__restrict__ y, const double *__restrict__ z, const double *__restrict__ sv,
                                                const double *__restrict__ t, const double *__restrict__ rhat, double *__restrict__ x, double *__restrict__ r,
                                                double *__restrict__ partial, unsigned int *__restrict__ counter, double *__restrict__ scal) {
-    const double alpha = scal[2 * par] / scal[S_PAP];
-    const double omega = scal[S_TS + 1] != 0. ? scal[S_TS] / scal[S_TS + 1] : 0.;
+    const double alpha = quot(scal[2 * par], scal[S_PAP]);
+    const double omega = quot(scal[S_TS], scal[S_TS + 1]);
     double acc[2] = {0., 0.};
     for (int i = blockIdx.x * BS + threadIdx.x; i < n; i += gridDim.x * BS) {
         x[i] += alpha * y[i] + omega * z[i];
@@ -388,16 +420,23 @@ void build_pattern(const int32_t *indices, int32_t Nn, int32_t Ne, std::vector<i
 }
 
 void colour_elements(const int32_t *indices, int32_t Nn, int32_t Ne, std::vector<int> &colour, int &ncol) {
-    // greedy: smallest colour not used by any element sharing a node (64 colours are plenty for a planar mesh)
-    std::vector<unsigned long long> used(Nn, 0ull);
+    // greedy: smallest colour not used by any element sharing a node.  A vertex of valence v needs v colours: 256 bits per
+    // node (colours 0 .. 255, what the assembly's one byte per element holds), and a mesh that wants more than that gets
+    // colour 256 for the rest -- ncol = 257, which the assembly refuses.
+    constexpr int W = 4;
+    std::vector<unsigned long long> used((size_t)Nn * W, 0ull);
     colour.assign(Ne, 0);
     ncol = 0;
     for (int e = 0; e < Ne; ++e) {
-        const unsigned long long m = used[indices[3 * e] - 1] | used[indices[3 * e + 1] - 1] | used[indices[3 * e + 2] - 1];
-        int c = 0;
-        while (c < 63 && ((m >> c) & 1ull)) ++c;
+        const unsigned long long *u0 = &used[(size_t)(indices[3 * e] - 1) * W], *u1 = &used[(size_t)(indices[3 * e + 1] - 1) * W],
+                                 *u2 = &used[(size_t)(indices[3 * e + 2] - 1) * W];
+        int c = 64 * W;
+        for (int w = 0; w < W; ++w) {
+            const unsigned long long m = u0[w] | u1[w] | u2[w];
+            if (~m) { c = 64 * w + __builtin_ctzll(~m); break; }
+        }
         colour[e] = c;
-        for (int k = 0; k < 3; ++k) used[indices[3 * e + k] - 1] |= (1ull << c);
+        if (c < 64 * W) for (int k = 0; k < 3; ++k) used[(size_t)(indices[3 * e + k] - 1) * W + c / 64] |= (1ull << (c % 64));
         ncol = std::max(ncol, c + 1);
     }
 }
@@ -504,9 +543,11 @@ int upload_matrix(nxs_krylov_handle *h, int n, int n_local, const std::vector<in
 }
 
 int finish_matrix(nxs_krylov_handle *h) {  // Jacobi preconditioner; refuses a row without a diagonal
+    drop_stale_error();
     KCHK(hipMemsetAsync(h->d_bad, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL(k_diag_inv, dim3((h->n + BS - 1) / BS), dim3(BS), 0, h->stream, h->n, h->nslices, (const int *)h->d_off, (const int *)h->d_col,
                        (const double *)h->d_val, h->d_dinv, h->d_bad);
+    KLAUNCHED("k_diag_inv");
     int bad = 0;
     KCHK(hipMemcpyAsync(&bad, h->d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     KCHK(hipStreamSynchronize(h->stream));
@@ -524,6 +565,7 @@ int exchange(nxs_krylov_handle *h, double *vec) {
     const int ns = (int)h->send_procs.size(), nr = (int)h->recv_procs.size();
     const int ts = h->send_offsets[ns], tr = h->recv_offsets[nr];
     if (ts > 0) hipLaunchKernelGGL(k_pack, dim3((ts + BS - 1) / BS), dim3(BS), 0, h->stream, ts, (const int *)h->d_send_index, (const double *)vec, h->d_send_buf);
+    if (ts > 0) KLAUNCHED("k_pack");
     if (h->exchange_fn) {  // the caller's communicator, host staged
         if (ts > 0) KCHK(hipMemcpyAsync(h->h_send, h->d_send_buf, (size_t)ts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         KCHK(hipStreamSynchronize(h->stream));
@@ -543,6 +585,7 @@ int exchange(nxs_krylov_handle *h, double *vec) {
         h->n_rccl_exchange++;
     }
     if (tr > 0) hipLaunchKernelGGL(k_unpack, dim3((tr + BS - 1) / BS), dim3(BS), 0, h->stream, tr, (const int *)h->d_recv_index, (const double *)h->d_recv_buf, vec);
+    if (tr > 0) KLAUNCHED("k_unpack");
     return NXS_OK;
 }
 
@@ -569,9 +612,11 @@ int allreduce(nxs_krylov_handle *h, int slot, int count) {
 }
 
 template <int ND>
-void spmv(nxs_krylov_handle *h, const double *in, double *out, const double *w0, int slot) {
+int spmv(nxs_krylov_handle *h, const double *in, double *out, const double *w0, int slot) {
     hipLaunchKernelGGL((k_spmv_sell<ND>), dim3(spmv_grid(h)), dim3(BS), 0, h->stream, h->n, h->nslices, (const int *)h->d_off, (const int *)h->d_col,
                        (const double *)h->d_val, in, out, w0, h->d_partial, h->d_counter, h->d_scal, slot);
+    KLAUNCHED("k_spmv_sell");
+    return NXS_OK;
 }
 
 // b, x on the device (vec[0] = x, vec[1] = b)
@@ -581,8 +626,10 @@ int run_solver(nxs_krylov_handle *h, int method, double rtol, int max_iter, int 
     double *x = h->vec[0], *b = h->vec[1], *r = h->vec[2], *p = h->vec[3], *q = h->vec[4], *z = h->vec[5], *rhat = h->vec[6], *y = h->vec[7], *sv = h->vec[8];
     double *partial = h->d_partial, *scal = h->d_scal;
     unsigned int *counter = h->d_counter;
-    hipEvent_t e0, e1;
-    KCHK(hipEventCreate(&e0)); KCHK(hipEventCreate(&e1));
+    EventPair ev;
+    drop_stale_error();
+    KCHK(ev.create());
+    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
     KCHK(hipEventRecord(e0, h->stream));
     int rc = NXS_OK, it = 0;
     double hs[8] = {0};
@@ -591,52 +638,54 @@ int run_solver(nxs_krylov_handle *h, int method, double rtol, int max_iter, int 
         KCHK(hipStreamSynchronize(h->stream));
         return NXS_OK;
     };
+    auto launched = [&](const char *kernel) -> int { KLAUNCHED(kernel); return NXS_OK; };
     const int check_every = 10;
     double bb = 1., rr = 0.;
     if (method == NXS_KRYLOV_CG) {
         hipLaunchKernelGGL(k_cg_init, G, B, 0, h->stream, n, (const double *)b, (const double *)h->d_dinv, x, r, z, p, partial, counter, scal);
-        if ((rc = allreduce(h, 0, 2)) || (rc = read_scal())) goto done;
+        if ((rc = launched("k_cg_init")) || (rc = allreduce(h, 0, 2)) || (rc = read_scal())) goto done;
         bb = hs[1] > 0. ? hs[1] : 1.;
         rr = hs[1];
         while (it < max_iter && hs[1] > 0.) {
             const int par = it & 1;
             if ((rc = exchange(h, p))) goto done;
-            spmv<1>(h, p, q, p, S_PAP);                                                   // q = A p, (p, Ap)
+            if ((rc = spmv<1>(h, p, q, p, S_PAP))) goto done;                            // q = A p, (p, Ap)
             if ((rc = allreduce(h, S_PAP, 1))) goto done;
             hipLaunchKernelGGL(k_cg_xr, G, B, 0, h->stream, n, par, (const double *)p, (const double *)q, (const double *)h->d_dinv, x, r, z, partial, counter, scal);
-            if ((rc = allreduce(h, 2 * (par ^ 1), 2))) goto done;
+            if ((rc = launched("k_cg_xr")) || (rc = allreduce(h, 2 * (par ^ 1), 2))) goto done;
             hipLaunchKernelGGL(k_cg_p, G, B, 0, h->stream, n, par, (const double *)scal, (const double *)z, p);
+            if ((rc = launched("k_cg_p"))) goto done;
             ++it;
             if (it % check_every == 0 || it == max_iter) {
                 if ((rc = read_scal())) goto done;
                 rr = hs[2 * (it & 1) + 1];
-                if (!(rr == rr) || std::sqrt(rr / bb) <= rtol) break;
+                if (!(rr == rr) || rr == 0. || std::sqrt(rr / bb) <= rtol) break;  // (rr == 0: converged exactly, whatever rtol)
             }
         }
     } else {
         hipLaunchKernelGGL(k_bicg_init, G, B, 0, h->stream, n, (const double *)b, x, r, rhat, p, q, partial, counter, scal);
-        if ((rc = allreduce(h, 0, 2)) || (rc = read_scal())) goto done;
+        if ((rc = launched("k_bicg_init")) || (rc = allreduce(h, 0, 2)) || (rc = read_scal())) goto done;
         bb = hs[1] > 0. ? hs[1] : 1.;
         rr = hs[1];
         double *v = q, *t = b;  // b is consumed once r and rhat hold it: its buffer takes t = A M^-1 s
         while (it < max_iter && hs[1] > 0.) {
             const int par = it & 1;
             hipLaunchKernelGGL(k_bicg_p, G, B, 0, h->stream, n, par, (const double *)scal, (const double *)r, (const double *)v, (const double *)h->d_dinv, p, y);
-            if ((rc = exchange(h, y))) goto done;
-            spmv<1>(h, y, v, rhat, S_PAP);                                                // v = A M^-1 p, (rhat, v)
+            if ((rc = launched("k_bicg_p")) || (rc = exchange(h, y))) goto done;
+            if ((rc = spmv<1>(h, y, v, rhat, S_PAP))) goto done;                         // v = A M^-1 p, (rhat, v)
             if ((rc = allreduce(h, S_PAP, 1))) goto done;
             hipLaunchKernelGGL(k_bicg_s, G, B, 0, h->stream, n, par, (const double *)scal, (const double *)r, (const double *)v, (const double *)h->d_dinv, sv, z);
-            if ((rc = exchange(h, z))) goto done;
-            spmv<2>(h, z, t, sv, S_TS);                                                   // t = A M^-1 s, (t, s), (t, t)
+            if ((rc = launched("k_bicg_s")) || (rc = exchange(h, z))) goto done;
+            if ((rc = spmv<2>(h, z, t, sv, S_TS))) goto done;                            // t = A M^-1 s, (t, s), (t, t)
             if ((rc = allreduce(h, S_TS, 2))) goto done;
             hipLaunchKernelGGL(k_bicg_x, G, B, 0, h->stream, n, par, (const double *)y, (const double *)z, (const double *)sv, (const double *)t, (const double *)rhat, x, r,
                                partial, counter, scal);
-            if ((rc = allreduce(h, 2 * (par ^ 1), 2))) goto done;
+            if ((rc = launched("k_bicg_x")) || (rc = allreduce(h, 2 * (par ^ 1), 2))) goto done;
             ++it;
             if (it % check_every == 0 || it == max_iter) {
                 if ((rc = read_scal())) goto done;
                 rr = hs[2 * (it & 1) + 1];
-                if (!(rr == rr) || std::sqrt(rr / bb) <= rtol) break;
+                if (!(rr == rr) || rr == 0. || std::sqrt(rr / bb) <= rtol) break;  // (rr == 0: converged exactly, whatever rtol)
                 if (hs[2 * (it & 1)] == 0.) break;  // breakdown (rho = 0)
             }
         }
@@ -646,7 +695,6 @@ done:
     hipError_t err = hipStreamSynchronize(h->stream);
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (rc) return rc;
     if (err != hipSuccess) return fail(NXS_ERR_HIP, "solver kernels failed: %s", hipGetErrorString(err));
     if (iterations) *iterations = it;
@@ -826,21 +874,22 @@ int nxs_krylov_spmv(nxs_krylov_handle *h, const double *in, double *out, int32_t
     if (!h || !in || !out || reps < 1) return fail(NXS_ERR_INVALID, "NULL argument / reps < 1");
     if (h->n < 1) return fail(NXS_ERR_STATE, "spmv before set_matrix");
     KCHK(hipSetDevice(h->device));
+    drop_stale_error();
     KCHK(hipMemcpyAsync(h->vec[0], in, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipEvent_t e0, e1;
-    KCHK(hipEventCreate(&e0)); KCHK(hipEventCreate(&e1));
+    EventPair ev;
+    KCHK(ev.create());
+    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
     int rc = exchange(h, h->vec[0]);  // (a warm-up SpMV when timing)
-    if (!rc && reps > 1) spmv<0>(h, h->vec[0], h->vec[1], nullptr, 0);
+    if (!rc && reps > 1) rc = spmv<0>(h, h->vec[0], h->vec[1], nullptr, 0);
     KCHK(hipEventRecord(e0, h->stream));
     for (int i = 0; i < reps && !rc; ++i) {
         if (i > 0) rc = exchange(h, h->vec[0]);
-        spmv<0>(h, h->vec[0], h->vec[1], nullptr, 0);
+        if (!rc) rc = spmv<0>(h, h->vec[0], h->vec[1], nullptr, 0);
     }
     KCHK(hipEventRecord(e1, h->stream));
     hipError_t err = hipStreamSynchronize(h->stream);
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (rc) return rc;
     if (err != hipSuccess) return fail(NXS_ERR_HIP, "spmv failed: %s", hipGetErrorString(err));
     KCHK(copy_on(h->stream, out, h->vec[1], (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost));
@@ -899,7 +948,7 @@ int nxs_fem_poisson_solve(const int32_t *indices, const double *x, const double 
     colour_elements(indices, Nn, Ne, colour, ncol);
     if (!csr_to_sell(Nn, rp.data(), ci.data(), nullptr, off, col, sval, &where)) return fail(NXS_ERR_INVALID, "matrix too large for 32-bit entry offsets");
     // patches of PROWS consecutive rows and, per patch, every element that touches one of its rows
-    if (ncol > 255) return fail(NXS_ERR_INVALID, "more than 255 element colours");
+    if (ncol > 256) return fail(NXS_ERR_INVALID, "more than 256 element colours (a vertex of that valence)");
     const int npatch = (Nn + PROWS - 1) / PROWS, nslices = (int)off.size() - 1;
     std::vector<int> pel_off(npatch + 1, 0);
     auto patches_of = [&](int e, int (&ps)[3]) {
@@ -961,21 +1010,33 @@ int nxs_fem_poisson_solve(const int32_t *indices, const double *x, const double 
 
     double *rhs = h->vec[1];
     const size_t lds = (size_t)(Lmax + PROWS) * sizeof(double);
-    hipEvent_t e0, e1;
-    KCHK(hipEventCreate(&e0)); KCHK(hipEventCreate(&e1));
+    drop_stale_error();
+    {   // a slice is as wide as its longest row and a patch holds two slices: one hub of valence >= 128 (a slice of 64 x 129 doubles) or a
+        // hub of valence >= 64 in either slice wants more than the 64 KiB a launch gets by default
+        int lds_max = 0;
+        KCHK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
+        if (lds > (size_t)lds_max)
+            return fail(NXS_ERR_INVALID, "patch assembly: a patch of %d rows holds %d matrix entries (its longest row sets the width), %zu B of LDS against the %d B of a workgroup",
+                        PROWS, Lmax, lds, lds_max);
+        if (lds > 64u * 1024u) KCHK(hipFuncSetAttribute((const void *)k_assemble_patches, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    EventPair ev;
+    KCHK(ev.create());
+    const hipEvent_t e0 = ev.e0, e1 = ev.e1;
     // the assembly is run twice and the second pass is the one timed (the first one also pays for first-touch page faults)
     for (int pass = 0; pass < 2; ++pass) {
         if (pass == 1) KCHK(hipEventRecord(e0, h->stream));
         hipLaunchKernelGGL(k_assemble_patches, dim3(npatch), dim3(PT), lds, h->stream, Nn, nslices, ncol, (const int *)h->d_off, (const int *)dpeo.p, (const int *)dptri.p,
                            (const double *)dpf.p, (const unsigned char *)dpcol.p, (const unsigned short *)dlpos.p, (const unsigned char *)dlrow.p, tot, (const double *)dx.p,
                            (const double *)dy.p, Lmax, h->d_val, rhs);
+        KLAUNCHED("k_assemble_patches");
         hipLaunchKernelGGL(k_apply_dirichlet, dim3((Nn + BS - 1) / BS), dim3(BS), 0, h->stream, Nn, (const int *)h->d_off, (const int *)h->d_col, (const unsigned char *)ddir.p, h->d_val, rhs);
+        KLAUNCHED("k_apply_dirichlet");
         if (pass == 1) KCHK(hipEventRecord(e1, h->stream));
     }
     KCHK(hipStreamSynchronize(h->stream));
     float msa = 0.f;
     (void)hipEventElapsedTime(&msa, e0, e1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if ((rc = finish_matrix(h))) return rc;
     if ((rc = run_solver(h, NXS_KRYLOV_CG, rtol, max_iter, iterations, rel_residual, ms_solve))) return rc;
     KCHK(copy_on(h->stream, u, h->vec[0], (size_t)Nn * sizeof(double), hipMemcpyDeviceToHost));
