@@ -25,6 +25,7 @@
  *   #ifdef OASIS: M_tau_wi in explicitSolve()   nxs_dyn_set_wave_stress (FE.cpp:10353-10354, 10408-10414, 10509-10518)
  *   #ifdef OASIS: M_cum_damage, M_conc_fsd      nxs_dyn_put_coupled / nxs_dyn_get_coupled (FE.cpp:4233-4238, 3991-3994)
  *   updateMeans(M_moorings, time_factor)        nxs_dyn_means_update    (FE.cpp:8518-9024; configure / get / to_grid / reset beside it)
+ *   interpFields() + assignVariables()          nxs_dyn_regrid          (FE.cpp:3071-3154, 2120-2151, 2196-2258, 3161-3297, 553-572)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -232,7 +233,8 @@ NXS_API int nxs_dyn_default_params(nxs_dyn_params *p); /* model/options.cpp defa
  * (model/constants.hpp:56-87), PI (contrib/bamg/include/OppositeAngle.h:4), days_in_sec (model/finiteelement.hpp:549).  Host only; lets a
  * caller (and tests/test_reference_constants.py, against values printed by a translation unit that includes the reference's headers) check
  * that library and model agree before the first step. */
-enum { NXS_CONST_RHOI = 0, NXS_CONST_RHOW, NXS_CONST_RHOS, NXS_CONST_RHOA, NXS_CONST_GRAVITY, NXS_CONST_OMEGA, NXS_CONST_PI, NXS_CONST_DAYS_IN_SEC, NXS_CONST_COUNT };
+enum { NXS_CONST_RHOI = 0, NXS_CONST_RHOW, NXS_CONST_RHOS, NXS_CONST_RHOA, NXS_CONST_GRAVITY, NXS_CONST_OMEGA, NXS_CONST_PI, NXS_CONST_DAYS_IN_SEC,
+       NXS_CONST_SI /* physical::si */, NXS_CONST_LF /* physical::Lf */, NXS_CONST_C /* physical::C: model/constants.hpp:17-68, the enthalpy transformation of nxs_dyn_regrid */, NXS_CONST_COUNT };
 NXS_API int nxs_dyn_physical_constants(double *out, int32_t count);
 /* Self-test of one arithmetic short-cut of the sub-step kernels (no reference call site).  The six shape coefficients of a triangle (FE.cpp:1951-1964) are six
  * quotients by ONE divisor, the Jacobian; where every operand of a step lies in a range the prep kernels check once per step (|coordinate| zero or in
@@ -494,6 +496,72 @@ NXS_API int nxs_dyn_drifters_move(nxs_dyn_handle *h, const double *bbox /* [4] o
 NXS_API int nxs_dyn_drifters_conc(nxs_dyn_handle *h, int32_t set, const double *bbox /* [4] or NULL */, double *conc_host /* [n] or NULL */);
 NXS_API int nxs_dyn_drifters_mask(nxs_dyn_handle *h, int32_t set, double conc_lim, const int32_t *keepers, int32_t n_keepers, int32_t *n_left);
 NXS_API int nxs_dyn_drifters_get(nxs_dyn_handle *h, int32_t set, int32_t *n, double *x, double *y, int32_t *id, double *conc, int32_t *found);
+
+/* ---- A regrid on the live handle: FiniteElement::interpFields() + assignVariables() (FE.cpp:3071-3154, 553-572) without the prognostic state leaving the device.
+ * The remesher stays the host's; what lies between the handle and the two interpolation kernels of include/nxs_interp.h happens here:
+ *   1. collectVariables (FE.cpp:2120-2151)   the element variables as interleaved [Ne_old][nb_var] rows, the interpTransformation of every variable applied
+ *      (operand order of FE.cpp:2139-2145).  Column order = sortPrognosticVars (FE.cpp:2087-2111): every variable of kind `none` first -- the handle's own in the
+ *      order of nxs_dyn_state (conc, thick, snow_thick, damage, ridge_ratio, sigma[0..2], conc_young, h_young, hs_young, conc_myi, thick_myi), then cum_damage and
+ *      the FSD bins while attached (nxs_dyn_put_coupled), then the caller's extras of kind none -- then the extras of kind conc, thick, enthalpy, each kind in
+ *      the caller's order.  cohesion, time_relaxation_damage and drag_ui* are not prognostic in the reference and are no columns.
+ *   2. ConservativeRemappingMeshToMesh through the context (nxs_regrid_remap_elements on device rows).
+ *   3. redistributeVariables with apply_maxima = true (FE.cpp:2196-2258): one thread per new element walks the columns in order -- the inverse transformation
+ *      with the clamped new M_conc / M_thick, the no_old_ice rule (M_tice: -mu * si, FE.cpp:2243-2245), max(minVal, .) then min(maxVal, .), and after the last
+ *      column the young-ice cap conc_young = 1 - conc (FE.cpp:2253-2256) when ice_cat_type is NXS_ICECAT_YOUNG_ICE.  The handle's own bounds are
+ *      model_variable.cpp's: conc, ridge_ratio, conc_young, conc_myi and every FSD bin in [0, 1]; thick, snow_thick, h_young, hs_young, thick_myi, cum_damage
+ *      >= 0; damage in [0, 1 - 1e-10]; sigma unbounded.  A row the remapping left NaN (num_failed) stays NaN in every variable: the caller decides, where the
+ *      reference asserts.
+ *   4. gatherFieldsNode / scatterFieldsNode (FE.cpp:3174-3198, 3273-3293): [Nn_old][6] = VT.u, VT.v, UM.u, UM.v, UT.u, UT.v through InterpFromMeshToMesh2dx
+ *      (isdefault = false) at the new nodes; M_VT from columns 0 and 1; M_UM = M_UT = 0 (assignVariables, FE.cpp:553-560), D_tau_w = D_tau_a = 0.
+ *   5. the new mesh through nxs_dyn_set_mesh's own path; the new state rows take the place of the old ones on the device.  Forcing is the caller's next
+ *      nxs_dyn_set_forcing, and the means / drifters attached to the handle see what they see after nxs_dyn_set_mesh.  cum_damage / FSD bins stay attached.
+ * Errors: everything is checked on the host before the first launch -- NXS_ERR_INVALID for a NULL required pointer, num_extra < 0, an unknown transformation, no
+ * context and no moved coordinates, a new mesh nxs_dyn_set_mesh would refuse; NXS_ERR_STATE before nxs_dyn_put_state and on a handle with halo lists (nranks > 1:
+ * the reference does this step on its root rank from gathered state; the gather / scatter of a partitioned run is not done here).  A failure before step 5
+ * leaves the handle on the old mesh with its state as it was (an extra's new_values may have been written). */
+/* ModelVariable::interpTransformation, model_variable.hpp */
+enum { NXS_TRANSFORM_NONE = 0, NXS_TRANSFORM_CONC = 1, NXS_TRANSFORM_THICK = 2, NXS_TRANSFORM_ENTHALPY = 3 };
+/* nxs_dyn_regrid_var::flags */
+enum { NXS_REGRID_VAR_HAS_MIN = 1,        /* ModelVariable::hasMinVal (FE.cpp:2247) */
+       NXS_REGRID_VAR_HAS_MAX = 2,        /* ModelVariable::hasMaxVal (FE.cpp:2249) */
+       NXS_REGRID_VAR_IS_TICE = 4,        /* varID() == M_tice: -mu * si where there is no ice (FE.cpp:2243-2245) */
+       NXS_REGRID_VAR_OLD_ON_DEVICE = 8,  /* old_values is a device pointer on the handle's device: used in place */
+       NXS_REGRID_VAR_NEW_ON_DEVICE = 16  /* new_values is: written in place */ };
+
+/* one element variable the HOST owns (thermodynamics: M_tice[k], M_sst, M_sss, M_tsurf_young, ...) that rides along */
+typedef struct nxs_dyn_regrid_var {
+    const double *old_values;   /* [Ne_old] (*vptr)[i] of collectVariables (FE.cpp:2135) */
+    double *new_values;         /* [Ne_new] (*vptr)[i] of redistributeVariables (FE.cpp:2250) */
+    int32_t transformation;     /* NXS_TRANSFORM_*: vptr->getInterpTransformation() (FE.cpp:2136, 2217-2241) */
+    int32_t flags;              /* NXS_REGRID_VAR_* */
+    double min_val, max_val;    /* vptr->minVal(), maxVal() (FE.cpp:2247-2249); read only with the HAS_ flag */
+} nxs_dyn_regrid_var;
+
+typedef struct nxs_dyn_regrid_args {
+    const nxs_dyn_mesh *new_mesh;            /* as for nxs_dyn_set_mesh: the adapted mesh after distributedMeshProcessing (FE.cpp:3743-3752) */
+    struct nxs_regrid *context;              /* nxs_regrid_create of the OLD mesh at x0 + M_UM (M_mesh_root.move(um_root, 1.), FE.cpp:3668-3671), on the handle's device; NULL = built and destroyed inside */
+    const double *x_old_moved, *y_old_moved; /* [Nn_old] those coordinates; needed when context == NULL (the host has them: it just ran the remesher on them) */
+    const double *previous_numbering;        /* [Nn_new] bamgmesh_root->PreviousNumbering as nxs_regrid_remap_elements takes it (ConservativeRemapping.cpp:263-289); may be NULL */
+    int32_t n_geom_vertices;                 /* bamgmesh_root->VerticesOnGeomVertexSize[0] */
+    int32_t num_extra;                       /* entries of `extra` */
+    const nxs_dyn_regrid_var *extra;         /* [num_extra] M_prognostic_variables_elt beyond the handle's own (FE.cpp:7127-7222); NULL with num_extra == 0 */
+    double freezingpoint_mu;                 /* thermo.freezingpoint_mu (FE.cpp:1238); physical::si, Lf, C are the library's own (NXS_CONST_SI, _LF, _C) */
+    /* inputs that are NOT prognostic in the reference and are re-made after a regrid (assignVariables, calcCohesion, thermo): [Ne_new] each, required */
+    const double *cohesion;                  /* M_Cohesion (calcCohesion, FE.cpp:3909-3914) */
+    const double *time_relaxation_damage;    /* M_time_relaxation_damage (FE.cpp:648-649) */
+    const double *drag_ui;                   /* M_drag_ui */
+    const double *drag_ui_young;             /* M_drag_ui_young */
+} nxs_dyn_regrid_args;
+
+typedef struct nxs_dyn_regrid_info {
+    int32_t num_failed;       /* new elements the conservative remapping could not do (nxs_regrid_remap_elements): their rows are NaN */
+    int32_t num_exterior;     /* new nodes in no triangle of the old mesh (nxs_regrid_interp_nodes) */
+    int32_t nb_var_element;   /* columns of the element rows: M_prognostic_variables_elt.size() (FE.cpp:2123) */
+    int32_t reserved0;
+    double collect_ms, remap_ms, redistribute_ms, nodes_ms, set_mesh_ms, total_ms;   /* host wall clock of the five phases (uploads of extras in collect_ms, their way back and the re-made inputs in set_mesh_ms) and of the call */
+} nxs_dyn_regrid_info;
+
+NXS_API int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regrid_info *info /* may be NULL */);
 
 /* One dynamics step on the device-resident state: FE.cpp:8197-8214.  Asynchronous on the
  * handle's stream; nxs_dyn_synchronize() waits for it. */

@@ -79,6 +79,12 @@ public:
         check(nxs_dyn_drifters_get(h_, set, &n, x, y, id, conc, found), "drifters_get");
         return n;
     }
+    // interpFields() + assignVariables() on the device-resident state (FE.cpp:3071-3154, 553-572): the handle goes on with a.new_mesh; forcing is the next setForcing
+    nxs_dyn_regrid_info regrid(const nxs_dyn_regrid_args &a) {
+        nxs_dyn_regrid_info info{};
+        check(nxs_dyn_regrid(h_, &a, &info), "regrid");
+        return info;
+    }
     nxs_dyn_handle *handle() { return h_; }
 
 private:

@@ -134,6 +134,30 @@ class Coupled(C.Structure):   # nxs_dyn_coupled
     _fields_ = [("cum_damage", c_double_p), ("conc_fsd", c_double_p), ("num_fsd_bins", C.c_int32), ("reserved0", C.c_int32)]
 
 
+# nxs_dyn_regrid (include/nxs_dyn.h): ModelVariable::interpTransformation and the flags of nxs_dyn_regrid_var
+NXS_TRANSFORM_NONE, NXS_TRANSFORM_CONC, NXS_TRANSFORM_THICK, NXS_TRANSFORM_ENTHALPY = range(4)
+TRANSFORMATIONS = {"none": NXS_TRANSFORM_NONE, "conc": NXS_TRANSFORM_CONC, "thick": NXS_TRANSFORM_THICK, "enthalpy": NXS_TRANSFORM_ENTHALPY}
+NXS_REGRID_VAR_HAS_MIN, NXS_REGRID_VAR_HAS_MAX, NXS_REGRID_VAR_IS_TICE, NXS_REGRID_VAR_OLD_ON_DEVICE, NXS_REGRID_VAR_NEW_ON_DEVICE = 1, 2, 4, 8, 16
+
+
+class RegridVar(C.Structure):   # nxs_dyn_regrid_var
+    _fields_ = [("old_values", C.c_void_p), ("new_values", C.c_void_p), ("transformation", C.c_int32), ("flags", C.c_int32),
+                ("min_val", C.c_double), ("max_val", C.c_double)]
+
+
+class RegridArgs(C.Structure):   # nxs_dyn_regrid_args
+    _fields_ = [("new_mesh", C.POINTER(Mesh)), ("context", C.c_void_p), ("x_old_moved", c_double_p), ("y_old_moved", c_double_p),
+                ("previous_numbering", c_double_p), ("n_geom_vertices", C.c_int32), ("num_extra", C.c_int32), ("extra", C.POINTER(RegridVar)),
+                ("freezingpoint_mu", C.c_double), ("cohesion", c_double_p), ("time_relaxation_damage", c_double_p), ("drag_ui", c_double_p),
+                ("drag_ui_young", c_double_p)]
+
+
+class RegridInfo(C.Structure):   # nxs_dyn_regrid_info
+    _fields_ = [("num_failed", C.c_int32), ("num_exterior", C.c_int32), ("nb_var_element", C.c_int32), ("reserved0", C.c_int32),
+                ("collect_ms", C.c_double), ("remap_ms", C.c_double), ("redistribute_ms", C.c_double), ("nodes_ms", C.c_double),
+                ("set_mesh_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 # enum nxs_means_var: the Moorings variables nxs_dyn_means_* accumulates, named after GridOutput::variableID
 MEANS_ELEMENTAL = ("conc", "thick", "snow", "conc_cons", "damage", "ridge_ratio", "conc_young", "h_young", "hs_young", "conc_myi", "thick_myi",
                    "dci_ridge_myi", "sigma_11", "sigma_22", "sigma_12", "sigma_n", "sigma_s", "divergence", "drag_ui", "ice_mask")

@@ -16,6 +16,7 @@
 //   k_update          FE.cpp:3946-4131    update()
 //   k_free_drift      FE.cpp:10140-10176
 //   k_regrid_*/k_check_* FE.cpp:8298-8309, 14536-14655 reductions
+//   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
 //
 // Determinism: the reference scatters element contributions into nodes in ascending element
 // order.  Here every node GATHERS over its element fan sorted ascending, which performs the same
@@ -24,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1556,6 +1558,28 @@ static unsigned means_sources(int kind, const std::vector<int> &ids, bool young_
     }
     return src;
 }
+namespace {
+// device memory of one nxs_dyn_regrid call: freed when the call ends, except what the new mesh has taken over (release)
+struct RegridScratch {
+    std::vector<void *> own;
+    ~RegridScratch() { for (void *q : own) if (q) (void)hipFree(q); }
+    template <typename T> T *alloc(size_t count) {
+        void *q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        own.push_back(q);
+        return static_cast<T *>(q);
+    }
+    void release(const void *q) { for (void *&o : own) if (o == q) o = nullptr; }
+};
+struct RegridContextGuard {   // a context made inside the call goes with it
+    nxs_regrid *r = nullptr;
+    ~RegridContextGuard() { if (r) (void)nxs_regrid_destroy(r); }
+};
+inline double ms_since(const std::chrono::steady_clock::time_point &t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+
 extern "C" {
 
 int nxs_dyn_abi_version(void) { return NXS_DYN_ABI_VERSION; }
@@ -1583,7 +1607,7 @@ int nxs_dyn_default_params(nxs_dyn_params *p) try {  // model/options.cpp:43,80,
 
 int nxs_dyn_physical_constants(double *out, int32_t count) try {  // model/constants.hpp:56-87, OppositeAngle.h:4, finiteelement.hpp:549
     if (!out || count < 0) return NXS_ERR_INVALID;
-    const double c[NXS_CONST_COUNT] = {NXS_RHOI, NXS_RHOW, NXS_RHOS, NXS_RHOA, NXS_GRAVITY, NXS_OMEGA, NXS_PI, NXS_DAYS_IN_SEC};
+    const double c[NXS_CONST_COUNT] = {NXS_RHOI, NXS_RHOW, NXS_RHOS, NXS_RHOA, NXS_GRAVITY, NXS_OMEGA, NXS_PI, NXS_DAYS_IN_SEC, NXS_SI, NXS_LF, NXS_HEAT_C};
     for (int i = 0; i < count && i < NXS_CONST_COUNT; ++i) out[i] = c[i];
     return NXS_OK;
 } catch (...) { return dyn_caught(nullptr, "nxs_dyn_physical_constants"); }
@@ -1856,9 +1880,14 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
 } catch (...) { return dyn_caught(h, "nxs_dyn_set_option"); }
 
 // ------------------------------------------------------------------------------------------------
-int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
-    if (!h || !m) return NXS_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->device));
+// The prognostic arrays of a new mesh that exist on the device already (nxs_dyn_regrid wrote them): set_mesh_impl takes them over instead of allocating
+// its own -- an entry it has taken is NULL afterwards, what is left is the caller's to free.  Order: RA_* below.
+enum { RA_VT = 0, RA_UM, RA_UT, RA_CONC, RA_THICK, RA_SNOW, RA_DAMAGE, RA_RIDGE, RA_S0, RA_S1, RA_S2, RA_CYOUNG, RA_HYOUNG, RA_HSYOUNG, RA_CMYI, RA_TMYI,
+       RA_COHESION, RA_THEAL, RA_DRAG_UI, RA_DRAG_UI_YOUNG, RA_COUNT };
+struct RegridAdopt { double *p[RA_COUNT]; };
+
+// what nxs_dyn_set_mesh refuses, checked without touching the handle's mesh (nxs_dyn_regrid asks before its first launch)
+static int check_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) {
     const int Nn = m->num_nodes, Ne = m->num_elements, No = m->local_ndof, Neo = m->local_nelements;
     if (Nn <= 0 || Ne <= 0 || No < 0 || No > Nn || Neo < 0 || Neo > Ne)
         return fail(h, NXS_ERR_INVALID, "mesh sizes invalid: Nn=%d Ne=%d No=%d Neo=%d", Nn, Ne, No, Neo);
@@ -1874,6 +1903,13 @@ int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
         if (m->neumann_flags[i] < 0 || m->neumann_flags[i] >= Nn) return fail(h, NXS_ERR_INVALID, "neumann_flags[%d] out of range", i);
         if (i > 0 && m->neumann_flags[i] <= m->neumann_flags[i - 1]) return fail(h, NXS_ERR_INVALID, "neumann_flags must be sorted and unique (FE.cpp:251-252)");
     }
+    return NXS_OK;
+}
+
+static int set_mesh_impl(nxs_dyn_handle *h, const nxs_dyn_mesh *m, RegridAdopt *adopt) {
+    HIPCHK(h, hipSetDevice(h->device));
+    if (int rc0 = check_mesh(h, m)) return rc0;
+    const int Nn = m->num_nodes, Ne = m->num_elements, No = m->local_ndof, Neo = m->local_nelements;
 
     if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));
     release_graph(h);
@@ -2011,12 +2047,14 @@ int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
     auto &P = h->state_allocs;
     const size_t n2 = 2 * (size_t)Nn, ne = Ne;
 #define A(ptr, cnt) if ((rc = dev_alloc(h, P, &(ptr), (cnt)))) return rc
-    A(s.VT, n2); A(s.VT2, n2); A(s.UM, n2); A(s.UT, n2);
-    A(s.conc, ne); A(s.thick, ne); A(s.snow, ne); A(s.damage, ne); A(s.ridge, ne);
-    A(s.s0, ne); A(s.s1, ne); A(s.s2, ne);
+    // (a prognostic array nxs_dyn_regrid has filled on the device already goes into the pool as it is)
+#define AS(ptr, cnt, ra) do { if (adopt && adopt->p[ra]) { P.push_back(adopt->p[ra]); (ptr) = adopt->p[ra]; adopt->p[ra] = nullptr; } else A(ptr, cnt); } while (0)
+    AS(s.VT, n2, RA_VT); A(s.VT2, n2); AS(s.UM, n2, RA_UM); AS(s.UT, n2, RA_UT);
+    AS(s.conc, ne, RA_CONC); AS(s.thick, ne, RA_THICK); AS(s.snow, ne, RA_SNOW); AS(s.damage, ne, RA_DAMAGE); AS(s.ridge, ne, RA_RIDGE);
+    AS(s.s0, ne, RA_S0); AS(s.s1, ne, RA_S1); AS(s.s2, ne, RA_S2);
     A(s.S4a, 4 * ne); A(s.S4b, 4 * ne);
-    A(s.cyoung, ne); A(s.hyoung, ne); A(s.hsyoung, ne); A(s.cmyi, ne); A(s.tmyi, ne);
-    A(s.cohesion, ne); A(s.theal, ne); A(s.drag_ui, ne); A(s.drag_ui_young, ne);
+    AS(s.cyoung, ne, RA_CYOUNG); AS(s.hyoung, ne, RA_HYOUNG); AS(s.hsyoung, ne, RA_HSYOUNG); AS(s.cmyi, ne, RA_CMYI); AS(s.tmyi, ne, RA_TMYI);
+    AS(s.cohesion, ne, RA_COHESION); AS(s.theal, ne, RA_THEAL); AS(s.drag_ui, ne, RA_DRAG_UI); AS(s.drag_ui_young, ne, RA_DRAG_UI_YOUNG);
     A(s.wind, n2); A(s.ocean, n2); A(s.ssh, (size_t)Nn); A(s.depth, ne);
     A(w.delta_x, ne); A(w.surface, ne); A(w.shape, 6 * ne); A(w.emass, ne); A(w.ecbu, ne); A(w.prec, 8 * ne); A(w.dragsurf, ne);
     A(w.expC, ne); A(w.pmax, ne); A(w.heal, ne); A(w.dxs, ne); A(w.volume, ne); A(w.eskip, ne); A(w.dxi, ne); A(w.open_blk, (size_t)nblocks(Nn)); A(w.shape_range, 1); A(w.erec, 6 * ne); A(w.nrec, 10 * (size_t)Nn);
@@ -2025,6 +2063,7 @@ int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
     w.srec = nullptr;  // (set per step: only the several-sub-steps kernel reads the records)
     A(w.rlmass, (size_t)Nn); A(w.node_mass, (size_t)Nn); A(w.C_bu, (size_t)Nn); A(w.grad_ssh, n2);
     A(w.fcor, (size_t)Nn); A(w.VTM, n2); A(w.xy, n2); A(w.D_tau_a, n2); A(w.D_tau_w, n2); A(w.D_del, ne);
+#undef AS
 #undef A
     HIPCHK(h, hipMemsetAsync(w.surface, 0, ne * sizeof(double), h->stream));
     HIPCHK(h, hipMemsetAsync(w.delta_x, 0, ne * sizeof(double), h->stream));
@@ -2042,6 +2081,11 @@ int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
     if ((rc = means_make_buffers(h))) return rc;   // resetMeshMean(bamgmesh, regrid = true, ...): the configured accumulators at the new sizes, zeroed
     h->have_mesh = true;
     return NXS_OK;
+}
+
+int nxs_dyn_set_mesh(nxs_dyn_handle *h, const nxs_dyn_mesh *m) try {
+    if (!h || !m) return NXS_ERR_INVALID;
+    return set_mesh_impl(h, m, nullptr);
 } catch (...) { return dyn_caught(h, "nxs_dyn_set_mesh"); }
 
 // ------------------------------------------------------------------------------------------------
@@ -2672,6 +2716,166 @@ int nxs_dyn_get_coupled(nxs_dyn_handle *h, nxs_dyn_coupled *c) try {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_get_coupled"); }
+
+// ---- nxs_dyn_regrid: interpFields() + assignVariables() on the live handle (include/nxs_dyn.h)
+int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regrid_info *info) try {
+    if (!h || !a) return NXS_ERR_INVALID;
+    // ---- everything that can be refused is refused here, on the host, before the first launch
+    if (!a->new_mesh) return fail(h, NXS_ERR_INVALID, "regrid: new_mesh is NULL");
+    if (!a->cohesion || !a->time_relaxation_damage || !a->drag_ui || !a->drag_ui_young)
+        return fail(h, NXS_ERR_INVALID, "regrid: cohesion, time_relaxation_damage, drag_ui and drag_ui_young of the new mesh are required (they are re-made after a regrid, not interpolated)");
+    if (a->num_extra < 0) return fail(h, NXS_ERR_INVALID, "regrid: num_extra = %d", a->num_extra);
+    if (a->num_extra > 0 && !a->extra) return fail(h, NXS_ERR_INVALID, "regrid: %d extra variables without an array", a->num_extra);
+    for (int k = 0; k < a->num_extra; ++k) {
+        const nxs_dyn_regrid_var &v = a->extra[k];
+        if (v.transformation < NXS_TRANSFORM_NONE || v.transformation > NXS_TRANSFORM_ENTHALPY)
+            return fail(h, NXS_ERR_INVALID, "regrid: extra[%d] has the unknown transformation %d (NXS_TRANSFORM_NONE .. NXS_TRANSFORM_ENTHALPY)", k, v.transformation);
+        if (!v.old_values || !v.new_values) return fail(h, NXS_ERR_INVALID, "regrid: extra[%d] has a NULL %s", k, v.old_values ? "new_values" : "old_values");
+    }
+    if (!a->context && (!a->x_old_moved || !a->y_old_moved))
+        return fail(h, NXS_ERR_INVALID, "regrid: without a context the coordinates of the old mesh moved by M_UM (x_old_moved, y_old_moved) are needed to build one");
+    if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "regrid before set_mesh / put_state");
+    if (multi_rank(h) || h->have_halo)
+        return fail(h, NXS_ERR_STATE, "regrid: this handle has halo lists set (rank %d of %d): the reference interpolates on its root rank from gathered state, and the gather / scatter "
+                                      "of a partitioned run is not done here", h->rank, h->nranks);
+    if (int rc = check_mesh(h, a->new_mesh)) return rc;
+    const nxs_dyn_mesh &nm = *a->new_mesh;
+    const int Nn_old = h->dm.Nn, Ne_old = h->dm.Ne, Nn_new = nm.num_nodes, Ne_new = nm.num_elements;
+    if (Nn_new < 3) return fail(h, NXS_ERR_INVALID, "regrid: a new mesh of %d nodes", Nn_new);
+    HIPCHK(h, hipSetDevice(h->device));
+    const auto t_start = std::chrono::steady_clock::now();
+    auto t_phase = t_start;
+    nxs_dyn_regrid_info inf{};
+    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    ensure_arrays(h);   // M_sigma / M_damage out of the sub-step loop's records
+
+    // ---- the column table: sortPrognosticVars (FE.cpp:2087-2111)
+    RegridScratch mem;
+    const DevState &so = h->ds;
+    const bool carry_cum = h->dw.cum_damage != nullptr, carry_fsd = h->dw.conc_fsd != nullptr;
+    const int nbins = carry_fsd ? h->dw.nbins : 0;
+    RegridAdopt ad{};
+    for (int k = 0; k < RA_COUNT; ++k) {
+        ad.p[k] = mem.alloc<double>(k <= RA_UT ? 2 * (size_t)Nn_new : (size_t)Ne_new);
+        if (!ad.p[k]) return fail(h, NXS_ERR_HIP, "regrid: no device memory for the state of the new mesh");
+    }
+    double *new_cum = nullptr, *new_fsd = nullptr;
+    if (carry_cum && !(new_cum = mem.alloc<double>(Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for cum_damage");
+    if (carry_fsd && !(new_fsd = mem.alloc<double>((size_t)nbins * Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for the FSD bins");
+    std::vector<RegridCol> cols;
+    const int LO = NXS_REGRID_VAR_HAS_MIN, LOHI = NXS_REGRID_VAR_HAS_MIN | NXS_REGRID_VAR_HAS_MAX;
+    auto own = [&](const double *src, int ra, int flags, double hi) { cols.push_back(RegridCol{src, ad.p[ra], NXS_TRANSFORM_NONE, flags, 0., hi}); };
+    // minVal / maxVal of model_variable.cpp (the table of include/nxs_dyn.h)
+    own(so.conc, RA_CONC, LOHI, 1.); own(so.thick, RA_THICK, LO, 0.); own(so.snow, RA_SNOW, LO, 0.);
+    own(so.damage, RA_DAMAGE, LOHI, 1. - 1e-10); own(so.ridge, RA_RIDGE, LOHI, 1.);
+    own(so.s0, RA_S0, 0, 0.); own(so.s1, RA_S1, 0, 0.); own(so.s2, RA_S2, 0, 0.);
+    const int cy_col = (int)cols.size();
+    own(so.cyoung, RA_CYOUNG, LOHI, 1.); own(so.hyoung, RA_HYOUNG, LO, 0.); own(so.hsyoung, RA_HSYOUNG, LO, 0.);
+    own(so.cmyi, RA_CMYI, LOHI, 1.); own(so.tmyi, RA_TMYI, LO, 0.);
+    if (carry_cum) cols.push_back(RegridCol{h->dw.cum_damage, new_cum, NXS_TRANSFORM_NONE, LO, 0., 0.});
+    for (int b = 0; b < nbins; ++b) cols.push_back(RegridCol{h->dw.conc_fsd + (size_t)b * Ne_old, new_fsd + (size_t)b * Ne_new, NXS_TRANSFORM_NONE, LOHI, 0., 1.});
+    // the caller's variables, kind by kind; host arrays get a device twin (up now, down after the swap)
+    struct Down { double *host; const double *dev; };
+    std::vector<Down> downs;
+    for (int kind = NXS_TRANSFORM_NONE; kind <= NXS_TRANSFORM_ENTHALPY; ++kind)
+        for (int k = 0; k < a->num_extra; ++k) {
+            const nxs_dyn_regrid_var &v = a->extra[k];
+            if (v.transformation != kind) continue;
+            const double *src = v.old_values;
+            double *dst = v.new_values;
+            if (!(v.flags & NXS_REGRID_VAR_OLD_ON_DEVICE)) {
+                double *d = mem.alloc<double>(Ne_old);
+                if (!d) return fail(h, NXS_ERR_HIP, "regrid: no device memory for extra[%d]", k);
+                HIPCHK(h, hipMemcpyAsync(d, v.old_values, (size_t)Ne_old * sizeof(double), hipMemcpyHostToDevice, h->stream));
+                src = d;
+            }
+            if (!(v.flags & NXS_REGRID_VAR_NEW_ON_DEVICE)) {
+                dst = mem.alloc<double>(Ne_new);
+                if (!dst) return fail(h, NXS_ERR_HIP, "regrid: no device memory for extra[%d]", k);
+                downs.push_back(Down{v.new_values, dst});
+            }
+            cols.push_back(RegridCol{src, dst, v.transformation, v.flags & (NXS_REGRID_VAR_HAS_MIN | NXS_REGRID_VAR_HAS_MAX | NXS_REGRID_VAR_IS_TICE), v.min_val, v.max_val});
+        }
+    const int n = (int)cols.size();
+    inf.nb_var_element = n;
+    RegridCol *d_cols = mem.alloc<RegridCol>(n);
+    double *rows_old = mem.alloc<double>((size_t)Ne_old * n), *rows_new = mem.alloc<double>((size_t)Ne_new * n);
+    double *nod_old = mem.alloc<double>(6 * (size_t)Nn_old), *nod_new = mem.alloc<double>(6 * (size_t)Nn_new);
+    if (!d_cols || !rows_old || !rows_new || !nod_old || !nod_new) return fail(h, NXS_ERR_HIP, "regrid: no device memory for the interleaved rows (%d columns)", n);
+    HIPCHK(h, hipMemcpyAsync(d_cols, cols.data(), (size_t)n * sizeof(RegridCol), hipMemcpyHostToDevice, h->stream));
+    // the re-made inputs of the new mesh (FE.cpp:648-649, 3909-3914): not columns
+    {
+        const double *src[4] = {a->cohesion, a->time_relaxation_damage, a->drag_ui, a->drag_ui_young};
+        for (int k = 0; k < 4; ++k) HIPCHK(h, hipMemcpyAsync(ad.p[RA_COHESION + k], src[k], (size_t)Ne_new * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    const double mu = a->freezingpoint_mu;
+    const double enth_a = mu * NXS_SI * NXS_LF;                  // FE.cpp:2145: M_freezingpoint_mu*physical::si*physical::Lf / (physical::C*val)
+    const double enth_b = 4 * mu * NXS_SI * NXS_LF / NXS_HEAT_C; // FE.cpp:2237: 4* M_freezingpoint_mu*physical::si*physical::Lf/physical::C
+    const double t_noice = -mu * NXS_SI;                         // FE.cpp:2245
+    const bool stage = n <= NXS_REGRID_STAGE_MAX;
+    const size_t lds = stage ? (size_t)BLOCK * (n | 1) * sizeof(double) : 0;
+
+    // ---- 1. collectVariables + gatherFieldsNode
+    if (stage) hipLaunchKernelGGL(k_regrid_collect<true>, dim3(nblocks(Ne_old)), dim3(BLOCK), lds, h->stream, Ne_old, n, (const RegridCol *)d_cols, enth_a, (double)NXS_HEAT_C, rows_old);
+    else hipLaunchKernelGGL(k_regrid_collect<false>, dim3(nblocks(Ne_old)), dim3(BLOCK), 0, h->stream, Ne_old, n, (const RegridCol *)d_cols, enth_a, (double)NXS_HEAT_C, rows_old);
+    hipLaunchKernelGGL(k_regrid_pack_nodes, dim3(nblocks(Nn_old)), dim3(BLOCK), 0, h->stream, Nn_old, (const double *)so.VT, (const double *)so.UM, (const double *)so.UT, nod_old);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (the interpolations run on a stream of their own)
+    inf.collect_ms = ms_since(t_phase); t_phase = std::chrono::steady_clock::now();
+
+    // ---- 2. ConservativeRemappingMeshToMesh (FE.cpp:3108) on the device rows
+    RegridContextGuard made;
+    nxs_regrid *ctx = a->context;
+    if (!ctx) {
+        std::vector<int32_t> index_old(3 * (size_t)Ne_old);
+        for (int e = 0; e < Ne_old; ++e) for (int k = 0; k < 3; ++k) index_old[3 * (size_t)e + k] = h->h_t[k][e] + 1;
+        if (nxs_regrid_create(index_old.data(), a->x_old_moved, a->y_old_moved, Nn_old, Ne_old, h->device, &made.r))
+            return fail(h, NXS_ERR_INVALID, "regrid: the context of the old mesh could not be made: %s", nxs_interp_last_error());
+        ctx = made.r;
+    }
+    int32_t nfail = 0, next = 0;
+    if (int rc = nxs_regrid_remap_elements(ctx, rows_new, rows_old, n, nullptr, 0, nullptr, nm.indices, nm.coord_x, nm.coord_y, Nn_new, Ne_new, a->previous_numbering,
+                                           a->n_geom_vertices, NXS_REGRID_IN_DEVICE | NXS_REGRID_OUT_DEVICE, &nfail, nullptr, nullptr))
+        return fail(h, rc, "regrid: the conservative remapping failed: %s", nxs_interp_last_error());
+    inf.num_failed = nfail;
+    inf.remap_ms = ms_since(t_phase); t_phase = std::chrono::steady_clock::now();
+
+    // ---- 3. redistributeVariables, straight into the arrays of the new mesh
+    HIPCHK(h, hipSetDevice(h->device));
+    const int cap_col = h->dp.young_cat ? cy_col : -1;
+    if (stage) hipLaunchKernelGGL(k_regrid_redistribute<true>, dim3(nblocks(Ne_new)), dim3(BLOCK), lds, h->stream, Ne_new, n, (const RegridCol *)d_cols, enth_b, t_noice, cap_col, (const double *)rows_new);
+    else hipLaunchKernelGGL(k_regrid_redistribute<false>, dim3(nblocks(Ne_new)), dim3(BLOCK), 0, h->stream, Ne_new, n, (const RegridCol *)d_cols, enth_b, t_noice, cap_col, (const double *)rows_new);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    inf.redistribute_ms = ms_since(t_phase); t_phase = std::chrono::steady_clock::now();
+
+    // ---- 4. InterpFromMeshToMesh2dx of the six nodal columns (FE.cpp:3131-3139), isdefault = false.  All six are interpolated although M_UM and M_UT are zeroed
+    // right after (assignVariables): that is what the reference computes, and the kernel's time does not depend on it (0.10 ms at 2 km)
+    if (int rc = nxs_regrid_interp_nodes(ctx, nod_new, nod_old, Nn_old, 6, nm.coord_x, nm.coord_y, Nn_new, 0, 0., NXS_REGRID_IN_DEVICE | NXS_REGRID_OUT_DEVICE, &next, nullptr))
+        return fail(h, rc, "regrid: the nodal interpolation failed: %s", nxs_interp_last_error());
+    inf.num_exterior = next;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_regrid_unpack_nodes, dim3(nblocks(Nn_new)), dim3(BLOCK), 0, h->stream, Nn_new, (const double *)nod_new, ad.p[RA_VT], ad.p[RA_UM], ad.p[RA_UT]);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    inf.nodes_ms = ms_since(t_phase); t_phase = std::chrono::steady_clock::now();
+
+    // ---- 5. the new mesh takes the handle: nxs_dyn_set_mesh's path with the arrays above in the place of fresh ones
+    RegridAdopt given = ad;
+    const int rc_mesh = set_mesh_impl(h, &nm, &ad);
+    for (int k = 0; k < RA_COUNT; ++k) if (!ad.p[k]) mem.release(given.p[k]);   // (taken: the state pool's now)
+    if (rc_mesh) return rc_mesh;
+    h->have_state = true;
+    if (carry_cum) { h->coupled_allocs.push_back(new_cum); mem.release(new_cum); h->d_cum = new_cum; h->dw.cum_damage = new_cum; }
+    if (carry_fsd) { h->coupled_allocs.push_back(new_fsd); mem.release(new_fsd); h->d_fsd = new_fsd; h->fsd_capacity = (size_t)nbins * Ne_new; h->dw.conc_fsd = new_fsd; h->dw.nbins = nbins; }
+    if (h->drift) nxs_drifters::state_changed(h->drift);
+    for (const Down &d : downs) HIPCHK(h, hipMemcpyAsync(d.host, d.dev, (size_t)Ne_new * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    inf.set_mesh_ms = ms_since(t_phase);
+    inf.total_ms = ms_since(t_start);
+    if (info) *info = inf;
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_regrid"); }
 
 int nxs_dyn_get_diag(nxs_dyn_handle *h, nxs_dyn_diag *dg) try {
     if (!h || !dg) return NXS_ERR_INVALID;

@@ -10,6 +10,9 @@
 #define NXS_OMEGA 7.292e-5
 #define NXS_PI 3.141592653589793238462643383279502884197169399375105820974944592308
 #define NXS_DAYS_IN_SEC 86400.
+#define NXS_SI 5.          // physical::si, model/constants.hpp:68
+#define NXS_LF 333.55e3    // physical::Lf, model/constants.hpp:44
+#define NXS_HEAT_C 2100.   // physical::C, model/constants.hpp:17
 
 #define STD_MAX(a, b) (((a) < (b)) ? (b) : (a))  // std::max
 #define STD_MIN(a, b) (((b) < (a)) ? (b) : (a))  // std::min
@@ -4294,3 +4297,132 @@ __global__ void __launch_bounds__(BLOCK) k_blend_forcing(int Nn, ForcingBlend b,
     if (i < Nn) ssh[i] = b.factor[2] * (b.c0 * b.s0[i] + b.c1 * b.s1[i]) + b.bias[2];
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// nxs_dyn_regrid: what FiniteElement::interpFields does between the member vectors and the two interpolation kernels of nxs_interp.hip (FE.cpp:3071-3154).
+// The interpolations read and write INTERLEAVED rows ([Ne][nb_var], [Nn][6]: one triangle's variables side by side, which is what their gathers want); the handle
+// keeps one array per variable.  A thread that walked its own row in global memory would touch nb_var * 8 bytes every nb_var * 8 bytes -- a wave's access spread
+// over 64 rows --, so a workgroup's rows pass through LDS and enter / leave global memory as ONE contiguous stream, the idiom of k_ice_diagnostics and the means
+// kernels; the per-variable arrays are read and written one element per lane.  The LDS row stride is odd (n | 1): 64 lanes walking column k of 64 rows hit 64
+// different 8-byte bank pairs.  The column table lives in device memory and is indexed uniformly: scalar loads, every branch on it wave-uniform.
+// -ffp-contract=off: every product, quotient, sum and square root below is rounded on its own, as in the reference's build.
+struct RegridCol {
+    const double *src;     // [Ne_old] the variable on the old mesh (the handle's array, or an extra's old_values on the device)
+    double *dst;           // [Ne_new] where it goes on the new mesh
+    int transformation;    // NXS_TRANSFORM_*
+    int flags;             // NXS_REGRID_VAR_HAS_MIN | HAS_MAX | IS_TICE
+    double min_val, max_val;
+};
+#define NXS_REGRID_STAGE_MAX 31   // columns whose rows a workgroup can stage: BLOCK * (n | 1) * 8 bytes <= 64 KB; wider rows are walked in global memory
+
+// rows [first_row * n, ...) of a workgroup between global memory and the padded LDS tile
+__device__ __forceinline__ void regrid_rows_to_lds(const double *__restrict__ rows, size_t base, int count, int n, int stride, double *stage) {
+    for (int i = threadIdx.x; i < count; i += BLOCK) { const int r = i / n, c = i - r * n; stage[r * stride + c] = rows[base + i]; }
+}
+__device__ __forceinline__ void regrid_rows_from_lds(double *__restrict__ rows, size_t base, int count, int n, int stride, const double *stage) {
+    for (int i = threadIdx.x; i < count; i += BLOCK) { const int r = i / n, c = i - r * n; rows[base + i] = stage[r * stride + c]; }
+}
+
+// collectVariables(), FE.cpp:2120-2151.  Columns 0 and 1 are M_conc and M_thick (the handle's own variables lead the table).
+// enth_a = M_freezingpoint_mu * physical::si * physical::Lf as the reference's expression associates it (FE.cpp:2145), heat_C = physical::C.
+template <bool STAGE>
+__global__ void __launch_bounds__(BLOCK) k_regrid_collect(int Ne, int n, const RegridCol *__restrict__ cols, double enth_a, double heat_C, double *__restrict__ rows) {
+    extern __shared__ double regrid_stage[];
+    const int stride = n | 1;
+    const int e = min(blockIdx.x * BLOCK + (int)threadIdx.x, Ne - 1);   // (threads past the end redo the last element: every thread reaches the barrier)
+    const bool live = blockIdx.x * BLOCK + (int)threadIdx.x < Ne;
+    const double conc = cols[0].src[e], thick = cols[1].src[e];
+    double *r = STAGE ? regrid_stage + (size_t)threadIdx.x * stride : rows + (size_t)e * n;
+    for (int k = 0; k < n; ++k) {
+        double val = cols[k].src[e];
+        switch (cols[k].transformation) {
+            case NXS_TRANSFORM_CONC: val *= conc; break;                                          // FE.cpp:2139
+            case NXS_TRANSFORM_THICK: val *= thick; break;                                        // FE.cpp:2142
+            case NXS_TRANSFORM_ENTHALPY: val = (val - enth_a / (heat_C * val)) * thick; break;    // FE.cpp:2145 (Winton, 2000, eq 39)
+            default: break;
+        }
+        if (STAGE || live) r[k] = val;
+    }
+    if (STAGE) {
+        __syncthreads();
+        regrid_rows_from_lds(rows, (size_t)blockIdx.x * BLOCK * n, min(BLOCK, Ne - (int)blockIdx.x * BLOCK) * n, n, stride, regrid_stage);
+    }
+}
+
+// redistributeVariables(out_elt_values, apply_maxima = true), FE.cpp:2196-2258: one thread per NEW element walks the columns in order, so that the clamped new
+// M_conc / M_thick exist before a transformed variable divides by them.  enth_b = 4 * mu * si * Lf / C (FE.cpp:2237), t_noice = -mu * si (FE.cpp:2245).
+// cy_col: the column of M_conc_young when the young-ice cap applies (FE.cpp:2253-2256), else -1.
+// A row the remapping marked failed (all NaN) is written NaN into every variable: std::max(minVal, NaN) would quietly turn it into minVal.
+template <bool STAGE>
+__global__ void __launch_bounds__(BLOCK) k_regrid_redistribute(int Ne, int n, const RegridCol *__restrict__ cols, double enth_b, double t_noice, int cy_col,
+                                                               const double *__restrict__ rows) {
+    extern __shared__ double regrid_stage[];
+    const int stride = n | 1;
+    const int e = blockIdx.x * BLOCK + (int)threadIdx.x;
+    if (STAGE) {
+        regrid_rows_to_lds(rows, (size_t)blockIdx.x * BLOCK * n, min(BLOCK, Ne - (int)blockIdx.x * BLOCK) * n, n, stride, regrid_stage);
+        __syncthreads();
+    }
+    if (e >= Ne) return;
+    const double *r = STAGE ? regrid_stage + (size_t)threadIdx.x * stride : rows + (size_t)e * n;
+    const bool failed = r[0] != r[0];
+    double conc = 0., thick = 0., cyoung = 0.;
+    for (int k = 0; k < n; ++k) {
+        const double raw = r[k];
+        double val = raw;
+        bool no_old_ice = false;
+        const int flags = cols[k].flags;
+        switch (cols[k].transformation) {
+            case NXS_TRANSFORM_CONC:                                                   // FE.cpp:2217-2223
+                if (conc > 0) val /= conc; else no_old_ice = true;
+                break;
+            case NXS_TRANSFORM_THICK:                                                  // FE.cpp:2224-2230
+                if (thick > 0) val /= thick; else no_old_ice = true;
+                break;
+            case NXS_TRANSFORM_ENTHALPY:                                               // FE.cpp:2231-2241 (Winton, 2000, eq 38)
+                if (thick > 0) { const double enth = raw / thick; val = 0.5 * (enth - sqrt(enth * enth + enth_b)); }
+                else no_old_ice = true;
+                break;
+            default: break;
+        }
+        if (no_old_ice && (flags & NXS_REGRID_VAR_IS_TICE)) val = t_noice;             // FE.cpp:2243-2245
+        if (flags & NXS_REGRID_VAR_HAS_MIN) val = STD_MAX(cols[k].min_val, val);       // FE.cpp:2247
+        if (flags & NXS_REGRID_VAR_HAS_MAX) val = STD_MIN(cols[k].max_val, val);       // FE.cpp:2249
+        if (failed) val = raw;
+        if (k == 0) conc = val;
+        if (k == 1) thick = val;
+        if (k == cy_col) cyoung = val;
+        cols[k].dst[e] = val;
+    }
+    if (cy_col >= 0 && !failed && (conc + cyoung) > 1.) cols[cy_col].dst[e] = 1. - conc;   // FE.cpp:2253-2256
+}
+
+// gatherFieldsNode(), FE.cpp:3174-3198: [Nn][6] = VT.u, VT.v, UM.u, UM.v, UT.u, UT.v, staged like k_ice_diagnostics' rows
+__global__ void __launch_bounds__(BLOCK) k_regrid_pack_nodes(int Nn, const double *__restrict__ VT, const double *__restrict__ UM, const double *__restrict__ UT,
+                                                             double *__restrict__ out) {
+    __shared__ double rows[BLOCK * 6];
+    const int i = min(blockIdx.x * BLOCK + (int)threadIdx.x, Nn - 1);
+    double *r = rows + 6 * threadIdx.x;
+    r[0] = VT[i]; r[1] = VT[i + Nn]; r[2] = UM[i]; r[3] = UM[i + Nn]; r[4] = UT[i]; r[5] = UT[i + Nn];
+    __syncthreads();
+    const size_t base = (size_t)blockIdx.x * BLOCK * 6;
+    const int count = min(BLOCK, Nn - (int)blockIdx.x * BLOCK) * 6;
+    for (int j = threadIdx.x; j < count; j += BLOCK) out[base + j] = rows[j];
+}
+
+// scatterFieldsNode() + assignVariables(), FE.cpp:3280-3293, 553-560: M_VT from columns 0 and 1 of the interpolated rows.  The reference interpolates and unpacks
+// all six columns and then overwrites M_UM and M_UT with zeros (assignVariables): the zeros are written here directly.  (D_tau_w = D_tau_a = 0, FE.cpp:3277-3278,
+// is what the mesh swap leaves in the new diagnostics arrays.)
+__global__ void __launch_bounds__(BLOCK) k_regrid_unpack_nodes(int Nn, const double *__restrict__ in, double *__restrict__ VT, double *__restrict__ UM,
+                                                               double *__restrict__ UT) {
+    __shared__ double rows[BLOCK * 6];
+    const size_t base = (size_t)blockIdx.x * BLOCK * 6;
+    const int count = min(BLOCK, Nn - (int)blockIdx.x * BLOCK) * 6;
+    for (int j = threadIdx.x; j < count; j += BLOCK) rows[j] = in[base + j];
+    __syncthreads();
+    const int i = blockIdx.x * BLOCK + (int)threadIdx.x;
+    if (i >= Nn) return;
+    VT[i] = rows[6 * threadIdx.x]; VT[i + Nn] = rows[6 * threadIdx.x + 1];
+    UM[i] = 0.; UM[i + Nn] = 0.;
+    UT[i] = 0.; UT[i + Nn] = 0.;
+}

@@ -89,6 +89,7 @@ def load_library():
     L.nxs_dyn_drifters_conc.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p]
     L.nxs_dyn_drifters_mask.argtypes = [H, C.c_int32, C.c_double, _abi.c_int32_p, C.c_int32, P(C.c_int32)]
     L.nxs_dyn_drifters_get.argtypes = [H, C.c_int32, P(C.c_int32), _abi.c_double_p, _abi.c_double_p, _abi.c_int32_p, _abi.c_double_p, _abi.c_int32_p]
+    L.nxs_dyn_regrid.argtypes = [H, P(_abi.RegridArgs), P(_abi.RegridInfo)]
     L.nxs_dyn_step.argtypes = [H]
     L.nxs_dyn_explicit_solve.argtypes = [H]
     L.nxs_dyn_update.argtypes = [H]
@@ -136,7 +137,7 @@ EXPORTS = (
     "nxs_dyn_set_wave_stress", "nxs_dyn_put_coupled", "nxs_dyn_get_coupled",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
-    "nxs_dyn_drifters_get",
+    "nxs_dyn_drifters_get", "nxs_dyn_regrid",
     "nxs_dyn_explicit_solve", "nxs_dyn_update", "nxs_dyn_synchronize", "nxs_dyn_step_host",
     "nxs_dyn_check_regridding", "nxs_dyn_check_fields_fast", "nxs_dyn_get_timing", "nxs_dyn_get_step_times", "nxs_dyn_get_traffic_model", "nxs_dyn_set_option",
     "nxs_dyn_debug_array", "nxs_dyn_get_branch_trace", "nxs_mesh_connectivity", "nxs_mesh_element_connectivity", "nxs_calc_cohesion",
@@ -194,6 +195,109 @@ def mesh_element_connectivity(indices: np.ndarray, num_nodes: int) -> np.ndarray
     if rc:
         raise NxsError(rc, "nxs_mesh_element_connectivity")
     return ec
+
+
+REGRID_INPUTS = ("cohesion", "time_relaxation_damage", "drag_ui", "drag_ui_young")
+
+
+def regrid_args(lm_new, previous_numbering, n_geom_vertices, inputs, extras=(), context=None, moved=None, num_nodes_old=None, num_elements_old=None,
+                freezingpoint_mu=0.055, validate=True):
+    """nxs_dyn_regrid_args for FiniteElementDynamics.regrid, and everything it points to: (args, keep-alive list, extras' result arrays).  Pure host code: with
+    `validate` the arguments nxs_dyn_regrid would refuse raise ValueError here, before any library call.
+    extras: dicts {"old": [Ne_old] array or device address (int), "new": [Ne_new] array to fill, device address, or absent (one is made and put into the
+    dict), "transformation": "none" | "conc" | "thick" | "enthalpy" (or NXS_TRANSFORM_*), "min": float or None, "max": float or None, "is_tice": bool}.
+    context: an interp.Regrid of the old mesh at x0 + M_UM, or None with moved = (x, y) of those coordinates."""
+    keep = []
+    a = _abi.RegridArgs()
+    Ne_new, Nn_new = lm_new.num_elements, lm_new.num_nodes
+
+    def bad(what):
+        if validate:
+            raise ValueError("regrid: " + what)
+
+    m = _abi.mesh_struct(lm_new)
+    keep.append(m)
+    a.new_mesh = C.pointer(m)
+    for k in REGRID_INPUTS:
+        v = None if inputs is None else inputs.get(k)
+        if v is None:
+            bad(f"inputs['{k}'] of the new mesh is required (re-made after a regrid, not interpolated)")
+            continue
+        v = np.ascontiguousarray(v, np.float64)
+        if v.shape != (Ne_new,):
+            raise ValueError(f"regrid: inputs['{k}'] has shape {v.shape}, expected ({Ne_new},)")
+        keep.append(v)
+        setattr(a, k, _abi.dptr(v))
+    if context is not None:
+        a.context = context.h if hasattr(context, "h") else C.c_void_p(int(context))
+        keep.append(context)
+    elif moved is not None:
+        x, y = (np.ascontiguousarray(q, np.float64) for q in moved)
+        if num_nodes_old is not None and (x.shape != (num_nodes_old,) or y.shape != (num_nodes_old,)):
+            raise ValueError(f"regrid: moved coordinates have shapes {x.shape}, {y.shape}, expected ({num_nodes_old},)")
+        keep += [x, y]
+        a.x_old_moved, a.y_old_moved = _abi.dptr(x), _abi.dptr(y)
+    else:
+        bad("neither a context nor the moved coordinates of the old mesh")
+    if previous_numbering is not None:
+        pn = np.ascontiguousarray(previous_numbering, np.float64)
+        if pn.shape != (Nn_new,):
+            raise ValueError(f"regrid: previous_numbering has shape {pn.shape}, expected ({Nn_new},)")
+        keep.append(pn)
+        a.previous_numbering = _abi.dptr(pn)
+    a.n_geom_vertices = int(n_geom_vertices)
+    a.freezingpoint_mu = float(freezingpoint_mu)
+    extras = list(extras) if not isinstance(extras, int) else extras
+    if isinstance(extras, int):           # (a bare count: only to show that a negative one is refused)
+        if extras < 0:
+            bad(f"num_extra = {extras}")
+        a.num_extra = extras
+        return a, keep, []
+    arr = (_abi.RegridVar * max(len(extras), 1))()
+    keep.append(arr)
+    results = []
+    for k, x in enumerate(extras):
+        v = arr[k]
+        t = x.get("transformation", "none")
+        t = _abi.TRANSFORMATIONS.get(t, t) if isinstance(t, str) else int(t)
+        if not isinstance(t, int) or not (_abi.NXS_TRANSFORM_NONE <= t <= _abi.NXS_TRANSFORM_ENTHALPY):
+            bad(f"extras[{k}] has the unknown transformation {x.get('transformation')!r}")
+            t = t if isinstance(t, int) else -1
+        v.transformation = t
+        flags = 0
+        old = x.get("old")
+        if old is None:
+            bad(f"extras[{k}] has no 'old' values")
+        elif isinstance(old, (int, np.integer)):
+            v.old_values = int(old); flags |= _abi.NXS_REGRID_VAR_OLD_ON_DEVICE
+        else:
+            old = np.ascontiguousarray(old, np.float64)
+            if num_elements_old is not None and old.shape != (num_elements_old,):
+                raise ValueError(f"regrid: extras[{k}]['old'] has shape {old.shape}, expected ({num_elements_old},)")
+            keep.append(old)
+            v.old_values = old.ctypes.data
+        new = x.get("new")
+        if isinstance(new, (int, np.integer)):
+            v.new_values = int(new); flags |= _abi.NXS_REGRID_VAR_NEW_ON_DEVICE
+            results.append(None)
+        else:
+            if new is None:
+                new = x["new"] = np.empty(Ne_new)
+            if not (isinstance(new, np.ndarray) and new.dtype == np.float64 and new.flags.c_contiguous and new.flags.writeable and new.shape == (Ne_new,)):
+                raise ValueError(f"regrid: extras[{k}]['new'] must be a writeable C-contiguous float64 array of shape ({Ne_new},)")
+            keep.append(new)
+            v.new_values = new.ctypes.data
+            results.append(new)
+        if x.get("min") is not None:
+            flags |= _abi.NXS_REGRID_VAR_HAS_MIN; v.min_val = float(x["min"])
+        if x.get("max") is not None:
+            flags |= _abi.NXS_REGRID_VAR_HAS_MAX; v.max_val = float(x["max"])
+        if x.get("is_tice"):
+            flags |= _abi.NXS_REGRID_VAR_IS_TICE
+        v.flags = flags
+    a.num_extra = len(extras)
+    a.extra = arr
+    return a, keep, results
 
 
 class FiniteElementDynamics:
@@ -470,6 +574,20 @@ class FiniteElementDynamics:
         dev = C.c_void_p()
         self._chk(self.L.nxs_dyn_ice_diagnostics(self.h, C.byref(d) if d is not None else None, C.byref(dev)))
         return out, dev.value
+
+    # ---- regrid: interpFields() + assignVariables() (FE.cpp:3071-3154, 553-572) without the state leaving the device ----
+    def regrid(self, lm_new, previous_numbering, n_geom_vertices, inputs, extras=(), context=None, moved=None, freezingpoint_mu=0.055, validate=True):
+        """nxs_dyn_regrid: the prognostic state moves onto the adapted mesh `lm_new` on the device -- collectVariables, the conservative remapping,
+        redistributeVariables (bounds, no_old_ice, the young-ice cap), the six nodal columns, M_UM = M_UT = 0 -- and the handle goes on with lm_new.
+        inputs: cohesion, time_relaxation_damage, drag_ui, drag_ui_young of the new mesh.  extras / context / moved: see regrid_args; host 'new' arrays of
+        the extras are filled in place.  Forcing is the next set_forcing.  Returns nxs_dyn_regrid_info as a dict."""
+        a, keep, _ = regrid_args(lm_new, previous_numbering, n_geom_vertices, inputs, extras, context, moved,
+                                 None if self.lm is None else self.lm.num_nodes, None if self.lm is None else self.lm.num_elements, freezingpoint_mu, validate)
+        info = _abi.RegridInfo()
+        self._chk(self.L.nxs_dyn_regrid(self.h, C.byref(a), C.byref(info)))
+        del keep
+        self.lm = lm_new
+        return {k: getattr(info, k) for k, _ in _abi.RegridInfo._fields_ if k != "reserved0"}
 
     # ---- the Moorings time means: updateMeans / updateGridMean / resetMeshMean (FE.cpp:8518-9024, gridoutput.cpp:387-550) ----
     @staticmethod
