@@ -26,6 +26,7 @@
  *   #ifdef OASIS: M_cum_damage, M_conc_fsd      nxs_dyn_put_coupled / nxs_dyn_get_coupled (FE.cpp:4233-4238, 3991-3994)
  *   updateMeans(M_moorings, time_factor)        nxs_dyn_means_update    (FE.cpp:8518-9024; configure / get / to_grid / reset beside it)
  *   interpFields() + assignVariables()          nxs_dyn_regrid          (FE.cpp:3071-3154, 2120-2151, 2196-2258, 3161-3297, 553-572)
+ *   #ifdef OASIS: initFsd / updateFSD / redistributeFSD / weldingRoach   nxs_fsd_bins, nxs_dyn_fsd_* (FE.cpp:7408-7576, 4674-4732, 4268-4483, 4737-4870, 5888-5896)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -171,7 +172,9 @@ typedef struct nxs_dyn_forcing {
 /* The element variables of the coupled build (#ifdef OASIS: a wave- or ocean-coupled neXtSIM) that the loops of this path touch:
  *   M_cum_damage[cpt] += del_damage   inside the damage branch of every BBM sub-step (updateSigmaDamage, FE.cpp:4233-4238)
  *   M_conc_fsd[k][cpt] *= surf_ratio  for every floe-size bin, where update() scales the other element variables (FE.cpp:3991-3994)
- * The FSD redistribution / welding / lateral melt (FE.cpp:4268-4876) and the second M_cum_damage += of FE.cpp:4470 stay with the host. */
+ * updateFSD, the wave break-up (with the second M_cum_damage += of FE.cpp:4470) and the welding work on the same bins through nxs_dyn_fsd_* below; the statements of
+ * thermo() that need thermo's own intermediates -- redistributeThermoFSD (lateral melt / growth, FE.cpp:4487-4670) and the melt-out branch (FE.cpp:5729-5764) -- stay
+ * with the host. */
 typedef struct nxs_dyn_coupled {
     double *cum_damage;      /* [Ne] M_cum_damage; NULL = not carried */
     double *conc_fsd;        /* [num_fsd_bins][Ne], bin-major like M_conc_fsd[k][cpt]; NULL = none */
@@ -502,7 +505,7 @@ NXS_API int nxs_dyn_drifters_get(nxs_dyn_handle *h, int32_t set, int32_t *n, dou
  *   1. collectVariables (FE.cpp:2120-2151)   the element variables as interleaved [Ne_old][nb_var] rows, the interpTransformation of every variable applied
  *      (operand order of FE.cpp:2139-2145).  Column order = sortPrognosticVars (FE.cpp:2087-2111): every variable of kind `none` first -- the handle's own in the
  *      order of nxs_dyn_state (conc, thick, snow_thick, damage, ridge_ratio, sigma[0..2], conc_young, h_young, hs_young, conc_myi, thick_myi), then cum_damage and
- *      the FSD bins while attached (nxs_dyn_put_coupled), then the caller's extras of kind none -- then the extras of kind conc, thick, enthalpy, each kind in
+ *      the FSD bins while attached (nxs_dyn_put_coupled; with M_conc_mech_fsd / M_cum_wave_damage attached see nxs_dyn_fsd_put), then the caller's extras of kind none -- then the extras of kind conc, thick, enthalpy, each kind in
  *      the caller's order.  cohesion, time_relaxation_damage and drag_ui* are not prognostic in the reference and are no columns.
  *   2. ConservativeRemappingMeshToMesh through the context (nxs_regrid_remap_elements on device rows).
  *   3. redistributeVariables with apply_maxima = true (FE.cpp:2196-2258): one thread per new element walks the columns in order -- the inverse transformation
@@ -562,6 +565,114 @@ typedef struct nxs_dyn_regrid_info {
 } nxs_dyn_regrid_info;
 
 NXS_API int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regrid_info *info /* may be NULL */);
+
+/* ---- The floe-size distribution on the device (#ifdef OASIS, M_num_fsd_bins > 0): the per-element loops a wave-coupled step() runs between two dynamics steps --
+ * updateFSD() after update(), after thermo() and after a regrid (FE.cpp:8144-8147, 8216-8219), redistributeFSD() on every coupling step (FE.cpp:8156-8168),
+ * weldingRoach() and the mechanical healing inside thermo() (FE.cpp:5783-5796, 5888-5896) -- on the bins nxs_dyn_put_coupled attached, so that a resident host no
+ * longer pulls the bins, conc, conc_young, thick, h_young and damage and pushes bins, damage and cum_damage every step.  Every loop is per element without a
+ * stencil, ghost elements included: no exchange, and a partitioned handle runs them unchanged.  Each entry point is ONE kernel over M_num_elements, a thread holds
+ * its element's bins in registers (bin-major rows: a wave reads and writes whole lines), asynchronous on the handle's stream.  Built uncontracted like the rest.
+ * STAYS WITH THE HOST THERMO: redistributeThermoFSD (FE.cpp:4487-4670, lateral melt and growth, called with thermo's lat_melt_rate / young_ice_growth / old_conc) and
+ * the melt-out branch of thermo() (FE.cpp:5729-5764): both need intermediates of thermo() that never reach the handle.
+ *   nxs_fsd_bins   HOST ONLY: the tables of initFsd() (FE.cpp:7408-7533) for FSDType CONSTANT_SIZE / CONSTANT_AREA, M_floe_shape = 0.66.  std::pow(x, 2) is
+ *                  written x * x (what GCC and clang make of it at -O1 and above; a libm pow may differ in the last bit); everything else is + - * / sqrt.
+ *                  alpha_merge is M_alpha_fsd_merge[m][n], row-major [n][n], -999 where no bin matches.  Any output of nxs_fsd_tables may be NULL.
+ *   nxs_fsd_config_check  HOST ONLY: what nxs_dyn_fsd_configure refuses, without a handle (attached_bins = the bins of the attached conc_fsd).
+ *   nxs_dyn_fsd_configure  copies the tables (the caller's own or nxs_fsd_bins') and the options of the loops.  NXS_ERR_INVALID: num_bins different from the
+ *                  attached conc_fsd's, < 1 or > NXS_FSD_MAX_BINS; an unknown breakup_type / welding_type / fsd_damage_type / breakup_prob_type; a NULL table;
+ *                  an alpha_merge[kx][ky] outside [1, num_bins] for a ky <= kx (weldingRoach indexes tmp_conc_fsd[a - 1] with it, FE.cpp:4780).  A refused
+ *                  configuration leaves the previous one.  Everything that does not depend on the element is computed HERE with the host's libm and uploaded:
+ *                  P = P_inf * (1 - exp(-P_inf * cpl_time_step / tau_w)) (FE.cpp:4335), the redistributors beta[j][k] of ZHANG and UNIFORM_SIZE
+ *                  (FE.cpp:4361, 4380-4381), pow(PI, 4) * floes_flex_young and 48 * rhow * g * (1 - pow(poisson, 2)) of d_flex (FE.cpp:4312-4313; physical::g =
+ *                  9.8, not physical::gravity), log(ksi).  The configuration is the handle's and survives nxs_dyn_set_mesh; the kernels refuse
+ *                  (NXS_ERR_STATE) while the attached number of bins is not the configured one.
+ *   nxs_dyn_fsd_put / _get  M_conc_mech_fsd [num_fsd_bins][Ne] and M_cum_wave_damage [Ne]; NULL = detached (put) / not wanted (get), as nxs_dyn_put_coupled.
+ *                  conc_fsd and cum_damage stay with nxs_dyn_put_coupled.  nxs_dyn_set_mesh detaches both.  get also reports and clears weld_crash (below).
+ *                  nxs_dyn_regrid carries them as further columns of kind none: the mechanical bins in [0, 1] behind M_conc_fsd, cum_wave_damage >= 0 behind
+ *                  cum_damage, which is where initModelVariables puts them (FE.cpp:7193-7212): with one of them attached the coupled columns are
+ *                  M_conc_fsd[..], M_conc_mech_fsd[..], M_cum_damage, M_cum_wave_damage; with neither the order is what it was (cum_damage, M_conc_fsd[..]).
+ *   nxs_dyn_fsd_init     the distribution at the end of initFsd() (FE.cpp:7562-7576): everything in the highest bin.
+ *   nxs_dyn_fsd_update   updateFSD() (FE.cpp:4674-4732), M_conc_mech_fsd included with distinguish_mech_fsd; the ctot2 == 0 < ctot branch and the division by
+ *                  a zero ctot2 where ctot >= 1 are the reference's.
+ *   nxs_dyn_fsd_breakup  redistributeFSD() (FE.cpp:4268-4483).  wlbk: M_wlbk [Ne], a host pointer or (flags & NXS_FSD_WLBK_ON_DEVICE) a device pointer.
+ *                  *breakup_in_dt = M_breakup_in_dt, *crash = the mini check of FE.cpp:4426-4436 under debug_fsd -- a flag, not an exception; both are reduced
+ *                  on the device; with both NULL the call stays asynchronous.  The reference's oddities are kept: the thickness is 0 before the max with
+ *                  breakup_thick_min when neither breakup_cell_average_thickness nor the young-ice category applies; every type redistributes within the
+ *                  broken bin too (k <= j); fsd_damage_type 1 falls through into 2 (no break at FE.cpp:4454); damage is written only where M_thick > 0;
+ *                  the bins are cleared in the else of ctot > 0.  M_damage is written where the sub-step loop keeps it (its records after a step, like
+ *                  update()), M_cum_damage / M_cum_wave_damage where attached.  fsd_damage_type 1 / 2 read M_conc_mech_fsd: NXS_ERR_STATE without it.
+ *                  tanh / pow / log are the device's: against a host libm the bins and damage of broken elements agree to 1e-15 with UNIFORM_SIZE and ZHANG and to
+ *                  3e-14 with DUMONT, whose redistributor divides differences of powers with exponents down to 1e-6; everything else is bitwise.
+ *   nxs_dyn_fsd_weld     weldingRoach(i, ddt) (FE.cpp:4737-4870) where welding_type is ROACH, then the mechanical healing (FE.cpp:5888-5896) where
+ *                  distinguish_mech_fsd, both only where freezing[i] != 0 (thermo's del_hi > 0; [Ne] uint8 on the host).  ndt_mrg = round(stability + 0.5),
+ *                  subdt = ddt / (float)ndt_mrg as written; the sums of sum_mergers and coag_pos in the reference's order: no libm call, the same bits.  The
+ *                  loop over ndt_mrg is per element and data-dependent: lanes diverge, no cap.  The reference's crash conditions (the sanity checks of the
+ *                  sub-steps under debug_fsd; |conc_loss| > 1e-6 and a bin below -1e-12 always, as written) raise weld_crash, which the next nxs_dyn_fsd_get
+ *                  reports; the element is finished as the arithmetic says.  Healing reads M_time_relaxation_damage as the handle holds it at the call.
+ * NXS_FSD_MAX_BINS = 16 is a CHOSEN cap: the kernels are builds for at most 2, 6, 12 and 16 bins in which the index into a thread's bins is meant to be a
+ * compile-time constant (the data-dependent tmp_conc_fsd[a - 1] of the welding is a chain of selects).  Measured for gfx950 (ROCm 7.2) at 16 bins: welding 104,
+ * break-up 180, update 84 VGPRs of the 512 a wave of a 256-thread workgroup may have, no scratch memory and no VGPR spill in any build; the 12- and 16-bin
+ * builds spill 63-79 SGPRs, which the compiler keeps in VGPR lanes, not in memory.  No build above 16 was tried.  tests/test_fsd_abi.py reads these figures from
+ * the built library and fails when a build uses scratch memory.
+ * M_damage: the kernels find it where the handle says it is after ANY family of the sub-step loop (the arrays, or the records of the last step), resident loop
+ * and data-flow launch included; tests/test_gpu_fsd.py runs the residency check on each family.
+ * abs(conc_loss) (FE.cpp:4831) is written unqualified in the reference; here it is the floating-point absolute value (what <cmath>'s overloads give a C++11
+ * build).  Were it C's int abs, that check could never fire; only weld_crash depends on it. */
+#define NXS_FSD_MAX_BINS 16
+/* setup::FSDType, WeldingType, BreakupType: model/enums.hpp:99-116 */
+enum { NXS_FSD_CONSTANT_SIZE = 0, NXS_FSD_CONSTANT_AREA = 1 };
+enum { NXS_WELDING_NONE = 0, NXS_WELDING_ROACH = 1 };
+enum { NXS_BREAKUP_NONE = 0, NXS_BREAKUP_UNIFORM_SIZE = 1, NXS_BREAKUP_ZHANG = 2, NXS_BREAKUP_DUMONT = 3 };
+enum { NXS_FSD_WLBK_ON_DEVICE = 1 };   /* nxs_dyn_fsd_breakup flags */
+
+typedef struct nxs_fsd_tables {      /* [num_bins] each */
+    double *bin_widths;              /* M_fsd_bin_widths */
+    double *bin_low_limits;          /* M_fsd_bin_low_limits */
+    double *bin_up_limits;           /* M_fsd_bin_up_limits */
+    double *bin_centres;             /* M_fsd_bin_centres */
+    double *area_scaled_up;          /* M_fsd_area_scaled_up */
+    double *area_scaled_low;         /* M_fsd_area_scaled_low */
+    double *area_scaled_centered;    /* M_fsd_area_scaled_centered */
+    double *area_scaled_binwidth;    /* M_fsd_area_scaled_binwidth */
+    int32_t *alpha_merge;            /* [num_bins][num_bins] M_alpha_fsd_merge[m][n] */
+} nxs_fsd_tables;
+
+typedef struct nxs_dyn_fsd_config {
+    int32_t num_bins;                          /* M_num_fsd_bins */
+    int32_t breakup_type;                      /* NXS_BREAKUP_*: wave_coupling.breakup_type */
+    int32_t breakup_prob_type;                 /* wave_coupling.breakup_prob_type: only 0 exists (FE.cpp:4331-4341) */
+    int32_t fsd_damage_type;                   /* wave_coupling.fsd_damage_type: 0, 1, 2 */
+    int32_t welding_type;                      /* NXS_WELDING_* */
+    int32_t distinguish_mech_fsd;              /* wave_coupling.distinguish_mech_fsd */
+    int32_t debug_fsd;                         /* wave_coupling.debug_fsd */
+    int32_t breakup_cell_average_thickness;    /* wave_coupling.breakup_cell_average_thickness */
+    double breakup_coef1, breakup_coef2, breakup_coef3;   /* FE.cpp:4274-4276 */
+    double breakup_prob_cutoff;                /* FE.cpp:4277 */
+    double breakup_timescale_tuning;           /* tau_w, FE.cpp:4329 */
+    double cpl_time_step;                      /* coupler.timestep [s] */
+    double floes_flex_young;                   /* M_floes_flex_young */
+    double breakup_thick_min;                  /* M_breakup_thick_min */
+    double fsd_damage_max;                     /* wave_coupling.fsd_damage_max */
+    double welding_kappa;                      /* M_welding_kappa */
+    nxs_fsd_tables tables;                     /* read, not written; area_scaled_low may be NULL (no loop reads it) */
+} nxs_dyn_fsd_config;
+
+typedef struct nxs_dyn_fsd_state {
+    double *conc_mech_fsd;     /* [num_fsd_bins][Ne] M_conc_mech_fsd, bin-major; NULL = none */
+    double *cum_wave_damage;   /* [Ne] M_cum_wave_damage; NULL = none */
+    int32_t num_fsd_bins;      /* with conc_mech_fsd: the number of bins of the attached conc_fsd */
+    int32_t weld_crash;        /* written by nxs_dyn_fsd_get: != 0 when a crash condition of weldingRoach was met since the last get */
+} nxs_dyn_fsd_state;
+
+NXS_API int nxs_fsd_bins(int32_t fsd_type, int32_t num_bins, double min_floe_size, double bin_cst_width, int32_t welding_use_scaled_area, nxs_fsd_tables *out);
+NXS_API int nxs_fsd_config_check(const nxs_dyn_fsd_config *c, int32_t attached_bins);
+NXS_API int nxs_dyn_fsd_configure(nxs_dyn_handle *h, const nxs_dyn_fsd_config *c);
+NXS_API int nxs_dyn_fsd_put(nxs_dyn_handle *h, const nxs_dyn_fsd_state *s);
+NXS_API int nxs_dyn_fsd_get(nxs_dyn_handle *h, nxs_dyn_fsd_state *s);
+NXS_API int nxs_dyn_fsd_init(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_fsd_update(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_fsd_breakup(nxs_dyn_handle *h, const double *wlbk /* [Ne] M_wlbk */, int32_t flags, int32_t *breakup_in_dt /* may be NULL */, int32_t *crash /* may be NULL */);
+NXS_API int nxs_dyn_fsd_weld(nxs_dyn_handle *h, double ddt, const uint8_t *freezing /* [Ne] del_hi > 0 */);
 
 /* One dynamics step on the device-resident state: FE.cpp:8197-8214.  Asynchronous on the
  * handle's stream; nxs_dyn_synchronize() waits for it. */

@@ -134,6 +134,62 @@ class Coupled(C.Structure):   # nxs_dyn_coupled
     _fields_ = [("cum_damage", c_double_p), ("conc_fsd", c_double_p), ("num_fsd_bins", C.c_int32), ("reserved0", C.c_int32)]
 
 
+# ---- the floe-size distribution (include/nxs_dyn.h, nxs_dyn_fsd_*): setup::FSDType, WeldingType, BreakupType of model/enums.hpp:99-116
+NXS_FSD_MAX_BINS = 16
+NXS_FSD_CONSTANT_SIZE, NXS_FSD_CONSTANT_AREA = 0, 1
+NXS_WELDING_NONE, NXS_WELDING_ROACH = 0, 1
+NXS_BREAKUP_NONE, NXS_BREAKUP_UNIFORM_SIZE, NXS_BREAKUP_ZHANG, NXS_BREAKUP_DUMONT = range(4)
+NXS_FSD_WLBK_ON_DEVICE = 1
+FSD_TYPES = {"constant_size": NXS_FSD_CONSTANT_SIZE, "constant_area": NXS_FSD_CONSTANT_AREA}
+WELDING_TYPES = {"none": NXS_WELDING_NONE, "roach": NXS_WELDING_ROACH}
+BREAKUP_TYPES = {"none": NXS_BREAKUP_NONE, "uniform_size": NXS_BREAKUP_UNIFORM_SIZE, "zhang": NXS_BREAKUP_ZHANG, "dumont": NXS_BREAKUP_DUMONT}
+FSD_TABLES = ("bin_widths", "bin_low_limits", "bin_up_limits", "bin_centres", "area_scaled_up", "area_scaled_low", "area_scaled_centered", "area_scaled_binwidth")
+
+
+class FsdTables(C.Structure):   # nxs_fsd_tables
+    _fields_ = [(k, c_double_p) for k in FSD_TABLES] + [("alpha_merge", c_int32_p)]
+
+
+FSD_CONFIG_INTS = ("num_bins", "breakup_type", "breakup_prob_type", "fsd_damage_type", "welding_type", "distinguish_mech_fsd", "debug_fsd", "breakup_cell_average_thickness")
+FSD_CONFIG_REALS = ("breakup_coef1", "breakup_coef2", "breakup_coef3", "breakup_prob_cutoff", "breakup_timescale_tuning", "cpl_time_step", "floes_flex_young",
+                    "breakup_thick_min", "fsd_damage_max", "welding_kappa")
+
+
+class FsdConfig(C.Structure):   # nxs_dyn_fsd_config
+    _fields_ = [(k, C.c_int32) for k in FSD_CONFIG_INTS] + [(k, C.c_double) for k in FSD_CONFIG_REALS] + [("tables", FsdTables)]
+
+
+class FsdState(C.Structure):   # nxs_dyn_fsd_state
+    _fields_ = [("conc_mech_fsd", c_double_p), ("cum_wave_damage", c_double_p), ("num_fsd_bins", C.c_int32), ("weld_crash", C.c_int32)]
+
+
+def fsd_tables_struct(tables: dict) -> FsdTables:
+    """nxs_fsd_tables pointing at the arrays of `tables` (float64 [n] each, alpha_merge int32 [n, n]; they must stay alive); a missing key stays NULL."""
+    t = FsdTables()
+    for k in FSD_TABLES:
+        if tables.get(k) is not None:
+            setattr(t, k, dptr(tables[k]))
+    if tables.get("alpha_merge") is not None:
+        t.alpha_merge = iptr(tables["alpha_merge"])
+    return t
+
+
+def fsd_config_struct(num_bins: int, tables: dict, **options) -> FsdConfig:
+    """nxs_dyn_fsd_config from keyword options named after its members (breakup_type / welding_type also by the reference's option strings)."""
+    c = FsdConfig()
+    c.num_bins = int(num_bins)
+    for k, v in options.items():
+        if k == "breakup_type" and isinstance(v, str):
+            v = BREAKUP_TYPES[v]
+        if k == "welding_type" and isinstance(v, str):
+            v = WELDING_TYPES[v]
+        if k not in FSD_CONFIG_INTS + FSD_CONFIG_REALS:
+            raise KeyError(f"nxs_dyn_fsd_config has no member {k!r}")
+        setattr(c, k, int(v) if k in FSD_CONFIG_INTS else float(v))
+    c.tables = fsd_tables_struct(tables)
+    return c
+
+
 # nxs_dyn_regrid (include/nxs_dyn.h): ModelVariable::interpTransformation and the flags of nxs_dyn_regrid_var
 NXS_TRANSFORM_NONE, NXS_TRANSFORM_CONC, NXS_TRANSFORM_THICK, NXS_TRANSFORM_ENTHALPY = range(4)
 TRANSFORMATIONS = {"none": NXS_TRANSFORM_NONE, "conc": NXS_TRANSFORM_CONC, "thick": NXS_TRANSFORM_THICK, "enthalpy": NXS_TRANSFORM_ENTHALPY}

@@ -16,6 +16,7 @@
 //   k_update          FE.cpp:3946-4131    update()
 //   k_free_drift      FE.cpp:10140-10176
 //   k_regrid_*/k_check_* FE.cpp:8298-8309, 14536-14655 reductions
+//   k_fsd_init / _update / _breakup / _weld   FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870 + 5888-5896: the floe-size distribution (nxs_fsd_kernels.inl, nxs_dyn_fsd_*)
 //   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
 //
 // Determinism: the reference scatters element contributions into nodes in ascending element
@@ -46,6 +47,7 @@
 #include "nxs_resident_registry.hpp"
 
 #include "nxs_dyn_kernels.inl"
+#include "nxs_fsd_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -202,6 +204,15 @@ struct nxs_dyn_handle {
     // conc_fsd non-NULL); a detached buffer is kept for the next attach (no hipFree between two steps: it would wait for the whole device, see `retired`)
     double *d_tau_wi = nullptr, *d_tau_sum = nullptr, *d_cum = nullptr, *d_fsd = nullptr;
     size_t fsd_capacity = 0;               // doubles d_fsd has room for
+    // the floe-size distribution (nxs_dyn_fsd_*): M_conc_mech_fsd / M_cum_wave_damage and the uploads of M_wlbk / freezing go with the mesh (coupled_allocs);
+    // ATTACHED is fsd_mech / fsd_cumw non-NULL.  The configuration (tables, options, flags) is the handle's and survives set_mesh
+    double *d_mech = nullptr, *d_cumw = nullptr, *d_wlbk = nullptr, *fsd_mech = nullptr, *fsd_cumw = nullptr;
+    unsigned char *d_freezing = nullptr;
+    size_t mech_capacity = 0;
+    FsdDev fsd_cfg{};
+    FsdDev *d_fsd_cfg = nullptr;
+    int *d_fsd_flags = nullptr;
+    bool fsd_configured = false;
     std::vector<void *> coupled_allocs;
     // v4: the whole sub-step loop in one resident launch (option "fused" = 4; see k_substep_resident)
     DevResident res{};
@@ -1700,6 +1711,7 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     free_pool(h->forcing_allocs);
     free_pool(h->coupled_allocs);   // (set_mesh: h->dw is reset below, which detaches the three)
     h->d_tau_wi = h->d_tau_sum = h->d_cum = h->d_fsd = nullptr; h->fsd_capacity = 0;
+    h->d_mech = h->d_cumw = h->d_wlbk = h->fsd_mech = h->fsd_cumw = nullptr; h->d_freezing = nullptr; h->mech_capacity = 0;
     for (auto &q : h->f_snap) q = nullptr;
     h->have_pair = false;
     unpin_all(h);
@@ -1708,6 +1720,8 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     if (h->d_partials) (void)hipFree(h->d_partials);
     if (h->d_regrid) (void)hipFree(h->d_regrid);
     if (h->d_crash) (void)hipFree(h->d_crash);
+    if (h->d_fsd_cfg) (void)hipFree(h->d_fsd_cfg);
+    if (h->d_fsd_flags) (void)hipFree(h->d_fsd_flags);
     if (h->d_dp) (void)hipFree(h->d_dp);
     for (auto &set : h->ev) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
     for (auto &set : h->ev_flush) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
@@ -1933,6 +1947,7 @@ static int set_mesh_impl(nxs_dyn_handle *h, const nxs_dyn_mesh *m, RegridAdopt *
     free_pool(h->forcing_allocs);
     free_pool(h->coupled_allocs);   // (set_mesh: h->dw is reset below, which detaches the three)
     h->d_tau_wi = h->d_tau_sum = h->d_cum = h->d_fsd = nullptr; h->fsd_capacity = 0;
+    h->d_mech = h->d_cumw = h->d_wlbk = h->fsd_mech = h->fsd_cumw = nullptr; h->d_freezing = nullptr; h->mech_capacity = 0;
     for (auto &q : h->f_snap) q = nullptr;
     h->have_pair = false;
     unpin_all(h);
@@ -2697,6 +2712,7 @@ int nxs_dyn_put_coupled(nxs_dyn_handle *h, const nxs_dyn_coupled *c) try {   // 
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->dw.cum_damage = c->cum_damage ? h->d_cum : nullptr;
     h->dw.conc_fsd = c->conc_fsd ? h->d_fsd : nullptr;
+    if (c->num_fsd_bins != h->dw.nbins) h->fsd_mech = nullptr;   // (M_conc_mech_fsd has the rows of the bins it was put with: nxs_dyn_fsd_put again)
     h->dw.nbins = c->num_fsd_bins;
     if (had_cum != (h->dw.cum_damage != nullptr) || had_fsd != (h->dw.conc_fsd != nullptr)) release_graph(h);   // (another family may run; kernel arguments are baked into the graphs)
     return NXS_OK;
@@ -2754,6 +2770,7 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     const DevState &so = h->ds;
     const bool carry_cum = h->dw.cum_damage != nullptr, carry_fsd = h->dw.conc_fsd != nullptr;
     const int nbins = carry_fsd ? h->dw.nbins : 0;
+    const bool carry_mech = carry_fsd && h->fsd_mech != nullptr, carry_cumw = h->fsd_cumw != nullptr;   // nxs_dyn_fsd_put
     RegridAdopt ad{};
     for (int k = 0; k < RA_COUNT; ++k) {
         ad.p[k] = mem.alloc<double>(k <= RA_UT ? 2 * (size_t)Nn_new : (size_t)Ne_new);
@@ -2762,6 +2779,9 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     double *new_cum = nullptr, *new_fsd = nullptr;
     if (carry_cum && !(new_cum = mem.alloc<double>(Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for cum_damage");
     if (carry_fsd && !(new_fsd = mem.alloc<double>((size_t)nbins * Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for the FSD bins");
+    double *new_mech = nullptr, *new_cumw = nullptr;
+    if (carry_mech && !(new_mech = mem.alloc<double>((size_t)nbins * Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for the mechanical FSD bins");
+    if (carry_cumw && !(new_cumw = mem.alloc<double>(Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for cum_wave_damage");
     std::vector<RegridCol> cols;
     const int LO = NXS_REGRID_VAR_HAS_MIN, LOHI = NXS_REGRID_VAR_HAS_MIN | NXS_REGRID_VAR_HAS_MAX;
     auto own = [&](const double *src, int ra, int flags, double hi) { cols.push_back(RegridCol{src, ad.p[ra], NXS_TRANSFORM_NONE, flags, 0., hi}); };
@@ -2772,8 +2792,14 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     const int cy_col = (int)cols.size();
     own(so.cyoung, RA_CYOUNG, LOHI, 1.); own(so.hyoung, RA_HYOUNG, LO, 0.); own(so.hsyoung, RA_HSYOUNG, LO, 0.);
     own(so.cmyi, RA_CMYI, LOHI, 1.); own(so.tmyi, RA_TMYI, LO, 0.);
-    if (carry_cum) cols.push_back(RegridCol{h->dw.cum_damage, new_cum, NXS_TRANSFORM_NONE, LO, 0., 0.});
+    // the coupled build's columns: cum_damage, M_conc_fsd[..] as they have always been; with M_conc_mech_fsd / M_cum_wave_damage attached the order of
+    // initModelVariables (FE.cpp:7193-7212): M_conc_fsd[..], M_conc_mech_fsd[..], M_cum_damage, M_cum_wave_damage
+    const bool fsd_order = carry_mech || carry_cumw;
+    if (carry_cum && !fsd_order) cols.push_back(RegridCol{h->dw.cum_damage, new_cum, NXS_TRANSFORM_NONE, LO, 0., 0.});
     for (int b = 0; b < nbins; ++b) cols.push_back(RegridCol{h->dw.conc_fsd + (size_t)b * Ne_old, new_fsd + (size_t)b * Ne_new, NXS_TRANSFORM_NONE, LOHI, 0., 1.});
+    if (carry_mech) for (int b = 0; b < nbins; ++b) cols.push_back(RegridCol{h->fsd_mech + (size_t)b * Ne_old, new_mech + (size_t)b * Ne_new, NXS_TRANSFORM_NONE, LOHI, 0., 1.});
+    if (carry_cum && fsd_order) cols.push_back(RegridCol{h->dw.cum_damage, new_cum, NXS_TRANSFORM_NONE, LO, 0., 0.});
+    if (carry_cumw) cols.push_back(RegridCol{h->fsd_cumw, new_cumw, NXS_TRANSFORM_NONE, LO, 0., 0.});
     // the caller's variables, kind by kind; host arrays get a device twin (up now, down after the swap)
     struct Down { double *host; const double *dev; };
     std::vector<Down> downs;
@@ -2868,6 +2894,8 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     h->have_state = true;
     if (carry_cum) { h->coupled_allocs.push_back(new_cum); mem.release(new_cum); h->d_cum = new_cum; h->dw.cum_damage = new_cum; }
     if (carry_fsd) { h->coupled_allocs.push_back(new_fsd); mem.release(new_fsd); h->d_fsd = new_fsd; h->fsd_capacity = (size_t)nbins * Ne_new; h->dw.conc_fsd = new_fsd; h->dw.nbins = nbins; }
+    if (carry_mech) { h->coupled_allocs.push_back(new_mech); mem.release(new_mech); h->d_mech = new_mech; h->mech_capacity = (size_t)nbins * Ne_new; h->fsd_mech = new_mech; }
+    if (carry_cumw) { h->coupled_allocs.push_back(new_cumw); mem.release(new_cumw); h->d_cumw = new_cumw; h->fsd_cumw = new_cumw; }
     if (h->drift) nxs_drifters::state_changed(h->drift);
     for (const Down &d : downs) HIPCHK(h, hipMemcpyAsync(d.host, d.dev, (size_t)Ne_new * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3535,5 +3563,7 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
     { int rc = resident_error(h); if (rc) return rc; }
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_check_fields_fast"); }
+
+#include "nxs_fsd.inl"
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 //                             that created it.
 //
 // Checked against the real contrib/bamg in tests/test_connectivity.py.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
@@ -166,3 +167,81 @@ extern "C" int nxs_calc_cohesion(double C_fix, double C_alea, const int32_t *glo
     }
     return NXS_OK;
 } catch (...) { return entry_caught("nxs_calc_cohesion"); }
+
+// The table part of initFsd() (FE.cpp:7408-7533): bin limits, widths and centres of the floe-size distribution, the scaled floe areas of the welding
+// (Roach et al. 2018) and M_alpha_fsd_merge, "which floe sizes can combine during merging".  Statement by statement the reference's; std::pow(x, 2) is written
+// x * x -- what GCC and clang make of a pow with the literal exponent 2 at -O1 and above (exact by definition, where a libm pow is only faithful) --, every other
+// operation is + - * / or sqrt, so the tables carry the reference's bits.  Host only.
+extern "C" int nxs_fsd_bins(int32_t fsd_type, int32_t num_bins, double min_floe_size, double bin_cst_width, int32_t welding_use_scaled_area, nxs_fsd_tables *out) try {
+    if (!out || num_bins < 1) return NXS_ERR_INVALID;
+    if (fsd_type != NXS_FSD_CONSTANT_SIZE && fsd_type != NXS_FSD_CONSTANT_AREA) return NXS_ERR_INVALID;   // "Wrong fsd_type" (FE.cpp:7484-7486)
+    const int n = num_bins;
+    const double floe_shape = 0.66;   // M_floe_shape (FE.cpp:7414)
+    std::vector<double> widths(n, 0.), low(n, 0.), up(n, 0.), centres(n);
+    std::vector<double> area_up(n, 0.), area_low(n, 0.), area_centered(n, 0.), area_binwidth(n, 0.);
+    std::vector<double> s_up(n, 0.), s_low(n, 0.), s_centered(n, 0.), s_binwidth(n, 0.), lims(n + 1, 0.), lims_scaled(n + 1, 0.);
+    const auto sq = [](double x) { return x * x; };
+    if (fsd_type == NXS_FSD_CONSTANT_SIZE) {   // FE.cpp:7430-7457
+        low[0] = min_floe_size;
+        widths[0] = bin_cst_width;
+        up[0] = min_floe_size + bin_cst_width;
+        centres[0] = (up[0] + low[0]) / 2;
+        for (int m = 1; m < n; m++) {
+            widths[m] = bin_cst_width;
+            low[m] = low[m - 1] + bin_cst_width;
+            up[m] = up[m - 1] + bin_cst_width;
+            centres[m] = (up[m] + low[m]) / 2;
+        }
+        for (int m = 0; m < n; m++) {
+            area_up[m] = floe_shape * sq(up[m]);
+            area_low[m] = floe_shape * sq(low[m]);
+            area_centered[m] = floe_shape * sq(centres[m]);
+            lims[m] = area_low[m];
+            area_binwidth[m] = area_up[m] - area_low[m];
+        }
+        lims[n] = area_up[n - 1];
+    } else {                                    // FE.cpp:7458-7482
+        low[0] = min_floe_size;
+        area_binwidth[0] = floe_shape * (sq(bin_cst_width) + 2 * min_floe_size * bin_cst_width);
+        area_low[0] = floe_shape * sq(low[0]);
+        area_up[0] = area_low[0] + area_binwidth[0];
+        for (int m = 1; m < n; m++) {
+            area_binwidth[m] = area_binwidth[0];
+            area_low[m] = area_up[m - 1];
+            area_up[m] = area_up[m - 1] + area_binwidth[m];
+        }
+        for (int m = 0; m < n; m++) {
+            lims[m] = area_low[m];
+            low[m] = std::sqrt(area_low[m] / floe_shape);
+            up[m] = std::sqrt(area_up[m] / floe_shape);
+            widths[m] = up[m] - low[m];
+            centres[m] = (up[m] + low[m]) / 2;
+            area_centered[m] = floe_shape * sq(centres[m]);
+        }
+        lims[n] = area_up[n - 1];
+    }
+    if (welding_use_scaled_area) {             // FE.cpp:7501-7511
+        const double widest = *std::max_element(area_binwidth.begin(), area_binwidth.end());
+        for (int m = 0; m < n + 1; m++) lims_scaled[m] = (lims[m] - lims[0]) / widest;
+    } else {
+        for (int m = 0; m < n + 1; m++) lims_scaled[m] = (lims[m] - lims[0]);
+    }
+    for (int m = 0; m < n; m++) {              // FE.cpp:7512-7518
+        s_up[m] = lims_scaled[m + 1];
+        s_low[m] = lims_scaled[m];
+        s_centered[m] = (s_up[m] + s_low[m]) / 2.;
+        s_binwidth[m] = s_up[m] - s_low[m];
+    }
+    std::vector<int32_t> alpha((size_t)n * n, -999);   // FE.cpp:7520-7533
+    for (int m = 0; m < n; m++)
+        for (int k = 0; k < n; k++) {
+            const double test = s_up[m] - s_centered[k];
+            for (int p = 0; p < n; p++)
+                if ((test >= s_low[p]) && (test < s_up[p])) alpha[(size_t)m * n + k] = p + 1;
+        }
+    const auto give = [n](double *dst, const std::vector<double> &v) { if (dst) std::copy(v.begin(), v.begin() + n, dst); };
+    give(out->bin_widths, widths); give(out->bin_low_limits, low); give(out->bin_up_limits, up); give(out->bin_centres, centres);
+    give(out->area_scaled_up, s_up); give(out->area_scaled_low, s_low); give(out->area_scaled_centered, s_centered); give(out->area_scaled_binwidth, s_binwidth);
+    if (out->alpha_merge) std::copy(alpha.begin(), alpha.end(), out->alpha_merge);
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_fsd_bins"); }

@@ -75,6 +75,15 @@ def load_library():
     L.nxs_dyn_set_wave_stress.argtypes = [H, _abi.c_double_p]
     L.nxs_dyn_put_coupled.argtypes = [H, P(_abi.Coupled)]
     L.nxs_dyn_get_coupled.argtypes = [H, P(_abi.Coupled)]
+    L.nxs_fsd_bins.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, P(_abi.FsdTables)]
+    L.nxs_fsd_config_check.argtypes = [P(_abi.FsdConfig), C.c_int32]
+    L.nxs_dyn_fsd_configure.argtypes = [H, P(_abi.FsdConfig)]
+    L.nxs_dyn_fsd_put.argtypes = [H, P(_abi.FsdState)]
+    L.nxs_dyn_fsd_get.argtypes = [H, P(_abi.FsdState)]
+    L.nxs_dyn_fsd_init.argtypes = [H]
+    L.nxs_dyn_fsd_update.argtypes = [H]
+    L.nxs_dyn_fsd_breakup.argtypes = [H, C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int32)]
+    L.nxs_dyn_fsd_weld.argtypes = [H, C.c_double, _abi.c_uint8_p]
     L.nxs_dyn_ice_diagnostics.argtypes = [H, P(_abi.IceDiag), P(C.c_void_p)]
     L.nxs_dyn_means_configure.argtypes = [H, P(_abi.MeansConfig)]
     L.nxs_dyn_means_set_tau_ow.argtypes = [H, _abi.c_double_p]
@@ -135,6 +144,8 @@ EXPORTS = (
     "nxs_dyn_put_state", "nxs_dyn_get_state", "nxs_dyn_set_forcing", "nxs_dyn_set_forcing_pair", "nxs_dyn_set_forcing_time",
     "nxs_dyn_get_diag", "nxs_dyn_ice_diagnostics", "nxs_dyn_step",
     "nxs_dyn_set_wave_stress", "nxs_dyn_put_coupled", "nxs_dyn_get_coupled",
+    "nxs_fsd_bins", "nxs_fsd_config_check", "nxs_dyn_fsd_configure", "nxs_dyn_fsd_put", "nxs_dyn_fsd_get", "nxs_dyn_fsd_init", "nxs_dyn_fsd_update", "nxs_dyn_fsd_breakup",
+    "nxs_dyn_fsd_weld",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
     "nxs_dyn_drifters_get", "nxs_dyn_regrid",
@@ -195,6 +206,73 @@ def mesh_element_connectivity(indices: np.ndarray, num_nodes: int) -> np.ndarray
     if rc:
         raise NxsError(rc, "nxs_mesh_element_connectivity")
     return ec
+
+
+_HIP = None
+
+
+def hip_runtime():
+    """The HIP runtime libnxsdyn.so itself is linked against (one runtime in the process), with the few prototypes a caller needs to hand the library a plain
+    device buffer (an `old_values` of nxs_dyn_regrid_var, the M_wlbk of nxs_dyn_fsd_breakup) without another GPU framework."""
+    global _HIP
+    if _HIP is None:
+        import re
+        load_library()
+        out = subprocess.check_output(["readelf", "-d", _LIB_PATH], text=True)
+        name = [n for n in re.findall(r"NEEDED.*\[(.*)\]", out) if "amdhip64" in n][0]
+        hip = C.CDLL(name)
+        hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        hip.hipFree.argtypes = [C.c_void_p]
+        hip.hipDeviceGetName.argtypes = [C.c_char_p, C.c_int, C.c_int]
+        _HIP = hip
+    return _HIP
+
+
+def device_put(a: np.ndarray) -> int:
+    """A new device buffer holding the C-contiguous array `a`; returns its address (free it with device_free)."""
+    a = np.ascontiguousarray(a)
+    p = C.c_void_p()
+    if hip_runtime().hipMalloc(C.byref(p), a.nbytes) != 0 or hip_runtime().hipMemcpy(p, a.ctypes.data, a.nbytes, 1) != 0:
+        raise NxsError(-3, "hipMalloc / hipMemcpy of a device buffer failed")
+    return p.value
+
+
+def device_free(address: int):
+    hip_runtime().hipFree(C.c_void_p(int(address)))
+
+
+def device_name(device: int = 0) -> str:
+    """hipDeviceGetName of `device`."""
+    buf = C.create_string_buffer(256)
+    if hip_runtime().hipDeviceGetName(buf, 256, int(device)) != 0:
+        raise NxsError(-3, "hipDeviceGetName failed")
+    return buf.value.decode(errors="replace")
+
+
+def fsd_bins(fsd_type, num_bins: int, min_floe_size: float, bin_cst_width: float, welding_use_scaled_area: bool = True) -> dict:
+    """The tables of initFsd() (FE.cpp:7408-7533; nxs_fsd_bins, host only): bin_widths, bin_low_limits, bin_up_limits, bin_centres, area_scaled_up / _low /
+    _centered / _binwidth ([num_bins] each) and alpha_merge ([num_bins, num_bins] int32, -999 where no bin matches).  fsd_type: "constant_size" / "constant_area"."""
+    L = load_library()
+    n = int(num_bins)
+    if n < 1:
+        raise NxsError(-1, f"fsd_bins: num_bins = {n}")
+    out = {k: np.empty(n) for k in _abi.FSD_TABLES}
+    out["alpha_merge"] = np.empty((n, n), np.int32)
+    t = _abi.fsd_tables_struct(out)
+    ft = _abi.FSD_TYPES[fsd_type] if isinstance(fsd_type, str) else int(fsd_type)
+    rc = L.nxs_fsd_bins(ft, n, float(min_floe_size), float(bin_cst_width), int(bool(welding_use_scaled_area)), C.byref(t))
+    if rc:
+        raise NxsError(rc, "nxs_fsd_bins")
+    return out
+
+
+def fsd_config_check(num_bins: int, tables: dict, attached_bins: int, **options) -> int:
+    """What fsd_configure would answer for this configuration on a handle whose conc_fsd has `attached_bins` bins (nxs_fsd_config_check, host only): 0 or
+    NXS_ERR_INVALID (-1)."""
+    L = load_library()
+    c = _abi.fsd_config_struct(num_bins, tables, **options)
+    return L.nxs_fsd_config_check(C.byref(c), int(attached_bins))
 
 
 REGRID_INPUTS = ("cohesion", "time_relaxation_damage", "drag_ui", "drag_ui_young")
@@ -535,6 +613,83 @@ class FiniteElementDynamics:
             c.num_fsd_bins = num_fsd_bins
         self._chk(self.L.nxs_dyn_get_coupled(self.h, C.byref(c)))
         return out
+
+    # ---- the floe-size distribution: initFsd / updateFSD / redistributeFSD / weldingRoach (FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870, 5888-5896) ----
+    def fsd_configure(self, tables: dict, **options):
+        """nxs_dyn_fsd_configure: the tables of fsd_bins (or the caller's own) and the options of the loops, keywords named after nxs_dyn_fsd_config
+        (breakup_type / welding_type also as the reference's strings).  The number of bins is the tables'; it must be the attached conc_fsd's."""
+        tables = {k: np.ascontiguousarray(v, np.int32 if k == "alpha_merge" else np.float64) for k, v in tables.items() if v is not None}
+        n = int(options.pop("num_bins", tables["bin_centres"].size if "bin_centres" in tables else 0))
+        c = _abi.fsd_config_struct(n, tables, **options)
+        self._chk(self.L.nxs_dyn_fsd_configure(self.h, C.byref(c)))
+        self._fsd_bins = n
+
+    def fsd_put(self, conc_mech_fsd=None, cum_wave_damage=None):
+        """M_conc_mech_fsd ([num_fsd_bins, Ne], bin-major) and M_cum_wave_damage ([Ne]) to the device; what is None is detached."""
+        s = _abi.FsdState()
+        Ne = self.lm.num_elements
+        if conc_mech_fsd is not None:
+            m = np.ascontiguousarray(conc_mech_fsd, np.float64)
+            if m.ndim != 2 or m.shape[1] != Ne:
+                raise ValueError(f"conc_mech_fsd has shape {m.shape}, expected (num_fsd_bins, {Ne})")
+            s.conc_mech_fsd = _abi.dptr(m)
+            s.num_fsd_bins = m.shape[0]
+        if cum_wave_damage is not None:
+            w = np.ascontiguousarray(cum_wave_damage, np.float64)
+            if w.shape != (Ne,):
+                raise ValueError(f"cum_wave_damage has shape {w.shape}, expected ({Ne},)")
+            s.cum_wave_damage = _abi.dptr(w)
+        self._chk(self.L.nxs_dyn_fsd_put(self.h, C.byref(s)))
+
+    def fsd_get(self, num_fsd_bins: int = 0, cum_wave_damage: bool = False) -> dict:
+        """{'conc_mech_fsd': [num_fsd_bins, Ne]} and / or {'cum_wave_damage': [Ne]} from the device, and 'weld_crash': whether a crash condition of
+        weldingRoach was met since the last fsd_get."""
+        s = _abi.FsdState()
+        out = {}
+        Ne = self.lm.num_elements
+        if num_fsd_bins > 0:
+            out["conc_mech_fsd"] = np.empty((num_fsd_bins, Ne))
+            s.conc_mech_fsd = _abi.dptr(out["conc_mech_fsd"])
+            s.num_fsd_bins = num_fsd_bins
+        if cum_wave_damage:
+            out["cum_wave_damage"] = np.empty(Ne)
+            s.cum_wave_damage = _abi.dptr(out["cum_wave_damage"])
+        self._chk(self.L.nxs_dyn_fsd_get(self.h, C.byref(s)))
+        out["weld_crash"] = int(s.weld_crash)
+        return out
+
+    def fsd_init(self):
+        """The distribution at the end of initFsd(): all the ice in the highest bin.  Asynchronous."""
+        self._chk(self.L.nxs_dyn_fsd_init(self.h))
+
+    def fsd_update(self):
+        """updateFSD(): the bins rescaled to the total concentration.  Asynchronous."""
+        self._chk(self.L.nxs_dyn_fsd_update(self.h))
+
+    def fsd_breakup(self, wlbk, want_flags: bool = True):
+        """redistributeFSD() with M_wlbk = wlbk ([Ne] array, or an int: a device address).  Returns (M_breakup_in_dt, crash) -- or None, the call staying
+        asynchronous, with want_flags False."""
+        flags = 0
+        if isinstance(wlbk, (int, np.integer)):
+            ptr, flags = C.c_void_p(int(wlbk)), _abi.NXS_FSD_WLBK_ON_DEVICE
+        else:
+            w = np.ascontiguousarray(wlbk, np.float64)
+            if w.shape != (self.lm.num_elements,):
+                raise ValueError(f"wlbk has shape {w.shape}, expected ({self.lm.num_elements},)")
+            ptr = C.c_void_p(w.ctypes.data)
+        if not want_flags:
+            self._chk(self.L.nxs_dyn_fsd_breakup(self.h, ptr, flags, None, None))
+            return None
+        b, c = C.c_int32(-1), C.c_int32(-1)
+        self._chk(self.L.nxs_dyn_fsd_breakup(self.h, ptr, flags, C.byref(b), C.byref(c)))
+        return bool(b.value), bool(c.value)
+
+    def fsd_weld(self, ddt: float, freezing):
+        """weldingRoach(i, ddt) and the mechanical healing where freezing[i] (thermo's del_hi > 0).  The kernel is asynchronous."""
+        f = np.ascontiguousarray(np.asarray(freezing) != 0, np.uint8)
+        if f.shape != (self.lm.num_elements,):
+            raise ValueError(f"freezing has shape {f.shape}, expected ({self.lm.num_elements},)")
+        self._chk(self.L.nxs_dyn_fsd_weld(self.h, float(ddt), _abi.bptr(f)))
 
     def get_state(self) -> dict:
         Nn, Ne = self.lm.num_nodes, self.lm.num_elements
