@@ -27,6 +27,7 @@
  *   updateMeans(M_moorings, time_factor)        nxs_dyn_means_update    (FE.cpp:8518-9024; configure / get / to_grid / reset beside it)
  *   interpFields() + assignVariables()          nxs_dyn_regrid          (FE.cpp:3071-3154, 2120-2151, 2196-2258, 3161-3297, 553-572)
  *   #ifdef OASIS: initFsd / updateFSD / redistributeFSD / weldingRoach   nxs_fsd_bins, nxs_dyn_fsd_* (FE.cpp:7408-7576, 4674-4732, 4268-4483, 4737-4870, 5888-5896)
+ *   thermo(): OWBulkFluxes + IABulkFluxes       nxs_dyn_fluxes, nxs_dyn_flux_* (FE.cpp:5214-5277, 5032-5159, 6148-6353, 4966-5019, 6359-6389, 6454-6535)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -674,6 +675,75 @@ NXS_API int nxs_dyn_fsd_update(nxs_dyn_handle *h);
 NXS_API int nxs_dyn_fsd_breakup(nxs_dyn_handle *h, const double *wlbk /* [Ne] M_wlbk */, int32_t flags, int32_t *breakup_in_dt /* may be NULL */, int32_t *crash /* may be NULL */);
 NXS_API int nxs_dyn_fsd_weld(nxs_dyn_handle *h, double ddt, const uint8_t *freezing /* [Ne] del_hi > 0 */);
 
+/* ---- The atmospheric bulk fluxes of thermo() on the device: its "fluxes" timer (FE.cpp:5214-5277) -- OWBulkFluxes (the `nextsim` formula, FE.cpp:5096-5132, and the
+ * radiative loop, FE.cpp:5138-5158), IABulkFluxes (FE.cpp:6148-6353: the constants block, the Grachev stability functions, thermo.force_neutral_atmosphere, the
+ * pond-fraction rule) for the old ice and, in the young-ice category, for the young ice, with specificHumidity (FE.cpp:4966-5019, all three schemes), albedo
+ * (FE.cpp:6454-6535, schemes 1-4), windSpeedElement (FE.cpp:6359-6370) and incomingLongwave (FE.cpp:6376-6389, both sources).  One launch, a thread per element,
+ * ghost elements included.  It reads M_conc, M_snow_thick, M_conc_young, M_hs_young and the wind the step's prep kernels read (nxs_dyn_set_forcing, or the pair
+ * blended by nxs_dyn_set_forcing_time) -- all resident --, the atmosphere and the thermodynamic rows below, and writes 25 rows for the slab loop, D_tau_ow into
+ * the row nxs_dyn_means_update reads (so no nxs_dyn_means_set_tau_ow) and M_drag_ui / M_drag_ti and their _young twins IN PLACE (the next call and the next step
+ * read them: no upload of drag_ui / drag_ui_young through nxs_dyn_put_state).
+ * OUT OF SCOPE: the #ifdef AEROBULK branch of OWBulkFluxes (a Fortran library; only the `nextsim` formula is built), the OceanType::COUPLED term
+ * Qow += Qsw * M_qsrml (FE.cpp:5153-5154), and thermo() from FE.cpp:5279 on (the slab loop), which consumes the rows of nxs_dyn_fluxes_get.
+ *   nxs_flux_default_config   model/options.cpp:388-438; humidity from the dew point, long wave from Qlw_in
+ *   nxs_flux_config_check     what nxs_dyn_flux_configure refuses, without a handle (so without a device): alb_scheme outside 1..4, zref_wind, zref_temp or
+ *                  limiting_lengthscale <= 0 (or NaN), an unknown humidity or long-wave source; NXS_ERR_INVALID, the text in nxs_dyn_last_error(NULL)
+ *   nxs_flux_constants        TEST DOOR, like nxs_dyn_physical_constants: the physical:: constants compiled into the kernel, in the order NXS_FLUX_CONST_* names them
+ *                  (host only), so that a caller and tests/test_fluxes_abi.py can check that library and model agree; no reference call site
+ *   nxs_dyn_flux_configure    the configuration is the handle's and survives nxs_dyn_set_mesh; quad_drag_coef_air (z0, FE.cpp:6170) is nxs_dyn_params'
+ *   nxs_dyn_flux_set_atmosphere   [Ne] host rows; a NULL row means "the device copy is current" (a row never given stays missing)
+ *   nxs_dyn_flux_put / _get   the thermodynamic rows the fluxes read or write; NULL members as in nxs_dyn_put_state / nxs_dyn_get_state (put: the device copy is
+ *                  current; get: not wanted).  sss is carried for the slab loop: specificHumidity(WATER) assigns it and never reads it (FE.cpp:4990-4993)
+ *   nxs_dyn_fluxes            the launch, asynchronous on the handle's stream.  NXS_ERR_STATE: before nxs_dyn_flux_configure, before nxs_dyn_put_state and a
+ *                  forcing, while an atmosphere or flux row is missing -- which is the state after nxs_dyn_set_mesh AND after nxs_dyn_regrid: the host's
+ *                  regrid re-makes those rows on the new mesh, the handle does not carry them
+ *   nxs_dyn_fluxes_get        synchronised on return.  out (may be NULL): host pointers, a NULL row is skipped.  device_rows (may be NULL): receives the
+ *                  NXS_FLUX_ROWS DEVICE pointers of the same rows ([Ne] each, library-owned, valid until nxs_dyn_set_mesh), for the slab loop or a host that
+ *                  lives on the GPU.  In the classic category the nine _young rows are zero (FE.cpp:5266-5272).  NXS_ERR_STATE before the first nxs_dyn_fluxes */
+enum { NXS_FLUX_HUM_DEWPOINT = 0 /* M_dair */, NXS_FLUX_HUM_SPHUMA = 1 /* M_sphuma */, NXS_FLUX_HUM_MIXRAT = 2 /* M_mixrat */ };
+enum { NXS_FLUX_LW_QLW_IN = 0 /* M_Qlw_in */, NXS_FLUX_LW_TCC = 1 /* M_tcc: thermo.use_parameterised_long_wave_radiation */ };
+enum { NXS_FLUX_CONST_TFRWK = 0, NXS_FLUX_CONST_RA_DRY, NXS_FLUX_CONST_RA_VAP, NXS_FLUX_CONST_CPA, NXS_FLUX_CONST_CPV, NXS_FLUX_CONST_LV0, NXS_FLUX_CONST_EPS,
+       NXS_FLUX_CONST_SIGMA_SB, NXS_FLUX_CONST_VONKARMAN, NXS_FLUX_CONST_GAMMA_D, NXS_FLUX_CONST_RHOA, NXS_FLUX_CONST_LF, NXS_FLUX_CONST_G, NXS_FLUX_CONST_COUNT };
+typedef struct nxs_dyn_flux_config {
+    int32_t alb_scheme;                /* thermo.alb_scheme, 1..4 */
+    int32_t humidity_source;           /* NXS_FLUX_HUM_*: which of M_dair, M_sphuma, M_mixrat the dataset initialised (FE.cpp:4980-4985) */
+    int32_t longwave_source;           /* NXS_FLUX_LW_* (FE.cpp:6378) */
+    int32_t force_neutral_atmosphere;  /* thermo.force_neutral_atmosphere: the drags are left as they are */
+    double alb_ice, alb_sn, alb_ponds; /* thermo.alb_ice, alb_sn, alb_ponds */
+    double I_0;                        /* thermo.I_0 */
+    double ocean_albedo;               /* thermo.albedoW (M_ocean_albedo) */
+    double drag_ocean_t, drag_ocean_q; /* thermo.drag_ocean_t, drag_ocean_q */
+    double zref_wind, zref_temp;       /* thermo.zref_wind, zref_temp [m] */
+    double limiting_lengthscale;       /* thermo.limiting_lengthscale [m] */
+} nxs_dyn_flux_config;
+typedef struct nxs_dyn_flux_atmosphere {
+    const double *tair, *mslp, *Qsw_in; /* [Ne] M_tair, M_mslp, M_Qsw_in */
+    const double *humidity;             /* [Ne] M_dair, M_sphuma or M_mixrat, as humidity_source says */
+    const double *longwave;             /* [Ne] M_Qlw_in or M_tcc, as longwave_source says */
+} nxs_dyn_flux_atmosphere;
+typedef struct nxs_dyn_flux_state {
+    double *tice0, *tsurf_young;        /* [Ne] M_tice[0], M_tsurf_young */
+    double *sst, *sss;                  /* [Ne] M_sst, M_sss */
+    double *drag_ti, *drag_ti_young;    /* [Ne] M_drag_ti, M_drag_ti_young (M_drag_ui and M_drag_ui_young are members of nxs_dyn_state) */
+    double *pond_fraction, *lid_volume; /* [Ne] D_pond_fraction, M_lid_volume */
+} nxs_dyn_flux_state;
+enum { NXS_FLUX_QOW = 0, NXS_FLUX_QLW_OW, NXS_FLUX_QSW_OW, NXS_FLUX_QLH_OW, NXS_FLUX_QSH_OW, NXS_FLUX_EVAP, NXS_FLUX_TAU_OW,
+       NXS_FLUX_QIA, NXS_FLUX_QLWI, NXS_FLUX_QSWI, NXS_FLUX_QLHI, NXS_FLUX_QSHI, NXS_FLUX_I, NXS_FLUX_SUBL, NXS_FLUX_DQIADT, NXS_FLUX_ALBEDO,
+       NXS_FLUX_QIA_YOUNG, NXS_FLUX_QLW_YOUNG, NXS_FLUX_QSW_YOUNG, NXS_FLUX_QLH_YOUNG, NXS_FLUX_QSH_YOUNG, NXS_FLUX_I_YOUNG, NXS_FLUX_SUBL_YOUNG,
+       NXS_FLUX_DQIADT_YOUNG, NXS_FLUX_ALBEDO_YOUNG };
+#define NXS_FLUX_ROWS 25
+typedef struct nxs_dyn_flux_rows { double *row[NXS_FLUX_ROWS]; } nxs_dyn_flux_rows;   /* [Ne] each, indexed by NXS_FLUX_* */
+
+NXS_API int nxs_flux_default_config(nxs_dyn_flux_config *c);
+NXS_API int nxs_flux_config_check(const nxs_dyn_flux_config *c);
+NXS_API int nxs_flux_constants(double *out, int32_t count);
+NXS_API int nxs_dyn_flux_configure(nxs_dyn_handle *h, const nxs_dyn_flux_config *c);
+NXS_API int nxs_dyn_flux_set_atmosphere(nxs_dyn_handle *h, const nxs_dyn_flux_atmosphere *a);
+NXS_API int nxs_dyn_flux_put(nxs_dyn_handle *h, const nxs_dyn_flux_state *s);
+NXS_API int nxs_dyn_flux_get(nxs_dyn_handle *h, nxs_dyn_flux_state *s);
+NXS_API int nxs_dyn_fluxes(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_fluxes_get(nxs_dyn_handle *h, const nxs_dyn_flux_rows *out /* may be NULL */, const double **device_rows /* [NXS_FLUX_ROWS], may be NULL */);
+
 /* One dynamics step on the device-resident state: FE.cpp:8197-8214.  Asynchronous on the
  * handle's stream; nxs_dyn_synchronize() waits for it. */
 NXS_API int nxs_dyn_step(nxs_dyn_handle *h);
@@ -825,7 +895,8 @@ NXS_API int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t);
 NXS_API int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value);
 
 /* Test door: copies a named internal work array (rlmass, node_mass, C_bu, grad_ssh, fcor, VTM, shape,
- * emass, ecbu, force, volume, expC) to the host so that parity tests can localise a difference. */
+ * emass, ecbu, force, volume, expC; drag_ui, drag_ui_young: the two inputs of nxs_dyn_state that nxs_dyn_fluxes updates in place) to the host so that
+ * parity tests can localise a difference. */
 NXS_API int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_t n);
 
 /* Test door: option "trace_branches" = 1 zeroes a per-element record and makes every following step run the one-kernel-per-loop

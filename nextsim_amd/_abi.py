@@ -190,6 +190,55 @@ def fsd_config_struct(num_bins: int, tables: dict, **options) -> FsdConfig:
     return c
 
 
+# ---- thermo()'s atmospheric bulk fluxes (include/nxs_dyn.h, nxs_dyn_flux_* / nxs_dyn_fluxes)
+NXS_FLUX_HUM_DEWPOINT, NXS_FLUX_HUM_SPHUMA, NXS_FLUX_HUM_MIXRAT = range(3)
+NXS_FLUX_LW_QLW_IN, NXS_FLUX_LW_TCC = 0, 1
+FLUX_HUMIDITY = {"dewpoint": NXS_FLUX_HUM_DEWPOINT, "sphuma": NXS_FLUX_HUM_SPHUMA, "mixrat": NXS_FLUX_HUM_MIXRAT}
+FLUX_LONGWAVE = {"Qlw_in": NXS_FLUX_LW_QLW_IN, "tcc": NXS_FLUX_LW_TCC}
+FLUX_CONSTANTS = ("tfrwK", "Ra_dry", "Ra_vap", "cpa", "cpv", "Lv0", "eps", "sigma_sb", "vonKarman", "Gamma_d", "rhoa", "Lf", "g")   # NXS_FLUX_CONST_*
+FLUX_CONFIG_INTS = ("alb_scheme", "humidity_source", "longwave_source", "force_neutral_atmosphere")
+FLUX_CONFIG_REALS = ("alb_ice", "alb_sn", "alb_ponds", "I_0", "ocean_albedo", "drag_ocean_t", "drag_ocean_q", "zref_wind", "zref_temp", "limiting_lengthscale")
+FLUX_ATMOSPHERE = ("tair", "mslp", "Qsw_in", "humidity", "longwave")
+FLUX_STATE = ("tice0", "tsurf_young", "sst", "sss", "drag_ti", "drag_ti_young", "pond_fraction", "lid_volume")
+FLUX_ICE_ROWS = ("Qia", "Qlw", "Qsw", "Qlh", "Qsh", "I", "subl", "dQiadT", "albedo")
+FLUX_ROWS = (("Qow", "Qlw_ow", "Qsw_ow", "Qlh_ow", "Qsh_ow", "evap", "tau_ow", "Qia", "Qlwi", "Qswi", "Qlhi", "Qshi", "I", "subl", "dQiadT", "albedo")
+             + tuple(k + "_young" for k in FLUX_ICE_ROWS))   # NXS_FLUX_*
+NXS_FLUX_ROWS = 25
+assert len(FLUX_ROWS) == NXS_FLUX_ROWS
+
+
+class FluxConfig(C.Structure):   # nxs_dyn_flux_config
+    _fields_ = [(k, C.c_int32) for k in FLUX_CONFIG_INTS] + [(k, C.c_double) for k in FLUX_CONFIG_REALS]
+
+
+class FluxAtmosphere(C.Structure):   # nxs_dyn_flux_atmosphere
+    _fields_ = [(k, c_double_p) for k in FLUX_ATMOSPHERE]
+
+
+class FluxState(C.Structure):   # nxs_dyn_flux_state
+    _fields_ = [(k, c_double_p) for k in FLUX_STATE]
+
+
+class FluxRows(C.Structure):   # nxs_dyn_flux_rows
+    _fields_ = [("row", c_double_p * NXS_FLUX_ROWS)]
+
+
+def flux_config_struct(base: "FluxConfig", **options) -> FluxConfig:
+    """A copy of `base` (the defaults of nxs_flux_default_config) with keyword options named after nxs_dyn_flux_config's members; humidity_source /
+    longwave_source also by name ("dewpoint" / "sphuma" / "mixrat", "Qlw_in" / "tcc")."""
+    c = FluxConfig()
+    C.memmove(C.byref(c), C.byref(base), C.sizeof(c))
+    for k, v in options.items():
+        if k == "humidity_source" and isinstance(v, str):
+            v = FLUX_HUMIDITY[v]
+        if k == "longwave_source" and isinstance(v, str):
+            v = FLUX_LONGWAVE[v]
+        if k not in FLUX_CONFIG_INTS + FLUX_CONFIG_REALS:
+            raise KeyError(f"nxs_dyn_flux_config has no member {k!r}")
+        setattr(c, k, int(v) if k in FLUX_CONFIG_INTS else float(v))
+    return c
+
+
 # nxs_dyn_regrid (include/nxs_dyn.h): ModelVariable::interpTransformation and the flags of nxs_dyn_regrid_var
 NXS_TRANSFORM_NONE, NXS_TRANSFORM_CONC, NXS_TRANSFORM_THICK, NXS_TRANSFORM_ENTHALPY = range(4)
 TRANSFORMATIONS = {"none": NXS_TRANSFORM_NONE, "conc": NXS_TRANSFORM_CONC, "thick": NXS_TRANSFORM_THICK, "enthalpy": NXS_TRANSFORM_ENTHALPY}

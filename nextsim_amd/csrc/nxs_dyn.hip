@@ -16,6 +16,7 @@
 //   k_update          FE.cpp:3946-4131    update()
 //   k_free_drift      FE.cpp:10140-10176
 //   k_regrid_*/k_check_* FE.cpp:8298-8309, 14536-14655 reductions
+//   k_fluxes                                  FE.cpp:5214-5277: thermo()'s atmospheric bulk fluxes, OWBulkFluxes + IABulkFluxes (nxs_flux_kernels.inl, nxs_dyn_fluxes)
 //   k_fsd_init / _update / _breakup / _weld   FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870 + 5888-5896: the floe-size distribution (nxs_fsd_kernels.inl, nxs_dyn_fsd_*)
 //   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
 //
@@ -48,6 +49,7 @@
 
 #include "nxs_dyn_kernels.inl"
 #include "nxs_fsd_kernels.inl"
+#include "nxs_flux_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -214,6 +216,17 @@ struct nxs_dyn_handle {
     int *d_fsd_flags = nullptr;
     bool fsd_configured = false;
     std::vector<void *> coupled_allocs;
+    // thermo()'s atmospheric bulk fluxes (nxs_dyn_flux_* / nxs_dyn_fluxes): the configuration is the handle's and survives set_mesh; the rows are in the state pool and go
+    // with the mesh -- after set_mesh / regrid every row is MISSING until it is given again (the host re-makes them on the new mesh)
+    nxs_dyn_flux_config flux_cfg{};
+    bool flux_configured = false, flux_done = false;
+    FluxDev flux_dev{};                            // what the kernel receives by value: derived once per configuration and quad_drag_coef_air (flux_derive)
+    double flux_dev_qda = 0.;
+    bool flux_dev_valid = false;
+    double *d_flux_atm[FLUX_ATM_ROWS] = {};        // tair, mslp, Qsw_in, humidity, longwave
+    double *d_flux_st[FLUX_ST_ROWS] = {};          // tice0, tsurf_young, sst, sss, drag_ti, drag_ti_young, pond_fraction, lid_volume
+    unsigned flux_atm_have = 0, flux_st_have = 0;  // bit k: row k was given on this mesh
+    double *d_flux_out = nullptr;                  // [FLUX_ROWS][Ne] what nxs_dyn_fluxes_get returns (D_tau_ow: d_tau_ow below)
     // v4: the whole sub-step loop in one resident launch (option "fused" = 4; see k_substep_resident)
     DevResident res{};
     std::vector<void *> res_allocs;  // its tables, exchange buffer and ghost ring (a pool of their own: rebuilt whenever an option of the loop changes)
@@ -2059,6 +2072,9 @@ static int set_mesh_impl(nxs_dyn_handle *h, const nxs_dyn_mesh *m, RegridAdopt *
     s = DevState{}; w = DevWork{};
     h->d_icediag = nullptr; h->d_icediag_soa = nullptr;
     h->d_means[0] = h->d_means[1] = h->d_means_pm = h->d_tau_ow = nullptr; h->tau_ow_attached = false;   // (freed with the state pool above)
+    for (auto &q : h->d_flux_atm) q = nullptr;
+    for (auto &q : h->d_flux_st) q = nullptr;
+    h->d_flux_out = nullptr; h->flux_atm_have = h->flux_st_have = 0; h->flux_done = false;   // (the same pool)
     auto &P = h->state_allocs;
     const size_t n2 = 2 * (size_t)Nn, ne = Ne;
 #define A(ptr, cnt) if ((rc = dev_alloc(h, P, &(ptr), (cnt)))) return rc
@@ -3246,6 +3262,7 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
         struct { const char *nm; const double *p; int64_t len; } rec[] = {
             {"erec", h->dw.erec, 6 * Ne}, {"nrec", h->dw.nrec, 10 * Nn}, {"xy", h->dw.xy, 2 * Nn}, {"delta_x", h->dw.delta_x, Ne},
             {"surface", h->dw.surface, Ne}, {"tau_a", h->dw.D_tau_a, 2 * Nn},
+            {"drag_ui", h->ds.drag_ui, Ne}, {"drag_ui_young", h->ds.drag_ui_young, Ne},   // (inputs of the state that nxs_dyn_fluxes updates in place)
         };
         for (auto &t : rec)
             if (!std::strcmp(t.nm, name)) {
@@ -3565,5 +3582,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 } catch (...) { return dyn_caught(h, "nxs_dyn_check_fields_fast"); }
 
 #include "nxs_fsd.inl"
+#include "nxs_flux.inl"
 
 }  // extern "C"

@@ -84,6 +84,15 @@ def load_library():
     L.nxs_dyn_fsd_update.argtypes = [H]
     L.nxs_dyn_fsd_breakup.argtypes = [H, C.c_void_p, C.c_int32, P(C.c_int32), P(C.c_int32)]
     L.nxs_dyn_fsd_weld.argtypes = [H, C.c_double, _abi.c_uint8_p]
+    L.nxs_flux_default_config.argtypes = [P(_abi.FluxConfig)]
+    L.nxs_flux_config_check.argtypes = [P(_abi.FluxConfig)]
+    L.nxs_flux_constants.argtypes = [P(C.c_double), C.c_int32]
+    L.nxs_dyn_flux_configure.argtypes = [H, P(_abi.FluxConfig)]
+    L.nxs_dyn_flux_set_atmosphere.argtypes = [H, P(_abi.FluxAtmosphere)]
+    L.nxs_dyn_flux_put.argtypes = [H, P(_abi.FluxState)]
+    L.nxs_dyn_flux_get.argtypes = [H, P(_abi.FluxState)]
+    L.nxs_dyn_fluxes.argtypes = [H]
+    L.nxs_dyn_fluxes_get.argtypes = [H, P(_abi.FluxRows), P(C.c_void_p)]
     L.nxs_dyn_ice_diagnostics.argtypes = [H, P(_abi.IceDiag), P(C.c_void_p)]
     L.nxs_dyn_means_configure.argtypes = [H, P(_abi.MeansConfig)]
     L.nxs_dyn_means_set_tau_ow.argtypes = [H, _abi.c_double_p]
@@ -146,6 +155,8 @@ EXPORTS = (
     "nxs_dyn_set_wave_stress", "nxs_dyn_put_coupled", "nxs_dyn_get_coupled",
     "nxs_fsd_bins", "nxs_fsd_config_check", "nxs_dyn_fsd_configure", "nxs_dyn_fsd_put", "nxs_dyn_fsd_get", "nxs_dyn_fsd_init", "nxs_dyn_fsd_update", "nxs_dyn_fsd_breakup",
     "nxs_dyn_fsd_weld",
+    "nxs_flux_default_config", "nxs_flux_config_check", "nxs_flux_constants", "nxs_dyn_flux_configure", "nxs_dyn_flux_set_atmosphere", "nxs_dyn_flux_put", "nxs_dyn_flux_get",
+    "nxs_dyn_fluxes", "nxs_dyn_fluxes_get",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
     "nxs_dyn_drifters_get", "nxs_dyn_regrid",
@@ -265,6 +276,38 @@ def fsd_bins(fsd_type, num_bins: int, min_floe_size: float, bin_cst_width: float
     if rc:
         raise NxsError(rc, "nxs_fsd_bins")
     return out
+
+
+def flux_default_config() -> dict:
+    """The thermo.* defaults of model/options.cpp:388-438 the bulk fluxes read (nxs_flux_default_config, host only), keyed like nxs_dyn_flux_config."""
+    L = load_library()
+    c = _abi.FluxConfig()
+    rc = L.nxs_flux_default_config(C.byref(c))
+    if rc:
+        raise NxsError(rc, "nxs_flux_default_config")
+    return {k: getattr(c, k) for k, _ in _abi.FluxConfig._fields_}
+
+
+def _flux_config(options: dict) -> "_abi.FluxConfig":
+    L = load_library()
+    base = _abi.FluxConfig()
+    L.nxs_flux_default_config(C.byref(base))
+    return _abi.flux_config_struct(base, **options)
+
+
+def flux_config_check(**options) -> int:
+    """What flux_configure would answer for the defaults changed by `options` (nxs_flux_config_check, host only): 0 or NXS_ERR_INVALID."""
+    c = _flux_config(options)
+    return load_library().nxs_flux_config_check(C.byref(c))
+
+
+def flux_constants() -> dict:
+    """The physical:: constants compiled into the flux kernel (nxs_flux_constants, host only)."""
+    out = (C.c_double * len(_abi.FLUX_CONSTANTS))()
+    rc = load_library().nxs_flux_constants(out, len(_abi.FLUX_CONSTANTS))
+    if rc:
+        raise NxsError(rc, "nxs_flux_constants")
+    return dict(zip(_abi.FLUX_CONSTANTS, out))
 
 
 def fsd_config_check(num_bins: int, tables: dict, attached_bins: int, **options) -> int:
@@ -691,6 +734,65 @@ class FiniteElementDynamics:
             raise ValueError(f"freezing has shape {f.shape}, expected ({self.lm.num_elements},)")
         self._chk(self.L.nxs_dyn_fsd_weld(self.h, float(ddt), _abi.bptr(f)))
 
+    # ---- thermo()'s atmospheric bulk fluxes: OWBulkFluxes + IABulkFluxes (FE.cpp:5214-5277) ----
+    def _element_rows(self, struct, names, rows: dict, what: str):
+        keep = []
+        for k, v in rows.items():
+            if k not in names:
+                raise KeyError(f"{what} has no row {k!r}")
+            if v is None:
+                continue
+            a = np.ascontiguousarray(v, np.float64)
+            if a.shape != (self.lm.num_elements,):
+                raise ValueError(f"{k} has shape {a.shape}, expected ({self.lm.num_elements},)")
+            setattr(struct, k, _abi.dptr(a))
+            keep.append(a)
+        return keep
+
+    def flux_configure(self, **options):
+        """nxs_dyn_flux_configure: the defaults of flux_default_config() changed by keywords named after nxs_dyn_flux_config's members.  Survives set_mesh."""
+        c = _flux_config(options)
+        self._chk(self.L.nxs_dyn_flux_configure(self.h, C.byref(c)))
+
+    def flux_set_atmosphere(self, **rows):
+        """tair, mslp, Qsw_in, humidity (dew point, specific humidity or mixing ratio, as configured), longwave (Qlw_in or tcc): [Ne] each; a row left out or
+        None keeps the device copy."""
+        a = _abi.FluxAtmosphere()
+        keep = self._element_rows(a, _abi.FLUX_ATMOSPHERE, rows, "nxs_dyn_flux_atmosphere")
+        self._chk(self.L.nxs_dyn_flux_set_atmosphere(self.h, C.byref(a)))
+        del keep
+
+    def flux_put(self, **rows):
+        """tice0, tsurf_young, sst, sss, drag_ti, drag_ti_young, pond_fraction, lid_volume: [Ne] each; a row left out or None keeps the device copy."""
+        s = _abi.FluxState()
+        keep = self._element_rows(s, _abi.FLUX_STATE, rows, "nxs_dyn_flux_state")
+        self._chk(self.L.nxs_dyn_flux_put(self.h, C.byref(s)))
+        del keep
+
+    def flux_get(self, names=_abi.FLUX_STATE) -> dict:
+        """The named rows of nxs_dyn_flux_state from the device (all of them by default)."""
+        out = {k: np.empty(self.lm.num_elements) for k in names}
+        s = _abi.FluxState()
+        self._element_rows(s, _abi.FLUX_STATE, out, "nxs_dyn_flux_state")
+        self._chk(self.L.nxs_dyn_flux_get(self.h, C.byref(s)))
+        return out
+
+    def fluxes(self):
+        """nxs_dyn_fluxes: one launch; D_tau_ow, M_drag_ui / M_drag_ti and their _young twins are updated on the device.  Asynchronous on the handle's stream."""
+        self._chk(self.L.nxs_dyn_fluxes(self.h))
+
+    def fluxes_get(self, names=_abi.FLUX_ROWS, want_device: bool = False):
+        """The named rows of _abi.FLUX_ROWS as host arrays; with want_device also {name: device pointer} of all 25 rows."""
+        out = {k: np.empty(self.lm.num_elements) for k in names}
+        r = _abi.FluxRows()
+        for k, v in out.items():
+            r.row[_abi.FLUX_ROWS.index(k)] = _abi.dptr(v)
+        dev = (C.c_void_p * _abi.NXS_FLUX_ROWS)()
+        self._chk(self.L.nxs_dyn_fluxes_get(self.h, C.byref(r), dev if want_device else None))
+        if want_device:
+            return out, dict(zip(_abi.FLUX_ROWS, (int(p or 0) for p in dev)))
+        return out
+
     def get_state(self) -> dict:
         Nn, Ne = self.lm.num_nodes, self.lm.num_elements
         out = {k: np.empty(2 * Nn) for k in _abi.STATE_NODAL}
@@ -890,7 +992,7 @@ class FiniteElementDynamics:
         Nn, Ne = self.lm.num_nodes, self.lm.num_elements
         n = {"rlmass": Nn, "node_mass": Nn, "C_bu": Nn, "grad_ssh": 2 * Nn, "fcor": Nn, "VTM": 2 * Nn,
              "shape": 6 * Ne, "emass": Ne, "ecbu": Ne, "force": 6 * Ne, "volume": Ne, "expC": Ne,
-             "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn,
+             "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn, "drag_ui": Ne, "drag_ui_young": Ne,
              "means_update_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1}[name]
         out = np.empty(n)
         self._chk(self.L.nxs_dyn_debug_array(self.h, name.encode(), _abi.dptr(out), n))
