@@ -754,7 +754,9 @@ NXS_API int nxs_dyn_synchronize(nxs_dyn_handle *h);
 NXS_API int nxs_dyn_step_host(nxs_dyn_handle *h, nxs_dyn_state *s, const nxs_dyn_forcing *f);
 
 /* checkRegridding(): local minimum angle [deg] and flip test; the cross-rank reduction
- * (FE.cpp:8306, 1812) is left to the caller's communicator. */
+ * (FE.cpp:8306, 1812) is left to the caller's communicator.  The extrema are those of std::min_element / std::max_element
+ * (FE.cpp:1806, 1835-1836): a NaN angle or Jacobian of element 0 IS the result (min_angle NaN, no flip, no regrid from the angle), a NaN of any
+ * later element loses every comparison and is skipped. */
 NXS_API int nxs_dyn_check_regridding(nxs_dyn_handle *h, double *min_angle, int32_t *flip, int32_t *regrid_local);
 /* checkFieldsFast(): crash_local != 0 when a field is out of range / NaN (FE.cpp:14541-14629) -- with a wave stress attached also its NaN test (FE.cpp:14631-14643). */
 NXS_API int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local);
@@ -896,7 +898,8 @@ NXS_API int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value
 
 /* Test door: copies a named internal work array (rlmass, node_mass, C_bu, grad_ssh, fcor, VTM, shape,
  * emass, ecbu, force, volume, expC; drag_ui, drag_ui_young: the two inputs of nxs_dyn_state that nxs_dyn_fluxes updates in place) to the host so that
- * parity tests can localise a difference. */
+ * parity tests can localise a difference.  "guard_launch" [2]: the launch shape of the guards -- threads per block of k_check_fields and
+ * k_regrid_partials, blocks of k_regrid_partials (beyond blocks x threads elements its grid-stride loop takes another trip). */
 NXS_API int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_t n);
 
 /* Test door: option "trace_branches" = 1 zeroes a per-element record and makes every following step run the one-kernel-per-loop

@@ -3292,6 +3292,11 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
         out[0] = (double)v;
         return NXS_OK;
     }
+    if (!std::strcmp(name, "guard_launch")) {   // [2] the launch shape of the guards: threads per block of k_check_fields / k_regrid_partials, blocks of k_regrid_partials
+        if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array guard_launch has 2 entries");
+        out[0] = (double)BLOCK; out[1] = (double)h->n_partials;
+        return NXS_OK;
+    }
 #ifdef NXS_PHASE_TIMING
     if (!std::strcmp(name, "phase_times")) {  // [8192][8] timestamps (100 MHz) of the last fused launch, as doubles
         std::vector<long long> t(8 * 8192);

@@ -4189,7 +4189,9 @@ __global__ void __launch_bounds__(BLOCK) k_free_drift(DevMesh m, DevState s, Dev
 
 // ------------------------------------------------------------------------------------------------
 // reductions: wave (64 lanes) shuffle -> LDS across the 4 waves of a block -> one partial per block
-struct RegridPartial { double min_angle, min_jac, max_jac; };
+// e0_nan: std::min_element / max_element start from element 0, so a NaN there IS the result (every later comparison with it is false) while a NaN anywhere
+// else is skipped: bit 0 = element 0's angle is NaN, bit 1 = its jacobian is.  Only block 0 sets it; k_regrid_final applies it.
+struct RegridPartial { double min_angle, min_jac, max_jac; int e0_nan; };
 
 __device__ __forceinline__ double wave_min(double x) {
 #pragma unroll
@@ -4206,6 +4208,7 @@ __device__ __forceinline__ double wave_max(double x) {
 __global__ void __launch_bounds__(BLOCK) k_regrid_partials(DevMesh m, DevState s, RegridPartial *out) {
     __shared__ double sh[3][BLOCK / 64];
     double ang = INFINITY, jmin = INFINITY, jmax = -INFINITY;
+    int e0_nan = 0;  // (thread 0 of block 0 owns element 0, and it is the thread that writes the block's partial)
     for (int e = blockIdx.x * BLOCK + threadIdx.x; e < m.Ne; e += gridDim.x * BLOCK) {
         double vx[3], vy[3];
         load_vertices(m, s.UM, e, vx, vy);
@@ -4222,6 +4225,7 @@ __global__ void __launch_bounds__(BLOCK) k_regrid_partials(DevMesh m, DevState s
         const double jac = jacobian(vx, vy);
         jmin = (jac < jmin) ? jac : jmin;
         jmax = (jmax < jac) ? jac : jmax;
+        if (e == 0) e0_nan = (isnan(minang) ? 1 : 0) | (isnan(jac) ? 2 : 0);
     }
     ang = wave_min(ang); jmin = wave_min(jmin); jmax = wave_max(jmax);
     const int wv = threadIdx.x >> 6;
@@ -4233,7 +4237,7 @@ __global__ void __launch_bounds__(BLOCK) k_regrid_partials(DevMesh m, DevState s
             jmin = (sh[1][i] < jmin) ? sh[1][i] : jmin;
             jmax = (jmax < sh[2][i]) ? sh[2][i] : jmax;
         }
-        out[blockIdx.x] = RegridPartial{ang, jmin, jmax};
+        out[blockIdx.x] = RegridPartial{ang, jmin, jmax, e0_nan};
     }
 }
 
@@ -4245,7 +4249,12 @@ __global__ void k_regrid_final(const RegridPartial *in, int n, RegridPartial *ou
         jmax = (jmax < in[i].max_jac) ? in[i].max_jac : jmax;
     }
     ang = wave_min(ang); jmin = wave_min(jmin); jmax = wave_max(jmax);
-    if (threadIdx.x == 0) *out = RegridPartial{ang, jmin, jmax};
+    if (threadIdx.x == 0) {
+        const int e0_nan = in[0].e0_nan;
+        if (e0_nan & 1) ang = __builtin_nan("");
+        if (e0_nan & 2) jmin = jmax = __builtin_nan("");
+        *out = RegridPartial{ang, jmin, jmax, e0_nan};
+    }
 }
 
 // K12 checkFieldsFast (FE.cpp:14536-14655) restricted to this path's fields
