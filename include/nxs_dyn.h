@@ -76,7 +76,9 @@ typedef struct nxs_dyn_params {
     int32_t dynamics_type;                  /* NXS_DYN_* */
     int32_t basal_stress_type;              /* NXS_BASAL_* */
     int32_t ice_cat_type;                   /* NXS_ICECAT_* (thermo.newice_type==4 -> YOUNG_ICE, FE.cpp:1206-1209) */
-    int32_t newice_type;                    /* thermo.newice_type (FE.cpp:3943) */
+    int32_t newice_type;                    /* thermo.newice_type (FE.cpp:3943).  The reference ties 4 to YOUNG_ICE (FE.cpp:1212-1215); with the classic category
+                                             * update() still bounds conc_myi by conc + conc_young as FE.cpp:4126-4128 is written: the array as put_state left it, so
+                                             * with use_young_ice_in_myi_reset the caller of a classic build has to put meaningful values into conc_young */
     int32_t equal_ridging;                  /* age.equal_ridging (FE.cpp:3942) */
     int32_t use_young_ice_in_myi_reset;     /* age.include_young_ice (FE.cpp:3944) */
     int32_t reserved0;
@@ -899,7 +901,9 @@ NXS_API int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value
 /* Test door: copies a named internal work array (rlmass, node_mass, C_bu, grad_ssh, fcor, VTM, shape,
  * emass, ecbu, force, volume, expC; drag_ui, drag_ui_young: the two inputs of nxs_dyn_state that nxs_dyn_fluxes updates in place) to the host so that
  * parity tests can localise a difference.  "guard_launch" [2]: the launch shape of the guards -- threads per block of k_check_fields and
- * k_regrid_partials, blocks of k_regrid_partials (beyond blocks x threads elements its grid-stride loop takes another trip). */
+ * k_regrid_partials, blocks of k_regrid_partials (beyond blocks x threads elements its grid-stride loop takes another trip).  "update_launch" [3]: the
+ * instantiation of k_update the last update() launched -- REC (M_sigma was in the sub-step loop's records), FSD (the bins were attached) -- and its threads per
+ * block; NXS_ERR_STATE before the first update(). */
 NXS_API int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_t n);
 
 /* Test door: option "trace_branches" = 1 zeroes a per-element record and makes every following step run the one-kernel-per-loop

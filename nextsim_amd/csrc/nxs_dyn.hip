@@ -262,6 +262,7 @@ struct nxs_dyn_handle {
     nxs_drifters::State *drift = nullptr;          // made by the first nxs_dyn_drifters_set
     int sig_loc = 0;                       // where M_sigma / M_damage are current: 0 = the state arrays, 1 = the records in S4a (left there by
                                            // the fused sub-step loop; k_update works on them, the arrays follow on demand: ensure_arrays)
+    int update_launch[3] = {-1, -1, 0};    // the last launch of k_update: REC, FSD, threads per block (nxs_dyn_debug_array "update_launch"; -1 = none yet)
     int trace_branches = 0;                // option "trace_branches": the per-loop kernels keep the branch trace of updateSigmaDamage (dw.trace)
     int shape_mem = -1;                    // option "shape_mem": the several-sub-steps kernel reads M_shape_coeff from per-step records (1, and -1 = automatic)
                                            // or rebuilds it from the staged coordinates like the one-sub-step kernel (0)
@@ -1371,6 +1372,7 @@ int run_substeps(nxs_dyn_handle *h) {
 
 // update(), FE.cpp:3919-4132 (with the floe-size bins attached: the build that scales them too)
 void launch_update(nxs_dyn_handle *h) {
+    h->update_launch[0] = h->sig_loc ? 1 : 0; h->update_launch[1] = h->dw.conc_fsd ? 1 : 0; h->update_launch[2] = BLOCK;
     if (h->dw.conc_fsd) {
         if (h->sig_loc) LAUNCH(h, (k_update<true, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
         else LAUNCH(h, (k_update<false, true>), h->dm.Ne, h->dm, h->ds, h->dw, h->dp);
@@ -3295,6 +3297,12 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
     if (!std::strcmp(name, "guard_launch")) {   // [2] the launch shape of the guards: threads per block of k_check_fields / k_regrid_partials, blocks of k_regrid_partials
         if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array guard_launch has 2 entries");
         out[0] = (double)BLOCK; out[1] = (double)h->n_partials;
+        return NXS_OK;
+    }
+    if (!std::strcmp(name, "update_launch")) {   // [3] the instantiation of k_update the last update() launched: REC (M_sigma in the records), FSD (bins attached), threads per block
+        if (n != 3) return fail(h, NXS_ERR_INVALID, "debug_array update_launch has 3 entries");
+        if (h->update_launch[0] < 0) return fail(h, NXS_ERR_STATE, "debug_array update_launch: no update() yet");
+        for (int k = 0; k < 3; ++k) out[k] = (double)h->update_launch[k];
         return NXS_OK;
     }
 #ifdef NXS_PHASE_TIMING

@@ -4152,8 +4152,8 @@ __global__ void __launch_bounds__(BLOCK) k_update(DevMesh m, DevState s, DevWork
     tmyi = ((tmyi > 0.) ? tmyi : 0.);
     snow = ((snow > 0.) ? snow : 0.);
     D_del = -cmyi;
-    if (p.newice_type == 4 && p.use_young_myi)
-        cmyi = STD_MAX(0., STD_MIN(cmyi, conc + cy));
+    if (p.newice_type == 4 && p.use_young_myi)   // FE.cpp:4126-4128 reads M_conc_young whatever the category: the classic one leaves the array as it came
+        cmyi = STD_MAX(0., STD_MIN(cmyi, conc + (p.young_cat ? cy : s.cyoung[e])));
     else
         cmyi = STD_MAX(0., STD_MIN(cmyi, conc));
     D_del += cmyi;
