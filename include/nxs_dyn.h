@@ -28,6 +28,7 @@
  *   interpFields() + assignVariables()          nxs_dyn_regrid          (FE.cpp:3071-3154, 2120-2151, 2196-2258, 3161-3297, 553-572)
  *   #ifdef OASIS: initFsd / updateFSD / redistributeFSD / weldingRoach   nxs_fsd_bins, nxs_dyn_fsd_* (FE.cpp:7408-7576, 4674-4732, 4268-4483, 4737-4870, 5888-5896)
  *   thermo(): OWBulkFluxes + IABulkFluxes       nxs_dyn_fluxes, nxs_dyn_flux_* (FE.cpp:5214-5277, 5032-5159, 6148-6353, 4966-5019, 6359-6389, 6454-6535)
+ *   thermo(): thermoWinton / thermoIce0 columns nxs_dyn_column, nxs_dyn_column_* (FE.cpp:5306-5411, 6396-6448, 6633-6962)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -745,6 +746,80 @@ NXS_API int nxs_dyn_flux_put(nxs_dyn_handle *h, const nxs_dyn_flux_state *s);
 NXS_API int nxs_dyn_flux_get(nxs_dyn_handle *h, nxs_dyn_flux_state *s);
 NXS_API int nxs_dyn_fluxes(nxs_dyn_handle *h);
 NXS_API int nxs_dyn_fluxes_get(nxs_dyn_handle *h, const nxs_dyn_flux_rows *out /* may be NULL */, const double **device_rows /* [NXS_FLUX_ROWS], may be NULL */);
+
+/* ---- The ice columns of thermo()'s slab loop on the device: its sections 3.2 to 5 (FE.cpp:5306-5411) -- the snowfall rule (FE.cpp:5321-5332), the ocean nudging
+ * flux (FE.cpp:5343-5366), iceOceanHeatflux (FE.cpp:6396-6428, BASIC and EXCHANGE), freezingPoint (FE.cpp:6432-6448, LINEAR and UNESCO), thermoWinton
+ * (FE.cpp:6633-6853) or thermoIce0 (FE.cpp:6860-6962) for the old ice and, in the young-ice category, thermoIce0 for the young ice with the stores
+ * M_h_young = hi_young*old_conc_young, M_hs_young = hs_young*old_conc_young (FE.cpp:5409-5410).  One launch, a thread per element, ghost elements included.  It
+ * reads the rows of nxs_dyn_fluxes (Qia, dQiadT, I, subl and their _young twins), M_conc, M_thick, M_snow_thick, M_conc_young, M_h_young, M_hs_young (resident),
+ * M_tice[0], M_tsurf_young, M_sst, M_sss (the device copies of nxs_dyn_flux_state: ONE copy that both launches use), M_tair (nxs_dyn_flux_set_atmosphere), and under
+ * EXCHANGE M_VT and M_ocean at the element's three nodes.  It writes NXS_COL_ROWS rows for sections 6 to 10 and, IN PLACE, M_tice[0] (under WINTON also M_tice[1],
+ * M_tice[2]) and in the young-ice category M_tsurf_young, M_h_young, M_hs_young -- the last two are rows of nxs_dyn_state, so the next nxs_dyn_step reads them.
+ * OUT OF SCOPE: thermo() from FE.cpp:5413 on (the assimilation flux, new ice, lateral melt, redistributeThermoFSD, meltPonds, the slab ocean, healing, diagnostics,
+ * tracers), OceanType::COUPLED (#ifdef OASIS), Winton's LOG(WARNING) and assert.
+ *   nxs_col_default_config    model/options.cpp:112, 291-293, 383-420; snowfall from precip*snowfr, the constant mixed layer depth
+ *   nxs_col_config_check      what nxs_dyn_column_configure refuses, without a handle: an unknown enum value, snow_cond, constant_mld, nudge_timeT or nudge_timeS
+ *                  <= 0 (or NaN), the coupled ocean; NXS_ERR_INVALID, the text in nxs_dyn_last_error(NULL)
+ *   nxs_col_constants         TEST DOOR like nxs_flux_constants: the physical:: constants compiled into the kernel, in the order NXS_COL_CONST_* names them
+ *   nxs_dyn_column_configure  the configuration is the handle's and survives nxs_dyn_set_mesh
+ *   nxs_dyn_column_set_forcing   [Ne] host rows; a NULL row means "the device copy is current" (a row never given stays missing).  Which rows the launch NEEDS
+ *                  follows from the configuration: precip unless snowfall_source is SNOWFALL, snow unless it is PRECIP_TAIR, ocean_temp and ocean_salt under a
+ *                  nudged ocean, mld under NXS_COL_MLD_ROW
+ *   nxs_dyn_column_put / nxs_dyn_column_get_state   the rows of M_tice the fluxes do not carry (tice1, tice2); NULL members as in nxs_dyn_flux_put / _get
+ *   nxs_dyn_column            the launch, asynchronous on the handle's stream; dt is thermo()'s integer argument (ddt = double(dt); BASIC divides by it as
+ *                  FE.cpp:6410 does).  NXS_ERR_INVALID: dt <= 0.  NXS_ERR_STATE: before nxs_dyn_column_configure, before the first nxs_dyn_fluxes since the last
+ *                  nxs_dyn_set_mesh / nxs_dyn_regrid, while a needed row is missing (again the state after set_mesh and after regrid), under WINTON without
+ *                  tice1 / tice2
+ *   nxs_dyn_column_get        exactly like nxs_dyn_fluxes_get.  In the classic category the nine _young rows are zero.  NXS_ERR_STATE before the first nxs_dyn_column */
+enum { NXS_COL_THERMO_ZERO_LAYER = 0, NXS_COL_THERMO_WINTON = 1 };                 /* setup::ThermoType */
+enum { NXS_COL_QIO_BASIC = 0, NXS_COL_QIO_EXCHANGE = 1 };                          /* setup::OceanHeatfluxScheme */
+enum { NXS_COL_FREEZINGPOINT_LINEAR = 0, NXS_COL_FREEZINGPOINT_UNESCO = 1 };       /* setup::FreezingPointType */
+enum { NXS_COL_OCEAN_CONSTANT = 0, NXS_COL_OCEAN_NUDGED = 1, NXS_COL_OCEAN_COUPLED = 7 };   /* setup::OceanType: CONSTANT, any nudged dataset (TOPAZ4R = 1 ...), COUPLED (refused) */
+enum { NXS_COL_SNOWFALL_PRECIP_SNOWFR = 0 /* M_precip*M_snowfr */, NXS_COL_SNOWFALL_SNOWFALL = 1 /* M_snowfall */, NXS_COL_SNOWFALL_PRECIP_TAIR = 2 /* M_precip where M_tair < 0 */ };
+enum { NXS_COL_MLD_CONSTANT = 0 /* ideal_simul.constant_mld */, NXS_COL_MLD_ROW = 1 /* M_mld */ };
+enum { NXS_COL_CONST_RHOW = 0, NXS_COL_CONST_CPW, NXS_COL_CONST_RHOI, NXS_COL_CONST_RHOS, NXS_COL_CONST_LF, NXS_COL_CONST_C, NXS_COL_CONST_KI, NXS_COL_CONST_SI,
+       NXS_COL_CONST_HMIN, NXS_COL_CONST_COUNT };
+typedef struct nxs_dyn_column_config {
+    int32_t thermo_type;               /* NXS_COL_THERMO_*: setup.thermo-type */
+    int32_t qio_type;                  /* NXS_COL_QIO_*: thermo.Qio-type */
+    int32_t freezingpoint_type;        /* NXS_COL_FREEZINGPOINT_*: thermo.freezingpoint-type */
+    int32_t ocean_type;                /* NXS_COL_OCEAN_*: setup.ocean-type */
+    int32_t snowfall_source;           /* NXS_COL_SNOWFALL_*: which of M_snowfr, M_snowfall the dataset initialised (FE.cpp:5323-5329) */
+    int32_t mld_source;                /* NXS_COL_MLD_* (FE.cpp:5335) */
+    int32_t flooding;                  /* thermo.flooding */
+    int32_t reserved;
+    double freezingpoint_mu;           /* thermo.freezingpoint_mu */
+    double snow_cond;                  /* thermo.snow_cond (M_ks) */
+    double Csens_io;                   /* thermo.Csens_io */
+    double constant_mld;               /* ideal_simul.constant_mld [m] */
+    double nudge_timeT, nudge_timeS;   /* days_in_sec * thermo.ocean_nudge_timeT_days, _timeS_days [s] */
+    double Qdw_const, Fdw_const;       /* ideal_simul.constant_Qdw, constant_Fdw */
+} nxs_dyn_column_config;
+typedef struct nxs_dyn_column_forcing {
+    const double *precip;               /* [Ne] M_precip */
+    const double *snow;                 /* [Ne] M_snowfr or M_snowfall, as snowfall_source says */
+    const double *ocean_temp, *ocean_salt; /* [Ne] M_ocean_temp, M_ocean_salt */
+    const double *mld;                  /* [Ne] M_mld */
+} nxs_dyn_column_forcing;
+typedef struct nxs_dyn_column_state {
+    double *tice1, *tice2;              /* [Ne] M_tice[1], M_tice[2] (WINTON) */
+} nxs_dyn_column_state;
+enum { NXS_COL_SNOWFALL = 0, NXS_COL_QDW, NXS_COL_FDW, NXS_COL_TFRW,
+       NXS_COL_QIO, NXS_COL_HI, NXS_COL_HS, NXS_COL_HI_OLD, NXS_COL_DEL_HI, NXS_COL_DEL_HS_MLT, NXS_COL_MLT_HI_TOP, NXS_COL_MLT_HI_BOT, NXS_COL_DEL_HI_S2I,
+       NXS_COL_QIO_YOUNG, NXS_COL_HI_YOUNG, NXS_COL_HS_YOUNG, NXS_COL_HI_YOUNG_OLD, NXS_COL_DEL_HI_YOUNG, NXS_COL_DEL_HS_YOUNG_MLT, NXS_COL_MLT_HI_TOP_YOUNG,
+       NXS_COL_MLT_HI_BOT_YOUNG, NXS_COL_DEL_HI_S2I_YOUNG };
+#define NXS_COL_ROWS 22
+typedef struct nxs_dyn_column_rows { double *row[NXS_COL_ROWS]; } nxs_dyn_column_rows;   /* [Ne] each, indexed by NXS_COL_* */
+
+NXS_API int nxs_col_default_config(nxs_dyn_column_config *c);
+NXS_API int nxs_col_config_check(const nxs_dyn_column_config *c);
+NXS_API int nxs_col_constants(double *out, int32_t count);
+NXS_API int nxs_dyn_column_configure(nxs_dyn_handle *h, const nxs_dyn_column_config *c);
+NXS_API int nxs_dyn_column_set_forcing(nxs_dyn_handle *h, const nxs_dyn_column_forcing *f);
+NXS_API int nxs_dyn_column_put(nxs_dyn_handle *h, const nxs_dyn_column_state *s);
+NXS_API int nxs_dyn_column_get_state(nxs_dyn_handle *h, nxs_dyn_column_state *s);
+NXS_API int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt);
+NXS_API int nxs_dyn_column_get(nxs_dyn_handle *h, const nxs_dyn_column_rows *out /* may be NULL */, const double **device_rows /* [NXS_COL_ROWS], may be NULL */);
 
 /* One dynamics step on the device-resident state: FE.cpp:8197-8214.  Asynchronous on the
  * handle's stream; nxs_dyn_synchronize() waits for it. */

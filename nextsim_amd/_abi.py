@@ -239,6 +239,56 @@ def flux_config_struct(base: "FluxConfig", **options) -> FluxConfig:
     return c
 
 
+# ---- thermo()'s ice columns (include/nxs_dyn.h, nxs_col_* / nxs_dyn_column_* / nxs_dyn_column)
+COL_THERMO = {"zero_layer": 0, "winton": 1}                 # NXS_COL_THERMO_*: setup::ThermoType
+COL_QIO = {"basic": 0, "exchange": 1}                       # NXS_COL_QIO_*: setup::OceanHeatfluxScheme
+COL_FREEZINGPOINT = {"linear": 0, "unesco": 1}              # NXS_COL_FREEZINGPOINT_*: setup::FreezingPointType
+COL_OCEAN = {"constant": 0, "nudged": 1, "coupled": 7}      # NXS_COL_OCEAN_*: setup::OceanType (coupled is refused)
+COL_SNOWFALL = {"precip_snowfr": 0, "snowfall": 1, "precip_tair": 2}   # NXS_COL_SNOWFALL_*
+COL_MLD = {"constant": 0, "row": 1}                         # NXS_COL_MLD_*
+COL_ENUMS = {"thermo_type": COL_THERMO, "qio_type": COL_QIO, "freezingpoint_type": COL_FREEZINGPOINT, "ocean_type": COL_OCEAN, "snowfall_source": COL_SNOWFALL,
+             "mld_source": COL_MLD}
+COL_CONSTANTS = ("rhow", "cpw", "rhoi", "rhos", "Lf", "C", "ki", "si", "hmin")   # NXS_COL_CONST_*
+COL_CONFIG_INTS = ("thermo_type", "qio_type", "freezingpoint_type", "ocean_type", "snowfall_source", "mld_source", "flooding", "reserved")
+COL_CONFIG_REALS = ("freezingpoint_mu", "snow_cond", "Csens_io", "constant_mld", "nudge_timeT", "nudge_timeS", "Qdw_const", "Fdw_const")
+COL_FORCING = ("precip", "snow", "ocean_temp", "ocean_salt", "mld")
+COL_STATE = ("tice1", "tice2")
+COL_ICE_ROWS = ("Qio", "hi", "hs", "hi_old", "del_hi", "del_hs_mlt", "mlt_hi_top", "mlt_hi_bot", "del_hi_s2i")
+COL_YOUNG_ROWS = ("Qio_young", "hi_young", "hs_young", "hi_young_old", "del_hi_young", "del_hs_young_mlt", "mlt_hi_top_young", "mlt_hi_bot_young", "del_hi_s2i_young")
+COL_ROWS = ("snowfall", "Qdw", "Fdw", "tfrw") + COL_ICE_ROWS + COL_YOUNG_ROWS   # NXS_COL_*
+NXS_COL_ROWS = 22
+assert len(COL_ROWS) == NXS_COL_ROWS
+
+
+class ColumnConfig(C.Structure):   # nxs_dyn_column_config
+    _fields_ = [(k, C.c_int32) for k in COL_CONFIG_INTS] + [(k, C.c_double) for k in COL_CONFIG_REALS]
+
+
+class ColumnForcing(C.Structure):   # nxs_dyn_column_forcing
+    _fields_ = [(k, c_double_p) for k in COL_FORCING]
+
+
+class ColumnState(C.Structure):   # nxs_dyn_column_state
+    _fields_ = [(k, c_double_p) for k in COL_STATE]
+
+
+class ColumnRows(C.Structure):   # nxs_dyn_column_rows
+    _fields_ = [("row", c_double_p * NXS_COL_ROWS)]
+
+
+def column_config_struct(base: "ColumnConfig", **options) -> ColumnConfig:
+    """A copy of `base` (the defaults of nxs_col_default_config) with keyword options named after nxs_dyn_column_config's members; the enums also by name."""
+    c = ColumnConfig()
+    C.memmove(C.byref(c), C.byref(base), C.sizeof(c))
+    for k, v in options.items():
+        if k in COL_ENUMS and isinstance(v, str):
+            v = COL_ENUMS[k][v]
+        if k not in COL_CONFIG_INTS + COL_CONFIG_REALS or k == "reserved":
+            raise KeyError(f"nxs_dyn_column_config has no member {k!r}")
+        setattr(c, k, int(v) if k in COL_CONFIG_INTS else float(v))
+    return c
+
+
 # nxs_dyn_regrid (include/nxs_dyn.h): ModelVariable::interpTransformation and the flags of nxs_dyn_regrid_var
 NXS_TRANSFORM_NONE, NXS_TRANSFORM_CONC, NXS_TRANSFORM_THICK, NXS_TRANSFORM_ENTHALPY = range(4)
 TRANSFORMATIONS = {"none": NXS_TRANSFORM_NONE, "conc": NXS_TRANSFORM_CONC, "thick": NXS_TRANSFORM_THICK, "enthalpy": NXS_TRANSFORM_ENTHALPY}

@@ -17,6 +17,7 @@
 //   k_free_drift      FE.cpp:10140-10176
 //   k_regrid_*/k_check_* FE.cpp:8298-8309, 14536-14655 reductions
 //   k_fluxes                                  FE.cpp:5214-5277: thermo()'s atmospheric bulk fluxes, OWBulkFluxes + IABulkFluxes (nxs_flux_kernels.inl, nxs_dyn_fluxes)
+//   k_column                                  FE.cpp:5306-5411: thermo()'s ice columns, thermoWinton / thermoIce0 with the nudging and ice-ocean fluxes (nxs_column_kernels.inl, nxs_dyn_column)
 //   k_fsd_init / _update / _breakup / _weld   FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870 + 5888-5896: the floe-size distribution (nxs_fsd_kernels.inl, nxs_dyn_fsd_*)
 //   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
 //
@@ -50,6 +51,7 @@
 #include "nxs_dyn_kernels.inl"
 #include "nxs_fsd_kernels.inl"
 #include "nxs_flux_kernels.inl"
+#include "nxs_column_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -227,6 +229,13 @@ struct nxs_dyn_handle {
     double *d_flux_st[FLUX_ST_ROWS] = {};          // tice0, tsurf_young, sst, sss, drag_ti, drag_ti_young, pond_fraction, lid_volume
     unsigned flux_atm_have = 0, flux_st_have = 0;  // bit k: row k was given on this mesh
     double *d_flux_out = nullptr;                  // [FLUX_ROWS][Ne] what nxs_dyn_fluxes_get returns (D_tau_ow: d_tau_ow below)
+    // thermo()'s ice columns (nxs_dyn_column_* / nxs_dyn_column): as above -- the configuration survives set_mesh, the rows are in the state pool and go with the mesh
+    nxs_dyn_column_config col_cfg{};
+    bool col_configured = false, col_done = false;
+    double *d_col_forcing[COL_FORCING_ROWS] = {};  // precip, snow, ocean_temp, ocean_salt, mld
+    double *d_col_st[COL_ST_ROWS] = {};            // tice1, tice2 (tice0, tsurf_young, sst, sss: d_flux_st)
+    unsigned col_forcing_have = 0, col_st_have = 0;
+    double *d_col_out = nullptr;                   // [COL_ROWS][Ne] what nxs_dyn_column_get returns
     // v4: the whole sub-step loop in one resident launch (option "fused" = 4; see k_substep_resident)
     DevResident res{};
     std::vector<void *> res_allocs;  // its tables, exchange buffer and ghost ring (a pool of their own: rebuilt whenever an option of the loop changes)
@@ -2077,6 +2086,9 @@ static int set_mesh_impl(nxs_dyn_handle *h, const nxs_dyn_mesh *m, RegridAdopt *
     for (auto &q : h->d_flux_atm) q = nullptr;
     for (auto &q : h->d_flux_st) q = nullptr;
     h->d_flux_out = nullptr; h->flux_atm_have = h->flux_st_have = 0; h->flux_done = false;   // (the same pool)
+    for (auto &q : h->d_col_forcing) q = nullptr;
+    for (auto &q : h->d_col_st) q = nullptr;
+    h->d_col_out = nullptr; h->col_forcing_have = h->col_st_have = 0; h->col_done = false;
     auto &P = h->state_allocs;
     const size_t n2 = 2 * (size_t)Nn, ne = Ne;
 #define A(ptr, cnt) if ((rc = dev_alloc(h, P, &(ptr), (cnt)))) return rc
@@ -3596,5 +3608,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 
 #include "nxs_fsd.inl"
 #include "nxs_flux.inl"
+#include "nxs_column.inl"
 
 }  // extern "C"

@@ -93,6 +93,15 @@ def load_library():
     L.nxs_dyn_flux_get.argtypes = [H, P(_abi.FluxState)]
     L.nxs_dyn_fluxes.argtypes = [H]
     L.nxs_dyn_fluxes_get.argtypes = [H, P(_abi.FluxRows), P(C.c_void_p)]
+    L.nxs_col_default_config.argtypes = [P(_abi.ColumnConfig)]
+    L.nxs_col_config_check.argtypes = [P(_abi.ColumnConfig)]
+    L.nxs_col_constants.argtypes = [P(C.c_double), C.c_int32]
+    L.nxs_dyn_column_configure.argtypes = [H, P(_abi.ColumnConfig)]
+    L.nxs_dyn_column_set_forcing.argtypes = [H, P(_abi.ColumnForcing)]
+    L.nxs_dyn_column_put.argtypes = [H, P(_abi.ColumnState)]
+    L.nxs_dyn_column_get_state.argtypes = [H, P(_abi.ColumnState)]
+    L.nxs_dyn_column.argtypes = [H, C.c_int32]
+    L.nxs_dyn_column_get.argtypes = [H, P(_abi.ColumnRows), P(C.c_void_p)]
     L.nxs_dyn_ice_diagnostics.argtypes = [H, P(_abi.IceDiag), P(C.c_void_p)]
     L.nxs_dyn_means_configure.argtypes = [H, P(_abi.MeansConfig)]
     L.nxs_dyn_means_set_tau_ow.argtypes = [H, _abi.c_double_p]
@@ -157,6 +166,8 @@ EXPORTS = (
     "nxs_dyn_fsd_weld",
     "nxs_flux_default_config", "nxs_flux_config_check", "nxs_flux_constants", "nxs_dyn_flux_configure", "nxs_dyn_flux_set_atmosphere", "nxs_dyn_flux_put", "nxs_dyn_flux_get",
     "nxs_dyn_fluxes", "nxs_dyn_fluxes_get",
+    "nxs_col_default_config", "nxs_col_config_check", "nxs_col_constants", "nxs_dyn_column_configure", "nxs_dyn_column_set_forcing", "nxs_dyn_column_put",
+    "nxs_dyn_column_get_state", "nxs_dyn_column", "nxs_dyn_column_get",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
     "nxs_dyn_drifters_get", "nxs_dyn_regrid",
@@ -299,6 +310,38 @@ def flux_config_check(**options) -> int:
     """What flux_configure would answer for the defaults changed by `options` (nxs_flux_config_check, host only): 0 or NXS_ERR_INVALID."""
     c = _flux_config(options)
     return load_library().nxs_flux_config_check(C.byref(c))
+
+
+def column_default_config() -> dict:
+    """The defaults of model/options.cpp:112, 291-293, 383-420 the ice columns read (nxs_col_default_config, host only), keyed like nxs_dyn_column_config."""
+    L = load_library()
+    c = _abi.ColumnConfig()
+    rc = L.nxs_col_default_config(C.byref(c))
+    if rc != 0:
+        raise NxsError(rc, "nxs_col_default_config")
+    return {k: getattr(c, k) for k, _ in _abi.ColumnConfig._fields_ if k != "reserved"}
+
+
+def _column_config(options: dict) -> "_abi.ColumnConfig":
+    L = load_library()
+    base = _abi.ColumnConfig()
+    L.nxs_col_default_config(C.byref(base))
+    return _abi.column_config_struct(base, **options)
+
+
+def column_config_check(**options) -> int:
+    """What column_configure would answer for the defaults changed by `options` (nxs_col_config_check, host only): 0 or NXS_ERR_INVALID."""
+    c = _column_config(options)
+    return load_library().nxs_col_config_check(C.byref(c))
+
+
+def column_constants() -> dict:
+    """The physical:: constants compiled into the column kernel (nxs_col_constants, host only)."""
+    out = (C.c_double * len(_abi.COL_CONSTANTS))()
+    rc = load_library().nxs_col_constants(out, len(_abi.COL_CONSTANTS))
+    if rc != 0:
+        raise NxsError(rc, "nxs_col_constants")
+    return dict(zip(_abi.COL_CONSTANTS, out))
 
 
 def flux_constants() -> dict:
@@ -791,6 +834,50 @@ class FiniteElementDynamics:
         self._chk(self.L.nxs_dyn_fluxes_get(self.h, C.byref(r), dev if want_device else None))
         if want_device:
             return out, dict(zip(_abi.FLUX_ROWS, (int(p or 0) for p in dev)))
+        return out
+
+    # ---- thermo()'s ice columns: sections 3.2 to 5 of the slab loop, thermoWinton / thermoIce0 (FE.cpp:5306-5411) ----
+    def column_configure(self, **options):
+        """nxs_dyn_column_configure: the defaults of column_default_config() changed by keywords named after nxs_dyn_column_config's members.  Survives set_mesh."""
+        c = _column_config(options)
+        self._chk(self.L.nxs_dyn_column_configure(self.h, C.byref(c)))
+
+    def column_set_forcing(self, **rows):
+        """precip, snow (snowfr or snowfall, as configured), ocean_temp, ocean_salt, mld: [Ne] each; a row left out or None keeps the device copy."""
+        f = _abi.ColumnForcing()
+        keep = self._element_rows(f, _abi.COL_FORCING, rows, "nxs_dyn_column_forcing")
+        self._chk(self.L.nxs_dyn_column_set_forcing(self.h, C.byref(f)))
+        del keep
+
+    def column_put(self, **rows):
+        """tice1, tice2: [Ne] each (tice0, tsurf_young, sst and sss are flux_put's); a row left out or None keeps the device copy."""
+        s = _abi.ColumnState()
+        keep = self._element_rows(s, _abi.COL_STATE, rows, "nxs_dyn_column_state")
+        self._chk(self.L.nxs_dyn_column_put(self.h, C.byref(s)))
+        del keep
+
+    def column_get(self, names=_abi.COL_STATE) -> dict:
+        """The named rows of nxs_dyn_column_state from the device (nxs_dyn_column_get_state; both by default)."""
+        out = {k: np.empty(self.lm.num_elements) for k in names}
+        s = _abi.ColumnState()
+        self._element_rows(s, _abi.COL_STATE, out, "nxs_dyn_column_state")
+        self._chk(self.L.nxs_dyn_column_get_state(self.h, C.byref(s)))
+        return out
+
+    def column(self, dt: int):
+        """nxs_dyn_column: one launch; dt is thermo()'s integer argument.  M_tice, M_tsurf_young, M_h_young and M_hs_young are updated on the device.  Asynchronous."""
+        self._chk(self.L.nxs_dyn_column(self.h, int(dt)))
+
+    def column_rows(self, names=_abi.COL_ROWS, want_device: bool = False):
+        """The named rows of _abi.COL_ROWS as host arrays (nxs_dyn_column_get); with want_device also {name: device pointer} of all 22 rows."""
+        out = {k: np.empty(self.lm.num_elements) for k in names}
+        r = _abi.ColumnRows()
+        for k, v in out.items():
+            r.row[_abi.COL_ROWS.index(k)] = _abi.dptr(v)
+        dev = (C.c_void_p * _abi.NXS_COL_ROWS)()
+        self._chk(self.L.nxs_dyn_column_get(self.h, C.byref(r), dev if want_device else None))
+        if want_device:
+            return out, dict(zip(_abi.COL_ROWS, (int(p or 0) for p in dev)))
         return out
 
     def get_state(self) -> dict:
