@@ -66,14 +66,14 @@ int nxs_dyn_column_set_forcing(nxs_dyn_handle *h, const nxs_dyn_column_forcing *
     if (!h || !f) return NXS_ERR_INVALID;
     if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "column_set_forcing before set_mesh");
     const double *src[COL_FORCING_ROWS] = {f->precip, f->snow, f->ocean_temp, f->ocean_salt, f->mld};
-    return flux_upload(h, h->d_col_forcing, src, COL_FORCING_ROWS, &h->col_forcing_have);
+    return upload_rows(h, h->d_col_forcing, src, COL_FORCING_ROWS, &h->col_forcing_have);
 } catch (...) { return dyn_caught(h, "nxs_dyn_column_set_forcing"); }
 
 int nxs_dyn_column_put(nxs_dyn_handle *h, const nxs_dyn_column_state *s) try {
     if (!h || !s) return NXS_ERR_INVALID;
     if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "column_put before set_mesh");
     const double *src[COL_ST_ROWS] = {s->tice1, s->tice2};
-    return flux_upload(h, h->d_col_st, src, COL_ST_ROWS, &h->col_st_have);
+    return upload_rows(h, h->d_col_st, src, COL_ST_ROWS, &h->col_st_have);
 } catch (...) { return dyn_caught(h, "nxs_dyn_column_put"); }
 
 int nxs_dyn_column_get_state(nxs_dyn_handle *h, nxs_dyn_column_state *s) try {
@@ -84,11 +84,7 @@ int nxs_dyn_column_get_state(nxs_dyn_handle *h, nxs_dyn_column_state *s) try {
     for (int k = 0; k < COL_ST_ROWS; ++k)
         if (dst[k] && !(h->col_st_have & (1u << k))) return fail(h, NXS_ERR_STATE, "column_get_state: %s was never put on this mesh", name[k]);
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t bytes = (size_t)h->dm.Ne * sizeof(double);
-    for (int k = 0; k < COL_ST_ROWS; ++k)
-        if (dst[k]) { pin_host_buffer(h, dst[k], bytes); HIPCHK(h, hipMemcpyAsync(dst[k], h->d_col_st[k], bytes, hipMemcpyDeviceToHost, h->stream)); }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NXS_OK;
+    return download_rows(h, dst, h->d_col_st, COL_ST_ROWS);
 } catch (...) { return dyn_caught(h, "nxs_dyn_column_get_state"); }
 
 int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt) try {   // thermo()'s slab loop, sections 3.2 to 5, FE.cpp:5306-5411
@@ -109,7 +105,7 @@ int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt) try {   // thermo()'s slab loo
     if (g.thermo_type == NXS_COL_THERMO_WINTON && h->col_st_have != (1u << COL_ST_ROWS) - 1)
         return fail(h, NXS_ERR_STATE, "column: WINTON needs tice1 and tice2 on this mesh (nxs_dyn_column_put; mask of the rows present 0x%x)", h->col_st_have);
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    if (int rc = launch_gave_up(h)) return rc;
     const size_t Ne = h->dm.Ne;
     if (!h->d_col_out) { if (int rc = dev_alloc(h, h->state_allocs, &h->d_col_out, (size_t)COL_ROWS * Ne)) return rc; }
     ColDev c{};
@@ -133,12 +129,8 @@ int nxs_dyn_column_get(nxs_dyn_handle *h, const nxs_dyn_column_rows *out, const 
     if (!h) return NXS_ERR_INVALID;
     if (!h->have_mesh || !h->col_done) return fail(h, NXS_ERR_STATE, "column_get before nxs_dyn_column on this mesh");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t Ne = h->dm.Ne, bytes = Ne * sizeof(double);
-    for (int k = 0; k < COL_ROWS; ++k) {
-        const double *row = h->d_col_out + (size_t)k * Ne;
-        if (device_rows) device_rows[k] = row;
-        if (out && out->row[k]) { pin_host_buffer(h, out->row[k], bytes); HIPCHK(h, hipMemcpyAsync(out->row[k], row, bytes, hipMemcpyDeviceToHost, h->stream)); }
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NXS_OK;
+    const double *row[COL_ROWS];
+    for (int k = 0; k < COL_ROWS; ++k) row[k] = h->d_col_out + (size_t)k * h->dm.Ne;
+    if (device_rows) std::copy(row, row + COL_ROWS, device_rows);
+    return download_rows(h, out ? out->row : nullptr, row, COL_ROWS);
 } catch (...) { return dyn_caught(h, "nxs_dyn_column_get"); }

@@ -101,7 +101,109 @@ struct StepPlan {
     int launches = 0;               // kernel launches of the sub-step loop (nxs_dyn_timing::substep_launches)
 };
 
-struct nxs_dyn_handle {
+// ---- What goes with the mesh: one struct per pool of device memory, holding the pool, every pointer into it and every fact that vouches for its contents, all with
+// default member initialisers.  The handle inherits them (their members are the handle's), and each has ONE owner below the handle -- release_<group>(), the model is
+// release_resident() -- that lets go of the pool and assigns the group a fresh value: a member added to a group is reset wherever its pool goes, at set_mesh and at
+// destroy, without anyone editing those.  release_mesh() calls the owners.  Nothing else frees a handle's pool or nulls a pointer into one.
+struct MeshArrays {        // the mesh and its tables (set_mesh)
+    std::vector<void *> mesh_allocs;
+    DevMesh dm{};
+    bool have_mesh = false;
+};
+struct FluxRows {          // thermo()'s atmospheric bulk fluxes: rows in the state pool -- after set_mesh / regrid every row is MISSING until it is given again
+    double *d_flux_atm[FLUX_ATM_ROWS] = {};        // tair, mslp, Qsw_in, humidity, longwave
+    double *d_flux_st[FLUX_ST_ROWS] = {};          // tice0, tsurf_young, sst, sss, drag_ti, drag_ti_young, pond_fraction, lid_volume
+    unsigned flux_atm_have = 0, flux_st_have = 0;  // bit k: row k was given on this mesh
+    double *d_flux_out = nullptr;                  // [FLUX_ROWS][Ne] what nxs_dyn_fluxes_get returns (D_tau_ow: StateArrays::d_tau_ow)
+    bool flux_done = false;
+};
+struct ColumnRows {        // thermo()'s ice columns: as above
+    double *d_col_forcing[COL_FORCING_ROWS] = {};  // precip, snow, ocean_temp, ocean_salt, mld
+    double *d_col_st[COL_ST_ROWS] = {};            // tice1, tice2 (tice0, tsurf_young, sst, sss: d_flux_st)
+    unsigned col_forcing_have = 0, col_st_have = 0;
+    double *d_col_out = nullptr;                   // [COL_ROWS][Ne] what nxs_dyn_column_get returns
+    bool col_done = false;
+};
+struct StateArrays : FluxRows, ColumnRows {   // the prognostic and work arrays (set_mesh) and everything made in their pool on demand
+    std::vector<void *> state_allocs;
+    DevState ds{};
+    DevWork dw{};                          // (tau_wi, tau_sum, cum_damage, conc_fsd: attachments of CoupledBuffers; trace: option "trace_branches")
+    bool have_state = false, have_forcing = false;
+    int sig_loc = 0;                       // where M_sigma / M_damage are current: 0 = the state arrays, 1 = the records in S4a (left there by
+                                           // the fused sub-step loop; k_update works on them, the arrays follow on demand: ensure_arrays)
+    int trace_branches = 0;                // option "trace_branches": the per-loop kernels keep the branch trace of updateSigmaDamage (dw.trace: gone with the pool, so off again)
+    double *d_srec = nullptr;              // the records (allocated at set_mesh)
+    double *d_icediag = nullptr;           // [Ne][NXS_ICE_DIAG_FIELDS] rows of nxs_dyn_ice_diagnostics
+    double *d_icediag_soa = nullptr;       // [NXS_ICE_DIAG_FIELDS][Ne] the same per field, made when the host asks for its vectors
+    double *d_means[2] = {nullptr, nullptr};       // the Moorings time means: [Ne][n_el], [Nn][n_nod] interleaved accumulators
+    double *d_means_pm = nullptr;                  // [Ne] setProcMask's column: 1 on owned elements, 0 on ghosts
+    double *d_tau_ow = nullptr;                    // [Ne] D_tau_ow: a row of d_flux_out, or as nxs_dyn_means_set_tau_ow uploaded it
+    bool tau_ow_attached = false;
+};
+struct PatchTables {       // the one-ring patches of the fused sub-step kernels (the resident loop's tables describe them: released with them)
+    std::vector<void *> patch_allocs;
+    DevPatches dpch{};
+    size_t prep_lds = 0;                   // LDS of k_prep_fused for the current patches; 0: the two separate prep kernels run
+};
+struct ResidentTables {    // v4: the resident loop's tables, exchange buffer and ghost ring (rebuilt whenever an option of the loop changes), with the handle's KIND_RESIDENT claim
+    std::vector<void *> res_allocs;
+    DevResident res{};
+    double *d_vt3 = nullptr;
+    bool res_ready = false, res_failed = false;
+};
+struct PairPatches {       // the D-ring patches of k_substep_multi / k_substep_pair, with the handle's KIND_PAIR claim on the device's workgroup slots (nxs_resident_registry.hpp)
+    std::vector<void *> pair_allocs;
+    DevPatches2 dpch2{};
+    bool pair_ready = false, pair_failed = false;   // failed: they could not be built for this mesh: one sub-step per launch instead
+    int pair_depth_built = 0;
+    bool pair_kernel = false;              // they were cut for k_substep_pair
+    PairHalo pairh{};                      // several ranks: the patches' duties in the exchange inside k_substep_pair<HALO>, the ticket words
+    bool pair_claim = false;               // ... and their claim
+    bool flow_ready = false;               // option "pair_flow": the same patches as one data-flow launch
+    PairFlow flow{};                       // its dependency lists, queues and counters
+    size_t flow_words = 0;                 // ... the words zeroed before every launch
+    int flow_grid = 0;
+};
+struct SmoothPatches {     // node-ring patches for the smoother alone (single rank, meshes on the one-sub-step-per-launch kernels): D sweeps per launch
+    std::vector<void *> sm_allocs;
+    DevPatches2 dsm{};
+    bool sm_ready = false, sm_failed = false;
+    size_t sm_lds = 0;
+};
+struct VelocityRing {      // the ring slots beyond M_VT and its twin (ensure_ring only ever adds)
+    std::vector<void *> ring_allocs;
+    VTRing ring{};
+};
+struct HaloFusedTables {   // the exchange fused into the sub-step kernels (device-direct transport + fused path): they refer to the patches AND to the halo lists
+    std::vector<void *> hf_allocs;
+    HaloFused hf{};
+    HaloFused *d_hf = nullptr;  // device copy of hf with the mailbox addresses filled in (what k_substep_fused<.., HALO> reads)
+    bool hf_ready = false, d_hf_dirty = true;
+};
+struct HaloLists {         // the lists of nxs_dyn_set_halo on the device, the pack / unpack buffers
+    std::vector<void *> halo_allocs;
+    int *d_send_index = nullptr, *d_send_seg = nullptr, *d_send_off = nullptr;
+    int *d_recv_index = nullptr, *d_recv_seg = nullptr, *d_recv_off = nullptr, *d_recv_procs = nullptr;
+    double *d_send_buf = nullptr, *d_recv_buf = nullptr;
+    bool have_halo = false;
+};
+struct ForcingPair {       // nxs_dyn_set_forcing_pair's snapshots
+    std::vector<void *> forcing_allocs;
+    double *f_snap[6] = {};                // wind0, wind1, ocean0, ocean1, ssh0, ssh1
+    bool have_pair = false;
+};
+struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stress / nxs_dyn_put_coupled) and the floe-size distribution's (nxs_dyn_fsd_*)
+    std::vector<void *> coupled_allocs;
+    // ATTACHED is what h->dw says (tau_wi, cum_damage, conc_fsd non-NULL) and fsd_mech / fsd_cumw non-NULL; a detached buffer is kept for the next attach (no hipFree
+    // between two steps: it would wait for the whole device, see `retired`)
+    double *d_tau_wi = nullptr, *d_tau_sum = nullptr, *d_cum = nullptr, *d_fsd = nullptr;
+    size_t fsd_capacity = 0;               // doubles d_fsd has room for
+    double *d_mech = nullptr, *d_cumw = nullptr, *d_wlbk = nullptr, *fsd_mech = nullptr, *fsd_cumw = nullptr;   // M_conc_mech_fsd, M_cum_wave_damage, M_wlbk
+    unsigned char *d_freezing = nullptr;
+    size_t mech_capacity = 0;
+};
+
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, CoupledBuffers {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -109,28 +211,16 @@ struct nxs_dyn_handle {
     DevParams dp{};
     DevParams *d_dp = nullptr;   // device copy (the fused sub-step kernels read their parameters from memory)
     bool dp_dirty = true;
-    bool have_mesh = false, have_state = false, have_forcing = false;
-    DevMesh dm{};
-    DevState ds{};
-    DevWork dw{};
-    DevPatches dpch{};
     int fused = 3;          // 3 (default): v3 (two sub-steps per launch) on single-rank meshes that live in the caches, else v2;
                             // 2: v3 wherever it is possible; 1: v2 fused sub-step kernel; 0: v1 two-kernel sub-step
     int pair_nodes = 0;     // v3: own nodes per patch; 0 = auto
     int pair_depth = 0;     // v3: sub-steps per launch, 2..NXS_MAX_DEPTH; 0 = auto
-    int pair_depth_built = 0;
     StepPlan plan{};        // what the last step launched (plan_step)
-    bool pair_failed = false;   // the D-ring patches could not be built for this mesh: v2 instead
-    DevPatches2 dpch2{};
     size_t pair_lds = 0;
     int pair_threads_chosen = 512;   // threads of a k_substep_pair / k_substep_multi workgroup as the planner CHOSE them for the patches in dpch2
-    bool pair_ready = false;
-    std::vector<void *> pair_allocs;
     int patch_nodes = 0;    // own nodes per patch; 0 = auto
     int um_ring = 0;        // fused path: apply the mesh move every um_ring sub-steps from a ring of VT buffers
                             // (1 = every sub-step; 0 = auto: once per step on meshes that stream from HBM, 1 on cache-resident ones)
-    VTRing ring{};
-    std::vector<void *> ring_allocs;
     int nt_mask = -1;       // non-temporal access classes of the fused kernel (1 sigma/damage, 2 UM/UT, 4 element constants); -1 = automatic:
                             // 3 where a sub-step streams more than the Infinity Cache holds (>= 1 M local triangles), 0 below
     size_t fused_lds = 0;
@@ -138,36 +228,22 @@ struct nxs_dyn_handle {
     std::vector<int> h_n2n, h_n2n_cnt;     // NodalConnectivity rows [W2][Nn] + counts (for the blocked smoother's tables)
     std::vector<int> h_n2e;                // NodalElementConnectivity rows [W1][Nn], -1 = pad (for k_prep_fused's rows in patch slots)
     int pair_own_max = 0;                  // most own nodes of a multi-sub-step patch
-    size_t prep_lds = 0;                   // LDS of k_prep_fused for the current patches; 0: the two separate prep kernels run
     int band_nodes = -1;                   // option "band_patch_nodes": several ranks, resident loop: the sent nodes in patches of their own of this size; -1 = 48, 0 = off
     int pair_regs = -1;                    // option "pair_regs": two sub-steps per launch with the stresses between them in registers (k_substep_pair): -1 = on
                                            // single-rank meshes of more than 65 k nodes (an even number of sub-steps), 0 = never, 1 = wherever depth 2 runs
-    bool pair_kernel = false;              // the multi-sub-step patches were cut for k_substep_pair
     int pair_hilbert = 0;                  // option "pair_hilbert": 1 = the two-ring patches of a single rank are cut along a Hilbert curve even where the caller's numbering has locality
     int pair_move = -1;                    // option "pair_move": k_substep_pair on a single rank applies the mesh move of its two sub-steps itself (no ring of velocity slots, no
                                            // k_move_ring): -1 = automatic (the same as 1), 0 = never (the move deferred to one flush per step), 1 = wherever that kernel runs on one rank
     int pair_flow = -1;                    // option "pair_flow": the pairs of sub-steps of a step as ONE data-flow launch (k_substep_flow): 1 = wherever k_substep_pair runs on a
                                            // single rank with 512 threads; anything else (0, and the default -1) = never (one launch per pair)
-    bool flow_ready = false, flow_failed = false;
-    PairFlow flow{};                       // its dependency lists, queues and counters (they go with the patches)
-    size_t flow_words = 0;                 // ... the words zeroed before every launch
-    int flow_grid = 0;
+    bool flow_failed = false;              // ... its launch gave up once: one launch per pair from then on (kept across set_mesh)
     int pair_threads_requested = 512;      // option "pair_threads": threads of a k_substep_pair workgroup on a single rank (512: two per CU; 256: four per CU, smaller patches)
-    PairHalo pairh{};                      // several ranks: the patches' duties in the exchange inside k_substep_pair<HALO>, the ticket words
-    bool pair_claim = false;               // ... and their claim on the device's workgroup slots (nxs_resident_registry.hpp)
     int pair_hint = 0;                     // the patch size the planner kept for the previous mesh (tried first after a regrid)
     int prep_fused = -1;                   // option "prep_fused": -1 where it pays (single rank, records only, >= 250 k triangles), 0 never, 1 wherever it can run
     size_t smooth_lds = 0;
-    // node-ring patches for the smoother alone (single rank, meshes on the one-sub-step-per-launch kernels): D sweeps per launch
-    DevPatches2 dsm{};
-    std::vector<void *> sm_allocs;
-    bool sm_ready = false, sm_failed = false;
     int sm_depth = 0;  // option smooth_depth: sweeps per launch of the smoother on its own node-ring patches (0 = automatic)
-    size_t sm_lds = 0;
     std::vector<unsigned char> h_ghost;
     std::vector<double> h_x0, h_y0;
-    std::vector<void *> patch_allocs;
-    std::vector<void *> mesh_allocs, state_allocs;
     // Device memory that a rebuild INSIDE a step lets go of is parked here and freed by the next call that is outside a step AND outside the time loop (set_mesh,
     // set_params, set_option, destroy -- NOT put_state / set_forcing, which a host with its thermodynamics on the CPU calls between any two steps): a hipFree
     // synchronises the whole device, and where ranks share one (tests, rehearsals, two MPI ranks per GPU) a neighbour rank's kernel may already be spinning for this
@@ -175,7 +251,6 @@ struct nxs_dyn_handle {
     std::vector<void *> retired;
     bool in_step = false;
     // halo
-    bool have_halo = false;
     int rank = 0, nranks = 1;
     std::vector<int> send_procs, send_offsets, recv_procs, recv_offsets;   // as nxs_dyn_set_halo keeps them: the caller's neighbours, then the directions it added (empty segments)
     int ns_caller = 0, nr_caller = 0;      // neighbours the caller's own lists named (the low-level nxs_dyn_ipc_connect takes tables for those)
@@ -183,10 +258,6 @@ struct nxs_dyn_handle {
     unsigned ipc_delay_opt = 0;            // test door "ipc_delay": rank << 16 | point << 8 | units (include/nxs_dyn.h)
     int ord_blocks = 0, ord_slots = 0;     // the largest grid of blocks that may WAIT inside this handle's ordinary kernels, as registered on the device (nxs_resident_registry.hpp)
     long long reg_touched = 0;             // when the registry entry was last touched (seconds)
-    int *d_send_index = nullptr, *d_send_seg = nullptr, *d_send_off = nullptr;
-    int *d_recv_index = nullptr, *d_recv_seg = nullptr, *d_recv_off = nullptr;
-    double *d_send_buf = nullptr, *d_recv_buf = nullptr;
-    std::vector<void *> halo_allocs;
     Rccl rccl;
     void *comm = nullptr;
     // device-direct transport (peer-mapped mailboxes)
@@ -199,94 +270,52 @@ struct nxs_dyn_handle {
     std::vector<void *> ipc_peer_base;     // opened peer mailboxes (to close)
     std::vector<void *> ipc_local_peers;   // mailboxes of other handles of THIS process this handle stores through (counted in g_mailboxes)
     std::vector<void *> ipc_allocs;
-    int *d_recv_procs = nullptr;
-    // halo exchange fused into the sub-step kernel (device-direct transport + fused path)
-    double *f_snap[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // wind0, wind1, ocean0, ocean1, ssh0, ssh1 (forcing pair)
-    bool have_pair = false;
-    std::vector<void *> forcing_allocs;
-    // the coupled build's arrays (nxs_dyn_set_wave_stress / nxs_dyn_put_coupled): buffers that go with the mesh.  ATTACHED is what h->dw says (tau_wi, cum_damage,
-    // conc_fsd non-NULL); a detached buffer is kept for the next attach (no hipFree between two steps: it would wait for the whole device, see `retired`)
-    double *d_tau_wi = nullptr, *d_tau_sum = nullptr, *d_cum = nullptr, *d_fsd = nullptr;
-    size_t fsd_capacity = 0;               // doubles d_fsd has room for
-    // the floe-size distribution (nxs_dyn_fsd_*): M_conc_mech_fsd / M_cum_wave_damage and the uploads of M_wlbk / freezing go with the mesh (coupled_allocs);
-    // ATTACHED is fsd_mech / fsd_cumw non-NULL.  The configuration (tables, options, flags) is the handle's and survives set_mesh
-    double *d_mech = nullptr, *d_cumw = nullptr, *d_wlbk = nullptr, *fsd_mech = nullptr, *fsd_cumw = nullptr;
-    unsigned char *d_freezing = nullptr;
-    size_t mech_capacity = 0;
+    // the floe-size distribution (nxs_dyn_fsd_*): the configuration (tables, options, flags) is the handle's and survives set_mesh; its buffers are CoupledBuffers
     FsdDev fsd_cfg{};
     FsdDev *d_fsd_cfg = nullptr;
     int *d_fsd_flags = nullptr;
     bool fsd_configured = false;
-    std::vector<void *> coupled_allocs;
-    // thermo()'s atmospheric bulk fluxes (nxs_dyn_flux_* / nxs_dyn_fluxes): the configuration is the handle's and survives set_mesh; the rows are in the state pool and go
-    // with the mesh -- after set_mesh / regrid every row is MISSING until it is given again (the host re-makes them on the new mesh)
+    // thermo()'s atmospheric bulk fluxes (nxs_dyn_flux_* / nxs_dyn_fluxes): the configuration is the handle's and survives set_mesh; the rows are FluxRows
     nxs_dyn_flux_config flux_cfg{};
-    bool flux_configured = false, flux_done = false;
+    bool flux_configured = false;
     FluxDev flux_dev{};                            // what the kernel receives by value: derived once per configuration and quad_drag_coef_air (flux_derive)
     double flux_dev_qda = 0.;
     bool flux_dev_valid = false;
-    double *d_flux_atm[FLUX_ATM_ROWS] = {};        // tair, mslp, Qsw_in, humidity, longwave
-    double *d_flux_st[FLUX_ST_ROWS] = {};          // tice0, tsurf_young, sst, sss, drag_ti, drag_ti_young, pond_fraction, lid_volume
-    unsigned flux_atm_have = 0, flux_st_have = 0;  // bit k: row k was given on this mesh
-    double *d_flux_out = nullptr;                  // [FLUX_ROWS][Ne] what nxs_dyn_fluxes_get returns (D_tau_ow: d_tau_ow below)
-    // thermo()'s ice columns (nxs_dyn_column_* / nxs_dyn_column): as above -- the configuration survives set_mesh, the rows are in the state pool and go with the mesh
+    // thermo()'s ice columns (nxs_dyn_column_* / nxs_dyn_column): as above -- the configuration survives set_mesh, the rows are ColumnRows
     nxs_dyn_column_config col_cfg{};
-    bool col_configured = false, col_done = false;
-    double *d_col_forcing[COL_FORCING_ROWS] = {};  // precip, snow, ocean_temp, ocean_salt, mld
-    double *d_col_st[COL_ST_ROWS] = {};            // tice1, tice2 (tice0, tsurf_young, sst, sss: d_flux_st)
-    unsigned col_forcing_have = 0, col_st_have = 0;
-    double *d_col_out = nullptr;                   // [COL_ROWS][Ne] what nxs_dyn_column_get returns
+    bool col_configured = false;
     // v4: the whole sub-step loop in one resident launch (option "fused" = 4; see k_substep_resident)
-    DevResident res{};
-    std::vector<void *> res_allocs;  // its tables, exchange buffer and ghost ring (a pool of their own: rebuilt whenever an option of the loop changes)
-    bool res_ready = false, res_failed = false;
     int res_wide = 0;     // option resident_wide
     bool res_pow4 = true; // the build for BBM's default exponent (two squarings instead of pow)
     bool res_big = false; // k_substep_resident_big: one large patch per CU (the patches hold more than one element per thread)
     bool cut_big = false; // the mesh was cut for that kernel (not what the one-launch-per-sub-step kernel wants: re-cut if the resident loop is refused)
-    bool no_big_cut = false;
+    bool no_big_cut = false;  // ... and that was refused: the mesh is cut for the one-launch-per-sub-step kernel (until the next mesh or value of option fused)
     int res_substeps = 0; // the number of sub-steps the tables (the ghosts' ring) were sized for
     int res_wpe = 4;      // waves per SIMD of the resident kernel build in use (2 on several ranks where one workgroup per CU covers the partition)
     int res_overlap = -1; // option resident_overlap: interior elements of the next sub-step computed while the exchange is awaited; -1 = where it pays
                           // (the large patches of k_substep_resident_big: one workgroup per CU, nothing else fills its wait), 0 never, 1 wherever built
     bool res_ovl = false; // what the tables of the resident loop were built for
     size_t res_lds = 0;
-    double *d_vt3 = nullptr;
-    double *d_icediag = nullptr;           // [Ne][NXS_ICE_DIAG_FIELDS] rows of nxs_dyn_ice_diagnostics (state pool: goes with the mesh)
-    double *d_icediag_soa = nullptr;       // [NXS_ICE_DIAG_FIELDS][Ne] the same per field, made when the host asks for its vectors
-    // the Moorings time means (nxs_dyn_means_*): the configuration is the handle's and survives set_mesh; the buffers are in the state pool and go with the mesh
+    // the Moorings time means (nxs_dyn_means_*): the configuration is the handle's and survives set_mesh; the buffers are in the state pool (StateArrays)
     std::vector<int> means_ids[2];                 // [0] elemental, [1] nodal: NXS_MEANS_* in column order
     std::vector<unsigned char> means_mask[2];      // Variable::mask per column
     int means_ice_mask_col = -1;                   // the elemental column that holds NXS_MEANS_ICE_MASK (M_ice_mask_indx); -1: none
     MeansTable means_tab[2] = {};                  // what the two kernels receive by value
-    double *d_means[2] = {nullptr, nullptr};       // [Ne][n_el], [Nn][n_nod] interleaved accumulators
-    double *d_means_pm = nullptr;                  // [Ne] setProcMask's column: 1 on owned elements, 0 on ghosts
-    double *d_tau_ow = nullptr;                    // [Ne] D_tau_ow as nxs_dyn_means_set_tau_ow uploaded it
-    bool tau_ow_attached = false;
     int means_timing = 0;                          // option "means_timing": events around the two launches of nxs_dyn_means_update (nxs_dyn_debug_array "means_update_ms")
     hipEvent_t means_ev[3] = {nullptr, nullptr, nullptr};
     bool means_timed = false;
     int means_stage = 1;                           // option "means_stage": the rows' read-modify-write staged through LDS (1) or walked by each thread (0)
     // the drifters (nxs_dyn_drifters_*): the sets are the handle's and survive set_mesh; the two locators go with the mesh / with M_UM (nxs_drifters.hpp)
     nxs_drifters::State *drift = nullptr;          // made by the first nxs_dyn_drifters_set
-    int sig_loc = 0;                       // where M_sigma / M_damage are current: 0 = the state arrays, 1 = the records in S4a (left there by
-                                           // the fused sub-step loop; k_update works on them, the arrays follow on demand: ensure_arrays)
     int update_launch[3] = {-1, -1, 0};    // the last launch of k_update: REC, FSD, threads per block (nxs_dyn_debug_array "update_launch"; -1 = none yet)
-    int trace_branches = 0;                // option "trace_branches": the per-loop kernels keep the branch trace of updateSigmaDamage (dw.trace)
     int shape_mem = -1;                    // option "shape_mem": the several-sub-steps kernel reads M_shape_coeff from per-step records (1, and -1 = automatic)
                                            // or rebuilds it from the staged coordinates like the one-sub-step kernel (0)
-    double *d_srec = nullptr;              // the records (allocated at set_mesh)
     int work_arrays = 0;                   // option "work_arrays": the prep kernels also fill the one-array-per-quantity work vectors
     int pin_host = 0;                      // option "pin_host": page-lock the caller's state / forcing vectors on first use
     std::map<const void *, size_t> pinned; // what this handle has registered with hipHostRegister
     int halo_fused = 1;                    // option "halo_fused"
     int res_no_release = 0;                // option "resident_release" = 0 (kept here: h->hf is rebuilt with the tables)
     int smooth_persist = -1;               // option "smooth_persist": the 50 sweeps with the exchange inside as ONE launch of persistent workgroups (k_smooth_persist): -1 / 1 = on, 0 = 50 launches of k_smooth_halo
-    bool hf_ready = false;
-    HaloFused *d_hf = nullptr;  // device copy of hf with the mailbox addresses filled in (what k_substep_fused<.., HALO> reads)
-    bool d_hf_dirty = true;
-    HaloFused hf{};
-    std::vector<void *> hf_allocs;
     std::vector<int> h_send_index, h_recv_index;   // host copies of the halo lists
     std::vector<char> h_sent;                      // [No] != 0: an own node this rank sends (the cut for the resident loop puts those in the small boundary patches)
     std::shared_ptr<HostPatches> hp;  // host copy of the patches (re-uploaded boundary-first for the fused halo)
@@ -520,13 +549,75 @@ void register_waiting_grid(nxs_dyn_handle *h, int blocks, int slots, bool reset 
     nxs_reg::table_for(h->reg_key).set_ordinary((uint64_t)(uintptr_t)h, h->ord_blocks, h->ord_slots);
 }
 
-// the resident loop's tables and its claim on the device's workgroup slots
+// ---- the owners of the handle's pools (see MeshArrays ... CoupledBuffers above the handle): the pool goes -- parked inside a step, freed outside one: drop_pool --
+// and the group starts afresh, so no pointer into it and no flag that vouches for it outlives the memory
+template <class Group> void release_group(nxs_dyn_handle *h, std::vector<void *> &pool) {
+    drop_pool(h, pool);
+    static_cast<Group &>(*h) = Group{};
+}
+// the resident loop's tables (alone where build_resident makes them again: its claim() replaces the handle's entry under the registry's lock, the slots are
+// never given up in between) ...
+void release_resident_tables(nxs_dyn_handle *h) { release_group<ResidentTables>(h, h->res_allocs); }
+// ... and with them its claim on the device's workgroup slots
 void release_resident(nxs_dyn_handle *h) {
-    drop_pool(h, h->res_allocs);
-    h->res = DevResident{};
-    h->d_vt3 = nullptr;
-    h->res_ready = false; h->res_failed = false;
+    release_resident_tables(h);
     resident_registry_release(h, nxs_reg::KIND_RESIDENT);
+}
+// the one-ring patches, and the resident loop's tables that describe them (the tables, the second exchange buffer, the claim on the device's slots)
+void release_patches(nxs_dyn_handle *h) {
+    release_group<PatchTables>(h, h->patch_allocs);
+    release_resident(h);
+}
+// the pair patches' claim alone: they are no longer the ones wanted (option fused, other send lists) or the handle's ONE claim went to the resident loop -- cut, and
+// claimed, again when they are wanted
+void unclaim_pair_patches(nxs_dyn_handle *h) {
+    if (!h->pair_claim) return;
+    resident_registry_release(h, nxs_reg::KIND_PAIR);   // (held by the resident loop by now: nothing happens)
+    h->pair_claim = false; h->pair_ready = false;
+}
+// the D-ring patches with their claim, their duties in the exchange and the data-flow launch's queues (flow.error among them: resident_error reads it while flow_ready)
+void release_pair_patches(nxs_dyn_handle *h) {
+    unclaim_pair_patches(h);
+    release_group<PairPatches>(h, h->pair_allocs);
+}
+// an option the tables were cut for has changed: they are built again, and what was refused is tried again, by the next step that wants them
+void rebuild_later(nxs_dyn_handle *h, bool &ready, bool &failed) { ready = false; failed = false; release_graph(h); }
+void release_smooth_patches(nxs_dyn_handle *h) { release_group<SmoothPatches>(h, h->sm_allocs); }
+void release_ring(nxs_dyn_handle *h) { release_group<VelocityRing>(h, h->ring_allocs); }
+void release_halo_fused(nxs_dyn_handle *h) { release_group<HaloFusedTables>(h, h->hf_allocs); }
+// the halo lists, and the fused exchange's tables, which hold a pointer into them (send_off)
+void release_halo(nxs_dyn_handle *h) {
+    release_group<HaloLists>(h, h->halo_allocs);
+    release_halo_fused(h);
+}
+void release_forcing_pair(nxs_dyn_handle *h) { release_group<ForcingPair>(h, h->forcing_allocs); }
+// the coupled build's buffers; their attachments are members of h->dw
+void release_coupled(nxs_dyn_handle *h) {
+    release_group<CoupledBuffers>(h, h->coupled_allocs);
+    h->dw.tau_wi = h->dw.tau_sum = nullptr; h->dw.cum_damage = h->dw.conc_fsd = nullptr; h->dw.nbins = 0;
+}
+// ... and take over a buffer that is on the device already (nxs_dyn_regrid carried it across): the pool's from now on, and attached
+void coupled_adopt(nxs_dyn_handle *h, double **member, double **attachment, double *buf) {
+    h->coupled_allocs.push_back(buf);
+    *member = *attachment = buf;
+}
+// the state pool: the prognostic and work arrays, the flux and column rows, the means' accumulators, D_tau_ow, the ice diagnostics, the branch trace
+void release_state(nxs_dyn_handle *h) { release_group<StateArrays>(h, h->state_allocs); }
+// Everything that goes with the mesh (nxs_dyn_set_mesh, nxs_dyn_regrid, nxs_dyn_destroy; never inside a step).  Kept: every option but trace_branches, the
+// parameters, the flux / column / FSD / means configurations, the drifter sets, pair_hint and flow_failed, the mailbox, the communicator, the timing sums.
+void release_mesh(nxs_dyn_handle *h) {
+    release_group<MeshArrays>(h, h->mesh_allocs);
+    release_state(h);
+    release_halo(h);
+    release_patches(h);
+    release_pair_patches(h);
+    release_smooth_patches(h);
+    release_ring(h);
+    release_forcing_pair(h);
+    release_coupled(h);
+    h->no_big_cut = false;
+    h->rank = 0; h->nranks = 1;   // (the partition is the mesh's: a single rank until nxs_dyn_set_halo says otherwise)
+    h->send_procs.clear(); h->recv_procs.clear(); h->send_offsets.assign(1, 0); h->recv_offsets.assign(1, 0);
 }
 
 #include "nxs_dyn_patches.inl"
@@ -675,6 +766,45 @@ int resident_error(nxs_dyn_handle *h) {
                                 : "unknown wait";
     return fail(h, NXS_ERR_HIP, "the resident sub-step launch gave up (code %d): %s; the step is lost and M_UM, M_UT, sigma and damage are undefined (patches that had finished "
                                 "before the time-out have written their result, the others have not): put the state again before going on; later steps run one kernel per sub-step", err, what);
+}
+
+// ... for every entry point that hands state to the host or works on it outside a step: never a half-made step without an error
+int launch_gave_up(nxs_dyn_handle *h) {
+    if (!h->res_ready && !h->flow_ready) return NXS_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return resident_error(h);
+}
+
+// The copies of one put / get: every row's host side page-locked on first use (option "pin_host"), all of them enqueued, then waited for.  A row whose host side
+// is NULL is skipped ("the device copy is current" / "not asked for").
+struct RowCopy { void *dst; const void *src; size_t bytes; const char *name; };
+int copy_rows(nxs_dyn_handle *h, const RowCopy *rows, int count, hipMemcpyKind kind) {
+    for (int k = 0; k < count; ++k) {
+        const void *host = kind == hipMemcpyHostToDevice ? rows[k].src : rows[k].dst;
+        if (!host) continue;
+        pin_host_buffer(h, host, rows[k].bytes);
+        HIPCHK(h, hipMemcpyAsync(rows[k].dst, rows[k].src, rows[k].bytes, kind, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return NXS_OK;
+}
+// `count` rows of Ne doubles each (the flux and column rows): from the device (dst NULL: none is asked for) ...
+int download_rows(nxs_dyn_handle *h, double *const *dst, const double *const *dev, int count) {
+    std::vector<RowCopy> rows(count);
+    for (int k = 0; k < count; ++k) rows[k] = RowCopy{dst ? dst[k] : nullptr, dev[k], (size_t)h->dm.Ne * sizeof(double), nullptr};
+    return copy_rows(h, rows.data(), count, hipMemcpyDeviceToHost);
+}
+// ... and to it: they live in the state pool (they go with the mesh), made when first given; a row is PRESENT (its bit in *have) once it was given on this mesh
+int upload_rows(nxs_dyn_handle *h, double **dev, const double *const *src, int count, unsigned *have) {
+    HIPCHK(h, hipSetDevice(h->device));
+    std::vector<RowCopy> rows(count);
+    for (int k = 0; k < count; ++k) {
+        if (src[k] && !dev[k]) { if (int rc = dev_alloc(h, h->state_allocs, &dev[k], (size_t)h->dm.Ne)) return rc; }
+        rows[k] = RowCopy{dev[k], src[k], (size_t)h->dm.Ne * sizeof(double), nullptr};
+    }
+    if (int rc = copy_rows(h, rows.data(), count, hipMemcpyHostToDevice)) return rc;
+    for (int k = 0; k < count; ++k) if (src[k]) *have |= 1u << k;
+    return NXS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1008,9 +1138,7 @@ void register_smoother_grid(nxs_dyn_handle *h) {
 
 // tables of the halo exchange fused into the sub-step kernel (see HaloFused)
 int build_halo_fused(nxs_dyn_handle *h) {
-    drop_pool(h, h->hf_allocs);
-    h->hf = HaloFused{};
-    h->hf_ready = false;
+    release_halo_fused(h);
     const int Nn = h->dm.Nn, No = h->dm.No, nP = h->dpch.nP;
     if (!h->hp || h->hp->nP != nP) return fail(h, NXS_ERR_STATE, "fused halo tables: patches / halo lists missing");
     const nxs_cut::HaloLists hl{&h->send_offsets, &h->recv_offsets, &h->h_send_index, &h->h_recv_index, (int)h->send_procs.size(), (int)h->recv_procs.size()};
@@ -1079,10 +1207,7 @@ int ensure_halo_device_copy(nxs_dyn_handle *h) {
 // means "not possible here" (the caller then runs one kernel per sub-step).  Everything lives in a pool of its own that is given back
 // before it is rebuilt (options fused / resident_wide / resident_overlap / resident_dryrun, a change of parameters, a timed-out launch).
 int build_resident(nxs_dyn_handle *h) {
-    h->res_ready = false;
-    drop_pool(h, h->res_allocs);
-    h->res = DevResident{};
-    h->d_vt3 = nullptr;
+    release_resident_tables(h);
     if (!h->hp || h->hp->nP != h->dpch.nP) return NXS_OK;
     const HostPatches &hp = *h->hp;
     const int nP = hp.nP, No = h->dm.No, Nn = h->dm.Nn, S = h->dp.substeps;
@@ -1123,7 +1248,7 @@ int build_resident(nxs_dyn_handle *h) {
     {
         std::string why;
         if (!resident_registry_claim(h, nP, per_cu * cus, &why, nxs_reg::KIND_RESIDENT)) return refuse(why.c_str());
-        if (h->pair_claim) { h->pair_claim = false; h->pair_ready = false; }   // (a handle holds ONE claim: the pair patches' went with it and are cut -- and claimed -- again if they are wanted)
+        unclaim_pair_patches(h);   // (a handle holds ONE claim: the pair patches' went with it)
     }
     int rc;
     DevResident &r = h->res;
@@ -1717,27 +1842,8 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     flush_retired(h);
     if (h->comm && h->rccl.CommDestroy) h->rccl.CommDestroy(h->comm);
     ipc_release(h);
-    free_pool(h->mesh_allocs);
-    free_pool(h->state_allocs);
-    free_pool(h->halo_allocs);
-    free_pool(h->patch_allocs);
-    release_resident(h);
+    release_mesh(h);
     if (!h->reg_key.empty()) nxs_reg::table_for(h->reg_key).remove((uint64_t)(uintptr_t)h);
-    free_pool(h->pair_allocs);
-    h->pair_ready = false;
-    h->pair_failed = false;
-    free_pool(h->sm_allocs);
-    h->sm_ready = false;
-    h->sm_failed = false;
-    free_pool(h->ring_allocs);
-    free_pool(h->hf_allocs);
-    h->hf_ready = false;
-    free_pool(h->forcing_allocs);
-    free_pool(h->coupled_allocs);   // (set_mesh: h->dw is reset below, which detaches the three)
-    h->d_tau_wi = h->d_tau_sum = h->d_cum = h->d_fsd = nullptr; h->fsd_capacity = 0;
-    h->d_mech = h->d_cumw = h->d_wlbk = h->fsd_mech = h->fsd_cumw = nullptr; h->d_freezing = nullptr; h->mech_capacity = 0;
-    for (auto &q : h->f_snap) q = nullptr;
-    h->have_pair = false;
     unpin_all(h);
     if (h->h_send) (void)hipHostFree(h->h_send);
     if (h->h_recv) (void)hipHostFree(h->h_recv);
@@ -1798,7 +1904,7 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
         if (value < 0 || value > 4) return fail(h, NXS_ERR_INVALID, "fused must be 0, 1, 2, 3 or 4");
         const bool was_resident = h->fused == 4, now_resident = value == 4;
         h->fused = (int)value; h->res_failed = false; h->no_big_cut = false; release_graph(h);
-        if (h->pair_claim) { resident_registry_release(h, nxs_reg::KIND_PAIR); h->pair_claim = false; h->pair_ready = false; }   // (the several-rank pair patches: cut again when they are wanted)
+        unclaim_pair_patches(h);   // (the several-rank pair patches)
         // the resident loop has a cut of its own (one round of workgroups; one LARGE patch per CU for partitions of 200 k - 400 k triangles, which is not what
         // the one-launch-per-sub-step kernel wants): asking for it or giving it up on a live mesh cuts the mesh again -- any cut gives the same bits
         if (h->have_mesh && was_resident != now_resident) {
@@ -1833,10 +1939,10 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
         return NXS_OK;
     }
     if (!std::strcmp(key, "resident_wide")) {
-        h->res_wide = value != 0; h->res_ready = false; h->res_failed = false; release_graph(h); return NXS_OK;
+        h->res_wide = value != 0; rebuild_later(h, h->res_ready, h->res_failed); return NXS_OK;
     }
     if (!std::strcmp(key, "resident_overlap")) {
-        h->res_overlap = value < 0 ? -1 : (value != 0); h->res_ready = false; h->res_failed = false; release_graph(h); return NXS_OK;
+        h->res_overlap = value < 0 ? -1 : (value != 0); rebuild_later(h, h->res_ready, h->res_failed); return NXS_OK;
     }
     if (!std::strcmp(key, "smooth_depth")) {
         if (value != 0 && value != 5 && value != 10 && value != 25) return fail(h, NXS_ERR_INVALID, "smooth_depth must be 0 (auto), 5, 10 or 25");
@@ -1848,7 +1954,7 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
     }
     if (!std::strcmp(key, "pair_nodes")) {
         if (value != 0 && (value < 16 || value > 1024)) return fail(h, NXS_ERR_INVALID, "pair_nodes must be 0 (auto) or in [16,1024]");
-        h->pair_nodes = (int)value; h->pair_ready = false; h->pair_failed = false; release_graph(h); return NXS_OK;
+        h->pair_nodes = (int)value; rebuild_later(h, h->pair_ready, h->pair_failed); return NXS_OK;
     }
     if (!std::strcmp(key, "work_arrays")) { h->work_arrays = value != 0; release_graph(h); return NXS_OK; }
     if (!std::strcmp(key, "band_patch_nodes")) {
@@ -1859,12 +1965,12 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
     }
     if (!std::strcmp(key, "pair_threads")) {
         if (value != 256 && value != 512) return fail(h, NXS_ERR_INVALID, "pair_threads must be 256 or 512");
-        h->pair_threads_requested = (int)value; h->pair_ready = false; h->pair_failed = false; h->pair_hint = 0; release_graph(h); return NXS_OK;
+        h->pair_threads_requested = (int)value; h->pair_hint = 0; rebuild_later(h, h->pair_ready, h->pair_failed); return NXS_OK;
     }
-    if (!std::strcmp(key, "pair_hilbert")) { h->pair_hilbert = value != 0; h->pair_ready = false; h->pair_failed = false; h->pair_hint = 0; release_graph(h); return NXS_OK; }
+    if (!std::strcmp(key, "pair_hilbert")) { h->pair_hilbert = value != 0; h->pair_hint = 0; rebuild_later(h, h->pair_ready, h->pair_failed); return NXS_OK; }
     if (!std::strcmp(key, "pair_move")) { h->pair_move = value < 0 ? -1 : (value != 0); release_graph(h); return NXS_OK; }
-    if (!std::strcmp(key, "pair_flow")) { h->pair_flow = value < 0 ? -1 : (value != 0); h->pair_ready = false; h->pair_failed = false; h->flow_failed = false; release_graph(h); return NXS_OK; }
-    if (!std::strcmp(key, "pair_regs")) { h->pair_regs = value < 0 ? -1 : (value != 0); h->pair_ready = false; h->pair_failed = false; release_graph(h); return NXS_OK; }
+    if (!std::strcmp(key, "pair_flow")) { h->pair_flow = value < 0 ? -1 : (value != 0); h->flow_failed = false; rebuild_later(h, h->pair_ready, h->pair_failed); return NXS_OK; }
+    if (!std::strcmp(key, "pair_regs")) { h->pair_regs = value < 0 ? -1 : (value != 0); rebuild_later(h, h->pair_ready, h->pair_failed); return NXS_OK; }
     if (!std::strcmp(key, "prep_fused")) { h->prep_fused = value < 0 ? -1 : (value != 0); release_graph(h); return NXS_OK; }
     if (!std::strcmp(key, "shape_mem")) {
         if (value < -1 || value > 1) return fail(h, NXS_ERR_INVALID, "shape_mem must be -1 (auto), 0 or 1");
@@ -1952,39 +2058,11 @@ static int set_mesh_impl(nxs_dyn_handle *h, const nxs_dyn_mesh *m, RegridAdopt *
     if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));
     release_graph(h);
     flush_retired(h);
-    free_pool(h->mesh_allocs);
-    free_pool(h->state_allocs);
-    free_pool(h->halo_allocs);
-    free_pool(h->patch_allocs);
+    release_mesh(h);
     if (h->drift) nxs_drifters::mesh_changed(h->drift);   // (the sets stay: positions do not depend on the mesh)
-    release_resident(h);
-    if (h->pair_claim) { resident_registry_release(h, nxs_reg::KIND_PAIR); h->pair_claim = false; }
-    free_pool(h->pair_allocs);
-    h->pair_ready = false;
-    h->pair_failed = false;
-    free_pool(h->sm_allocs);
-    h->sm_ready = false;
-    h->sm_failed = false;
-    free_pool(h->ring_allocs);
-    free_pool(h->hf_allocs);
-    h->hf_ready = false;
-    free_pool(h->forcing_allocs);
-    free_pool(h->coupled_allocs);   // (set_mesh: h->dw is reset below, which detaches the three)
-    h->d_tau_wi = h->d_tau_sum = h->d_cum = h->d_fsd = nullptr; h->fsd_capacity = 0;
-    h->d_mech = h->d_cumw = h->d_wlbk = h->fsd_mech = h->fsd_cumw = nullptr; h->d_freezing = nullptr; h->mech_capacity = 0;
-    for (auto &q : h->f_snap) q = nullptr;
-    h->have_pair = false;
     unpin_all(h);
-    h->ring = VTRing{};
-    h->have_mesh = h->have_state = h->have_forcing = h->have_halo = false;
-    h->no_big_cut = false;
-    h->sig_loc = 0;
-    h->trace_branches = 0;
-    h->rank = 0; h->nranks = 1;
-    h->send_procs.clear(); h->recv_procs.clear(); h->send_offsets.assign(1, 0); h->recv_offsets.assign(1, 0);
 
     DevMesh &d = h->dm;
-    d = DevMesh{};
     d.Nn = Nn; d.Ne = Ne; d.No = No; d.Neo = Neo;
     int rc;
     // triangles, SoA, 0-based
@@ -2080,15 +2158,6 @@ static int set_mesh_impl(nxs_dyn_handle *h, const nxs_dyn_mesh *m, RegridAdopt *
     // state + work arrays
     DevState &s = h->ds;
     DevWork &w = h->dw;
-    s = DevState{}; w = DevWork{};
-    h->d_icediag = nullptr; h->d_icediag_soa = nullptr;
-    h->d_means[0] = h->d_means[1] = h->d_means_pm = h->d_tau_ow = nullptr; h->tau_ow_attached = false;   // (freed with the state pool above)
-    for (auto &q : h->d_flux_atm) q = nullptr;
-    for (auto &q : h->d_flux_st) q = nullptr;
-    h->d_flux_out = nullptr; h->flux_atm_have = h->flux_st_have = 0; h->flux_done = false;   // (the same pool)
-    for (auto &q : h->d_col_forcing) q = nullptr;
-    for (auto &q : h->d_col_st) q = nullptr;
-    h->d_col_out = nullptr; h->col_forcing_have = h->col_st_have = 0; h->col_done = false;
     auto &P = h->state_allocs;
     const size_t n2 = 2 * (size_t)Nn, ne = Ne;
 #define A(ptr, cnt) if ((rc = dev_alloc(h, P, &(ptr), (cnt)))) return rc
@@ -2140,9 +2209,8 @@ int nxs_dyn_set_halo(nxs_dyn_handle *h, const nxs_dyn_halo *halo) try {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     release_graph(h);
-    free_pool(h->halo_allocs);
+    release_halo(h);
     ipc_release(h);
-    h->have_halo = false;
     h->h_sent.clear();
     const int Nn = h->dm.Nn, No = h->dm.No;
     if (halo->nranks < 1 || halo->rank < 0 || halo->rank >= halo->nranks) return fail(h, NXS_ERR_INVALID, "rank/nranks invalid");
@@ -2160,8 +2228,8 @@ int nxs_dyn_set_halo(nxs_dyn_handle *h, const nxs_dyn_halo *halo) try {
         if (off[n] > 0 && !(side ? halo->recv_index : halo->send_index)) return fail(h, NXS_ERR_INVALID, "%s_index is NULL", side ? "recv" : "send");
     }
     h->rank = halo->rank; h->nranks = halo->nranks;
-    if (h->pair_claim) { resident_registry_release(h, nxs_reg::KIND_PAIR); h->pair_claim = false; }
-    h->pair_ready = false; h->pair_failed = false;   // (the several-rank pair patches depend on the send lists)
+    unclaim_pair_patches(h);
+    rebuild_later(h, h->pair_ready, h->pair_failed);   // (the several-rank pair patches depend on the send lists)
     h->send_procs.assign(halo->send_procs, halo->send_procs + ns);
     h->recv_procs.assign(halo->recv_procs, halo->recv_procs + nr);
     if (ns > 0) h->send_offsets.assign(halo->send_offsets, halo->send_offsets + ns + 1); else h->send_offsets.assign(1, 0);
@@ -2176,7 +2244,6 @@ int nxs_dyn_set_halo(nxs_dyn_handle *h, const nxs_dyn_halo *halo) try {
     }
     std::vector<int> sidx(halo->send_index, halo->send_index + ts), ridx(halo->recv_index, halo->recv_index + tr);
     h->h_send_index = sidx; h->h_recv_index = ridx;
-    h->hf_ready = false;
     std::vector<int> sseg(ts), rseg(tr);
     for (int k = 0; k < ns; ++k) {
         if (h->send_procs[k] < 0 || h->send_procs[k] >= halo->nranks || h->send_procs[k] == halo->rank) return fail(h, NXS_ERR_INVALID, "send_procs[%d] invalid", k);
@@ -2605,7 +2672,7 @@ int nxs_dyn_put_state(nxs_dyn_handle *h, const nxs_dyn_state *s) try {
     HIPCHK(h, hipSetDevice(h->device));
     const size_t n2 = 2 * (size_t)h->dm.Nn * sizeof(double), ne = (size_t)h->dm.Ne * sizeof(double);
     DevState &d = h->ds;
-    struct { double *dst; const double *src; size_t bytes; const char *name; } cp[] = {
+    const RowCopy cp[] = {
         {d.VT, s->VT, n2, "VT"}, {d.UM, s->UM, n2, "UM"}, {d.UT, s->UT, n2, "UT"},
         {d.conc, s->conc, ne, "conc"}, {d.thick, s->thick, ne, "thick"}, {d.snow, s->snow_thick, ne, "snow_thick"},
         {d.damage, s->damage, ne, "damage"}, {d.ridge, s->ridge_ratio, ne, "ridge_ratio"},
@@ -2620,9 +2687,7 @@ int nxs_dyn_put_state(nxs_dyn_handle *h, const nxs_dyn_state *s) try {
     if (!h->have_state)
         for (auto &c : cp) if (!c.src) return fail(h, NXS_ERR_INVALID, "put_state: %s is NULL", c.name);
     if (s->damage || s->sigma[0] || s->sigma[1] || s->sigma[2]) ensure_arrays(h);  // the members not given must not be lost
-    for (auto &c : cp) if (c.src) pin_host_buffer(h, c.src, c.bytes);
-    for (auto &c : cp) if (c.src) HIPCHK(h, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (int rc = copy_rows(h, cp, (int)(sizeof cp / sizeof *cp), hipMemcpyHostToDevice)) return rc;
     h->have_state = true;
     if (h->drift) nxs_drifters::state_changed(h->drift);
     return NXS_OK;
@@ -2634,20 +2699,17 @@ int nxs_dyn_get_state(nxs_dyn_handle *h, nxs_dyn_state *s) try {
     HIPCHK(h, hipSetDevice(h->device));
     const size_t n2 = 2 * (size_t)h->dm.Nn * sizeof(double), ne = (size_t)h->dm.Ne * sizeof(double);
     DevState &d = h->ds;
-    struct { double *dst; const double *src; size_t bytes; } cp[] = {
-        {s->VT, d.VT, n2}, {s->UM, d.UM, n2}, {s->UT, d.UT, n2},
-        {s->conc, d.conc, ne}, {s->thick, d.thick, ne}, {s->snow_thick, d.snow, ne},
-        {s->damage, d.damage, ne}, {s->ridge_ratio, d.ridge, ne},
-        {s->sigma[0], d.s0, ne}, {s->sigma[1], d.s1, ne}, {s->sigma[2], d.s2, ne},
-        {s->conc_young, d.cyoung, ne}, {s->h_young, d.hyoung, ne}, {s->hs_young, d.hsyoung, ne},
-        {s->conc_myi, d.cmyi, ne}, {s->thick_myi, d.tmyi, ne},
+    const RowCopy cp[] = {
+        {s->VT, d.VT, n2, "VT"}, {s->UM, d.UM, n2, "UM"}, {s->UT, d.UT, n2, "UT"},
+        {s->conc, d.conc, ne, "conc"}, {s->thick, d.thick, ne, "thick"}, {s->snow_thick, d.snow, ne, "snow_thick"},
+        {s->damage, d.damage, ne, "damage"}, {s->ridge_ratio, d.ridge, ne, "ridge_ratio"},
+        {s->sigma[0], d.s0, ne, "sigma[0]"}, {s->sigma[1], d.s1, ne, "sigma[1]"}, {s->sigma[2], d.s2, ne, "sigma[2]"},
+        {s->conc_young, d.cyoung, ne, "conc_young"}, {s->h_young, d.hyoung, ne, "h_young"}, {s->hs_young, d.hsyoung, ne, "hs_young"},
+        {s->conc_myi, d.cmyi, ne, "conc_myi"}, {s->thick_myi, d.tmyi, ne, "thick_myi"},
     };
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }  // never a half-made step without an error
+    if (int rc = launch_gave_up(h)) return rc;
     if (s->damage || s->sigma[0] || s->sigma[1] || s->sigma[2]) ensure_arrays(h);
-    for (auto &c : cp) if (c.dst) pin_host_buffer(h, c.dst, c.bytes);
-    for (auto &c : cp) if (c.dst) HIPCHK(h, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NXS_OK;
+    return copy_rows(h, cp, (int)(sizeof cp / sizeof *cp), hipMemcpyDeviceToHost);
 } catch (...) { return dyn_caught(h, "nxs_dyn_get_state"); }
 
 int nxs_dyn_set_forcing(nxs_dyn_handle *h, const nxs_dyn_forcing *f) try {
@@ -2755,12 +2817,10 @@ int nxs_dyn_get_coupled(nxs_dyn_handle *h, nxs_dyn_coupled *c) try {
     if (c->conc_fsd && !h->dw.conc_fsd) return fail(h, NXS_ERR_INVALID, "get_coupled: conc_fsd is not attached");
     if (c->conc_fsd && c->num_fsd_bins != h->dw.nbins) return fail(h, NXS_ERR_INVALID, "get_coupled: %d bins asked for, %d attached", c->num_fsd_bins, h->dw.nbins);
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    if (int rc = launch_gave_up(h)) return rc;
     const size_t Ne = h->dm.Ne, nf = (size_t)h->dw.nbins * Ne;
-    if (c->cum_damage) { pin_host_buffer(h, c->cum_damage, Ne * sizeof(double)); HIPCHK(h, hipMemcpyAsync(c->cum_damage, h->dw.cum_damage, Ne * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
-    if (c->conc_fsd) { pin_host_buffer(h, c->conc_fsd, nf * sizeof(double)); HIPCHK(h, hipMemcpyAsync(c->conc_fsd, h->dw.conc_fsd, nf * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NXS_OK;
+    const RowCopy cp[2] = {{c->cum_damage, h->dw.cum_damage, Ne * sizeof(double), "cum_damage"}, {c->conc_fsd, h->dw.conc_fsd, nf * sizeof(double), "conc_fsd"}};
+    return copy_rows(h, cp, 2, hipMemcpyDeviceToHost);
 } catch (...) { return dyn_caught(h, "nxs_dyn_get_coupled"); }
 
 // ---- nxs_dyn_regrid: interpFields() + assignVariables() on the live handle (include/nxs_dyn.h)
@@ -2792,7 +2852,7 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     const auto t_start = std::chrono::steady_clock::now();
     auto t_phase = t_start;
     nxs_dyn_regrid_info inf{};
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    if (int rc = launch_gave_up(h)) return rc;
     ensure_arrays(h);   // M_sigma / M_damage out of the sub-step loop's records
 
     // ---- the column table: sortPrognosticVars (FE.cpp:2087-2111)
@@ -2922,10 +2982,10 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     for (int k = 0; k < RA_COUNT; ++k) if (!ad.p[k]) mem.release(given.p[k]);   // (taken: the state pool's now)
     if (rc_mesh) return rc_mesh;
     h->have_state = true;
-    if (carry_cum) { h->coupled_allocs.push_back(new_cum); mem.release(new_cum); h->d_cum = new_cum; h->dw.cum_damage = new_cum; }
-    if (carry_fsd) { h->coupled_allocs.push_back(new_fsd); mem.release(new_fsd); h->d_fsd = new_fsd; h->fsd_capacity = (size_t)nbins * Ne_new; h->dw.conc_fsd = new_fsd; h->dw.nbins = nbins; }
-    if (carry_mech) { h->coupled_allocs.push_back(new_mech); mem.release(new_mech); h->d_mech = new_mech; h->mech_capacity = (size_t)nbins * Ne_new; h->fsd_mech = new_mech; }
-    if (carry_cumw) { h->coupled_allocs.push_back(new_cumw); mem.release(new_cumw); h->d_cumw = new_cumw; h->fsd_cumw = new_cumw; }
+    if (carry_cum) { coupled_adopt(h, &h->d_cum, &h->dw.cum_damage, new_cum); mem.release(new_cum); }
+    if (carry_fsd) { coupled_adopt(h, &h->d_fsd, &h->dw.conc_fsd, new_fsd); mem.release(new_fsd); h->fsd_capacity = (size_t)nbins * Ne_new; h->dw.nbins = nbins; }
+    if (carry_mech) { coupled_adopt(h, &h->d_mech, &h->fsd_mech, new_mech); mem.release(new_mech); h->mech_capacity = (size_t)nbins * Ne_new; }
+    if (carry_cumw) { coupled_adopt(h, &h->d_cumw, &h->fsd_cumw, new_cumw); mem.release(new_cumw); }
     if (h->drift) nxs_drifters::state_changed(h->drift);
     for (const Down &d : downs) HIPCHK(h, hipMemcpyAsync(d.host, d.dev, (size_t)Ne_new * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2954,7 +3014,7 @@ int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *dg, const doubl
     if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "ice_diagnostics needs set_mesh and put_state");
     HIPCHK(h, hipSetDevice(h->device));
     const size_t Ne = (size_t)h->dm.Ne;
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    if (int rc = launch_gave_up(h)) return rc;
     if (!h->d_icediag) { int rc = dev_alloc(h, h->state_allocs, &h->d_icediag, NXS_ICE_DIAG_FIELDS * Ne); if (rc) return rc; }
     hipLaunchKernelGGL(k_ice_diagnostics, dim3(nblocks(h->dm.Ne)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, h->dp.young_cat ? 1 : 0,
                        h->sig_loc ? (const double *)h->ds.S4a : (const double *)nullptr, h->d_icediag);
@@ -3035,7 +3095,7 @@ int nxs_dyn_means_update(nxs_dyn_handle *h, double time_factor) try {
     }
     HIPCHK(h, hipSetDevice(h->device));
     // (the opt-in one-launch loops can give up half-way: never a mean of a half-made step without an error -- as nxs_dyn_ice_diagnostics; the default path stays asynchronous)
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    if (int rc = launch_gave_up(h)) return rc;
     const int young = h->dp.young_cat ? 1 : 0;
     for (int k = 0; k < 2; ++k) {
         MeansTable &t = h->means_tab[k];
@@ -3109,7 +3169,7 @@ int nxs_dyn_means_to_grid(nxs_dyn_handle *h, const nxs_dyn_means_grid *g, double
     std::vector<double> um(2 * (size_t)Nn), x(Nn), y(Nn);
     HIPCHK(h, hipMemcpyAsync(um.data(), h->ds.UM, um.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (also: the accumulators are complete before the sampling, which runs on the interpolation's own stream)
-    if (h->res_ready || h->flow_ready) { int rc = resident_error(h); if (rc) return rc; }
+    if (h->res_ready || h->flow_ready) { int rc = resident_error(h); if (rc) return rc; }   // (synchronised above)
     for (int i = 0; i < Nn; ++i) { x[i] = h->h_x0[i] + um[i]; y[i] = h->h_y0[i] + um[(size_t)i + Nn]; }
     std::vector<int32_t> index(3 * (size_t)Ne);
     for (int e = 0; e < Ne; ++e) for (int k = 0; k < 3; ++k) index[3 * (size_t)e + k] = h->h_t[k][e] + 1;
@@ -3563,7 +3623,7 @@ int nxs_dyn_step_host(nxs_dyn_handle *h, nxs_dyn_state *s, const nxs_dyn_forcing
     for (const Cp &c : up) HIPCHK(h, hipMemcpyAsync(c.dev, c.host, c.bytes, hipMemcpyHostToDevice, h->stream));
     h->have_state = true; h->have_forcing = true;
     if ((rc = nxs_dyn_step(h))) { (void)hipStreamSynchronize(h->stream); return rc; }
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); if ((rc = resident_error(h))) return rc; }
+    if ((rc = launch_gave_up(h))) return rc;
     ensure_arrays(h);
     const Cp down[] = {{d.VT, s->VT, n2}, {d.UM, s->UM, n2}, {d.UT, s->UT, n2}, {d.conc, s->conc, ne}, {d.thick, s->thick, ne}, {d.snow, s->snow_thick, ne}, {d.damage, s->damage, ne},
                        {d.ridge, s->ridge_ratio, ne}, {d.s0, s->sigma[0], ne}, {d.s1, s->sigma[1], ne}, {d.s2, s->sigma[2], ne}, {d.cmyi, s->conc_myi, ne}, {d.tmyi, s->thick_myi, ne}};

@@ -15,10 +15,35 @@ int device_cus(const nxs_dyn_handle *h) {
     return std::max(cus, 1);
 }
 
+// sums over the D-ring tables, for nxs_dyn_get_traffic_model; the most own nodes of a patch
+void pair_patch_sums(nxs_dyn_handle *h, const HostPatches2 &hp, int D) {
+    auto &S2 = h->sums2;
+    S2 = nxs_dyn_handle::PatchSums2{};
+    S2.nP = hp.nP; S2.N.assign(D + 1, 0.); S2.E.assign(D, 0.);
+    h->pair_own_max = 0;
+    for (int q = 0; q < hp.nP; ++q) {
+        h->pair_own_max = std::max(h->pair_own_max, hp.ncnt[(size_t)q * (D + 1)]);
+        for (int i = 0; i <= D; ++i) S2.N[i] += hp.ncnt[(size_t)q * (D + 1) + i];
+        for (int i = 0; i < D; ++i) S2.E[i] += hp.ecnt[(size_t)q * D + i];
+        S2.E1_second_round += std::max(0, hp.ecnt[(size_t)q * D] - 512);
+        for (int l = 0; l < hp.ecnt[(size_t)q * D]; ++l) S2.W += hp.pelem[(size_t)q * hp.EDmax + l] >= 0 ? 1. : 0.;
+    }
+}
+// k_substep_pair's {element, corner slots in ten bits each}: 8 bytes per element instead of 12 (pair_kernel_fits: at most 1024 staged nodes)
+int upload_pet2(nxs_dyn_handle *h, const HostPatches2 &hp, DevPatches2 &d) {
+    std::vector<int> pet(2 * hp.pelem.size());
+    for (size_t i = 0; i < hp.pelem.size(); ++i) {
+        pet[2 * i] = hp.pelem[i];
+        pet[2 * i + 1] = (int)hp.ptri[4 * i] | ((int)hp.ptri[4 * i + 1] << 10) | ((int)hp.ptri[4 * i + 2] << 20);
+    }
+    const int *dpet = nullptr;
+    if (int rc = dev_upload(h, h->pair_allocs, &dpet, pet)) return rc;
+    d.pet = reinterpret_cast<const int2 *>(dpet);
+    return NXS_OK;
+}
+
 int upload_patches2(nxs_dyn_handle *h, int D, bool single_round_only, bool for_pair_kernel = false) {
-    drop_pool(h, h->pair_allocs);
-    h->dpch2 = DevPatches2{};
-    h->pair_ready = false;
+    release_pair_patches(h);
     const DevMesh &m = h->dm;
     nxs_cut::Patch2Plan plan;
     const std::string why = nxs_cut::plan_patches2(mesh_view(h), (h->hp && h->hp->used_hilbert) || h->pair_hilbert == 1, h->pair_nodes, D, single_round_only, device_cus(h),
@@ -29,8 +54,7 @@ int upload_patches2(nxs_dyn_handle *h, int D, bool single_round_only, bool for_p
     h->pair_threads_chosen = plan.threads;
     h->pair_kernel = plan.pair_kernel;
     if (plan.pair_kernel && h->pair_nodes == 0) h->pair_hint = plan.P_fit;
-    h->pair_own_max = 0;
-    for (int q = 0; q < hp.nP; ++q) h->pair_own_max = std::max(h->pair_own_max, hp.ncnt[(size_t)q * (D + 1)]);
+    pair_patch_sums(h, hp, D);
     if (getenv("NXS_DEBUG_PATCHES")) {
         std::vector<double> se(D, 0.), sn(D + 1, 0.);
         for (int q = 0; q < hp.nP; ++q) { for (int i = 0; i < D; ++i) se[i] += hp.ecnt[(size_t)q * D + i]; for (int i = 0; i <= D; ++i) sn[i] += hp.ncnt[(size_t)q * (D + 1) + i]; }
@@ -40,17 +64,6 @@ int upload_patches2(nxs_dyn_handle *h, int D, bool single_round_only, bool for_p
         fprintf(stderr, "; nodes per level x");
         for (int i = 0; i <= D; ++i) fprintf(stderr, " %.3f", sn[i] / std::max(m.Nn, 1));
         fprintf(stderr, "\n");
-    }
-    {   // sums over the tables, for nxs_dyn_get_traffic_model
-        auto &S2 = h->sums2;
-        S2 = nxs_dyn_handle::PatchSums2{};
-        S2.nP = hp.nP; S2.N.assign(D + 1, 0.); S2.E.assign(D, 0.);
-        for (int q = 0; q < hp.nP; ++q) {
-            for (int i = 0; i <= D; ++i) S2.N[i] += hp.ncnt[(size_t)q * (D + 1) + i];
-            for (int i = 0; i < D; ++i) S2.E[i] += hp.ecnt[(size_t)q * D + i];
-            S2.E1_second_round += std::max(0, hp.ecnt[(size_t)q * D] - 512);
-            for (int l = 0; l < hp.ecnt[(size_t)q * D]; ++l) S2.W += hp.pelem[(size_t)q * hp.EDmax + l] >= 0 ? 1. : 0.;
-        }
     }
     DevPatches2 &d = h->dpch2;
     d.nP = hp.nP; d.D = D; d.NDmax = hp.NDmax; d.NSmax = hp.NSmax; d.EDmax = hp.EDmax; d.ESmax = hp.ESmax; d.Wp = hp.Wp;
@@ -62,16 +75,7 @@ int upload_patches2(nxs_dyn_handle *h, int D, bool single_round_only, bool for_p
     if ((rc = dev_upload(h, h->pair_allocs, &d.ptri, hp.ptri))) return rc;
     if ((rc = dev_upload(h, h->pair_allocs, &d.pfan, hp.pfan))) return rc;
     d.pet = nullptr;
-    if (plan.pair_kernel) {   // {element, corner slots in ten bits each}: 8 bytes per element instead of 12 (pair_kernel_fits: at most 1024 staged nodes)
-        std::vector<int> pet(2 * hp.pelem.size());
-        for (size_t i = 0; i < hp.pelem.size(); ++i) {
-            pet[2 * i] = hp.pelem[i];
-            pet[2 * i + 1] = (int)hp.ptri[4 * i] | ((int)hp.ptri[4 * i + 1] << 10) | ((int)hp.ptri[4 * i + 2] << 20);
-        }
-        const int *dpet = nullptr;
-        if ((rc = dev_upload(h, h->pair_allocs, &dpet, pet))) return rc;
-        d.pet = reinterpret_cast<const int2 *>(dpet);
-    }
+    if (plan.pair_kernel && (rc = upload_pet2(h, hp, d))) return rc;
     d.pfan8 = nullptr;
     {   // the first eight fan entries of every solved node, decoded: the LDS index of the corner's force, two per word (nxs_cut::decode_fan8)
         std::vector<unsigned int> f8;
@@ -86,8 +90,6 @@ int upload_patches2(nxs_dyn_handle *h, int D, bool single_round_only, bool for_p
     h->pair_ready = true;
     h->pair_depth_built = D;
     // the same patches as ONE data-flow launch per step (k_substep_flow): what each patch waits for, the queues, the counters
-    h->flow = PairFlow{};
-    h->flow_ready = false;
     if (plan.pair_kernel && plan.threads == 512 && flow_wanted(h) && !h->flow_failed) {
         std::vector<int> ptr, dep;
         auto refuse = [&](const char *w) { if (getenv("NXS_DEBUG_PATCHES")) fprintf(stderr, "[nxs] one data-flow launch per step not possible: %s\n", w); return NXS_OK; };
@@ -121,11 +123,7 @@ int upload_patches2(nxs_dyn_handle *h, int D, bool single_round_only, bool for_p
 // ticket words -- and the claim on the device's workgroup slots for the patches that wait for a neighbour rank INSIDE the launch (they all have to be on
 // a CU at once; ranks that share a device share its slots: nxs_resident_registry.hpp).  NXS_OK with pair_ready == false: not possible here.
 int upload_pair_patches_mr(nxs_dyn_handle *h) {
-    drop_pool(h, h->pair_allocs);
-    h->dpch2 = DevPatches2{};
-    h->pair_ready = false;
-    h->pairh = PairHalo{};
-    if (h->pair_claim) { resident_registry_release(h, nxs_reg::KIND_PAIR); h->pair_claim = false; }
+    release_pair_patches(h);
     const DevMesh &m = h->dm;
     std::vector<char> sent((size_t)std::max(m.No, 1), 0);
     for (int n : h->h_send_index) if (n >= 0 && n < m.No) sent[n] = 1;
@@ -149,19 +147,7 @@ int upload_pair_patches_mr(nxs_dyn_handle *h) {
     }
     if (h->pair_nodes == 0) h->pair_hint = plan.P;
     h->pair_lds = plan.lds; h->pair_threads_chosen = 512; h->pair_kernel = true;
-    h->pair_own_max = 0;
-    for (int q = 0; q < hp.nP; ++q) h->pair_own_max = std::max(h->pair_own_max, hp.ncnt[(size_t)q * 3]);
-    {
-        auto &S2 = h->sums2;
-        S2 = nxs_dyn_handle::PatchSums2{};
-        S2.nP = hp.nP; S2.N.assign(3, 0.); S2.E.assign(2, 0.);
-        for (int q = 0; q < hp.nP; ++q) {
-            for (int i = 0; i <= 2; ++i) S2.N[i] += hp.ncnt[(size_t)q * 3 + i];
-            for (int i = 0; i < 2; ++i) S2.E[i] += hp.ecnt[(size_t)q * 2 + i];
-            S2.E1_second_round += std::max(0, hp.ecnt[(size_t)q * 2] - 512);
-            for (int l = 0; l < hp.ecnt[(size_t)q * 2]; ++l) S2.W += hp.pelem[(size_t)q * hp.EDmax + l] >= 0 ? 1. : 0.;
-        }
-    }
+    pair_patch_sums(h, hp, 2);
     if (getenv("NXS_DEBUG_PATCHES"))
         fprintf(stderr, "[nxs] rank %d pair patches (several ranks): P=%d nP=%d (%d in the exchange, %d of them band) EDmax=%d ESmax=%d NDmax=%d NSmax=%d lds=%zu B; elements x %.3f / %.3f, nodes x %.3f / %.3f\n",
                 h->rank, plan.P, hp.nP, plan.nG, plan.nBand, hp.EDmax, hp.ESmax, hp.NDmax, hp.NSmax, plan.lds, h->sums2.E[0] / std::max(m.Ne, 1), h->sums2.E[1] / std::max(m.Ne, 1),
@@ -175,16 +161,7 @@ int upload_pair_patches_mr(nxs_dyn_handle *h) {
     if ((rc = dev_upload(h, h->pair_allocs, &d.pelem, hp.pelem))) return rc;
     if ((rc = dev_upload(h, h->pair_allocs, &d.ptri, hp.ptri))) return rc;
     if ((rc = dev_upload(h, h->pair_allocs, &d.pfan, hp.pfan))) return rc;
-    {
-        std::vector<int> pet(2 * hp.pelem.size());
-        for (size_t i = 0; i < hp.pelem.size(); ++i) {
-            pet[2 * i] = hp.pelem[i];
-            pet[2 * i + 1] = (int)hp.ptri[4 * i] | ((int)hp.ptri[4 * i + 1] << 10) | ((int)hp.ptri[4 * i + 2] << 20);
-        }
-        const int *dpet = nullptr;
-        if ((rc = dev_upload(h, h->pair_allocs, &dpet, pet))) return rc;
-        d.pet = reinterpret_cast<const int2 *>(dpet);
-    }
+    if ((rc = upload_pet2(h, hp, d))) return rc;
     {
         std::vector<unsigned int> f8;
         nxs_cut::decode_fan8(hp, f8);
@@ -206,8 +183,7 @@ int upload_pair_patches_mr(nxs_dyn_handle *h) {
 }
 
 int upload_host_patches(nxs_dyn_handle *h, const HostPatches &hp) {
-    drop_pool(h, h->patch_allocs);
-    release_resident(h);  // (the resident loop's tables describe the patches that go now: the tables, the second exchange buffer, the claim on the device's slots)
+    release_patches(h);
     {   // sums over the tables, for nxs_dyn_get_traffic_model
         auto &S1 = h->sums1;
         S1 = nxs_dyn_handle::PatchSums{};
@@ -218,7 +194,6 @@ int upload_host_patches(nxs_dyn_handle *h, const HostPatches &hp) {
         }
     }
     DevPatches &d = h->dpch;
-    d = DevPatches{};
     if (hp.Mmax > 1024) return fail(h, NXS_ERR_INVALID, "a patch stages %d nodes (at most 1024: choose smaller patches)", hp.Mmax);
     d.nP = hp.nP; d.Pmax = hp.Pmax; d.Emax = hp.Emax; d.Mmax = hp.Mmax; d.Wp = hp.Wp;
     int rc;
@@ -236,7 +211,6 @@ int upload_host_patches(nxs_dyn_handle *h, const HostPatches &hp) {
     d.pet = reinterpret_cast<const int2 *>(dpet);
     // k_prep_fused: the bamg-order rows in patch slots; a table that does not fit this mesh, or patches too large for its LDS, leave
     // the two separate prep kernels in place
-    h->prep_lds = 0;
     d.prow = nullptr; d.W1 = h->dm.W1;
     if (!h->h_n2e.empty() && nxs_cut::prep_fused_lds_of(hp) <= 160 * 1024) {   // (several ranks too, since round 5: the rows of the OWN nodes; the ghosts have a pass of their own)
         std::vector<unsigned short> rows;
@@ -251,11 +225,9 @@ int upload_host_patches(nxs_dyn_handle *h, const HostPatches &hp) {
 }
 
 int upload_patches(nxs_dyn_handle *h) {
-    drop_pool(h, h->patch_allocs);
-    release_resident(h);
-    h->dpch = DevPatches{};
+    release_patches(h);
+    release_halo_fused(h);   // (its tables refer to the patches that go now)
     h->fused_lds = 0;
-    h->hf_ready = false;
     const DevMesh &m = h->dm;
     nxs_cut::PatchPlan plan;
     const std::string why = nxs_cut::plan_patches(mesh_view(h), h->patch_nodes, h->fused == 4, device_cus(h), plan, NXS_CUT_RES_EPT, !h->no_big_cut, h->band_nodes < 0 ? 48 : h->band_nodes);
@@ -276,9 +248,7 @@ int upload_patches(nxs_dyn_handle *h) {
 
 // Node-ring patches for the open-water smoother alone (see nxs_cut::plan_smooth_patches).
 int build_smooth_patches(nxs_dyn_handle *h, int D) {
-    drop_pool(h, h->sm_allocs);
-    h->dsm = DevPatches2{};
-    h->sm_ready = false;
+    release_smooth_patches(h);
     const DevMesh &m = h->dm;
     nxs_cut::SmoothPlan plan;
     const std::string why = nxs_cut::plan_smooth_patches(mesh_view(h), h->hp && h->hp->used_hilbert, D, h->h_n2n, h->h_n2n_cnt, m.W2, plan);

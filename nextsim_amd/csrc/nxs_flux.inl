@@ -55,33 +55,18 @@ int nxs_dyn_flux_configure(nxs_dyn_handle *h, const nxs_dyn_flux_config *c) try 
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_flux_configure"); }
 
-// the rows of the atmosphere and of nxs_dyn_flux_state live in the state pool (they go with the mesh); a row is PRESENT once it was given
-static int flux_upload(nxs_dyn_handle *h, double **dev, const double *const *src, int count, unsigned *have) {
-    const size_t Ne = h->dm.Ne;
-    HIPCHK(h, hipSetDevice(h->device));
-    for (int k = 0; k < count; ++k) {
-        if (!src[k]) continue;
-        if (!dev[k]) { if (int rc = dev_alloc(h, h->state_allocs, &dev[k], Ne)) return rc; }
-        pin_host_buffer(h, src[k], Ne * sizeof(double));
-        HIPCHK(h, hipMemcpyAsync(dev[k], src[k], Ne * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < count; ++k) if (src[k]) *have |= 1u << k;
-    return NXS_OK;
-}
-
 int nxs_dyn_flux_set_atmosphere(nxs_dyn_handle *h, const nxs_dyn_flux_atmosphere *a) try {
     if (!h || !a) return NXS_ERR_INVALID;
     if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "flux_set_atmosphere before set_mesh");
     const double *src[FLUX_ATM_ROWS] = {a->tair, a->mslp, a->Qsw_in, a->humidity, a->longwave};
-    return flux_upload(h, h->d_flux_atm, src, FLUX_ATM_ROWS, &h->flux_atm_have);
+    return upload_rows(h, h->d_flux_atm, src, FLUX_ATM_ROWS, &h->flux_atm_have);
 } catch (...) { return dyn_caught(h, "nxs_dyn_flux_set_atmosphere"); }
 
 int nxs_dyn_flux_put(nxs_dyn_handle *h, const nxs_dyn_flux_state *s) try {
     if (!h || !s) return NXS_ERR_INVALID;
     if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "flux_put before set_mesh");
     const double *src[FLUX_ST_ROWS] = {s->tice0, s->tsurf_young, s->sst, s->sss, s->drag_ti, s->drag_ti_young, s->pond_fraction, s->lid_volume};
-    return flux_upload(h, h->d_flux_st, src, FLUX_ST_ROWS, &h->flux_st_have);
+    return upload_rows(h, h->d_flux_st, src, FLUX_ST_ROWS, &h->flux_st_have);
 } catch (...) { return dyn_caught(h, "nxs_dyn_flux_put"); }
 
 int nxs_dyn_flux_get(nxs_dyn_handle *h, nxs_dyn_flux_state *s) try {
@@ -92,11 +77,7 @@ int nxs_dyn_flux_get(nxs_dyn_handle *h, nxs_dyn_flux_state *s) try {
     for (int k = 0; k < FLUX_ST_ROWS; ++k)
         if (dst[k] && !(h->flux_st_have & (1u << k))) return fail(h, NXS_ERR_STATE, "flux_get: %s was never put on this mesh", name[k]);
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t bytes = (size_t)h->dm.Ne * sizeof(double);
-    for (int k = 0; k < FLUX_ST_ROWS; ++k)
-        if (dst[k]) { pin_host_buffer(h, dst[k], bytes); HIPCHK(h, hipMemcpyAsync(dst[k], h->d_flux_st[k], bytes, hipMemcpyDeviceToHost, h->stream)); }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NXS_OK;
+    return download_rows(h, dst, h->d_flux_st, FLUX_ST_ROWS);
 } catch (...) { return dyn_caught(h, "nxs_dyn_flux_get"); }
 
 int nxs_dyn_fluxes(nxs_dyn_handle *h) try {   // thermo()'s "fluxes" timer, FE.cpp:5214-5277
@@ -108,7 +89,7 @@ int nxs_dyn_fluxes(nxs_dyn_handle *h) try {   // thermo()'s "fluxes" timer, FE.c
     if (h->flux_st_have != (1u << FLUX_ST_ROWS) - 1)
         return fail(h, NXS_ERR_STATE, "fluxes: a flux row is missing on this mesh (nxs_dyn_flux_put after set_mesh / regrid; mask of the rows present 0x%x)", h->flux_st_have);
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    if (int rc = launch_gave_up(h)) return rc;
     const size_t Ne = h->dm.Ne;
     if (!h->d_flux_out) { if (int rc = dev_alloc(h, h->state_allocs, &h->d_flux_out, (size_t)FLUX_ROWS * Ne)) return rc; }
     if (!h->d_tau_ow) h->d_tau_ow = h->d_flux_out + (size_t)FLUX_TAU_OW * Ne;   // (else: the row nxs_dyn_means_set_tau_ow made; both are the state pool's)
@@ -133,12 +114,8 @@ int nxs_dyn_fluxes_get(nxs_dyn_handle *h, const nxs_dyn_flux_rows *out, const do
     if (!h) return NXS_ERR_INVALID;
     if (!h->have_mesh || !h->flux_done) return fail(h, NXS_ERR_STATE, "fluxes_get before nxs_dyn_fluxes on this mesh");
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t Ne = h->dm.Ne, bytes = Ne * sizeof(double);
-    for (int k = 0; k < FLUX_ROWS; ++k) {
-        const double *row = k == FLUX_TAU_OW ? h->d_tau_ow : h->d_flux_out + (size_t)k * Ne;
-        if (device_rows) device_rows[k] = row;
-        if (out && out->row[k]) { pin_host_buffer(h, out->row[k], bytes); HIPCHK(h, hipMemcpyAsync(out->row[k], row, bytes, hipMemcpyDeviceToHost, h->stream)); }
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return NXS_OK;
+    const double *row[FLUX_ROWS];
+    for (int k = 0; k < FLUX_ROWS; ++k) row[k] = k == FLUX_TAU_OW ? h->d_tau_ow : h->d_flux_out + (size_t)k * h->dm.Ne;
+    if (device_rows) std::copy(row, row + FLUX_ROWS, device_rows);
+    return download_rows(h, out ? out->row : nullptr, row, FLUX_ROWS);
 } catch (...) { return dyn_caught(h, "nxs_dyn_fluxes_get"); }

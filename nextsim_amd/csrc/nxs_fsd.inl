@@ -107,14 +107,13 @@ int nxs_dyn_fsd_get(nxs_dyn_handle *h, nxs_dyn_fsd_state *s) try {
     if (s->conc_mech_fsd && s->num_fsd_bins != h->dw.nbins) return fail(h, NXS_ERR_INVALID, "fsd_get: %d bins asked for, %d attached", s->num_fsd_bins, h->dw.nbins);
     HIPCHK(h, hipSetDevice(h->device));
     const size_t Ne = h->dm.Ne, nf = (size_t)h->dw.nbins * Ne;
-    if (s->conc_mech_fsd) { pin_host_buffer(h, s->conc_mech_fsd, nf * sizeof(double)); HIPCHK(h, hipMemcpyAsync(s->conc_mech_fsd, h->fsd_mech, nf * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
-    if (s->cum_wave_damage) { pin_host_buffer(h, s->cum_wave_damage, Ne * sizeof(double)); HIPCHK(h, hipMemcpyAsync(s->cum_wave_damage, h->fsd_cumw, Ne * sizeof(double), hipMemcpyDeviceToHost, h->stream)); }
     int crash = 0;
     if (h->d_fsd_flags) {   // the crash conditions of weldingRoach since the last get: reported once
         HIPCHK(h, hipMemcpyAsync(&crash, h->d_fsd_flags + FSD_FLAG_WELD_CRASH, sizeof crash, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_fsd_flags + FSD_FLAG_WELD_CRASH, 0, sizeof(int), h->stream));
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const RowCopy cp[2] = {{s->conc_mech_fsd, h->fsd_mech, nf * sizeof(double), "conc_mech_fsd"}, {s->cum_wave_damage, h->fsd_cumw, Ne * sizeof(double), "cum_wave_damage"}};
+    if (int rc = copy_rows(h, cp, 2, hipMemcpyDeviceToHost)) return rc;
     s->weld_crash = crash;
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_fsd_get"); }
@@ -129,7 +128,7 @@ static int fsd_ready(nxs_dyn_handle *h, const char *what, bool need_mech, FsdArr
     if ((need_mech || h->fsd_cfg.distinguish) && !h->fsd_mech)
         return fail(h, NXS_ERR_STATE, "%s reads M_conc_mech_fsd (%s): attach it with nxs_dyn_fsd_put", what, h->fsd_cfg.distinguish ? "distinguish_mech_fsd" : "fsd_damage_type 1 / 2");
     HIPCHK(h, hipSetDevice(h->device));
-    if (h->res_ready || h->flow_ready) { HIPCHK(h, hipStreamSynchronize(h->stream)); int rc = resident_error(h); if (rc) return rc; }
+    if (int rc = launch_gave_up(h)) return rc;
     const bool rec = h->sig_loc && h->dp.dynamics_type == NXS_DYN_BBM;   // M_damage in the records the sub-step loop left behind (k_pack_state)
     *a = FsdArrays{h->dm.Ne, h->dp.young_cat, h->dw.conc_fsd, h->fsd_mech, h->dw.cum_damage, h->fsd_cumw, h->ds.conc, h->ds.cyoung, h->ds.thick, h->ds.hyoung, h->ds.theal,
                    rec ? h->ds.S4a + 3 : h->ds.damage, rec ? 4 : 1, h->d_fsd_flags};
