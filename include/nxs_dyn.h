@@ -29,6 +29,7 @@
  *   #ifdef OASIS: initFsd / updateFSD / redistributeFSD / weldingRoach   nxs_fsd_bins, nxs_dyn_fsd_* (FE.cpp:7408-7576, 4674-4732, 4268-4483, 4737-4870, 5888-5896)
  *   thermo(): OWBulkFluxes + IABulkFluxes       nxs_dyn_fluxes, nxs_dyn_flux_* (FE.cpp:5214-5277, 5032-5159, 6148-6353, 4966-5019, 6359-6389, 6454-6535)
  *   thermo(): thermoWinton / thermoIce0 columns nxs_dyn_column, nxs_dyn_column_* (FE.cpp:5306-5411, 6396-6448, 6633-6962)
+ *   thermo(): the slab loop from new ice to tracers nxs_dyn_slab, nxs_dyn_slab_*, nxs_slab_* (FE.cpp:5413-6133, 6538-6627)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -820,6 +821,117 @@ NXS_API int nxs_dyn_column_put(nxs_dyn_handle *h, const nxs_dyn_column_state *s)
 NXS_API int nxs_dyn_column_get_state(nxs_dyn_handle *h, nxs_dyn_column_state *s);
 NXS_API int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt);
 NXS_API int nxs_dyn_column_get(nxs_dyn_handle *h, const nxs_dyn_column_rows *out /* may be NULL */, const double **device_rows /* [NXS_COL_ROWS], may be NULL */);
+
+/* ---- The rest of thermo()'s slab loop on the device: FE.cpp:5413-6133 as a default (non-OASIS) build compiles it -- the assimilation flux (FE.cpp:5415-5425),
+ * section 6: new ice over open water and lateral melt (FE.cpp:5434-5646; newice_type 1 .. 4, type 3 with windSpeedElement, FE.cpp:6359-6370; melt_type 1, 2), the
+ * freeze-days block (FE.cpp:5649-5682), the new concentration and thickness with Winton's (38), (39), (26) (FE.cpp:5685-5711), the limit block (FE.cpp:5714-5728),
+ * section 7, section 8: the slab ocean with meltPonds (FE.cpp:5812-5846, 6538-6627), section 9: the temperature-dependent healing (FE.cpp:5854-5881), section 10: the
+ * diagnostics (FE.cpp:5903-5976) and the age and type tracers (FE.cpp:5980-6132).  One launch, a thread per element, ghost elements included.  It reads the rows of
+ * nxs_dyn_fluxes and of nxs_dyn_column -- both stay READ-ONLY: Qow, the reference's function-local vector, is a register copy, so nxs_dyn_fluxes_get answers the
+ * same after the call -- M_precip and, under NXS_COL_MLD_ROW, M_mld (nxs_dyn_column_set_forcing), and under newice_type 3 M_wind at the element's three nodes.
+ * The thermo type, the freezing point, freezingpoint_mu, snow_cond, the mixed-layer source and constant_mld are the column's configuration and ocean_albedo is the
+ * fluxes': one copy of each.  UPDATED IN PLACE: in nxs_dyn_state conc, thick, snow_thick, ridge_ratio, conc_young, h_young, hs_young, conc_myi, thick_myi and (under
+ * temp_dep_healing) time_relaxation_damage, so the next nxs_dyn_step reads them; in nxs_dyn_flux_state sst, sss and (under use_meltponds) pond_fraction,
+ * lid_volume; tice0 and under WINTON the column's tice1 / tice2; nxs_dyn_slab_state except conc_upd.  It writes NXS_SLAB_ROWS rows, the D_* diagnostics of thermo().
+ * The library knows no dates: the caller derives the five flags of nxs_dyn_slab_clock from M_current_time (FE.cpp:5653-5655, 5208, 5999, 6028, 6044).
+ * NOT BUILT, all of it #ifdef OASIS in the reference: melt_type 3 (FE.cpp:5592-5640; refused by the configuration check), the FSD branches of the limit block
+ * (FE.cpp:5729-5764), redistributeThermoFSD (FE.cpp:5768-5776), the in-loop weldingRoach (FE.cpp:5779-5797), the mechanical FSD healing of 9.b (FE.cpp:5883-5898),
+ * the OceanType::COUPLED guards (FE.cpp:5826-5841).  Because FE.cpp:5729-5764 would have to touch the bins, nxs_dyn_slab answers NXS_ERR_STATE while floe-size
+ * bins are attached (nxs_dyn_put_coupled with num_fsd_bins > 0): such a host keeps its loop.  The throw of a wrong newice_type / melt_type is NXS_ERR_INVALID at
+ * configuration.  nxs_dyn_regrid does NOT carry nxs_dyn_slab_state across a regrid: nxs_dyn_set_mesh and nxs_dyn_regrid make it missing again, like tice1 /
+ * tice2; the host fetches it before a regrid and puts it back after.  The rows are not wired into nxs_dyn_means_*: their device pointers are available.
+ *   nxs_slab_default_config   model/options.cpp:329-331, 397-403, 428-449, 543-548
+ *   nxs_slab_config_check     what nxs_dyn_slab_configure refuses, without a handle: newice_type outside 1 .. 4, melt_type outside 1 .. 2 (3 is the OASIS branch),
+ *                  hnull, PhiF, h_young_min, meltpond_depth_to_fraction, time_relaxation_damage or deltaT_relaxation_damage <= 0 (or NaN), h_young_max <=
+ *                  h_young_min; NXS_ERR_INVALID, the text in nxs_dyn_last_error(NULL)
+ *   nxs_slab_constants        TEST DOOR like nxs_col_constants: the constants compiled into the kernel, in the order NXS_SLAB_CONST_* names them
+ *   nxs_dyn_slab_configure    the configuration is the handle's and survives nxs_dyn_set_mesh
+ *   nxs_dyn_slab_put / nxs_dyn_slab_get_state   [Ne] host rows, NULL members as in nxs_dyn_flux_put / _get.  Which rows the launch NEEDS follows from the
+ *                  configuration: conc_upd only under use_assim_flux, pond_volume only under use_meltponds, the other eight always.  time_relaxation_damage is
+ *                  ignored by _put (it is nxs_dyn_put_state's) and returned by _get_state, which nxs_dyn_get_state cannot do (the member is const there)
+ *   nxs_dyn_slab              the launch, asynchronous on the handle's stream; dt is thermo()'s integer argument (ddt = dtime_step = double(dt): FE.cpp:1083-1084,
+ *                  8140).  NXS_ERR_INVALID: dt <= 0, a NULL clock.  NXS_ERR_STATE: before nxs_dyn_slab_configure; before the first nxs_dyn_column since the last
+ *                  nxs_dyn_set_mesh / nxs_dyn_regrid; while a needed row is missing; while floe-size bins are attached; newice_type 4 on a handle of the classic
+ *                  category and another newice_type on one of the young-ice category (the category is the handle's); on a second nxs_dyn_slab without a new
+ *                  nxs_dyn_column in between (the state has moved on and the column's rows are stale)
+ *   nxs_dyn_slab_get          exactly like nxs_dyn_column_get.  NXS_ERR_STATE before the first nxs_dyn_slab
+ * Debug array "slab_branches" [Ne] (nxs_dyn_debug_array): one word per element, a bit NXS_SLAB_BR_* per decision the element took; written by every launch. */
+enum { NXS_SLAB_CONST_CMIN = 0, NXS_SLAB_CONST_HMIN, NXS_SLAB_CONST_RHOW, NXS_SLAB_CONST_CPW, NXS_SLAB_CONST_RHOI, NXS_SLAB_CONST_RHOS, NXS_SLAB_CONST_LF,
+       NXS_SLAB_CONST_C, NXS_SLAB_CONST_KI, NXS_SLAB_CONST_SI, NXS_SLAB_CONST_DAYS_IN_SEC, NXS_SLAB_CONST_COUNT };
+enum { NXS_SLAB_BR_SUPERCOOLED = 1,     /* tw_new < tfrw (FE.cpp:5438) */
+       NXS_SLAB_BR_N2_HI_OLD = 2,       /* newice_type 2: hi_old > 0 */
+       NXS_SLAB_BR_N2_NEWICE = 4,       /* newice_type 2: no old ice, newice > 0 */
+       NXS_SLAB_BR_N3_H0 = 8,           /* newice_type 3: the wind's h0 is the larger */
+       NXS_SLAB_BR_N4_YOUNG = 16,        /* newice_type 4: M_conc_young > 0 */
+       NXS_SLAB_BR_N4_NOT_FILLED = 32,   /* ... the young ice does not fill its concentration (FE.cpp:5515) */
+       NXS_SLAB_BR_N4_SHARP = 64,        /* ... thicker than h_young_max_sharp (FE.cpp:5523) */
+       NXS_SLAB_BR_N4_NO_ROOM = 128,      /* ... no room for young ice (FE.cpp:5542) */
+       NXS_SLAB_BR_MELT = 256,            /* del_hi < 0 */
+       NXS_SLAB_BR_MELT_SIDE = 512,       /* melt_type 2: hi > 0; melt_type 1: M_conc < 1 */
+       NXS_SLAB_BR_DAY_FREEZE = 1024,     /* last step of the day, M_del_vi_tend > 0 */
+       NXS_SLAB_BR_DAY_MELT = 2048,       /* last step of the day, M_del_vi_tend < 0 */
+       NXS_SLAB_BR_CONC_GE_CMIN = 4096,   /* FE.cpp:5689 */
+       NXS_SLAB_BR_DEL_C_NEG = 8192,      /* FE.cpp:5692 */
+       NXS_SLAB_BR_LIMIT = 16384,          /* the limit block, FE.cpp:5714 */
+       NXS_SLAB_BR_RIDGE = 32768,          /* M_thick > old_vol (FE.cpp:5845) */
+       NXS_SLAB_BR_HEAL_ICE = 65536,       /* temp_dep_healing with M_thick > 0 */
+       NXS_SLAB_BR_POND_FLUSHED = 131072, NXS_SLAB_BR_LID_EXISTS = 262144, NXS_SLAB_BR_LID_FORMS = 524288, NXS_SLAB_BR_LID_REMOVED = 1048576,   /* meltPonds */
+       NXS_SLAB_BR_NO_ICE_TRACERS = 2097152, /* FE.cpp:5984 */
+       NXS_SLAB_BR_RESET = 4194304,          /* reset_myi */
+       NXS_SLAB_BR_OLD_MELT = 8388608,       /* FE.cpp:6101 */
+       NXS_SLAB_BR_ASSIM = 16777216,          /* the assimilation flux is taken (the pow) */
+       NXS_SLAB_BR_DENOM_CLAMP = 33554432,    /* FE.cpp:5833 */
+       NXS_SLAB_BR_SSS_BELOW_SI = 67108864,   /* si_eff = M_sss */
+       NXS_SLAB_BR_FREEZE_DAYS_GE = 134217728  /* M_freeze_days >= reset_freeze_days */ };
+typedef struct nxs_dyn_slab_config {
+    int32_t newice_type;               /* thermo.newice_type, 1 .. 4 */
+    int32_t melt_type;                 /* thermo.melt_type, 1 .. 2 */
+    int32_t use_assim_flux;            /* thermo.use_assim_flux */
+    int32_t temp_dep_healing;          /* dynamics.use_temperature_dependent_healing */
+    int32_t use_meltponds;             /* thermo.use_meltponds */
+    int32_t reset_by_date;             /* age.reset_by_date */
+    int32_t include_young_ice;         /* age.include_young_ice (forced false when reset_by_date is false: FE.cpp:5649-5650) */
+    int32_t equal_melting;             /* age.equal_melting */
+    double hnull;                      /* thermo.hnull */
+    double PhiF, PhiM;                 /* thermo.PhiF, thermo.PhiM */
+    double h_young_min, h_young_max;   /* thermo.h_young_min, _max [m]; h_young_max_sharp = .5*(h_young_min + h_young_max), FE.cpp:1198 */
+    double assim_flux_exponent;        /* thermo.assim_flux_exponent */
+    double reset_freeze_days;          /* age.reset_freeze_days */
+    double meltpond_runoff_fraction;   /* thermo.meltpond_runoff_fraction */
+    double meltpond_depth_to_fraction; /* thermo.meltpond_depth_to_fraction */
+    double time_relaxation_damage;     /* days_in_sec * dynamics.time_relaxation_damage [s] */
+    double deltaT_relaxation_damage;   /* dynamics.deltaT_relaxation_damage */
+} nxs_dyn_slab_config;
+typedef struct nxs_dyn_slab_state {
+    double *conc_upd;                  /* [Ne] M_conc_upd (read; needed under use_assim_flux) */
+    double *pond_volume;               /* [Ne] M_pond_volume (needed under use_meltponds) */
+    double *del_vi_tend, *freeze_days, *freeze_onset, *conc_summer, *thick_summer;   /* [Ne] M_del_vi_tend ... M_thick_summer */
+    double *fyi_fraction, *age_det, *age;                                            /* [Ne] M_fyi_fraction, M_age_det, M_age */
+    double *time_relaxation_damage;    /* [Ne] nxs_dyn_slab_get_state only: the device copy of nxs_dyn_state's row */
+} nxs_dyn_slab_state;
+typedef struct nxs_dyn_slab_clock {
+    int32_t first_step_of_day;         /* step_in_day == 1 (FE.cpp:5656) */
+    int32_t last_step_of_day;          /* step_in_day == num_steps_in_day (FE.cpp:5661) */
+    int32_t fyi_reset_now;             /* "%m%d" == "0915" && fmod(M_current_time, 1) == 0 (FE.cpp:5999) */
+    int32_t myi_reset_now;             /* "%m%d" == age.reset_date at midnight (FE.cpp:6028) */
+    int32_t onset_reset_now;           /* "%m%d" == "0801" at midnight (FE.cpp:6044) */
+} nxs_dyn_slab_clock;
+enum { NXS_SLAB_QA = 0, NXS_SLAB_QSW, NXS_SLAB_QLW, NXS_SLAB_QSH, NXS_SLAB_QLH, NXS_SLAB_QO, NXS_SLAB_QNOSUN, NXS_SLAB_QSW_OCEAN, NXS_SLAB_QASSIM, NXS_SLAB_DELS,
+       NXS_SLAB_FWFLUX_ICE, NXS_SLAB_FWFLUX, NXS_SLAB_BRINE, NXS_SLAB_EVAP, NXS_SLAB_RAIN,
+       NXS_SLAB_VICE_MELT, NXS_SLAB_DEL_VI_YOUNG, NXS_SLAB_DEL_HI, NXS_SLAB_DEL_HI_YOUNG, NXS_SLAB_NEWICE, NXS_SLAB_MLT_TOP, NXS_SLAB_MLT_BOT, NXS_SLAB_SNOW2ICE,
+       NXS_SLAB_ALBEDO, NXS_SLAB_SIALB,
+       NXS_SLAB_DEL_CI_MLT_MYI, NXS_SLAB_DEL_VI_MLT_MYI, NXS_SLAB_DEL_CI_RPLNT_MYI, NXS_SLAB_DEL_VI_RPLNT_MYI };
+#define NXS_SLAB_ROWS 29
+typedef struct nxs_dyn_slab_rows { double *row[NXS_SLAB_ROWS]; } nxs_dyn_slab_rows;   /* [Ne] each, indexed by NXS_SLAB_* */
+
+NXS_API int nxs_slab_default_config(nxs_dyn_slab_config *c);
+NXS_API int nxs_slab_config_check(const nxs_dyn_slab_config *c);
+NXS_API int nxs_slab_constants(double *out, int32_t count);
+NXS_API int nxs_dyn_slab_configure(nxs_dyn_handle *h, const nxs_dyn_slab_config *c);
+NXS_API int nxs_dyn_slab_put(nxs_dyn_handle *h, const nxs_dyn_slab_state *s);
+NXS_API int nxs_dyn_slab_get_state(nxs_dyn_handle *h, nxs_dyn_slab_state *s);
+NXS_API int nxs_dyn_slab(nxs_dyn_handle *h, int32_t dt, const nxs_dyn_slab_clock *clock);
+NXS_API int nxs_dyn_slab_get(nxs_dyn_handle *h, const nxs_dyn_slab_rows *out /* may be NULL */, const double **device_rows /* [NXS_SLAB_ROWS], may be NULL */);
 
 /* One dynamics step on the device-resident state: FE.cpp:8197-8214.  Asynchronous on the
  * handle's stream; nxs_dyn_synchronize() waits for it. */

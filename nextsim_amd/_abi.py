@@ -289,6 +289,51 @@ def column_config_struct(base: "ColumnConfig", **options) -> ColumnConfig:
     return c
 
 
+# ---- thermo()'s slab loop from new ice to tracers (include/nxs_dyn.h, nxs_slab_* / nxs_dyn_slab_* / nxs_dyn_slab)
+SLAB_CONSTANTS = ("cmin", "hmin", "rhow", "cpw", "rhoi", "rhos", "Lf", "C", "ki", "si", "days_in_sec")   # NXS_SLAB_CONST_*
+SLAB_CONFIG_INTS = ("newice_type", "melt_type", "use_assim_flux", "temp_dep_healing", "use_meltponds", "reset_by_date", "include_young_ice", "equal_melting")
+SLAB_CONFIG_REALS = ("hnull", "PhiF", "PhiM", "h_young_min", "h_young_max", "assim_flux_exponent", "reset_freeze_days", "meltpond_runoff_fraction",
+                     "meltpond_depth_to_fraction", "time_relaxation_damage", "deltaT_relaxation_damage")
+SLAB_STATE = ("conc_upd", "pond_volume", "del_vi_tend", "freeze_days", "freeze_onset", "conc_summer", "thick_summer", "fyi_fraction", "age_det", "age")
+SLAB_STATE_GET = SLAB_STATE + ("time_relaxation_damage",)   # what nxs_dyn_slab_get_state also returns
+SLAB_CLOCK = ("first_step_of_day", "last_step_of_day", "fyi_reset_now", "myi_reset_now", "onset_reset_now")
+SLAB_ROWS = ("Qa", "Qsw", "Qlw", "Qsh", "Qlh", "Qo", "Qnosun", "Qsw_ocean", "Qassim", "delS", "fwflux_ice", "fwflux", "brine", "evap", "rain",
+             "vice_melt", "del_vi_young", "del_hi", "del_hi_young", "newice", "mlt_top", "mlt_bot", "snow2ice", "albedo", "sialb",
+             "del_ci_mlt_myi", "del_vi_mlt_myi", "del_ci_rplnt_myi", "del_vi_rplnt_myi")   # NXS_SLAB_*: D_Qa ... D_del_vi_rplnt_myi
+NXS_SLAB_ROWS = 29
+assert len(SLAB_ROWS) == NXS_SLAB_ROWS
+SLAB_BRANCHES = ("supercooled", "n2_hi_old", "n2_newice", "n3_h0", "n4_young", "n4_not_filled", "n4_sharp", "n4_no_room", "melt", "melt_side", "day_freeze", "day_melt",
+                 "conc_ge_cmin", "del_c_neg", "limit", "ridge", "heal_ice", "pond_flushed", "lid_exists", "lid_forms", "lid_removed", "no_ice_tracers", "reset", "old_melt",
+                 "assim", "denom_clamp", "sss_below_si", "freeze_days_ge")   # NXS_SLAB_BR_*: bit k of the word of debug array "slab_branches"
+
+
+class SlabConfig(C.Structure):   # nxs_dyn_slab_config
+    _fields_ = [(k, C.c_int32) for k in SLAB_CONFIG_INTS] + [(k, C.c_double) for k in SLAB_CONFIG_REALS]
+
+
+class SlabState(C.Structure):   # nxs_dyn_slab_state
+    _fields_ = [(k, c_double_p) for k in SLAB_STATE_GET]
+
+
+class SlabClock(C.Structure):   # nxs_dyn_slab_clock
+    _fields_ = [(k, C.c_int32) for k in SLAB_CLOCK]
+
+
+class SlabRows(C.Structure):   # nxs_dyn_slab_rows
+    _fields_ = [("row", c_double_p * NXS_SLAB_ROWS)]
+
+
+def slab_config_struct(base: "SlabConfig", **options) -> SlabConfig:
+    """A copy of `base` (the defaults of nxs_slab_default_config) with keyword options named after nxs_dyn_slab_config's members."""
+    c = SlabConfig()
+    C.memmove(C.byref(c), C.byref(base), C.sizeof(c))
+    for k, v in options.items():
+        if k not in SLAB_CONFIG_INTS + SLAB_CONFIG_REALS:
+            raise KeyError(f"nxs_dyn_slab_config has no member {k!r}")
+        setattr(c, k, int(v) if k in SLAB_CONFIG_INTS else float(v))
+    return c
+
+
 # nxs_dyn_regrid (include/nxs_dyn.h): ModelVariable::interpTransformation and the flags of nxs_dyn_regrid_var
 NXS_TRANSFORM_NONE, NXS_TRANSFORM_CONC, NXS_TRANSFORM_THICK, NXS_TRANSFORM_ENTHALPY = range(4)
 TRANSFORMATIONS = {"none": NXS_TRANSFORM_NONE, "conc": NXS_TRANSFORM_CONC, "thick": NXS_TRANSFORM_THICK, "enthalpy": NXS_TRANSFORM_ENTHALPY}

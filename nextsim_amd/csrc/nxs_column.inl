@@ -122,6 +122,7 @@ int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt) try {   // thermo()'s slab loo
     LAUNCH(h, k_column, h->dm.Ne, a, c);
     HIPCHK(h, hipGetLastError());
     h->col_done = true;
+    h->col_fresh = true;   // (what nxs_dyn_slab spends: nxs_slab.inl)
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_column"); }
 

@@ -18,6 +18,7 @@
 //   k_regrid_*/k_check_* FE.cpp:8298-8309, 14536-14655 reductions
 //   k_fluxes                                  FE.cpp:5214-5277: thermo()'s atmospheric bulk fluxes, OWBulkFluxes + IABulkFluxes (nxs_flux_kernels.inl, nxs_dyn_fluxes)
 //   k_column                                  FE.cpp:5306-5411: thermo()'s ice columns, thermoWinton / thermoIce0 with the nudging and ice-ocean fluxes (nxs_column_kernels.inl, nxs_dyn_column)
+//   k_slab                                    FE.cpp:5413-6133: thermo()'s slab loop from new ice to tracers, with meltPonds (nxs_slab_kernels.inl, nxs_dyn_slab)
 //   k_fsd_init / _update / _breakup / _weld   FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870 + 5888-5896: the floe-size distribution (nxs_fsd_kernels.inl, nxs_dyn_fsd_*)
 //   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
 //
@@ -52,6 +53,7 @@
 #include "nxs_fsd_kernels.inl"
 #include "nxs_flux_kernels.inl"
 #include "nxs_column_kernels.inl"
+#include "nxs_slab_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -124,7 +126,15 @@ struct ColumnRows {        // thermo()'s ice columns: as above
     double *d_col_out = nullptr;                   // [COL_ROWS][Ne] what nxs_dyn_column_get returns
     bool col_done = false;
 };
-struct StateArrays : FluxRows, ColumnRows {   // the prognostic and work arrays (set_mesh) and everything made in their pool on demand
+struct SlabRows {          // thermo()'s slab loop from new ice to tracers: as above
+    double *d_slab_st[SLAB_ST_ROWS] = {};          // conc_upd, pond_volume, del_vi_tend, freeze_days, freeze_onset, conc_summer, thick_summer, fyi_fraction, age_det, age
+    unsigned slab_st_have = 0;
+    double *d_slab_out = nullptr;                  // [SLAB_ROWS][Ne] what nxs_dyn_slab_get returns
+    unsigned *d_slab_br = nullptr;                 // [Ne] the branch words (debug array "slab_branches")
+    bool col_fresh = false;                        // nxs_dyn_column ran and no nxs_dyn_slab has spent its rows yet
+    bool slab_done = false;
+};
+struct StateArrays : FluxRows, ColumnRows, SlabRows {   // the prognostic and work arrays (set_mesh) and everything made in their pool on demand
     std::vector<void *> state_allocs;
     DevState ds{};
     DevWork dw{};                          // (tau_wi, tau_sum, cum_damage, conc_fsd: attachments of CoupledBuffers; trace: option "trace_branches")
@@ -284,6 +294,8 @@ struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, Pa
     // thermo()'s ice columns (nxs_dyn_column_* / nxs_dyn_column): as above -- the configuration survives set_mesh, the rows are ColumnRows
     nxs_dyn_column_config col_cfg{};
     bool col_configured = false;
+    nxs_dyn_slab_config slab_cfg{};
+    bool slab_configured = false;
     // v4: the whole sub-step loop in one resident launch (option "fused" = 4; see k_substep_resident)
     int res_wide = 0;     // option resident_wide
     bool res_pow4 = true; // the build for BBM's default exponent (two squarings instead of pow)
@@ -3366,6 +3378,15 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
         out[0] = (double)v;
         return NXS_OK;
     }
+    if (!std::strcmp(name, "slab_branches")) {   // [Ne] the NXS_SLAB_BR_* word of every element from the last nxs_dyn_slab, as doubles
+        if (n != Ne) return fail(h, NXS_ERR_INVALID, "debug_array slab_branches has %lld entries, caller asked %lld", (long long)Ne, (long long)n);
+        if (!h->slab_done) return fail(h, NXS_ERR_STATE, "debug_array slab_branches: no nxs_dyn_slab on this mesh");
+        std::vector<unsigned> w((size_t)Ne);
+        HIPCHK(h, hipMemcpyAsync(w.data(), h->d_slab_br, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int64_t i = 0; i < Ne; ++i) out[i] = (double)w[(size_t)i];
+        return NXS_OK;
+    }
     if (!std::strcmp(name, "guard_launch")) {   // [2] the launch shape of the guards: threads per block of k_check_fields / k_regrid_partials, blocks of k_regrid_partials
         if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array guard_launch has 2 entries");
         out[0] = (double)BLOCK; out[1] = (double)h->n_partials;
@@ -3669,5 +3690,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_fsd.inl"
 #include "nxs_flux.inl"
 #include "nxs_column.inl"
+#include "nxs_slab.inl"
 
 }  // extern "C"

@@ -102,6 +102,14 @@ def load_library():
     L.nxs_dyn_column_get_state.argtypes = [H, P(_abi.ColumnState)]
     L.nxs_dyn_column.argtypes = [H, C.c_int32]
     L.nxs_dyn_column_get.argtypes = [H, P(_abi.ColumnRows), P(C.c_void_p)]
+    L.nxs_slab_default_config.argtypes = [P(_abi.SlabConfig)]
+    L.nxs_slab_config_check.argtypes = [P(_abi.SlabConfig)]
+    L.nxs_slab_constants.argtypes = [P(C.c_double), C.c_int32]
+    L.nxs_dyn_slab_configure.argtypes = [H, P(_abi.SlabConfig)]
+    L.nxs_dyn_slab_put.argtypes = [H, P(_abi.SlabState)]
+    L.nxs_dyn_slab_get_state.argtypes = [H, P(_abi.SlabState)]
+    L.nxs_dyn_slab.argtypes = [H, C.c_int32, P(_abi.SlabClock)]
+    L.nxs_dyn_slab_get.argtypes = [H, P(_abi.SlabRows), P(C.c_void_p)]
     L.nxs_dyn_ice_diagnostics.argtypes = [H, P(_abi.IceDiag), P(C.c_void_p)]
     L.nxs_dyn_means_configure.argtypes = [H, P(_abi.MeansConfig)]
     L.nxs_dyn_means_set_tau_ow.argtypes = [H, _abi.c_double_p]
@@ -168,6 +176,8 @@ EXPORTS = (
     "nxs_dyn_fluxes", "nxs_dyn_fluxes_get",
     "nxs_col_default_config", "nxs_col_config_check", "nxs_col_constants", "nxs_dyn_column_configure", "nxs_dyn_column_set_forcing", "nxs_dyn_column_put",
     "nxs_dyn_column_get_state", "nxs_dyn_column", "nxs_dyn_column_get",
+    "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
+    "nxs_dyn_slab_get",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
     "nxs_dyn_drifters_get", "nxs_dyn_regrid",
@@ -342,6 +352,59 @@ def column_constants() -> dict:
     if rc != 0:
         raise NxsError(rc, "nxs_col_constants")
     return dict(zip(_abi.COL_CONSTANTS, out))
+
+
+def slab_default_config() -> dict:
+    """The defaults of model/options.cpp:329-331, 397-403, 428-449, 543-548 the slab loop reads (nxs_slab_default_config, host only), keyed like nxs_dyn_slab_config."""
+    c = _abi.SlabConfig()
+    rc = load_library().nxs_slab_default_config(C.byref(c))
+    if rc != 0:
+        raise NxsError(rc, "nxs_slab_default_config")
+    return {k: getattr(c, k) for k, _ in _abi.SlabConfig._fields_}
+
+
+def _slab_config(options: dict) -> "_abi.SlabConfig":
+    base = _abi.SlabConfig()
+    load_library().nxs_slab_default_config(C.byref(base))
+    return _abi.slab_config_struct(base, **options)
+
+
+def slab_config_check(**options) -> int:
+    """What slab_configure would answer for the defaults changed by `options` (nxs_slab_config_check, host only): 0 or NXS_ERR_INVALID."""
+    c = _slab_config(options)
+    return load_library().nxs_slab_config_check(C.byref(c))
+
+
+def slab_constants() -> dict:
+    """The constants compiled into the slab kernel (nxs_slab_constants, host only)."""
+    out = (C.c_double * len(_abi.SLAB_CONSTANTS))()
+    rc = load_library().nxs_slab_constants(out, len(_abi.SLAB_CONSTANTS))
+    if rc != 0:
+        raise NxsError(rc, "nxs_slab_constants")
+    return dict(zip(_abi.SLAB_CONSTANTS, out))
+
+
+def slab_clock(current_time: float, dt: float, reset_date: str = "0915") -> dict:
+    """The five flags of nxs_dyn_slab_clock as thermo() derives them from M_current_time (FE.cpp:5653-5655, 5208, 5999, 6028, 6044).  current_time is a day number
+    in the epoch of the reference's core/include/date.hpp (days since 1900-01-01, fractions are the time of day); dt is dtime_step in seconds."""
+    import math
+    days_in_sec = 86400.
+    t = float(current_time)
+    frac = math.fmod(t, 1.)
+    num_steps_in_day = int(_c_round(days_in_sec / float(dt)))
+    step_in_day = 1 + int(_c_round(num_steps_in_day * frac))
+    import datetime
+    day = datetime.date(1900, 1, 1) + datetime.timedelta(days=int(t))   # date.hpp:24-26, 89-92: getEpoch() + static_cast<long>(date_time) days
+    md = f"{day.month:02d}{day.day:02d}"
+    midnight = frac == 0.
+    return {"first_step_of_day": int(step_in_day == 1), "last_step_of_day": int(step_in_day == num_steps_in_day), "fyi_reset_now": int(md == "0915" and midnight),
+            "myi_reset_now": int(md == str(reset_date) and midnight), "onset_reset_now": int(md == "0801" and midnight)}
+
+
+def _c_round(x: float) -> float:
+    """std::round: halves away from zero"""
+    import math
+    return math.floor(x + 0.5) if x >= 0 else -math.floor(-x + 0.5)
 
 
 def flux_constants() -> dict:
@@ -880,6 +943,50 @@ class FiniteElementDynamics:
             return out, dict(zip(_abi.COL_ROWS, (int(p or 0) for p in dev)))
         return out
 
+    # ---- thermo()'s slab loop from new ice to tracers: sections 6 to 10 (FE.cpp:5413-6133) ----
+    def slab_configure(self, **options):
+        """nxs_dyn_slab_configure: the defaults of slab_default_config() changed by keywords named after nxs_dyn_slab_config's members.  Survives set_mesh."""
+        c = _slab_config(options)
+        self._chk(self.L.nxs_dyn_slab_configure(self.h, C.byref(c)))
+
+    def slab_put(self, **rows):
+        """conc_upd, pond_volume, del_vi_tend, freeze_days, freeze_onset, conc_summer, thick_summer, fyi_fraction, age_det, age: [Ne] each; a row left out or None
+        keeps the device copy."""
+        s = _abi.SlabState()
+        keep = self._element_rows(s, _abi.SLAB_STATE, rows, "nxs_dyn_slab_state")
+        self._chk(self.L.nxs_dyn_slab_put(self.h, C.byref(s)))
+        del keep
+
+    def slab_get(self, names=_abi.SLAB_STATE_GET) -> dict:
+        """The named rows of nxs_dyn_slab_state from the device (nxs_dyn_slab_get_state), time_relaxation_damage among them."""
+        out = {k: np.empty(self.lm.num_elements) for k in names}
+        s = _abi.SlabState()
+        self._element_rows(s, _abi.SLAB_STATE_GET, out, "nxs_dyn_slab_state")
+        self._chk(self.L.nxs_dyn_slab_get_state(self.h, C.byref(s)))
+        return out
+
+    def slab(self, dt: int, clock: dict):
+        """nxs_dyn_slab: one launch; dt is thermo()'s integer argument, clock the five flags of slab_clock().  The ice state, the slab ocean, the ice temperatures
+        and the tracers are updated on the device.  Asynchronous."""
+        k = _abi.SlabClock()
+        for name, v in clock.items():
+            if name not in _abi.SLAB_CLOCK:
+                raise KeyError(f"nxs_dyn_slab_clock has no member {name!r}")
+            setattr(k, name, int(bool(v)))
+        self._chk(self.L.nxs_dyn_slab(self.h, int(dt), C.byref(k)))
+
+    def slab_rows(self, names=_abi.SLAB_ROWS, want_device: bool = False):
+        """The named rows of _abi.SLAB_ROWS as host arrays (nxs_dyn_slab_get); with want_device also {name: device pointer} of all 29 rows."""
+        out = {k: np.empty(self.lm.num_elements) for k in names}
+        r = _abi.SlabRows()
+        for k, v in out.items():
+            r.row[_abi.SLAB_ROWS.index(k)] = _abi.dptr(v)
+        dev = (C.c_void_p * _abi.NXS_SLAB_ROWS)()
+        self._chk(self.L.nxs_dyn_slab_get(self.h, C.byref(r), dev if want_device else None))
+        if want_device:
+            return out, dict(zip(_abi.SLAB_ROWS, (int(p or 0) for p in dev)))
+        return out
+
     def get_state(self) -> dict:
         Nn, Ne = self.lm.num_nodes, self.lm.num_elements
         out = {k: np.empty(2 * Nn) for k in _abi.STATE_NODAL}
@@ -1079,7 +1186,7 @@ class FiniteElementDynamics:
         Nn, Ne = self.lm.num_nodes, self.lm.num_elements
         n = {"rlmass": Nn, "node_mass": Nn, "C_bu": Nn, "grad_ssh": 2 * Nn, "fcor": Nn, "VTM": 2 * Nn,
              "shape": 6 * Ne, "emass": Ne, "ecbu": Ne, "force": 6 * Ne, "volume": Ne, "expC": Ne,
-             "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn, "drag_ui": Ne, "drag_ui_young": Ne,
+             "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn, "drag_ui": Ne, "drag_ui_young": Ne, "slab_branches": Ne,
              "means_update_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3}[name]
         out = np.empty(n)
         self._chk(self.L.nxs_dyn_debug_array(self.h, name.encode(), _abi.dptr(out), n))
