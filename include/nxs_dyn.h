@@ -577,8 +577,8 @@ NXS_API int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_
  * longer pulls the bins, conc, conc_young, thick, h_young and damage and pushes bins, damage and cum_damage every step.  Every loop is per element without a
  * stencil, ghost elements included: no exchange, and a partitioned handle runs them unchanged.  Each entry point is ONE kernel over M_num_elements, a thread holds
  * its element's bins in registers (bin-major rows: a wave reads and writes whole lines), asynchronous on the handle's stream.  Built uncontracted like the rest.
- * STAYS WITH THE HOST THERMO: redistributeThermoFSD (FE.cpp:4487-4670, lateral melt and growth, called with thermo's lat_melt_rate / young_ice_growth / old_conc) and
- * the melt-out branch of thermo() (FE.cpp:5729-5764): both need intermediates of thermo() that never reach the handle.
+ * NOT AMONG nxs_dyn_fsd_*: redistributeThermoFSD (FE.cpp:4487-4670, lateral melt and growth, called with thermo's lat_melt_rate / young_ice_growth / old_conc) and
+ * the melt-out branch of thermo() (FE.cpp:5729-5764) need intermediates of thermo(): they run inside nxs_dyn_slab_coupled, where those exist on the device.
  *   nxs_fsd_bins   HOST ONLY: the tables of initFsd() (FE.cpp:7408-7533) for FSDType CONSTANT_SIZE / CONSTANT_AREA, M_floe_shape = 0.66.  std::pow(x, 2) is
  *                  written x * x (what GCC and clang make of it at -O1 and above; a libm pow may differ in the last bit); everything else is + - * / sqrt.
  *                  alpha_merge is M_alpha_fsd_merge[m][n], row-major [n][n], -999 where no bin matches.  Any output of nxs_fsd_tables may be NULL.
@@ -834,10 +834,10 @@ NXS_API int nxs_dyn_column_get(nxs_dyn_handle *h, const nxs_dyn_column_rows *out
  * temp_dep_healing) time_relaxation_damage, so the next nxs_dyn_step reads them; in nxs_dyn_flux_state sst, sss and (under use_meltponds) pond_fraction,
  * lid_volume; tice0 and under WINTON the column's tice1 / tice2; nxs_dyn_slab_state except conc_upd.  It writes NXS_SLAB_ROWS rows, the D_* diagnostics of thermo().
  * The library knows no dates: the caller derives the five flags of nxs_dyn_slab_clock from M_current_time (FE.cpp:5653-5655, 5208, 5999, 6028, 6044).
- * NOT BUILT, all of it #ifdef OASIS in the reference: melt_type 3 (FE.cpp:5592-5640; refused by the configuration check), the FSD branches of the limit block
- * (FE.cpp:5729-5764), redistributeThermoFSD (FE.cpp:5768-5776), the in-loop weldingRoach (FE.cpp:5779-5797), the mechanical FSD healing of 9.b (FE.cpp:5883-5898),
- * the OceanType::COUPLED guards (FE.cpp:5826-5841).  Because FE.cpp:5729-5764 would have to touch the bins, nxs_dyn_slab answers NXS_ERR_STATE while floe-size
- * bins are attached (nxs_dyn_put_coupled with num_fsd_bins > 0): such a host keeps its loop.  The throw of a wrong newice_type / melt_type is NXS_ERR_INVALID at
+ * NOT IN nxs_dyn_slab, all of it #ifdef OASIS in the reference: melt_type 3 (FE.cpp:5592-5640; refused by the configuration check), the FSD branches of the limit
+ * block (FE.cpp:5729-5764), redistributeThermoFSD (FE.cpp:5768-5776), the in-loop weldingRoach (FE.cpp:5779-5797), the mechanical FSD healing of 9.b
+ * (FE.cpp:5883-5898): these are nxs_dyn_slab_coupled's, below.  Because FE.cpp:5729-5764 would have to touch the bins, nxs_dyn_slab answers NXS_ERR_STATE while
+ * floe-size bins are attached (nxs_dyn_put_coupled with num_fsd_bins > 0): such a host calls nxs_dyn_slab_coupled.  The throw of a wrong newice_type / melt_type is NXS_ERR_INVALID at
  * configuration.  nxs_dyn_regrid does NOT carry nxs_dyn_slab_state across a regrid: nxs_dyn_set_mesh and nxs_dyn_regrid make it missing again, like tice1 /
  * tice2; the host fetches it before a regrid and puts it back after.  The rows are not wired into nxs_dyn_means_*: their device pointers are available.
  *   nxs_slab_default_config   model/options.cpp:329-331, 397-403, 428-449, 543-548
@@ -932,6 +932,55 @@ NXS_API int nxs_dyn_slab_put(nxs_dyn_handle *h, const nxs_dyn_slab_state *s);
 NXS_API int nxs_dyn_slab_get_state(nxs_dyn_handle *h, nxs_dyn_slab_state *s);
 NXS_API int nxs_dyn_slab(nxs_dyn_handle *h, int32_t dt, const nxs_dyn_slab_clock *clock);
 NXS_API int nxs_dyn_slab_get(nxs_dyn_handle *h, const nxs_dyn_slab_rows *out /* may be NULL */, const double **device_rows /* [NXS_SLAB_ROWS], may be NULL */);
+
+/* ---- thermo()'s slab loop with floe-size bins attached: the loop as an OASIS build compiles it, FE.cpp:5413-6133, on the bins of nxs_dyn_put_coupled and, while
+ * attached, the M_conc_mech_fsd of nxs_dyn_fsd_put.  It is nxs_dyn_slab's loop (ONE source: the same device function) plus every line that touches the bins:
+ *   FE.cpp:5592-5640        melt_type 3 (Roach et al. 2018): the unbroken test, melt_type 2's rule on ctot, else lat_melt_rate = -m1 * pow(tw_new - tfrw, m2) * 2
+ *                           (m1 = 3.e-6, m2 = 1.36), cat0_del_c, the sum over the bins, Qow, del_c, M_conc_young; the early break at ctot < 1e-11
+ *   FE.cpp:5729-5764        the FSD branches of the limit block AS WRITTEN: the else of 5754 belongs to if (M_distinguish_mech_fsd), so without the mechanical
+ *                           bins every bin is zeroed even after the rescaling, and with them none is
+ *   FE.cpp:5768-5776, 4487-4670   redistributeThermoFSD under melt_type 3 where the limit block was not taken; abs(lat_melt_rate) of 4519 is the floating-point
+ *                           absolute value (as argued for 4831 under nxs_dyn_fsd_weld)
+ *   FE.cpp:5779-5797, 4737-4870   the in-loop weldingRoach where del_hi > 0: nxs_dyn_fsd_weld's device code and its weld_crash rule
+ *   FE.cpp:5883-5898        9.b, the mechanical healing, with the M_time_relaxation_damage section 9 has just written
+ * Two launches on the handle's stream: the loop (the bins are read as a stream, four intermediates of thermo() are left as rows), then a thread per element with
+ * its bins in registers (builds for 2 / 6 / 12 / 16 bins like nxs_dyn_fsd_*).  distinguish_mech_fsd, welding_type, welding_kappa, debug_fsd and the tables are
+ * nxs_dyn_fsd_configure's: one copy of each.  nxs_dyn_slab and its refusals are unchanged.
+ * OUT OF SCOPE, each needs the coupled ocean's received fields, which no entry point carries: the OceanType::COUPLED guards (FE.cpp:5826-5841: M_sst and M_sss
+ * are updated as by a slab ocean), their counterpart in the column (FE.cpp:5348-5358), M_qsrml (FE.cpp:5150-5156).
+ *   nxs_slab_coupled_config_check   HOST ONLY: nxs_slab_config_check with the configuration's melt_type replaced by `melt_type` (1, 2, 3); 3 needs attached_bins >=
+ *                  1 (the throw of FE.cpp:5595).  NXS_ERR_INVALID, the text in nxs_dyn_last_error(NULL)
+ *   nxs_dyn_slab_coupled_configure  the melt type of nxs_dyn_slab_coupled, on top of nxs_dyn_slab_configure (NXS_ERR_STATE before it); nothing else is
+ *                  overridden and nxs_dyn_slab keeps its own.  Survives nxs_dyn_set_mesh, which the bins do not: so 3 is accepted whether or not bins are
+ *                  attached, and nxs_dyn_slab_coupled asks for them.  NXS_ERR_INVALID outside 1 .. 3.  Without it nxs_dyn_slab_coupled uses the slab's melt_type
+ *   nxs_dyn_slab_coupled   NXS_ERR_STATE, naming what is missing: everything nxs_dyn_slab refuses except attached bins; no bins attached; before
+ *                  nxs_dyn_fsd_configure; attached bins that differ from the configured number; distinguish_mech_fsd without M_conc_mech_fsd (so
+ *                  melt_type 3 never runs without bins: the throw of FE.cpp:5595).  It spends the column's rows like nxs_dyn_slab; nxs_dyn_slab_get, nxs_dyn_slab_get_state and
+ *                  "slab_branches" answer after it as after nxs_dyn_slab.  The welding's ndt_mrg loop is data-dependent and uncapped, as in nxs_dyn_fsd_weld
+ *   nxs_dyn_slab_coupled_info   thermo_fsd_crash: any of the M_debug_fsd conditions of redistributeThermoFSD (FE.cpp:4531, 4568, 4617-4646) held on some element
+ *                  since the last call (only under debug_fsd; the mechanical bins' sum of 4631 where distinguish_mech_fsd keeps them); reduced on the device, cleared by the call; the element is finished as the arithmetic says.  The
+ *                  welding's conditions raise weld_crash (nxs_dyn_fsd_get)
+ * Debug array "slab_fsd_branches" [Ne]: the NXS_SLAB_FSD_BR_* word of every element from the last nxs_dyn_slab_coupled. */
+enum { NXS_SLAB_FSD_BR_MELT3 = 1,             /* melt_type 3 taken: del_hi < 0 and tw_new > tfrw (FE.cpp:5596) */
+       NXS_SLAB_FSD_BR_UNBROKEN = 2,          /* ... abs(M_conc_fsd[nb-1] - ctot) < 1e-7: melt_type 2's rule (FE.cpp:5616) */
+       NXS_SLAB_FSD_BR_CTOT_BREAK = 4,        /* ... ctot < 1e-11: the break (FE.cpp:5610) */
+       NXS_SLAB_FSD_BR_LIMIT_RESCALED = 8,    /* the limit block rescaled the bins (FE.cpp:5739) */
+       NXS_SLAB_FSD_BR_LIMIT_MECH_RESCALED = 16, /* ... the mechanical bins (FE.cpp:5748) */
+       NXS_SLAB_FSD_BR_LIMIT_ZEROED = 32,     /* ... zeroed the bins (FE.cpp:5754) */
+       NXS_SLAB_FSD_BR_LATERAL = 64,          /* redistributeThermoFSD: the Horvat & Tziperman branch (FE.cpp:4519) */
+       NXS_SLAB_FSD_BR_LAT_MELTING = 128,     /* ... lat_melt_rate < 0 (FE.cpp:4550) */
+       NXS_SLAB_FSD_BR_FILLS_LEAD = 256,      /* ... M_conc + M_conc_young == 1. (FE.cpp:4579) */
+       NXS_SLAB_FSD_BR_DEL_C_FSD_GE0 = 512,   /* ... refreezing of the young-ice category with del_c_fsd >= 0 (FE.cpp:4585) */
+       NXS_SLAB_FSD_BR_YOUNG_SHRINKS = 1024,  /* ... young_ice_growth < 0 (FE.cpp:4562) */
+       NXS_SLAB_FSD_BR_WELDED = 2048,         /* weldingRoach merged floes (FE.cpp:4757) */
+       NXS_SLAB_FSD_BR_HEALED = 4096          /* 9.b (FE.cpp:5888) */ };
+struct nxs_dyn_slab_coupled_info {   /* (no typedef: the entry point has the name, the tag names the type) */
+    int32_t thermo_fsd_crash;
+};
+NXS_API int nxs_slab_coupled_config_check(const nxs_dyn_slab_config *c, int32_t melt_type, int32_t attached_bins);
+NXS_API int nxs_dyn_slab_coupled_configure(nxs_dyn_handle *h, int32_t melt_type);
+NXS_API int nxs_dyn_slab_coupled(nxs_dyn_handle *h, int32_t dt, const nxs_dyn_slab_clock *clock);
+NXS_API int nxs_dyn_slab_coupled_info(nxs_dyn_handle *h, struct nxs_dyn_slab_coupled_info *info);
 
 /* One dynamics step on the device-resident state: FE.cpp:8197-8214.  Asynchronous on the
  * handle's stream; nxs_dyn_synchronize() waits for it. */
@@ -1080,6 +1129,8 @@ NXS_API int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t);
  *                  variables; 8-byte otherwise).  The same bits; scripts/time_means.py times both
  *   "means_timing" 1 = nxs_dyn_means_update records events around its two launches; nxs_dyn_debug_array "means_update_ms" returns their device times
  *                  [elemental, nodal] in ms.  Default 0
+ *   "slab_coupled_timing" 1 = nxs_dyn_slab_coupled records events around its two launches; nxs_dyn_debug_array "slab_coupled_ms" returns their device times
+ *                  [k_coupled_thermo, k_coupled_bins] in ms.  Default 0
  *   "drifters_timing" 1 = the nxs_dyn_drifters_* calls record events around their launches and wait for them; nxs_dyn_debug_array "drifters_ms" returns the device
  *                  times [locator build, move kernels, conc kernel, mask kernels] of the last of each in ms.  Default 0
  *   "ipc_delay", "halo_one_directional"   test doors of the exchange protocols, see NXS_DELAY_* above */

@@ -307,6 +307,14 @@ SLAB_BRANCHES = ("supercooled", "n2_hi_old", "n2_newice", "n3_h0", "n4_young", "
                  "assim", "denom_clamp", "sss_below_si", "freeze_days_ge")   # NXS_SLAB_BR_*: bit k of the word of debug array "slab_branches"
 
 
+SLAB_FSD_BRANCHES = ("melt3", "unbroken", "ctot_break", "limit_rescaled", "limit_mech_rescaled", "limit_zeroed", "lateral", "lat_melting", "fills_lead",
+                     "del_c_fsd_ge0", "young_shrinks", "welded", "healed")   # NXS_SLAB_FSD_BR_*: bit k of the word of debug array "slab_fsd_branches"
+
+
+class SlabCoupledInfo(C.Structure):   # nxs_dyn_slab_coupled_info
+    _fields_ = [("thermo_fsd_crash", C.c_int32)]
+
+
 class SlabConfig(C.Structure):   # nxs_dyn_slab_config
     _fields_ = [(k, C.c_int32) for k in SLAB_CONFIG_INTS] + [(k, C.c_double) for k in SLAB_CONFIG_REALS]
 

@@ -19,6 +19,7 @@
 //   k_fluxes                                  FE.cpp:5214-5277: thermo()'s atmospheric bulk fluxes, OWBulkFluxes + IABulkFluxes (nxs_flux_kernels.inl, nxs_dyn_fluxes)
 //   k_column                                  FE.cpp:5306-5411: thermo()'s ice columns, thermoWinton / thermoIce0 with the nudging and ice-ocean fluxes (nxs_column_kernels.inl, nxs_dyn_column)
 //   k_slab                                    FE.cpp:5413-6133: thermo()'s slab loop from new ice to tracers, with meltPonds (nxs_slab_kernels.inl, nxs_dyn_slab)
+//   k_coupled_thermo, k_coupled_bins          the same loop as an OASIS build compiles it, on the attached floe-size bins (nxs_slab_fsd_kernels.inl, nxs_dyn_slab_coupled)
 //   k_fsd_init / _update / _breakup / _weld   FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870 + 5888-5896: the floe-size distribution (nxs_fsd_kernels.inl, nxs_dyn_fsd_*)
 //   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
 //
@@ -54,6 +55,7 @@
 #include "nxs_flux_kernels.inl"
 #include "nxs_column_kernels.inl"
 #include "nxs_slab_kernels.inl"
+#include "nxs_slab_fsd_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -133,6 +135,9 @@ struct SlabRows {          // thermo()'s slab loop from new ice to tracers: as a
     unsigned *d_slab_br = nullptr;                 // [Ne] the branch words (debug array "slab_branches")
     bool col_fresh = false;                        // nxs_dyn_column ran and no nxs_dyn_slab has spent its rows yet
     bool slab_done = false;
+    double *d_slab_scr = nullptr;                  // [SLAB_SCR_ROWS][Ne] nxs_dyn_slab_coupled: what its first launch hands its second
+    unsigned *d_slab_br2 = nullptr;                // [Ne] NXS_SLAB_FSD_BR_* (debug array "slab_fsd_branches")
+    bool slab_coupled_done = false;
 };
 struct StateArrays : FluxRows, ColumnRows, SlabRows {   // the prognostic and work arrays (set_mesh) and everything made in their pool on demand
     std::vector<void *> state_allocs;
@@ -296,6 +301,11 @@ struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, Pa
     bool col_configured = false;
     nxs_dyn_slab_config slab_cfg{};
     bool slab_configured = false;
+    int slab_coupled_melt_type = 0;                // nxs_dyn_slab_coupled_configure; 0: the slab's own
+    int *d_slab_crash = nullptr;                   // thermo_fsd_crash of nxs_dyn_slab_coupled_info
+    int slab_coupled_timing = 0;                   // option "slab_coupled_timing": events around the two launches of nxs_dyn_slab_coupled (debug array "slab_coupled_ms")
+    hipEvent_t slab_ev[3] = {nullptr, nullptr, nullptr};
+    bool slab_coupled_timed = false;
     // v4: the whole sub-step loop in one resident launch (option "fused" = 4; see k_substep_resident)
     int res_wide = 0;     // option resident_wide
     bool res_pow4 = true; // the build for BBM's default exponent (two squarings instead of pow)
@@ -1864,10 +1874,12 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     if (h->d_crash) (void)hipFree(h->d_crash);
     if (h->d_fsd_cfg) (void)hipFree(h->d_fsd_cfg);
     if (h->d_fsd_flags) (void)hipFree(h->d_fsd_flags);
+    if (h->d_slab_crash) (void)hipFree(h->d_slab_crash);
     if (h->d_dp) (void)hipFree(h->d_dp);
     for (auto &set : h->ev) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
     for (auto &set : h->ev_flush) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : h->means_ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : h->slab_ev) if (ev) (void)hipEventDestroy(ev);
     nxs_drifters::destroy(h->drift); h->drift = nullptr;
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -2014,6 +2026,11 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
     if (!std::strcmp(key, "means_timing")) {
         h->means_timing = value != 0; h->means_timed = false;
         if (h->means_timing) { HIPCHK(h, hipSetDevice(h->device)); for (auto &ev : h->means_ev) if (!ev) HIPCHK(h, hipEventCreate(&ev)); }
+        return NXS_OK;
+    }
+    if (!std::strcmp(key, "slab_coupled_timing")) {
+        h->slab_coupled_timing = value != 0; h->slab_coupled_timed = false;
+        if (h->slab_coupled_timing) { HIPCHK(h, hipSetDevice(h->device)); for (auto &ev : h->slab_ev) if (!ev) HIPCHK(h, hipEventCreate(&ev)); }
         return NXS_OK;
     }
     if (!std::strcmp(key, "halo_fused")) { h->halo_fused = value != 0; release_graph(h); return NXS_OK; }
@@ -3387,6 +3404,22 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
         for (int64_t i = 0; i < Ne; ++i) out[i] = (double)w[(size_t)i];
         return NXS_OK;
     }
+    if (!std::strcmp(name, "slab_coupled_ms")) {   // [2] device time of the last nxs_dyn_slab_coupled with option "slab_coupled_timing" 1: k_coupled_thermo, k_coupled_bins
+        if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array slab_coupled_ms has 2 entries");
+        if (!h->slab_coupled_timed) return fail(h, NXS_ERR_STATE, "debug_array slab_coupled_ms: no timed nxs_dyn_slab_coupled (option slab_coupled_timing)");
+        HIPCHK(h, hipEventSynchronize(h->slab_ev[2]));
+        for (int k = 0; k < 2; ++k) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->slab_ev[k], h->slab_ev[k + 1])); out[k] = ms; }
+        return NXS_OK;
+    }
+    if (!std::strcmp(name, "slab_fsd_branches")) {   // [Ne] the NXS_SLAB_FSD_BR_* word of every element from the last nxs_dyn_slab_coupled, as doubles
+        if (n != Ne) return fail(h, NXS_ERR_INVALID, "debug_array slab_fsd_branches has %lld entries, caller asked %lld", (long long)Ne, (long long)n);
+        if (!h->slab_coupled_done) return fail(h, NXS_ERR_STATE, "debug_array slab_fsd_branches: no nxs_dyn_slab_coupled on this mesh");
+        std::vector<unsigned> w((size_t)Ne);
+        HIPCHK(h, hipMemcpyAsync(w.data(), h->d_slab_br2, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int64_t i = 0; i < Ne; ++i) out[i] = (double)w[(size_t)i];
+        return NXS_OK;
+    }
     if (!std::strcmp(name, "guard_launch")) {   // [2] the launch shape of the guards: threads per block of k_check_fields / k_regrid_partials, blocks of k_regrid_partials
         if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array guard_launch has 2 entries");
         out[0] = (double)BLOCK; out[1] = (double)h->n_partials;
@@ -3691,5 +3724,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_flux.inl"
 #include "nxs_column.inl"
 #include "nxs_slab.inl"
+#include "nxs_slab_fsd.inl"
 
 }  // extern "C"

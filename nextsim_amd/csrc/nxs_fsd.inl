@@ -51,6 +51,7 @@ int nxs_dyn_fsd_configure(nxs_dyn_handle *h, const nxs_dyn_fsd_config *c) try {
     for (int k = 0; k < n; ++k) {
         d.centres[k] = t.bin_centres[k]; d.low[k] = t.bin_low_limits[k]; d.up[k] = t.bin_up_limits[k];
         d.asu[k] = t.area_scaled_up[k]; d.asc[k] = t.area_scaled_centered[k]; d.asb[k] = t.area_scaled_binwidth[k];
+        d.widths[k] = t.bin_widths[k];
     }
     for (int j = 0; j < n; ++j)
         for (int k = 0; k < n; ++k) {

@@ -93,22 +93,27 @@ int nxs_dyn_slab_get_state(nxs_dyn_handle *h, nxs_dyn_slab_state *s) try {
     return download_rows(h, dst, dev, SLAB_ST_ROWS + 1);
 } catch (...) { return dyn_caught(h, "nxs_dyn_slab_get_state"); }
 
-int nxs_dyn_slab(nxs_dyn_handle *h, int32_t dt, const nxs_dyn_slab_clock *clock) try {   // thermo()'s slab loop from FE.cpp:5413 to its end, 6133
-    if (!h) return NXS_ERR_INVALID;
-    if (dt <= 0) return fail(h, NXS_ERR_INVALID, "slab: dt = %d must be positive", dt);
-    if (!clock) return fail(h, NXS_ERR_INVALID, "slab: no clock (nxs_dyn_slab_clock: the five flags the reference derives from M_current_time)");
-    if (!h->slab_configured) return fail(h, NXS_ERR_STATE, "slab before nxs_dyn_slab_configure");
+static int slab_coupled_ready(nxs_dyn_handle *h);   // nxs_slab_fsd.inl
+
+// what nxs_dyn_slab and nxs_dyn_slab_coupled (nxs_slab_fsd.inl) share: the refusals -- about the bins each has its own, at the same place --, the output rows, and
+// the arguments of slab_element
+static int slab_launch_args(nxs_dyn_handle *h, bool coupled, int32_t dt, const nxs_dyn_slab_clock *clock, SlabArrays *pa, SlabDev *pc) {
+    const char *const what = coupled ? "slab_coupled" : "slab";
+    if (dt <= 0) return fail(h, NXS_ERR_INVALID, "%s: dt = %d must be positive", what, dt);
+    if (!clock) return fail(h, NXS_ERR_INVALID, "%s: no clock (nxs_dyn_slab_clock: the five flags the reference derives from M_current_time)", what);
+    if (!h->slab_configured) return fail(h, NXS_ERR_STATE, "%s before nxs_dyn_slab_configure", what);
     if (!h->have_mesh || !h->have_state || !h->flux_done || !h->col_done)
-        return fail(h, NXS_ERR_STATE, "slab before nxs_dyn_column on this mesh (its rows and those of nxs_dyn_fluxes are the slab's inputs)");
+        return fail(h, NXS_ERR_STATE, "%s before nxs_dyn_column on this mesh (its rows and those of nxs_dyn_fluxes are the slab's inputs)", what);
     if (!h->col_fresh)
-        return fail(h, NXS_ERR_STATE, "slab: a second nxs_dyn_slab without a new nxs_dyn_column in between (the state has moved on: the column's rows are stale)");
+        return fail(h, NXS_ERR_STATE, "%s: a second nxs_dyn_slab without a new nxs_dyn_column in between (the state has moved on: the column's rows are stale)", what);
     const nxs_dyn_slab_config &g = h->slab_cfg;
     const nxs_dyn_column_config &cg = h->col_cfg;
-    if (h->dw.conc_fsd)
-        return fail(h, NXS_ERR_STATE, "slab: floe-size bins are attached (%d; nxs_dyn_put_coupled): the limit block's FSD branches, FE.cpp:5729-5764, are not built", h->dw.nbins);
+    if (!coupled && h->dw.conc_fsd)
+        return fail(h, NXS_ERR_STATE, "slab: floe-size bins are attached (%d; nxs_dyn_put_coupled): the limit block's FSD branches, FE.cpp:5729-5764, are nxs_dyn_slab_coupled's", h->dw.nbins);
+    if (coupled) { if (int rc = slab_coupled_ready(h)) return rc; }
     const bool young = h->dp.young_cat != 0;
     if ((g.newice_type == 4) != young)
-        return fail(h, NXS_ERR_STATE, "slab: newice_type = %d on a handle of the %s category (newice_type 4 is the young-ice category's, and only its)", g.newice_type,
+        return fail(h, NXS_ERR_STATE, "%s: newice_type = %d on a handle of the %s category (newice_type 4 is the young-ice category's, and only its)", what, g.newice_type,
                     young ? "young-ice" : "classic");
     unsigned need = ((1u << SLAB_ST_ROWS) - 1) & ~3u;   // bits of nxs_dyn_slab_state: conc_upd, pond_volume, then the eight rows every launch needs
     if (g.use_assim_flux) need |= 1u << 0;
@@ -116,22 +121,22 @@ int nxs_dyn_slab(nxs_dyn_handle *h, int32_t dt, const nxs_dyn_slab_clock *clock)
     if ((h->slab_st_have & need) != need) {
         int k = 0;
         while (!((need & ~h->slab_st_have) & (1u << k))) ++k;
-        return fail(h, NXS_ERR_STATE, "slab: %s is missing on this mesh (nxs_dyn_slab_put after set_mesh / regrid; needed 0x%x, present 0x%x)", slab_st_name[k], need, h->slab_st_have);
+        return fail(h, NXS_ERR_STATE, "%s: %s is missing on this mesh (nxs_dyn_slab_put after set_mesh / regrid; needed 0x%x, present 0x%x)", what, slab_st_name[k], need, h->slab_st_have);
     }
     unsigned fneed = 1u << 0;   // bits of nxs_dyn_column_forcing: precip (the rain), mld
     if (cg.mld_source == NXS_COL_MLD_ROW) fneed |= 1u << 4;
     if ((h->col_forcing_have & fneed) != fneed)
-        return fail(h, NXS_ERR_STATE, "slab: %s is missing on this mesh (nxs_dyn_column_set_forcing)", (h->col_forcing_have & 1u) ? "mld" : "precip");
-    if (h->flux_st_have != (1u << FLUX_ST_ROWS) - 1) return fail(h, NXS_ERR_STATE, "slab: a flux row is missing on this mesh");
+        return fail(h, NXS_ERR_STATE, "%s: %s is missing on this mesh (nxs_dyn_column_set_forcing)", what, (h->col_forcing_have & 1u) ? "mld" : "precip");
+    if (h->flux_st_have != (1u << FLUX_ST_ROWS) - 1) return fail(h, NXS_ERR_STATE, "%s: a flux row is missing on this mesh", what);
     const bool winton = cg.thermo_type == NXS_COL_THERMO_WINTON;
-    if (winton && h->col_st_have != (1u << COL_ST_ROWS) - 1) return fail(h, NXS_ERR_STATE, "slab: WINTON needs tice1 and tice2 on this mesh");
+    if (winton && h->col_st_have != (1u << COL_ST_ROWS) - 1) return fail(h, NXS_ERR_STATE, "%s: WINTON needs tice1 and tice2 on this mesh", what);
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = launch_gave_up(h)) return rc;
     const size_t Ne = h->dm.Ne;
     if (!h->d_slab_out) { if (int rc = dev_alloc(h, h->state_allocs, &h->d_slab_out, (size_t)SLAB_ROWS * Ne)) return rc; }
     if (!h->d_slab_br) { if (int rc = dev_alloc(h, h->state_allocs, &h->d_slab_br, Ne)) return rc; }
     SlabDev c{};
-    c.newice_type = g.newice_type; c.melt_type = g.melt_type; c.freezingpoint_type = cg.freezingpoint_type;
+    c.newice_type = g.newice_type; c.melt_type = coupled && h->slab_coupled_melt_type ? h->slab_coupled_melt_type : g.melt_type; c.freezingpoint_type = cg.freezingpoint_type;
     c.flags = (g.use_assim_flux ? SF_ASSIM : 0) | (g.temp_dep_healing ? SF_HEALING : 0) | (g.use_meltponds ? SF_PONDS : 0) | (g.reset_by_date ? SF_RESET_BY_DATE : 0) |
               (g.include_young_ice && g.reset_by_date ? SF_YOUNG_IN_MYI_RESET : 0) /* FE.cpp:5649-5650 */ | (g.equal_melting ? SF_EQUAL_MELTING : 0) |
               (young ? SF_YOUNG_CAT : 0) | (winton ? SF_WINTON : 0) | (cg.mld_source == NXS_COL_MLD_ROW ? SF_MLD_ROW : 0) |
@@ -149,6 +154,14 @@ int nxs_dyn_slab(nxs_dyn_handle *h, int32_t dt, const nxs_dyn_slab_clock *clock)
     const SlabArrays a{h->dm.Ne, h->dm.Nn, h->dm.t0, h->dm.t1, h->dm.t2, h->ds.wind, h->d_flux_out, h->d_col_out, fo[0], fo[4] ? fo[4] : any,
                        h->ds.conc, h->ds.thick, h->ds.snow, h->ds.ridge, h->ds.cyoung, h->ds.hyoung, h->ds.hsyoung, h->ds.cmyi, h->ds.tmyi, h->ds.theal,
                        st[2], st[3], st[6], st[7], st[0], winton ? h->d_col_st[0] : any, winton ? h->d_col_st[1] : any, h->d_slab_st[0], h->d_slab_out, h->d_slab_br};
+    *pa = a; *pc = c;
+    return NXS_OK;
+}
+
+int nxs_dyn_slab(nxs_dyn_handle *h, int32_t dt, const nxs_dyn_slab_clock *clock) try {   // thermo()'s slab loop from FE.cpp:5413 to its end, 6133
+    if (!h) return NXS_ERR_INVALID;
+    SlabArrays a; SlabDev c;
+    if (int rc = slab_launch_args(h, false, dt, clock, &a, &c)) return rc;
     LAUNCH(h, k_slab, h->dm.Ne, a, c);
     HIPCHK(h, hipGetLastError());
     h->col_fresh = false;   // the column's rows are spent: the next nxs_dyn_slab wants a new nxs_dyn_column

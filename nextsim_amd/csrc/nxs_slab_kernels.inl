@@ -10,9 +10,14 @@
 // branches of one body.  Everything of an element is worked on as locals and stored once, as soon as it is final (conditional stores through references cost scratch: see
 // nxs_column_kernels.inl; early stores and late loads keep the live registers down).  Qow is the reference's function-local vector: the kernel works on a register copy and the flux rows stay READ-ONLY, like the column rows.
 // Where the reference makes a NaN (0 / 0 in f1 of FE.cpp:5706 when there is neither old nor new ice) the kernel makes the same one.
-// NOT here, all of it #ifdef OASIS: melt_type 3 (FE.cpp:5592-5640), the FSD branches of the limit block (5729-5764), redistributeThermoFSD (5768-5776), the in-loop
-// weldingRoach (5779-5797), the mechanical FSD healing of 9.b (5883-5898), the OceanType::COUPLED guards (5826-5841).  The throw of a wrong newice_type / melt_type
-// is NXS_ERR_INVALID at configuration.
+// The body is slab_element<COUPLED>, ONE source of the loop's arithmetic: k_slab is its COUPLED = false instance (a default build's loop), k_coupled_thermo
+// (nxs_slab_fsd_kernels.inl, nxs_dyn_slab_coupled) its COUPLED = true instance, which adds what an OASIS build compiles into these lines: melt_type 3
+// (FE.cpp:5592-5640), reading the bins as a stream, and the four intermediates the bins' own launch needs (old_conc, old_conc_young, lat_melt_rate,
+// young_ice_growth) as rows.  Everything COUPLED adds stands behind `if constexpr`, so k_slab is the kernel it was.
+// NOT here: the FSD branches of the limit block (5729-5764), redistributeThermoFSD (5768-5776), the in-loop weldingRoach (5779-5797) and the mechanical FSD healing
+// of 9.b (5883-5898) are k_coupled_bins (nxs_slab_fsd_kernels.inl).  In NO kernel, because they need the coupled ocean's received fields: the OceanType::COUPLED
+// guards (5826-5841), their counterpart in the column (5348-5358), M_qsrml (5150-5156).  The throw of a wrong newice_type / melt_type is NXS_ERR_INVALID at
+// configuration.
 
 // physical::, model/constants.hpp (cpw, ki and hmin are nxs_column_kernels.inl's)
 #define NXS_CMIN 1e-12
@@ -56,9 +61,18 @@ struct SlabArrays {
 enum { SLAB_ST_CONC_UPD = 0, SLAB_ST_POND_VOLUME, SLAB_ST_DEL_VI_TEND, SLAB_ST_FREEZE_DAYS, SLAB_ST_FREEZE_ONSET, SLAB_ST_CONC_SUMMER, SLAB_ST_THICK_SUMMER,
        SLAB_ST_FYI_FRACTION, SLAB_ST_AGE_DET, SLAB_ST_AGE };
 
-__global__ void __launch_bounds__(BLOCK) k_slab(SlabArrays a, SlabDev c) {
-    const int e = blockIdx.x * BLOCK + threadIdx.x;
-    if (e >= a.Ne) return;
+// what the COUPLED instance adds to the arrays of a launch (nxs_dyn_slab_coupled)
+struct SlabCoupled {
+    const double *fsd;                  // [nb][Ne] M_conc_fsd, read-only here
+    const double *widths, *centres;     // [nb] M_fsd_bin_widths, M_fsd_bin_centres (device copies: the tables of nxs_dyn_fsd_configure)
+    int nb;
+    double *scr;                        // [SLAB_SCR_ROWS][Ne] what thermo() hands redistributeThermoFSD
+    unsigned *br2;                      // [Ne] NXS_SLAB_FSD_BR_*
+};
+enum { SLAB_SCR_OLD_CONC = 0, SLAB_SCR_OLD_CONC_YOUNG, SLAB_SCR_LAT_MELT_RATE, SLAB_SCR_YOUNG_ICE_GROWTH, SLAB_SCR_ROWS };
+
+template <bool COUPLED>
+__device__ __forceinline__ void slab_element(const SlabArrays &a, const SlabDev &c, const SlabCoupled &x, const int e) {
     const size_t n = (size_t)a.Ne;
     const double ddt = c.dt;
     const double dtime_step = c.dt;
@@ -66,6 +80,9 @@ __global__ void __launch_bounds__(BLOCK) k_slab(SlabArrays a, SlabDev c) {
     const double qs = NXS_LF * NXS_RHOS;
     const bool young = (c.flags & SF_YOUNG_CAT) != 0, winton = (c.flags & SF_WINTON) != 0, young_in_myi_reset = (c.flags & SF_YOUNG_IN_MYI_RESET) != 0;
     unsigned br = 0;
+    [[maybe_unused]] unsigned br2 = 0;                  // NXS_SLAB_FSD_BR_* (COUPLED)
+    [[maybe_unused]] double lat_melt_rate = 0.;         // FE.cpp:5471 (COUPLED)
+    [[maybe_unused]] double young_ice_growth = 0.;      // FE.cpp:5473 (COUPLED)
     const double *const F = a.flux + e, *const K = a.col + e;
     double *const o = a.out + e, *const S = a.st + e;
     // FE.cpp:5306-5319 (the column left M_conc, M_thick, M_snow_thick and M_conc_young as they were)
@@ -193,6 +210,7 @@ __global__ void __launch_bounds__(BLOCK) k_slab(SlabArrays a, SlabDev c) {
             if (hy < c.h_young_min * cy) {
                 br |= NXS_SLAB_BR_N4_NOT_FILLED;
                 cy = hy / c.h_young_min;
+                if constexpr (COUPLED) young_ice_growth = cy - old_conc_young;   // FE.cpp:5518
             } else {
                 const double hiy = hy / cy;
                 if (hiy > c.h_young_max_sharp) {
@@ -234,14 +252,52 @@ __global__ void __launch_bounds__(BLOCK) k_slab(SlabArrays a, SlabDev c) {
                 del_c += del_hi * conc * c.PhiM / hi_old;
             } else
                 del_c += 0.;
-        } else {
+        } else if (!COUPLED || c.melt_type == 2) {
             if (hi > 0.) {
                 br |= NXS_SLAB_BR_MELT_SIDE;
                 del_c += c.PhiM * (1. - conc) * STD_MIN(0., Qow) * ddt / (hi * qi + hs * qs);
                 Qow *= (1. - c.PhiM);
             } else
                 del_c = -conc;
+        } else if constexpr (COUPLED) {   // 3: Roach et al. (2018), FE.cpp:5592-5640 (M_num_fsd_bins >= 1: the configuration check)
+            if (tw_new > tfrw) {
+                br2 |= NXS_SLAB_FSD_BR_MELT3;
+                const double m1 = 3.e-6;
+                const double m2 = 1.36;
+                double del_c_melt = 0.;
+                double cat0_del_c = 0.;
+                if (hi > 0) {
+                    const double ctot = conc + cy;
+                    if (ctot < 1e-11)
+                        br2 |= NXS_SLAB_FSD_BR_CTOT_BREAK;   // the break of FE.cpp:5611
+                    else {
+                        double h0 = 0.;
+                        if (cy > 0.) h0 = c.h_young_min + 2. * (hy - c.h_young_min * cy) / (cy);
+                        if (fabs(x.fsd[(size_t)(x.nb - 1) * n + e] - ctot) < 1e-7) {   // unbroken: melt_type 2's rule on ctot
+                            br2 |= NXS_SLAB_FSD_BR_UNBROKEN;
+                            del_c_melt += c.PhiM * (1. - ctot) * STD_MIN(0., Qow) * ddt / (hi * qi + hs * qs);
+                            const double all = -ctot;
+                            del_c_melt = STD_MAX(del_c_melt, all);
+                            Qow *= (1. - c.PhiM);
+                        } else {
+                            lat_melt_rate = -m1 * pow(tw_new - tfrw, m2);
+                            lat_melt_rate = lat_melt_rate * 2.;
+                            cat0_del_c = lat_melt_rate * x.fsd[e] / x.widths[0] * ddt;
+                            del_c_melt += cat0_del_c;
+                            for (int j = 0; j < x.nb - 1; ++j) del_c_melt += lat_melt_rate * (x.fsd[(size_t)j * n + e] * 2. / x.centres[j]) * ddt;
+                            Qow -= del_c_melt * (hi * qi * conc + h0 * qi * cy) / (ddt * ctot);
+                        }
+                        del_c += (conc / ctot) * del_c_melt;
+                        cy += del_c_melt * (cy / ctot);
+                    }
+                }
+            }
         }
+    }
+    if constexpr (COUPLED) {   // what redistributeThermoFSD is called with (FE.cpp:5772), stored while at hand
+        double *const X = x.scr + e;
+        X[SLAB_SCR_OLD_CONC * n] = old_conc; X[SLAB_SCR_OLD_CONC_YOUNG * n] = old_conc_young; X[SLAB_SCR_LAT_MELT_RATE * n] = lat_melt_rate;
+        X[SLAB_SCR_YOUNG_ICE_GROWTH * n] = young_ice_growth;
     }
 
     // the freeze days, FE.cpp:5649-5682
@@ -532,4 +588,11 @@ __global__ void __launch_bounds__(BLOCK) k_slab(SlabArrays a, SlabDev c) {
     S[SLAB_ST_FREEZE_DAYS * n] = freeze_days; S[SLAB_ST_FREEZE_ONSET * n] = freeze_onset; S[SLAB_ST_CONC_SUMMER * n] = conc_summer_row;
     S[SLAB_ST_THICK_SUMMER * n] = thick_summer_row; S[SLAB_ST_FYI_FRACTION * n] = fyi_fraction; S[SLAB_ST_AGE_DET * n] = age_det; S[SLAB_ST_AGE * n] = age;
     a.branches[e] = br;
+    if constexpr (COUPLED) x.br2[e] = br2;
+}
+
+__global__ void __launch_bounds__(BLOCK) k_slab(SlabArrays a, SlabDev c) {
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= a.Ne) return;
+    slab_element<false>(a, c, SlabCoupled{}, e);
 }

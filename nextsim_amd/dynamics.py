@@ -110,6 +110,10 @@ def load_library():
     L.nxs_dyn_slab_get_state.argtypes = [H, P(_abi.SlabState)]
     L.nxs_dyn_slab.argtypes = [H, C.c_int32, P(_abi.SlabClock)]
     L.nxs_dyn_slab_get.argtypes = [H, P(_abi.SlabRows), P(C.c_void_p)]
+    L.nxs_slab_coupled_config_check.argtypes = [P(_abi.SlabConfig), C.c_int32, C.c_int32]
+    L.nxs_dyn_slab_coupled_configure.argtypes = [H, C.c_int32]
+    L.nxs_dyn_slab_coupled.argtypes = [H, C.c_int32, P(_abi.SlabClock)]
+    L.nxs_dyn_slab_coupled_info.argtypes = [H, P(_abi.SlabCoupledInfo)]
     L.nxs_dyn_ice_diagnostics.argtypes = [H, P(_abi.IceDiag), P(C.c_void_p)]
     L.nxs_dyn_means_configure.argtypes = [H, P(_abi.MeansConfig)]
     L.nxs_dyn_means_set_tau_ow.argtypes = [H, _abi.c_double_p]
@@ -177,7 +181,7 @@ EXPORTS = (
     "nxs_col_default_config", "nxs_col_config_check", "nxs_col_constants", "nxs_dyn_column_configure", "nxs_dyn_column_set_forcing", "nxs_dyn_column_put",
     "nxs_dyn_column_get_state", "nxs_dyn_column", "nxs_dyn_column_get",
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
-    "nxs_dyn_slab_get",
+    "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
     "nxs_dyn_drifters_get", "nxs_dyn_regrid",
@@ -373,6 +377,13 @@ def slab_config_check(**options) -> int:
     """What slab_configure would answer for the defaults changed by `options` (nxs_slab_config_check, host only): 0 or NXS_ERR_INVALID."""
     c = _slab_config(options)
     return load_library().nxs_slab_config_check(C.byref(c))
+
+
+def slab_coupled_config_check(coupled_melt_type: int, attached_bins: int, **options) -> int:
+    """What slab_coupled_configure(coupled_melt_type) would answer on a slab configured with the defaults changed by `options` (its own melt_type among them) and
+    `attached_bins` floe-size bins attached (nxs_slab_coupled_config_check, host only): 0 or NXS_ERR_INVALID."""
+    c = _slab_config(options)
+    return load_library().nxs_slab_coupled_config_check(C.byref(c), int(coupled_melt_type), int(attached_bins))
 
 
 def slab_constants() -> dict:
@@ -975,6 +986,26 @@ class FiniteElementDynamics:
             setattr(k, name, int(bool(v)))
         self._chk(self.L.nxs_dyn_slab(self.h, int(dt), C.byref(k)))
 
+    def slab_coupled_configure(self, melt_type: int):
+        """nxs_dyn_slab_coupled_configure: the melt type (1, 2, 3) of slab_coupled(), on top of slab_configure().  Survives set_mesh."""
+        self._chk(self.L.nxs_dyn_slab_coupled_configure(self.h, int(melt_type)))
+
+    def slab_coupled(self, dt: int, clock: dict):
+        """nxs_dyn_slab_coupled: slab() as a wave-coupled build compiles it, on the attached floe-size bins (put_coupled, fsd_put): melt_type 3, the FSD branches
+        of the limit block, redistributeThermoFSD, the in-loop welding and the mechanical healing.  Two launches; everything else as slab()."""
+        k = _abi.SlabClock()
+        for name, v in clock.items():
+            if name not in _abi.SLAB_CLOCK:
+                raise KeyError(f"nxs_dyn_slab_clock has no member {name!r}")
+            setattr(k, name, int(v))
+        self._chk(self.L.nxs_dyn_slab_coupled(self.h, int(dt), C.byref(k)))
+
+    def slab_coupled_info(self) -> dict:
+        """nxs_dyn_slab_coupled_info: thermo_fsd_crash, the debug_fsd conditions of redistributeThermoFSD since the last call (cleared by it)."""
+        i = _abi.SlabCoupledInfo()
+        self._chk(self.L.nxs_dyn_slab_coupled_info(self.h, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in _abi.SlabCoupledInfo._fields_}
+
     def slab_rows(self, names=_abi.SLAB_ROWS, want_device: bool = False):
         """The named rows of _abi.SLAB_ROWS as host arrays (nxs_dyn_slab_get); with want_device also {name: device pointer} of all 29 rows."""
         out = {k: np.empty(self.lm.num_elements) for k in names}
@@ -1186,8 +1217,8 @@ class FiniteElementDynamics:
         Nn, Ne = self.lm.num_nodes, self.lm.num_elements
         n = {"rlmass": Nn, "node_mass": Nn, "C_bu": Nn, "grad_ssh": 2 * Nn, "fcor": Nn, "VTM": 2 * Nn,
              "shape": 6 * Ne, "emass": Ne, "ecbu": Ne, "force": 6 * Ne, "volume": Ne, "expC": Ne,
-             "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn, "drag_ui": Ne, "drag_ui_young": Ne, "slab_branches": Ne,
-             "means_update_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3}[name]
+             "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn, "drag_ui": Ne, "drag_ui_young": Ne, "slab_branches": Ne, "slab_fsd_branches": Ne,
+             "means_update_ms": 2, "slab_coupled_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3}[name]
         out = np.empty(n)
         self._chk(self.L.nxs_dyn_debug_array(self.h, name.encode(), _abi.dptr(out), n))
         return out
