@@ -385,9 +385,10 @@ NXS_API int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *d, cons
  * live here as interleaved rows ([Ne][n_el] and [Nn][n_nod], the layout nxs_interp_mesh_to_grid_device samples), one launch per kind and step updates them, and
  * nxs_dyn_means_to_grid samples them at output time -- the state never crosses PCIe for a time-mean Moorings file.
  * The identifiers are named after GridOutput::variableID (model/gridoutput.hpp) and cover the variables whose sources the handle holds.
- * OUT OF SCOPE (the host keeps summing those itself): variables whose sources never reach the handle -- thermodynamic fields, fluxes, atmosphere and ocean forcing
- * other than the wind, age, melt ponds, the *_rplnt_* / *_mlt_* multi-year-ice terms --, loaded (non-regular) grids, ConservativeRemappingMeshToGrid,
- * rotateVectors, the land-sea mask, and the coupler's means (M_cpl_out). */
+ * The thermodynamic variables (NXS_MEANS_THERMO_BEGIN ..) read the rows nxs_dyn_fluxes / nxs_dyn_column / nxs_dyn_slab left on the handle: the flux, column and slab
+ * state, the slab's D_* rows, the atmosphere and the column's forcing -- a host whose thermodynamics runs here fetches none of them for a time-mean Moorings file.
+ * OUT OF SCOPE (the host keeps summing those itself): dmax / dmean (the FSD diagnostics of the coupled build), loaded (non-regular) grids,
+ * ConservativeRemappingMeshToGrid, rotateVectors, the land-sea mask, and the coupler's means (M_cpl_out). */
 enum nxs_means_var {
     /* elemental: accumulated over the owned elements i < M_local_nelements, the rows of ghost elements stay 0 (FE.cpp:8527) */
     NXS_MEANS_CONC = 0,           /* FE.cpp:8526  D_conc */
@@ -411,6 +412,70 @@ enum nxs_means_var {
     NXS_MEANS_DRAG_UI = 18,       /* FE.cpp:8756-8766  M_drag_ui, concentration-weighted with M_drag_ui_young in the young-ice category */
     NXS_MEANS_ICE_MASK = 19,      /* FE.cpp:8912-8920  += 1 where M_thick (+ M_h_young) > 0 -- NOT multiplied by time_factor */
     NXS_MEANS_ELEMENTAL_END = 20,
+    /* elemental, the thermodynamics: the same loop over the owned elements; each reads a row the handle holds (see nxs_dyn_means_update) */
+    NXS_MEANS_SST = 128,                 /* FE.cpp:8556  M_sst (nxs_dyn_flux_state) */
+    NXS_MEANS_SSS = 129,                 /* FE.cpp:8561  M_sss */
+    NXS_MEANS_TSURF_ICE = 130,           /* FE.cpp:8566  M_tice[0] */
+    NXS_MEANS_MELTPOND_LID_VOLUME = 131, /* FE.cpp:8626  M_lid_volume */
+    NXS_MEANS_MELTPOND_FRACTION = 132,   /* FE.cpp:8779  D_pond_fraction */
+    NXS_MEANS_DRAG_TI = 133,             /* FE.cpp:8767-8777  M_drag_ti, concentration-weighted with M_drag_ti_young in the young-ice category */
+    NXS_MEANS_T1 = 134,                  /* FE.cpp:8571  M_tice[1] (nxs_dyn_column_state; WINTON) */
+    NXS_MEANS_T2 = 135,                  /* FE.cpp:8576  M_tice[2] */
+    NXS_MEANS_CONC_UPD = 136,            /* FE.cpp:8616  M_conc_upd (nxs_dyn_slab_state) */
+    NXS_MEANS_MELTPOND_VOLUME = 137,     /* FE.cpp:8621  M_pond_volume */
+    NXS_MEANS_DEL_VI_TEND = 138,         /* FE.cpp:8656  M_del_vi_tend */
+    NXS_MEANS_FREEZE_DAYS = 139,         /* FE.cpp:8640  M_freeze_days */
+    NXS_MEANS_FREEZE_ONSET = 140,        /* FE.cpp:8652  M_freeze_onset */
+    NXS_MEANS_CONC_SUMMER = 141,         /* FE.cpp:8644  M_conc_summer */
+    NXS_MEANS_THICK_SUMMER = 142,        /* FE.cpp:8648  M_thick_summer */
+    NXS_MEANS_FYI_FRACTION = 143,        /* FE.cpp:8601  M_fyi_fraction */
+    NXS_MEANS_AGE_DET = 144,             /* FE.cpp:8606  M_age_det * time_factor / years_in_sec */
+    NXS_MEANS_AGE = 145,                 /* FE.cpp:8611  M_age * time_factor / years_in_sec */
+    NXS_MEANS_QA = 146,                  /* FE.cpp:8697  D_Qa (NXS_SLAB_QA; the rows of nxs_dyn_slab from here on) */
+    NXS_MEANS_QSW = 147,                 /* FE.cpp:8701  D_Qsw */
+    NXS_MEANS_QLW = 148,                 /* FE.cpp:8705  D_Qlw */
+    NXS_MEANS_QSH = 149,                 /* FE.cpp:8709  D_Qsh */
+    NXS_MEANS_QLH = 150,                 /* FE.cpp:8713  D_Qlh */
+    NXS_MEANS_QO = 151,                  /* FE.cpp:8717  D_Qo */
+    NXS_MEANS_DELS = 152,                /* FE.cpp:8721  D_delS */
+    NXS_MEANS_EVAP = 153,                /* FE.cpp:8725  D_evap */
+    NXS_MEANS_RAIN = 154,                /* FE.cpp:8729  D_rain */
+    NXS_MEANS_SIALB = 155,               /* FE.cpp:8733  D_sialb */
+    NXS_MEANS_ALBEDO = 156,              /* FE.cpp:8737  D_albedo */
+    NXS_MEANS_DEL_VI_YOUNG = 157,        /* FE.cpp:8833  D_del_vi_young */
+    NXS_MEANS_VICE_MELT = 158,           /* FE.cpp:8837  D_vice_melt */
+    NXS_MEANS_DEL_HI = 159,              /* FE.cpp:8841  D_del_hi */
+    NXS_MEANS_DEL_HI_YOUNG = 160,        /* FE.cpp:8845  D_del_hi_young */
+    NXS_MEANS_NEWICE = 161,              /* FE.cpp:8849  D_newice */
+    NXS_MEANS_SNOW2ICE = 162,            /* FE.cpp:8853  D_snow2ice */
+    NXS_MEANS_MLT_TOP = 163,             /* FE.cpp:8857  D_mlt_top */
+    NXS_MEANS_MLT_BOT = 164,             /* FE.cpp:8861  D_mlt_bot */
+    NXS_MEANS_DVI_RPLNT_MYI = 165,       /* FE.cpp:8664  D_del_vi_rplnt_myi */
+    NXS_MEANS_DCI_RPLNT_MYI = 166,       /* FE.cpp:8668  D_del_ci_rplnt_myi */
+    NXS_MEANS_DVI_MLT_MYI = 167,         /* FE.cpp:8672  D_del_vi_mlt_myi */
+    NXS_MEANS_DCI_MLT_MYI = 168,         /* FE.cpp:8676  D_del_ci_mlt_myi */
+    NXS_MEANS_FWFLUX_ICE = 169,          /* FE.cpp:8829  -= D_fwflux_ice * time_factor: the reversed sign, here and in the next four */
+    NXS_MEANS_FWFLUX = 170,              /* FE.cpp:8894  -= D_fwflux */
+    NXS_MEANS_QNOSW = 171,               /* FE.cpp:8898  -= D_Qnosun */
+    NXS_MEANS_QSWOCEAN = 172,            /* FE.cpp:8902  -= D_Qsw_ocean */
+    NXS_MEANS_SALTFLUX = 173,            /* FE.cpp:8906  -= D_brine */
+    NXS_MEANS_TAIR = 174,                /* FE.cpp:8785  M_tair (nxs_dyn_flux_atmosphere) */
+    NXS_MEANS_MSLP = 175,                /* FE.cpp:8789  M_mslp */
+    NXS_MEANS_QSW_IN = 176,              /* FE.cpp:8805  M_Qsw_in */
+    NXS_MEANS_SPHUMA = 177,              /* FE.cpp:8793  M_sphuma: the humidity row under NXS_FLUX_HUM_SPHUMA */
+    NXS_MEANS_MIXRAT = 178,              /* FE.cpp:8797  M_mixrat: ... under NXS_FLUX_HUM_MIXRAT */
+    NXS_MEANS_D2M = 179,                 /* FE.cpp:8801  M_dair: ... under NXS_FLUX_HUM_DEWPOINT */
+    NXS_MEANS_QLW_IN = 180,              /* FE.cpp:8809  M_Qlw_in: the long-wave row under NXS_FLUX_LW_QLW_IN */
+    NXS_MEANS_TCC = 181,                 /* FE.cpp:8813  M_tcc: ... under NXS_FLUX_LW_TCC */
+    NXS_MEANS_PRECIP = 182,              /* FE.cpp:8825  M_precip (nxs_dyn_column_forcing) */
+    NXS_MEANS_SNOWFALL = 183,            /* FE.cpp:8817  M_snowfall: the snow row under NXS_COL_SNOWFALL_SNOWFALL */
+    NXS_MEANS_SNOWFR = 184,              /* FE.cpp:8821  M_snowfr: ... under NXS_COL_SNOWFALL_PRECIP_SNOWFR */
+    NXS_MEANS_OCEAN_TEMP = 185,          /* FE.cpp:8873  M_ocean_temp */
+    NXS_MEANS_OCEAN_SALT = 186,          /* FE.cpp:8877  M_ocean_salt */
+    NXS_MEANS_MLD = 187,                 /* FE.cpp:8869  M_mld */
+    NXS_MEANS_TSURF = 188,               /* FE.cpp:8551  D_tsurf of updateIceDiagnostics (FE.cpp:7875-7883) */
+    NXS_MEANS_WSPEED = 189,              /* FE.cpp:8865  windSpeedElement(i) (FE.cpp:6359-6370) of the wind the step reads */
+    NXS_MEANS_THERMO_END = 190,
     /* nodal: accumulated over all M_num_nodes, ghosts included */
     NXS_MEANS_VT_X = 64,          /* FE.cpp:8931  M_VT[i] */
     NXS_MEANS_VT_Y = 65,          /* FE.cpp:8936  M_VT[i + M_num_nodes] */
@@ -426,6 +491,7 @@ enum nxs_means_var {
     NXS_MEANS_NODAL_END = 75
 };
 #define NXS_MEANS_NODAL_BEGIN 64
+#define NXS_MEANS_THERMO_BEGIN 128
 #define NXS_MEANS_MAX_VARS 24   /* entries per list (the list travels to the kernel by value; a workgroup stages 256 rows of it in LDS) */
 
 typedef struct nxs_dyn_means_config {
@@ -445,14 +511,19 @@ typedef struct nxs_dyn_means_grid {
 } nxs_dyn_means_grid;
 
 /*   nxs_dyn_means_configure  the two lists (copied).  The configuration survives nxs_dyn_set_mesh: the accumulators are re-sized and zeroed there, which is
- *                  resetMeshMean(bamgmesh, regrid = true, ...).  NXS_ERR_INVALID: an unknown id, an elemental id in the nodal list or the reverse, more than
+ *                  resetMeshMean(bamgmesh, regrid = true, ...).  The elemental list takes the ids below NXS_MEANS_ELEMENTAL_END and those of NXS_MEANS_THERMO_BEGIN
+ *                  .. NXS_MEANS_THERMO_END - 1, in any mixture.  NXS_ERR_INVALID: an unknown id, an elemental id in the nodal list or the reverse, more than
  *                  NXS_MEANS_MAX_VARS entries, a mask flag without NXS_MEANS_ICE_MASK among the elemental ids.  A refused configuration leaves the previous one.
  *   nxs_dyn_means_set_tau_ow  D_tau_ow ([Ne], written by the thermodynamics): the one input of taux / tauy / taumod that is not the handle's; uploaded like
  *                  a forcing member, NULL detaches.  nxs_dyn_set_mesh detaches it (the size changes).
  *   nxs_dyn_means_update   updateMeans(means, time_factor): one launch over the owned elements, one over the nodes; asynchronous on the handle's stream.  It
  *                  includes the part of updateIceDiagnostics() the configured ids need (no nxs_dyn_ice_diagnostics call first) and only READS state and
  *                  diagnostics.  NXS_ERR_STATE: before nxs_dyn_set_mesh / nxs_dyn_put_state, nothing configured, tauwix / tauwiy without a wave stress
- *                  attached, taux / tauy / taumod without tau_ow attached.
+ *                  attached, taux / tauy / taumod without tau_ow attached.  For a thermodynamic id, naming the variable: its source row was never given on
+ *                  this mesh (nxs_dyn_set_mesh and nxs_dyn_regrid make every such row missing); a row of the slab before the first nxs_dyn_slab /
+ *                  nxs_dyn_slab_coupled on this mesh; t1 / t2 without WINTON rows; an alias that is not the configured source (tcc under NXS_FLUX_LW_QLW_IN,
+ *                  snowfr under NXS_COL_SNOWFALL_SNOWFALL, mixrat under a dew-point humidity ...); wspeed before a forcing.  A list of ids below
+ *                  NXS_MEANS_ELEMENTAL_END launches the kernel it always launched.
  *   nxs_dyn_means_get      synchronised on return.  elemental [Ne][num_elemental], nodal [Nn][num_nodal] host arrays (either may be NULL);
  *                  *elemental_dev / *nodal_dev (either may be NULL) receive the DEVICE pointers of the same interleaved rows (library-owned, valid until
  *                  nxs_dyn_means_configure / nxs_dyn_set_mesh; NULL for an empty list).
@@ -839,7 +910,7 @@ NXS_API int nxs_dyn_column_get(nxs_dyn_handle *h, const nxs_dyn_column_rows *out
  * (FE.cpp:5883-5898): these are nxs_dyn_slab_coupled's, below.  Because FE.cpp:5729-5764 would have to touch the bins, nxs_dyn_slab answers NXS_ERR_STATE while
  * floe-size bins are attached (nxs_dyn_put_coupled with num_fsd_bins > 0): such a host calls nxs_dyn_slab_coupled.  The throw of a wrong newice_type / melt_type is NXS_ERR_INVALID at
  * configuration.  nxs_dyn_regrid does NOT carry nxs_dyn_slab_state across a regrid: nxs_dyn_set_mesh and nxs_dyn_regrid make it missing again, like tice1 /
- * tice2; the host fetches it before a regrid and puts it back after.  The rows are not wired into nxs_dyn_means_*: their device pointers are available.
+ * tice2; the host fetches it before a regrid and puts it back after.  nxs_dyn_means_update accumulates the rows (NXS_MEANS_QA .. NXS_MEANS_SALTFLUX) where they lie.
  *   nxs_slab_default_config   model/options.cpp:329-331, 397-403, 428-449, 543-548
  *   nxs_slab_config_check     what nxs_dyn_slab_configure refuses, without a handle: newice_type outside 1 .. 4, melt_type outside 1 .. 2 (3 is the OASIS branch),
  *                  hnull, PhiF, h_young_min, meltpond_depth_to_fraction, time_relaxation_damage or deltaT_relaxation_damage <= 0 (or NaN), h_young_max <=

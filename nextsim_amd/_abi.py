@@ -370,10 +370,20 @@ class RegridInfo(C.Structure):   # nxs_dyn_regrid_info
 MEANS_ELEMENTAL = ("conc", "thick", "snow", "conc_cons", "damage", "ridge_ratio", "conc_young", "h_young", "hs_young", "conc_myi", "thick_myi",
                    "dci_ridge_myi", "sigma_11", "sigma_22", "sigma_12", "sigma_n", "sigma_s", "divergence", "drag_ui", "ice_mask")
 MEANS_NODAL = ("VT_x", "VT_y", "wind_x", "wind_y", "tau_ax", "tau_ay", "tauwix", "tauwiy", "taux", "tauy", "taumod")
+# the thermodynamic variables, a second elemental range: the rows nxs_dyn_fluxes / nxs_dyn_column / nxs_dyn_slab keep on the handle (C names: upper case)
+MEANS_THERMO = ("sst", "sss", "tsurf_ice", "meltpond_lid_volume", "meltpond_fraction", "drag_ti", "t1", "t2",
+                "conc_upd", "meltpond_volume", "del_vi_tend", "freeze_days", "freeze_onset", "conc_summer", "thick_summer", "fyi_fraction", "age_det", "age",
+                "Qa", "Qsw", "Qlw", "Qsh", "Qlh", "Qo", "delS", "evap", "rain", "sialb", "albedo",
+                "del_vi_young", "vice_melt", "del_hi", "del_hi_young", "newice", "snow2ice", "mlt_top", "mlt_bot",
+                "dvi_rplnt_myi", "dci_rplnt_myi", "dvi_mlt_myi", "dci_mlt_myi", "fwflux_ice", "fwflux", "QNoSw", "QSwOcean", "saltflux",
+                "tair", "mslp", "Qsw_in", "sphuma", "mixrat", "d2m", "Qlw_in", "tcc", "precip", "snowfall", "snowfr", "ocean_temp", "ocean_salt", "mld",
+                "tsurf", "wspeed")
 NXS_MEANS_NODAL_BEGIN = 64
+NXS_MEANS_THERMO_BEGIN = 128
 NXS_MEANS_MAX_VARS = 24
 MEANS_ID = {k: i for i, k in enumerate(MEANS_ELEMENTAL)}
 MEANS_ID.update({k: NXS_MEANS_NODAL_BEGIN + i for i, k in enumerate(MEANS_NODAL)})
+MEANS_ID.update({k: NXS_MEANS_THERMO_BEGIN + i for i, k in enumerate(MEANS_THERMO)})
 
 
 class MeansConfig(C.Structure):   # nxs_dyn_means_config

@@ -1740,6 +1740,126 @@ static unsigned means_sources(int kind, const std::vector<int> &ids, bool young_
     }
     return src;
 }
+
+// the thermodynamic variables (NXS_MEANS_THERMO_BEGIN ..): where each one's source row lies on the handle and what the kernel does with it
+enum MeansFrom { MF_FLUX_ST, MF_COL_ST, MF_SLAB_ST, MF_SLAB_OUT, MF_ATM, MF_COL_FORCING, MF_COMPUTED };
+struct MeansThermoVar { const char *name; int from, row, op; };
+static const MeansThermoVar means_thermo_var[NXS_MEANS_THERMO_END - NXS_MEANS_THERMO_BEGIN] = {
+    // nxs_dyn_flux_state: tice0, tsurf_young, sst, sss, drag_ti, drag_ti_young, pond_fraction, lid_volume
+    {"sst", MF_FLUX_ST, 2, MT_PLAIN}, {"sss", MF_FLUX_ST, 3, MT_PLAIN}, {"tsurf_ice", MF_FLUX_ST, 0, MT_PLAIN}, {"meltpond_lid_volume", MF_FLUX_ST, 7, MT_PLAIN},
+    {"meltpond_fraction", MF_FLUX_ST, 6, MT_PLAIN}, {"drag_ti", MF_COMPUTED, 0, MT_DRAG_TI},
+    // nxs_dyn_column_state
+    {"t1", MF_COL_ST, 0, MT_PLAIN}, {"t2", MF_COL_ST, 1, MT_PLAIN},
+    // nxs_dyn_slab_state
+    {"conc_upd", MF_SLAB_ST, SLAB_ST_CONC_UPD, MT_PLAIN}, {"meltpond_volume", MF_SLAB_ST, SLAB_ST_POND_VOLUME, MT_PLAIN}, {"del_vi_tend", MF_SLAB_ST, SLAB_ST_DEL_VI_TEND, MT_PLAIN},
+    {"freeze_days", MF_SLAB_ST, SLAB_ST_FREEZE_DAYS, MT_PLAIN}, {"freeze_onset", MF_SLAB_ST, SLAB_ST_FREEZE_ONSET, MT_PLAIN}, {"conc_summer", MF_SLAB_ST, SLAB_ST_CONC_SUMMER, MT_PLAIN},
+    {"thick_summer", MF_SLAB_ST, SLAB_ST_THICK_SUMMER, MT_PLAIN}, {"fyi_fraction", MF_SLAB_ST, SLAB_ST_FYI_FRACTION, MT_PLAIN}, {"age_det", MF_SLAB_ST, SLAB_ST_AGE_DET, MT_YEARS},
+    {"age", MF_SLAB_ST, SLAB_ST_AGE, MT_YEARS},
+    // the rows of nxs_dyn_slab
+    {"Qa", MF_SLAB_OUT, SLAB_QA, MT_PLAIN}, {"Qsw", MF_SLAB_OUT, SLAB_QSW, MT_PLAIN}, {"Qlw", MF_SLAB_OUT, SLAB_QLW, MT_PLAIN}, {"Qsh", MF_SLAB_OUT, SLAB_QSH, MT_PLAIN},
+    {"Qlh", MF_SLAB_OUT, SLAB_QLH, MT_PLAIN}, {"Qo", MF_SLAB_OUT, SLAB_QO, MT_PLAIN}, {"delS", MF_SLAB_OUT, SLAB_DELS, MT_PLAIN}, {"evap", MF_SLAB_OUT, SLAB_EVAP, MT_PLAIN},
+    {"rain", MF_SLAB_OUT, SLAB_RAIN, MT_PLAIN}, {"sialb", MF_SLAB_OUT, SLAB_SIALB, MT_PLAIN}, {"albedo", MF_SLAB_OUT, SLAB_ALBEDO, MT_PLAIN},
+    {"del_vi_young", MF_SLAB_OUT, SLAB_DEL_VI_YOUNG, MT_PLAIN}, {"vice_melt", MF_SLAB_OUT, SLAB_VICE_MELT, MT_PLAIN}, {"del_hi", MF_SLAB_OUT, SLAB_DEL_HI, MT_PLAIN},
+    {"del_hi_young", MF_SLAB_OUT, SLAB_DEL_HI_YOUNG, MT_PLAIN}, {"newice", MF_SLAB_OUT, SLAB_NEWICE, MT_PLAIN}, {"snow2ice", MF_SLAB_OUT, SLAB_SNOW2ICE, MT_PLAIN},
+    {"mlt_top", MF_SLAB_OUT, SLAB_MLT_TOP, MT_PLAIN}, {"mlt_bot", MF_SLAB_OUT, SLAB_MLT_BOT, MT_PLAIN}, {"dvi_rplnt_myi", MF_SLAB_OUT, SLAB_DEL_VI_RPLNT_MYI, MT_PLAIN},
+    {"dci_rplnt_myi", MF_SLAB_OUT, SLAB_DEL_CI_RPLNT_MYI, MT_PLAIN}, {"dvi_mlt_myi", MF_SLAB_OUT, SLAB_DEL_VI_MLT_MYI, MT_PLAIN}, {"dci_mlt_myi", MF_SLAB_OUT, SLAB_DEL_CI_MLT_MYI, MT_PLAIN},
+    {"fwflux_ice", MF_SLAB_OUT, SLAB_FWFLUX_ICE, MT_NEG}, {"fwflux", MF_SLAB_OUT, SLAB_FWFLUX, MT_NEG}, {"QNoSw", MF_SLAB_OUT, SLAB_QNOSUN, MT_NEG},
+    {"QSwOcean", MF_SLAB_OUT, SLAB_QSW_OCEAN, MT_NEG}, {"saltflux", MF_SLAB_OUT, SLAB_BRINE, MT_NEG},
+    // nxs_dyn_flux_atmosphere: tair, mslp, Qsw_in, humidity, longwave
+    {"tair", MF_ATM, 0, MT_PLAIN}, {"mslp", MF_ATM, 1, MT_PLAIN}, {"Qsw_in", MF_ATM, 2, MT_PLAIN}, {"sphuma", MF_ATM, 3, MT_PLAIN}, {"mixrat", MF_ATM, 3, MT_PLAIN},
+    {"d2m", MF_ATM, 3, MT_PLAIN}, {"Qlw_in", MF_ATM, 4, MT_PLAIN}, {"tcc", MF_ATM, 4, MT_PLAIN},
+    // nxs_dyn_column_forcing: precip, snow, ocean_temp, ocean_salt, mld
+    {"precip", MF_COL_FORCING, 0, MT_PLAIN}, {"snowfall", MF_COL_FORCING, 1, MT_PLAIN}, {"snowfr", MF_COL_FORCING, 1, MT_PLAIN}, {"ocean_temp", MF_COL_FORCING, 2, MT_PLAIN},
+    {"ocean_salt", MF_COL_FORCING, 3, MT_PLAIN}, {"mld", MF_COL_FORCING, 4, MT_PLAIN},
+    {"tsurf", MF_COMPUTED, 0, MT_TSURF}, {"wspeed", MF_COMPUTED, 0, MT_WSPEED},
+};
+static_assert(NXS_MEANS_SST == NXS_MEANS_THERMO_BEGIN && NXS_MEANS_T1 == NXS_MEANS_THERMO_BEGIN + 6 && NXS_MEANS_CONC_UPD == NXS_MEANS_THERMO_BEGIN + 8 &&
+              NXS_MEANS_QA == NXS_MEANS_THERMO_BEGIN + 18 && NXS_MEANS_FWFLUX_ICE == NXS_MEANS_THERMO_BEGIN + 41 && NXS_MEANS_TAIR == NXS_MEANS_THERMO_BEGIN + 46 &&
+              NXS_MEANS_PRECIP == NXS_MEANS_THERMO_BEGIN + 54 && NXS_MEANS_TSURF == NXS_MEANS_THERMO_BEGIN + 60 && NXS_MEANS_WSPEED + 1 == NXS_MEANS_THERMO_END &&
+              NXS_MEANS_THERMO_END <= 256, "means_thermo_var is in the order of enum nxs_means_var; MeansTable::id is an unsigned char");
+
+static bool means_is_thermo(int id) { return id >= NXS_MEANS_THERMO_BEGIN && id < NXS_MEANS_THERMO_END; }
+
+// The by-value table of the thermodynamic columns of the elemental list, with every refusal of nxs_dyn_means_update about them; *src gains the MS_* bits of the
+// computed variables.  Returns NXS_OK with *any = false for a list without such a column.
+static int means_thermo_table(nxs_dyn_handle *h, bool young, MeansThermo *th, unsigned *src, bool *any) {
+    *th = MeansThermo{};
+    *any = false;
+    const std::vector<int> &ids = h->means_ids[0];
+    for (size_t k = 0; k < ids.size(); ++k) {
+        th->row[k] = h->ds.conc;   // (a column that reads no row: the kernel's unconditional load has a valid address)
+        if (!means_is_thermo(ids[k])) continue;
+        *any = true;
+        const MeansThermoVar &v = means_thermo_var[ids[k] - NXS_MEANS_THERMO_BEGIN];
+        th->op[k] = (unsigned char)v.op;
+        const unsigned bit = 1u << v.row;
+        switch (v.from) {
+            case MF_FLUX_ST:
+                if (!(h->flux_st_have & bit)) return fail(h, NXS_ERR_STATE, "means_update: %s is configured but its row was never given on this mesh (nxs_dyn_flux_put)", v.name);
+                th->row[k] = h->d_flux_st[v.row];
+                break;
+            case MF_COL_ST:
+                if ((h->col_configured && h->col_cfg.thermo_type != NXS_COL_THERMO_WINTON) || !(h->col_st_have & bit))
+                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured without WINTON rows (tice1 / tice2: nxs_dyn_column_put under NXS_COL_THERMO_WINTON)", v.name);
+                th->row[k] = h->d_col_st[v.row];
+                break;
+            case MF_SLAB_ST:
+                if (!(h->slab_st_have & bit)) return fail(h, NXS_ERR_STATE, "means_update: %s is configured but its row was never given on this mesh (nxs_dyn_slab_put)", v.name);
+                th->row[k] = h->d_slab_st[v.row];
+                break;
+            case MF_SLAB_OUT:
+                if (!h->slab_done || !h->d_slab_out)
+                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but reads a row of the slab before the first nxs_dyn_slab / nxs_dyn_slab_coupled on this mesh", v.name);
+                th->row[k] = h->d_slab_out + (size_t)v.row * h->dm.Ne;
+                break;
+            case MF_ATM: {
+                if (v.row >= 3 && !h->flux_configured)
+                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured before nxs_dyn_flux_configure (which row it is follows from the configured source)", v.name);
+                const int id = ids[k], hs = h->flux_cfg.humidity_source, ls = h->flux_cfg.longwave_source;
+                if ((id == NXS_MEANS_SPHUMA && hs != NXS_FLUX_HUM_SPHUMA) || (id == NXS_MEANS_MIXRAT && hs != NXS_FLUX_HUM_MIXRAT) || (id == NXS_MEANS_D2M && hs != NXS_FLUX_HUM_DEWPOINT))
+                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but the humidity row is %s (humidity_source = %d)", v.name,
+                                hs == NXS_FLUX_HUM_SPHUMA ? "sphuma" : hs == NXS_FLUX_HUM_MIXRAT ? "mixrat" : "d2m", hs);
+                if ((id == NXS_MEANS_QLW_IN && ls != NXS_FLUX_LW_QLW_IN) || (id == NXS_MEANS_TCC && ls != NXS_FLUX_LW_TCC))
+                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but the long-wave row is %s (longwave_source = %d)", v.name, ls == NXS_FLUX_LW_TCC ? "tcc" : "Qlw_in", ls);
+                if (!(h->flux_atm_have & bit))
+                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but its row was never given on this mesh (nxs_dyn_flux_set_atmosphere)", v.name);
+                th->row[k] = h->d_flux_atm[v.row];
+                break;
+            }
+            case MF_COL_FORCING: {
+                if (v.row == 1) {
+                    if (!h->col_configured)
+                        return fail(h, NXS_ERR_STATE, "means_update: %s is configured before nxs_dyn_column_configure (which row it is follows from the configured source)", v.name);
+                    const int ss = h->col_cfg.snowfall_source;
+                    if (ss != (ids[k] == NXS_MEANS_SNOWFALL ? NXS_COL_SNOWFALL_SNOWFALL : NXS_COL_SNOWFALL_PRECIP_SNOWFR))
+                        return fail(h, NXS_ERR_STATE, "means_update: %s is configured but the snow row is %s (snowfall_source = %d)", v.name,
+                                    ss == NXS_COL_SNOWFALL_SNOWFALL ? "snowfall" : ss == NXS_COL_SNOWFALL_PRECIP_SNOWFR ? "snowfr" : "not read", ss);
+                }
+                if (!(h->col_forcing_have & bit))
+                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but its row was never given on this mesh (nxs_dyn_column_set_forcing)", v.name);
+                th->row[k] = h->d_col_forcing[v.row];
+                break;
+            }
+            default:   // MF_COMPUTED
+                if (v.op == MT_DRAG_TI) {
+                    const unsigned need = 1u << 4 | (young ? 1u << 5 : 0);
+                    if ((h->flux_st_have & need) != need)
+                        return fail(h, NXS_ERR_STATE, "means_update: drag_ti is configured but drag_ti%s was never given on this mesh (nxs_dyn_flux_put)", young ? " / drag_ti_young" : "");
+                    th->drag_ti = h->d_flux_st[4]; th->drag_ti_young = h->d_flux_st[5];
+                    if (young) *src |= MS_CONC | MS_CYOUNG;
+                } else if (v.op == MT_TSURF) {
+                    const unsigned need = 1u << 0 | 1u << 2 | (young ? 1u << 1 : 0);
+                    if ((h->flux_st_have & need) != need)
+                        return fail(h, NXS_ERR_STATE, "means_update: tsurf is configured but tice0, sst%s were not all given on this mesh (nxs_dyn_flux_put)", young ? ", tsurf_young" : "");
+                    th->tice0 = h->d_flux_st[0]; th->tsurf_young = h->d_flux_st[1]; th->sst = h->d_flux_st[2];
+                    *src |= MS_CONC | (young ? MS_CYOUNG : 0);
+                } else if (!h->have_forcing)
+                    return fail(h, NXS_ERR_STATE, "means_update: wspeed is configured before a forcing (the wind: nxs_dyn_set_forcing)");
+                break;
+        }
+    }
+    return NXS_OK;
+}
 namespace {
 // device memory of one nxs_dyn_regrid call: freed when the call ends, except what the new mesh has taken over (release)
 struct RegridScratch {
@@ -3077,7 +3197,7 @@ int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) tr
     int ice_col = -1;
     bool any_mask = false;
     for (size_t k = 0; k < ids[0].size(); ++k) {
-        if (ids[0][k] < 0 || ids[0][k] >= NXS_MEANS_ELEMENTAL_END)
+        if ((ids[0][k] < 0 || ids[0][k] >= NXS_MEANS_ELEMENTAL_END) && !means_is_thermo(ids[0][k]))
             return fail(h, NXS_ERR_INVALID, "means_configure: elemental_ids[%d] = %d is not an elemental NXS_MEANS_* id", (int)k, ids[0][k]);
         if (ids[0][k] == NXS_MEANS_ICE_MASK && ice_col < 0) ice_col = (int)k;
         any_mask = any_mask || mask[0][k];
@@ -3122,15 +3242,19 @@ int nxs_dyn_means_update(nxs_dyn_handle *h, double time_factor) try {
         if ((id == NXS_MEANS_TAUX || id == NXS_MEANS_TAUY || id == NXS_MEANS_TAUMOD) && !h->tau_ow_attached)
             return fail(h, NXS_ERR_STATE, "means_update: taux / tauy / taumod are configured but no D_tau_ow is attached (nxs_dyn_means_set_tau_ow)");
     }
+    const int young = h->dp.young_cat ? 1 : 0;
+    MeansThermo th;
+    unsigned thermo_src = 0;
+    bool thermo = false;
+    if (int rc = means_thermo_table(h, young != 0, &th, &thermo_src, &thermo)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     // (the opt-in one-launch loops can give up half-way: never a mean of a half-made step without an error -- as nxs_dyn_ice_diagnostics; the default path stays asynchronous)
     if (int rc = launch_gave_up(h)) return rc;
-    const int young = h->dp.young_cat ? 1 : 0;
     for (int k = 0; k < 2; ++k) {
         MeansTable &t = h->means_tab[k];
         t = MeansTable{};
         t.n = (int)h->means_ids[k].size();
-        t.src = means_sources(k, h->means_ids[k], young != 0);
+        t.src = means_sources(k, h->means_ids[k], young != 0) | (k ? 0 : thermo_src);
         for (int q = 0; q < t.n; ++q) t.id[q] = (unsigned char)(h->means_ids[k][q] - (k ? NXS_MEANS_NODAL_BEGIN : 0));
     }
     const bool stage = h->means_stage != 0;
@@ -3138,7 +3262,12 @@ int nxs_dyn_means_update(nxs_dyn_handle *h, double time_factor) try {
     if (h->means_tab[0].n > 0 && h->dm.Neo > 0) {
         const MeansTable &t = h->means_tab[0];
         const double *S4 = h->sig_loc ? (const double *)h->ds.S4a : (const double *)nullptr;
-        if (stage) hipLaunchKernelGGL(k_means_elements<true>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), (size_t)BLOCK * t.n * sizeof(double), h->stream, h->dm, h->ds,
+        if (thermo) {   // the list names a thermodynamic variable: the same kernel with their table
+            if (stage) hipLaunchKernelGGL(k_means_elements_thermo<true>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), (size_t)BLOCK * t.n * sizeof(double), h->stream, h->dm, h->ds,
+                                          (const double *)h->dw.D_del, young, S4, t, th, time_factor, h->d_means[0]);
+            else hipLaunchKernelGGL(k_means_elements_thermo<false>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->dw.D_del, young, S4,
+                                    t, th, time_factor, h->d_means[0]);
+        } else if (stage) hipLaunchKernelGGL(k_means_elements<true>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), (size_t)BLOCK * t.n * sizeof(double), h->stream, h->dm, h->ds,
                                       (const double *)h->dw.D_del, young, S4, t, time_factor, h->d_means[0]);
         else hipLaunchKernelGGL(k_means_elements<false>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->dw.D_del, young, S4, t,
                                 time_factor, h->d_means[0]);

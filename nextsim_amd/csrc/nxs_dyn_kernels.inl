@@ -10,6 +10,7 @@
 #define NXS_OMEGA 7.292e-5
 #define NXS_PI 3.141592653589793238462643383279502884197169399375105820974944592308
 #define NXS_DAYS_IN_SEC 86400.
+#define NXS_YEARS_IN_SEC (365.25 * NXS_DAYS_IN_SEC)   // model/constants.hpp: 31557600, exact
 #define NXS_SI 5.          // physical::si, model/constants.hpp:68
 #define NXS_LF 333.55e3    // physical::Lf, model/constants.hpp:44
 #define NXS_HEAT_C 2100.   // physical::C, model/constants.hpp:17
@@ -3196,6 +3197,8 @@ __global__ void __launch_bounds__(BLOCK) k_ghost_ring_move(DevMesh m, DevState s
     s.UT[n] = utu; s.UT[n + Nn] = utv;
 }
 
+#include "nxs_wind_speed.inl"   // wind_speed_element: k_fluxes, k_slab and the Moorings mean `wspeed` share it
+
 // The arithmetic of updateIceDiagnostics() (FE.cpp:7860-7905) that k_ice_diagnostics and the Moorings means (k_means_elements) share -- one statement of it,
 // so that the two give the same bits: the principal stresses, and the divergence of M_VT on the mesh displaced by M_UM (shapeCoeff, FE.cpp:1951-1964).
 __device__ __forceinline__ void ice_diag_sigma(double s0, double s1, double s2, double &sigma_n, double &sigma_s) {
@@ -3253,6 +3256,25 @@ enum { MS_CONC = 1, MS_THICK = 2, MS_SNOW = 4, MS_SIGMA = 8 /* + damage when it 
        MS_HSYOUNG = 256, MS_CMYI = 512, MS_TMYI = 1024, MS_DEL = 2048, MS_DRAG = 4096, MS_DRAGY = 8192, MS_DIV = 16384 };
 enum { MN_VT = 1, MN_WIND = 2, MN_TAUA = 4, MN_TAUW = 8, MN_TAUWI = 16, MN_GATHER = 32 };
 
+// The thermodynamic variables (NXS_MEANS_THERMO_BEGIN ..): some sixty sources do not fit the MS_* word, and nearly all of them are `row[e] * tf` of a row that lies
+// on the handle already.  So a list that names one travels with a second by-value table: per column the row's device pointer (a scalar load, then one coalesced
+// read) and what to do with it.  A row is read once per variable that names it.  The three computed variables take conc / conc_young from MeansElem (the host sets
+// their MS_* bits) and their other sources from the named members.  The rows are read UNCONDITIONALLY, four columns at a time before the first is used (a column
+// without a row reads M_conc, a line the element has in cache anyway): one load at a time behind a branch on the op code left the launch waiting on 24 latencies in
+// a row at the occupancy 48 KB of LDS per workgroup allow.
+enum { MT_PLAIN = 0,      // += x * tf
+       MT_NEG,            // -= x * tf (FE.cpp:8829-8832, 8894-8909), staged as -(x * tf): a - b and a + (-b) are the same bits
+       MT_YEARS,          // += x * tf / years_in_sec (FE.cpp:8606-8614): a rounded product, then a rounded quotient
+       MT_DRAG_TI,        // FE.cpp:8767-8777
+       MT_TSURF,          // D_tsurf, FE.cpp:7875-7883
+       MT_WSPEED };       // windSpeedElement, FE.cpp:6359-6370
+struct MeansThermo {
+    const double *row[NXS_MEANS_MAX_VARS];    // [Ne] per column (MT_PLAIN, MT_NEG, MT_YEARS); every other column of the list points at M_conc: read, not used
+    const double *drag_ti, *drag_ti_young;    // MT_DRAG_TI
+    const double *tice0, *tsurf_young, *sst;  // MT_TSURF
+    unsigned char op[NXS_MEANS_MAX_VARS];     // MT_* per column (ignored where the id is below NXS_MEANS_THERMO_BEGIN)
+};
+
 struct MeansElem { double conc, thick, snow, damage, ridge, s0, s1, s2, cy, hy, hsy, cmyi, tmyi, del, drag, dragy, div, sn, ss; };
 
 // the increment of one elemental variable (already multiplied by time_factor where the reference multiplies)
@@ -3286,6 +3308,28 @@ __device__ __forceinline__ double means_elem_value(int id, const MeansElem &f, i
     }
 }
 
+// the increment of one thermodynamic variable, column k of the list; x = th.row[k][e]
+__device__ __forceinline__ double means_thermo_value(const MeansThermo &th, int k, double x, int e, const MeansElem &f, const DevMesh &m, const DevState &s, int young_cat, double tf) {
+    switch (th.op[k]) {
+        case MT_PLAIN: return x * tf;
+        case MT_NEG: return -(x * tf);
+        case MT_YEARS: return x * tf / NXS_YEARS_IN_SEC;
+        case MT_DRAG_TI: {                                                               // FE.cpp:8767-8777, as drag_ui above
+            double drag = th.drag_ti[e];
+            if (young_cat) drag = (drag * f.conc + th.drag_ti_young[e] * f.cy) / (f.conc + f.cy);
+            return drag * tf;
+        }
+        case MT_TSURF: {                                                                 // FE.cpp:7872-7883: every product and sum rounded on its own
+            double d_conc = f.conc, tsurf = f.conc * th.tice0[e];
+            if (young_cat) { d_conc += f.cy; tsurf += f.cy * th.tsurf_young[e]; }
+            tsurf += (1 - d_conc) * th.sst[e];
+            return tsurf * tf;
+        }
+        default: /* MT_WSPEED */
+            return wind_speed_element(s.wind, m.Nn, m.t0[e], m.t1[e], m.t2[e]) * tf;
+    }
+}
+
 // acc[base .. base + count) += stage[0 .. count): a workgroup's rows as ONE contiguous stream, 16 bytes per lane (base is even: a multiple of BLOCK)
 __device__ __forceinline__ void means_add_staged(double *__restrict__ acc, size_t base, const double *stage, int count) {
     typedef double d2 __attribute__((ext_vector_type(2)));
@@ -3297,9 +3341,10 @@ __device__ __forceinline__ void means_add_staged(double *__restrict__ acc, size_
 
 // Elemental pass: one thread per OWNED element (ghost rows are not touched: FE.cpp:8527 loops i < M_local_nelements).
 // STAGE: the increments of a workgroup go to LDS ([BLOCK][n], dynamic) and are added to the rows as one stream; else every thread walks its own row.
-template <bool STAGE>
-__global__ void __launch_bounds__(BLOCK) k_means_elements(DevMesh m, DevState s, const double *__restrict__ D_del, int young_cat, const double *__restrict__ S4,
-                                                          MeansTable t, double tf, double *__restrict__ acc) {
+// THERMO: the list names a thermodynamic variable and `th` is its table; without, nothing of `th` is compiled in and the kernel is the one it was.
+template <bool STAGE, bool THERMO>
+__device__ __forceinline__ void means_elements_body(const DevMesh &m, const DevState &s, const double *__restrict__ D_del, int young_cat, const double *__restrict__ S4,
+                                                    const MeansTable &t, const MeansThermo &th, double tf, double *__restrict__ acc) {
     extern __shared__ double means_stage[];
     const int e = min(blockIdx.x * BLOCK + (int)threadIdx.x, m.Neo - 1);  // (threads past the end redo the last owned element: every thread reaches the barrier)
     const bool live = blockIdx.x * BLOCK + (int)threadIdx.x < m.Neo;
@@ -3330,25 +3375,54 @@ __global__ void __launch_bounds__(BLOCK) k_means_elements(DevMesh m, DevState s,
     if (src & MS_SIGMA) ice_diag_sigma(f.s0, f.s1, f.s2, f.sn, f.ss);
     if (src & MS_DIV) f.div = ice_diag_divergence(m, s, e);
     const int n = t.n;
+    // the increment of column k, x its row's entry: the id is the list's, so the branch is wave-uniform
+    auto value_of = [&](int k, double x) -> double {
+        if constexpr (THERMO) { if (t.id[k] >= NXS_MEANS_THERMO_BEGIN) return means_thermo_value(th, k, x, e, f, m, s, young_cat, tf); }
+        return means_elem_value(t.id[k], f, young_cat, tf);
+    };
+    auto value = [&](int k) -> double {
+        if constexpr (THERMO) return value_of(k, th.row[k][e]);
+        return value_of(k, 0.);
+    };
     if (STAGE) {
         double *r = means_stage + (size_t)threadIdx.x * n;
-        for (int k = 0; k < n; ++k) r[k] = means_elem_value(t.id[k], f, young_cat, tf);
+        if constexpr (THERMO) {
+            for (int k0 = 0; k0 < n; k0 += 4) {   // four rows requested, then four increments
+                double x[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[j] = th.row[min(k0 + j, n - 1)][e];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) if (k0 + j < n) r[k0 + j] = value_of(k0 + j, x[j]);
+            }
+        } else {
+            for (int k = 0; k < n; ++k) r[k] = value(k);
+        }
         __syncthreads();
         means_add_staged(acc, (size_t)blockIdx.x * BLOCK * n, means_stage, min(BLOCK, m.Neo - (int)blockIdx.x * BLOCK) * n);
     } else if (live) {
         double *row = acc + (size_t)e * n;
         if (n & 1) {
-            for (int k = 0; k < n; ++k) row[k] += means_elem_value(t.id[k], f, young_cat, tf);
+            for (int k = 0; k < n; ++k) row[k] += value(k);
         } else {
             typedef double d2 __attribute__((ext_vector_type(2)));
             d2 *row2 = reinterpret_cast<d2 *>(row);
             for (int k = 0; k < n; k += 2) {
                 d2 a = row2[k / 2];
-                a.x += means_elem_value(t.id[k], f, young_cat, tf); a.y += means_elem_value(t.id[k + 1], f, young_cat, tf);
+                a.x += value(k); a.y += value(k + 1);
                 row2[k / 2] = a;
             }
         }
     }
+}
+template <bool STAGE>
+__global__ void __launch_bounds__(BLOCK) k_means_elements(DevMesh m, DevState s, const double *__restrict__ D_del, int young_cat, const double *__restrict__ S4,
+                                                          MeansTable t, double tf, double *__restrict__ acc) {
+    means_elements_body<STAGE, false>(m, s, D_del, young_cat, S4, t, MeansThermo{}, tf, acc);
+}
+template <bool STAGE>
+__global__ void __launch_bounds__(BLOCK) k_means_elements_thermo(DevMesh m, DevState s, const double *__restrict__ D_del, int young_cat, const double *__restrict__ S4,
+                                                                 MeansTable t, MeansThermo th, double tf, double *__restrict__ acc) {
+    means_elements_body<STAGE, true>(m, s, D_del, young_cat, S4, t, th, tf, acc);
 }
 
 // hypot for the Moorings stresses (FE.cpp:8980, 8996).  The reference calls the host C library's, which rounds correctly in all but rare cases; OCML's is allowed a

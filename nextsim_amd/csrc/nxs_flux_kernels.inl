@@ -22,6 +22,8 @@
 #define NXS_GAMMA_D 0.0098
 #define NXS_PHYS_G 9.8   // physical::g (NOT physical::gravity)
 
+#include "nxs_wind_speed.inl"   // wind_speed_element: shared with k_slab and the Moorings means
+
 enum { FLUX_QOW = 0, FLUX_QLW_OW, FLUX_QSW_OW, FLUX_QLH_OW, FLUX_QSH_OW, FLUX_EVAP, FLUX_TAU_OW,
        FLUX_QIA, FLUX_QLWI, FLUX_QSWI, FLUX_QLHI, FLUX_QSHI, FLUX_I, FLUX_SUBL, FLUX_DQIADT, FLUX_ALBEDO, FLUX_YOUNG = 16 /* the nine rows again */, FLUX_ROWS = 25 };
 enum { FLUX_ATM_ROWS = 5 /* nxs_dyn_flux_atmosphere */, FLUX_ST_ROWS = 8 /* nxs_dyn_flux_state */ };
@@ -225,13 +227,7 @@ __global__ void __launch_bounds__(BLOCK) k_fluxes(FluxArrays a, FluxDev c) {
         const double taa = at.tair + NXS_TFRWK;
         at.Qlw_in = NXS_SIGMA_SB * pow(taa, 4.) * (1. - 0.261 * exp(-7.77e-4 * pow(taa - NXS_TFRWK, 2.))) * (1. + 0.275 * a.lw[e]);
     }
-    {   // windSpeedElement, FE.cpp:6359-6370
-        const int nd[3] = {a.t0[e], a.t1[e], a.t2[e]};
-        double wspd = 0.;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) wspd += hypot(a.wind[nd[j]], a.wind[nd[j] + a.Nn]);
-        at.wspeed = wspd / 3.;
-    }
+    at.wspeed = wind_speed_element(a.wind, a.Nn, a.t0[e], a.t1[e], a.t2[e]);   // windSpeedElement, FE.cpp:6359-6370
     at.rhoair = at.mslp / (NXS_RA_DRY * (at.tair + NXS_TFRWK)) * (1. - at.sphuma * (1. - NXS_RA_VAP / NXS_RA_DRY));   // FE.cpp:5110, 6227
     {   // OWBulkFluxes, FE.cpp:5096-5132 and 5138-5158
         const double sst = a.sst[e];

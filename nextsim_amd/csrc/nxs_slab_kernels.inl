@@ -22,6 +22,8 @@
 // physical::, model/constants.hpp (cpw, ki and hmin are nxs_column_kernels.inl's)
 #define NXS_CMIN 1e-12
 
+#include "nxs_wind_speed.inl"   // wind_speed_element: shared with k_fluxes and the Moorings means
+
 enum { SLAB_QA = 0, SLAB_QSW, SLAB_QLW, SLAB_QSH, SLAB_QLH, SLAB_QO, SLAB_QNOSUN, SLAB_QSW_OCEAN, SLAB_QASSIM, SLAB_DELS, SLAB_FWFLUX_ICE, SLAB_FWFLUX, SLAB_BRINE,
        SLAB_EVAP, SLAB_RAIN, SLAB_VICE_MELT, SLAB_DEL_VI_YOUNG, SLAB_DEL_HI, SLAB_DEL_HI_YOUNG, SLAB_NEWICE, SLAB_MLT_TOP, SLAB_MLT_BOT, SLAB_SNOW2ICE, SLAB_ALBEDO,
        SLAB_SIALB, SLAB_DEL_CI_MLT_MYI, SLAB_DEL_VI_MLT_MYI, SLAB_DEL_CI_RPLNT_MYI, SLAB_DEL_VI_RPLNT_MYI, SLAB_ROWS = 29 };
@@ -190,11 +192,7 @@ __device__ __forceinline__ void slab_element(const SlabArrays &a, const SlabDev 
         } else
             del_c = 0.;
     } else if (c.newice_type == 3) {
-        const int nd[3] = {a.t0[e], a.t1[e], a.t2[e]};
-        double wspeed = 0.;   // windSpeedElement, FE.cpp:6359-6370
-#pragma unroll
-        for (int j = 0; j < 3; ++j) wspeed += hypot(a.wind[nd[j]], a.wind[nd[j] + a.Nn]);
-        wspeed = wspeed / 3.;
+        const double wspeed = wind_speed_element(a.wind, a.Nn, a.t0[e], a.t1[e], a.t2[e]);   // windSpeedElement, FE.cpp:6359-6370
         const double h0 = (1. + 0.1 * wspeed) / 15.;
         const double hp = c.rPhiF * hi_old;
         if (hp < h0) br |= NXS_SLAB_BR_N3_H0;

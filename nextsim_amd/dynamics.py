@@ -1083,8 +1083,10 @@ class FiniteElementDynamics:
         return np.asarray(ids, np.int32), np.asarray(masks, np.uint8)
 
     def means_configure(self, elemental=(), nodal=()):
-        """The output variables of the Moorings (GridOutput's M_elemental_variables / M_nodal_variables): names of _abi.MEANS_ELEMENTAL / MEANS_NODAL (or
-        NXS_MEANS_* numbers), each optionally as (name, mask) for Variable::mask.  Two empty lists switch the feature off.  Survives set_mesh."""
+        """The output variables of the Moorings (GridOutput's M_elemental_variables / M_nodal_variables): names of _abi.MEANS_ELEMENTAL and MEANS_THERMO (the
+        elemental list takes both, mixed) / MEANS_NODAL (or NXS_MEANS_* numbers), each optionally as (name, mask) for Variable::mask.  Two empty lists switch the
+        feature off.  Survives set_mesh.  A thermodynamic variable reads the row fluxes() / column() / slab() left on the handle: means_update refuses while it is
+        missing."""
         ei, em = self._means_list(elemental, 0, len(_abi.MEANS_ELEMENTAL))
         ni, nm = self._means_list(nodal, _abi.NXS_MEANS_NODAL_BEGIN, _abi.NXS_MEANS_NODAL_BEGIN + len(_abi.MEANS_NODAL))
         c = _abi.MeansConfig()

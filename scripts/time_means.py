@@ -3,6 +3,7 @@ nxs_dyn_get_state / nxs_dyn_get_diag of the members the variables need, numpy su
 
     python scripts/time_means.py [mesh] [--out DIR]      measure on the GPU, write DIR/means_accumulate.json (default profiles/) and DESIGN.md's table
     python scripts/time_means.py --from-json FILE        no GPU: copy FILE to profiles/means_accumulate.json and rewrite DESIGN.md's table from it
+    python scripts/time_means.py --thermo [mesh] [--out DIR]   the thermodynamic variables: DIR/means_thermo.json (see measure_thermo); --old-only: its first part
 
 Workload: ten elemental variables + VT_x, VT_y, taux, tauy.  Reported: device time of means_update from HIP events (option "means_timing"), warm, median
 of 25, for both read-modify-write patterns (option "means_stage"); its share of the step; the bytes it has to move (every distinct source field once +
@@ -147,6 +148,85 @@ def measure(kind, out_dir):
     return res
 
 
+# the 24-variable thermodynamic list: 19 rows of the slab (five of them negated), four of its state, tsurf -- what a time-mean Moorings file with the heat and
+# fresh-water budget asks for
+THERMO = ("Qa", "Qsw", "Qlw", "Qsh", "Qlh", "Qo", "delS", "evap", "rain", "sialb", "albedo", "vice_melt", "del_hi", "newice", "snow2ice", "mlt_top", "mlt_bot",
+          "fwflux_ice", "fwflux", "QNoSw", "QSwOcean", "saltflux", "sst", "tsurf")
+THERMO_SLAB_ROWS = ("Qa", "Qsw", "Qlw", "Qsh", "Qlh", "Qo", "delS", "evap", "rain", "sialb", "albedo", "vice_melt", "del_hi", "newice", "snow2ice", "mlt_top", "mlt_bot",
+                    "fwflux_ice", "fwflux", "Qnosun", "Qsw_ocean", "brine")                    # the same rows under the names of nxs_dyn_slab_get
+THERMO_FLUX_ROWS = ("sst", "tice0", "tsurf_young")                                              # ... and of nxs_dyn_flux_get (tsurf's sources beside conc, conc_young)
+
+
+def _timed_updates(fe, np, n=25):
+    """the elemental launch of n warm means_update calls [us]: median, smallest, largest -- the spread a comparison of two builds has to exceed"""
+    for _ in range(3):
+        fe.means_update(0.01)
+    t = []
+    for _ in range(n):
+        fe.means_update(0.01)
+        t.append(fe.debug_array("means_update_ms")[0])
+    t = np.array(t) * 1e3
+    return {"median_us": float(np.median(t)), "min_us": float(t.min()), "max_us": float(t.max()), "samples": n}
+
+
+def measure_thermo(kind, out_dir, old_only=False):
+    """Two figures of the same run on the mesh `kind`, the designed thermodynamic inputs of tests/slab_ref.py, WINTON, the young-ice category:
+    nxs_dyn_means_update with the 24-variable list THERMO (device time of the elemental launch, HIP events), and what a host pays for the same variables
+    without it: nxs_dyn_slab_get / nxs_dyn_flux_get of those rows into host memory (wall time, the copies alone: the sums come on top).
+    Before them the twenty ids the handle always had (_abi.MEANS_ELEMENTAL), a list that launches the kernel it always launched: with --old-only the script stops
+    there, which is the part an earlier build of the library can run too -- the figure to hold against this one's, with the spread printed."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import column_ref as CR
+    import fluxes_ref as FR
+    import slab_ref as R
+    from nextsim_amd import _abi, dynamics, forcing as F, mesh as M
+
+    gm = M.make_mesh(kind)
+    p, C_fix, C_alea = F.scale_params_to_mesh(F.default_params(ice_cat_type=_abi.NXS_ICECAT_YOUNG_ICE), gm, alea_factor=0.33)
+    g = F.global_fields(gm, p, "arctic", C_fix, C_alea)
+    lm = M.localize(gm, 1)[0]
+    f = F.localize_fields(g, lm, gm.num_nodes)
+    Ne = lm.num_elements
+    tri = lm.indices.reshape(-1, 3).astype(np.int64) - 1
+    inp, _, _ = R.make_inputs(lm.coord_x, lm.coord_y, tri)
+    inp = R.sane_inputs(inp, f)
+    finp, _ = FR.make_inputs(lm.coord_x, lm.coord_y, tri, drag_ui0=p.quad_drag_coef_air)
+    fe, f = R.gpu_handle(p, lm, f, inp, finp, CR.default_config(thermo_type="winton"), R.default_config(), put=R.SLAB_STATE)
+    fe.fluxes(); fe.column(R.DT); fe.slab(R.DT, R.clock()); fe.step()
+    fe.synchronize()
+    fe.set_option("means_timing", 1)
+    res = {"mesh": kind, "num_elements": int(Ne), "device": dynamics.device_name(0)}
+    fe.means_configure(_abi.MEANS_ELEMENTAL)
+    res["old_20_variables"] = _timed_updates(fe, np)
+    print("old 20-variable list", res["old_20_variables"], flush=True)
+    if not old_only:
+        fe.means_configure(THERMO)
+        res["thermo_24_variables"] = dict(_timed_updates(fe, np), variables=THERMO)
+        # sources: 22 slab rows + sst, tice0, tsurf_young, conc, conc_young once each, 8 B; the rows read and written, 16 B per column
+        nbytes = lm.local_nelements * ((len(THERMO_SLAB_ROWS) + 5) * 8 + len(THERMO) * 16)
+        res["thermo_24_variables"]["model_bytes"] = int(nbytes)
+        res["thermo_24_variables"]["GBps"] = nbytes / (res["thermo_24_variables"]["median_us"] * 1e-6) / 1e9
+        print("thermo 24-variable list", res["thermo_24_variables"], flush=True)
+        walls = []
+        for _ in range(7):
+            fe.synchronize()
+            t0 = time.perf_counter()
+            fe.slab_rows(THERMO_SLAB_ROWS); fe.flux_get(THERMO_FLUX_ROWS)
+            walls.append((time.perf_counter() - t0) * 1e3)
+        w = np.array(walls[2:])
+        res["host_fetch"] = {"median_ms": float(np.median(w)), "min_ms": float(w.min()), "max_ms": float(w.max()), "samples": len(w),
+                             "rows": len(THERMO_SLAB_ROWS) + len(THERMO_FLUX_ROWS), "bytes": int(Ne * 8 * (len(THERMO_SLAB_ROWS) + len(THERMO_FLUX_ROWS)))}
+        res["host_fetch_over_means_update"] = res["host_fetch"]["median_ms"] * 1e3 / res["thermo_24_variables"]["median_us"]
+        print("host fetch of the same rows", res["host_fetch"], flush=True)
+    fe.close()
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "means_thermo_old_only.json" if old_only else "means_thermo.json"), "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def design_table(r):
     s, d, h = r["stage"], r["direct"], r["host_route"]
     rows = [
@@ -188,6 +268,13 @@ if __name__ == "__main__":
         out = os.path.join(ROOT, "profiles")
         if "--out" in args:
             i = args.index("--out"); out = args[i + 1]; del args[i:i + 2]
+        if "--thermo" in args:
+            args.remove("--thermo")
+            old_only = "--old-only" in args
+            if old_only:
+                args.remove("--old-only")
+            measure_thermo(args[0] if args else "2km", out, old_only)
+            sys.exit(0)
         r = measure(args[0] if args else "2km", out)
         if os.path.abspath(out) == os.path.join(ROOT, "profiles"):
             write_design(r)
