@@ -893,6 +893,71 @@ NXS_API int nxs_dyn_column_get_state(nxs_dyn_handle *h, nxs_dyn_column_state *s)
 NXS_API int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt);
 NXS_API int nxs_dyn_column_get(nxs_dyn_handle *h, const nxs_dyn_column_rows *out /* may be NULL */, const double **device_rows /* [NXS_COL_ROWS], may be NULL */);
 
+/* ---- thermo()'s element forcing on the device: the ten rows of nxs_dyn_flux_atmosphere and nxs_dyn_column_forcing without a host -> device copy per step.  A
+ * dataset interpolated linearly in time changes its bits EVERY model step (M_tair.getVector() evaluates ExternalData::get, model/externaldata.cpp:324-439, for the
+ * current time), so a host that goes through nxs_dyn_flux_set_atmosphere / nxs_dyn_column_set_forcing uploads ten [Ne] rows per step.  Here both snapshots of a
+ * forcing interval (dataset->variables[].interpolated_data[0] and [1]) become resident once per interval -- from host rows (nxs_dyn_thermo_forcing_pair) or from
+ * the source grid by the device's InterpFromGridToMeshx at the element barycentres (nxs_dyn_thermo_forcing_targets + _ingest: the arithmetic of
+ * nxs_interp_grid_to_mesh, the same bits) -- and every step one launch (nxs_dyn_thermo_forcing_time) evaluates ExternalData::get's expression into the SAME device
+ * rows the two old calls fill: nxs_dyn_fluxes, nxs_dyn_column, nxs_dyn_slab, nxs_dyn_slab_coupled and nxs_dyn_means_update read them unchanged, and a handle that
+ * never calls these entry points is the library without them.  Rows in the fixed order NXS_TF_*: the first five are nxs_dyn_flux_atmosphere's members, the last
+ * five nxs_dyn_column_forcing's; what humidity, longwave and snow MEAN is still chosen by the flux and column configurations.
+ * MEMORY: the snapshots, the targets and the uploaded grid (axes and data) are one pool of their own that goes with the mesh: nxs_dyn_set_mesh and nxs_dyn_regrid
+ * drop it (the reference sets interpolated = false after a regrid too) and the host gives targets and snapshots again on the new mesh.  Twenty snapshot rows are
+ * 20 * 8 B * Ne: 233 MB on the 2 km mesh (Ne = 1 456 798).
+ *   nxs_dyn_thermo_forcing_pair     [Ne] host rows of snapshot 0 (s0) and 1 (s1).  A NULL row means "that snapshot's device copy is current"; s1 may be NULL as
+ *                  a whole.  A row may exist with snapshot 0 only (a `constant` or `nearest_daily` dataset); a row never given stays missing.
+ *                  NXS_ERR_INVALID: h or s0 NULL.  NXS_ERR_STATE before nxs_dyn_set_mesh
+ *   nxs_dyn_thermo_forcing_time     per row its own mode, coefficients, M_factor and M_bias_correction (every ExternalData has its own dataset, so its own
+ *                  ftime_range): NXS_TF_OFF leaves the row alone (the host still gives it through the old calls), NXS_TF_LINEAR writes
+ *                  factor*(fcoeff0*d0[i] + fcoeff1*d1[i]) + bias (externaldata.cpp:401-403, 438), NXS_TF_STEP writes factor*d0[i] + bias (externaldata.cpp:434, 438)
+ *                  and never reads d1 -- it is NOT LINEAR with (1, 0): those differ in the sign of zero and where d1 holds NaN or Inf.  One asynchronous launch on
+ *                  the handle's stream; the written rows then count as given on this mesh, exactly as after an upload.  NXS_ERR_INVALID: h or t NULL, an
+ *                  unknown mode.  NXS_ERR_STATE: before nxs_dyn_set_mesh, a LINEAR row without both snapshots, a STEP row without snapshot 0 (which is every
+ *                  row after nxs_dyn_set_mesh / nxs_dyn_regrid)
+ *   nxs_dyn_thermo_forcing_targets  [Ne] element barycentres in the coordinates of dataset `set` (0 .. NXS_TF_SETS - 1: atmosphere, ocean, a third product) --
+ *                  what convertTargetXY made: the projection stays the host's.  Resident until the mesh changes.  NXS_ERR_INVALID: a NULL argument, a set out
+ *                  of range.  NXS_ERR_STATE before nxs_dyn_set_mesh
+ *   nxs_dyn_thermo_forcing_ingest   the grid descriptor and data ([M][N][N_data], or [N][M][N_data] with row_major) mean exactly what nxs_interp_grid_to_mesh's
+ *                  arguments mean (include/nxs_interp.h).  Column j goes to snapshot snapshot[j] (0 or 1) of row row[j] (NXS_TF_*); row[j] = -1 skips the
+ *                  column: the nb_var*nb_forcing_step columns of one InterpFromGridToMeshx call of loadDataset are taken as they lie.  One launch, a thread
+ *                  per element, one contiguous [Ne] stream per column; the host arrays are free on return, the launch is asynchronous.  NXS_ERR_INVALID: a
+ *                  NULL argument, a set out of range, M or N < 2, N_data outside 1 .. NXS_TF_MAX_COLUMNS, axes that are neither centres nor contours, an unknown
+ *                  interpolation, a row outside -1 .. NXS_TF_ROWS - 1, a snapshot other than 0 / 1, two columns for one snapshot of one row.  NXS_ERR_STATE:
+ *                  before nxs_dyn_set_mesh, before nxs_dyn_thermo_forcing_targets of that set on this mesh
+ *   nxs_dyn_thermo_forcing_get      which = 0 / 1: the snapshots; which = 2: the rows as the launches will read them (blended or uploaded, whichever came
+ *                  last).  Synchronised on return; NULL rows are skipped; a missing row that is asked for is NXS_ERR_STATE.  The tests' door and a restart
+ *                  writer's.  NXS_ERR_INVALID: h or out NULL, which outside 0 .. 2 */
+enum { NXS_TF_TAIR = 0, NXS_TF_MSLP, NXS_TF_QSW_IN, NXS_TF_HUMIDITY, NXS_TF_LONGWAVE, NXS_TF_PRECIP, NXS_TF_SNOW, NXS_TF_OCEAN_TEMP, NXS_TF_OCEAN_SALT, NXS_TF_MLD };
+#define NXS_TF_ROWS 10
+#define NXS_TF_SETS 4
+#define NXS_TF_MAX_COLUMNS 32
+enum { NXS_TF_OFF = 0, NXS_TF_LINEAR = 1, NXS_TF_STEP = 2 };
+typedef struct nxs_dyn_thermo_forcing_rows { double *row[NXS_TF_ROWS]; } nxs_dyn_thermo_forcing_rows;   /* [Ne] each, indexed by NXS_TF_* (read by _pair, written by _get) */
+/* (a struct TAG only: the entry point of the same name is the ordinary identifier, so C and C++ callers write `struct nxs_dyn_thermo_forcing_time`) */
+struct nxs_dyn_thermo_forcing_time {
+    int32_t mode[NXS_TF_ROWS];          /* NXS_TF_OFF / _LINEAR / _STEP */
+    double fcoeff0[NXS_TF_ROWS];        /* |t - ftime_range[1]| / fdt of the row's dataset (LINEAR) */
+    double fcoeff1[NXS_TF_ROWS];        /* |t - ftime_range[0]| / fdt */
+    double factor[NXS_TF_ROWS];         /* M_factor */
+    double bias[NXS_TF_ROWS];           /* M_bias_correction */
+};
+typedef struct nxs_dyn_forcing_grid {   /* the source grid of one dataset: the arguments of nxs_interp_grid_to_mesh */
+    const double *x_in, *y_in;          /* pixel centres (x_rows == N, y_rows == M) or their contours (one more entry each) */
+    int32_t x_rows, y_rows;
+    int32_t M, N;                       /* rows (y) and columns (x) of data */
+    int32_t interp;                     /* NXS_INTERP_TRIANGLE / _BILINEAR / _NEAREST (include/nxs_interp.h: 0 / 1 / 2) */
+    int32_t row_major;                  /* 0: data [M][N][N_data]; else [N][M][N_data] */
+    double default_value;               /* NaN and targets outside the grid */
+} nxs_dyn_forcing_grid;
+
+NXS_API int nxs_dyn_thermo_forcing_pair(nxs_dyn_handle *h, const nxs_dyn_thermo_forcing_rows *s0, const nxs_dyn_thermo_forcing_rows *s1 /* may be NULL */);
+NXS_API int nxs_dyn_thermo_forcing_time(nxs_dyn_handle *h, const struct nxs_dyn_thermo_forcing_time *t);
+NXS_API int nxs_dyn_thermo_forcing_targets(nxs_dyn_handle *h, int32_t set, const double *RX, const double *RY);
+NXS_API int nxs_dyn_thermo_forcing_ingest(nxs_dyn_handle *h, int32_t set, const nxs_dyn_forcing_grid *g, const double *data, int32_t N_data, const int32_t *row,
+                                          const int32_t *snapshot);
+NXS_API int nxs_dyn_thermo_forcing_get(nxs_dyn_handle *h, int32_t which, const nxs_dyn_thermo_forcing_rows *out);
+
 /* ---- The rest of thermo()'s slab loop on the device: FE.cpp:5413-6133 as a default (non-OASIS) build compiles it -- the assimilation flux (FE.cpp:5415-5425),
  * section 6: new ice over open water and lateral melt (FE.cpp:5434-5646; newice_type 1 .. 4, type 3 with windSpeedElement, FE.cpp:6359-6370; melt_type 1, 2), the
  * freeze-days block (FE.cpp:5649-5682), the new concentration and thickness with Winton's (38), (39), (26) (FE.cpp:5685-5711), the limit block (FE.cpp:5714-5728),

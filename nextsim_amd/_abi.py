@@ -289,6 +289,28 @@ def column_config_struct(base: "ColumnConfig", **options) -> ColumnConfig:
     return c
 
 
+# ---- thermo()'s element forcing on the device (include/nxs_dyn.h, nxs_dyn_thermo_forcing_*)
+TF_ROWS = FLUX_ATMOSPHERE + COL_FORCING   # NXS_TF_*: tair .. longwave are d_flux_atm's rows, precip .. mld d_col_forcing's
+NXS_TF_ROWS = 10
+NXS_TF_SETS = 4
+NXS_TF_MAX_COLUMNS = 32
+NXS_TF_OFF, NXS_TF_LINEAR, NXS_TF_STEP = 0, 1, 2
+TF_MODES = {"off": NXS_TF_OFF, "linear": NXS_TF_LINEAR, "step": NXS_TF_STEP}
+assert len(TF_ROWS) == NXS_TF_ROWS
+
+
+class ThermoForcingRows(C.Structure):   # nxs_dyn_thermo_forcing_rows
+    _fields_ = [("row", c_double_p * NXS_TF_ROWS)]
+
+
+class ThermoForcingTime(C.Structure):   # struct nxs_dyn_thermo_forcing_time
+    _fields_ = [("mode", C.c_int32 * NXS_TF_ROWS)] + [(k, C.c_double * NXS_TF_ROWS) for k in ("fcoeff0", "fcoeff1", "factor", "bias")]
+
+
+class ForcingGrid(C.Structure):   # nxs_dyn_forcing_grid
+    _fields_ = [("x_in", c_double_p), ("y_in", c_double_p)] + [(k, C.c_int32) for k in ("x_rows", "y_rows", "M", "N", "interp", "row_major")] + [("default_value", C.c_double)]
+
+
 # ---- thermo()'s slab loop from new ice to tracers (include/nxs_dyn.h, nxs_slab_* / nxs_dyn_slab_* / nxs_dyn_slab)
 SLAB_CONSTANTS = ("cmin", "hmin", "rhow", "cpw", "rhoi", "rhos", "Lf", "C", "ki", "si", "days_in_sec")   # NXS_SLAB_CONST_*
 SLAB_CONFIG_INTS = ("newice_type", "melt_type", "use_assim_flux", "temp_dep_healing", "use_meltponds", "reset_by_date", "include_young_ice", "equal_melting")

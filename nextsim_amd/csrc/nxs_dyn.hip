@@ -20,6 +20,7 @@
 //   k_column                                  FE.cpp:5306-5411: thermo()'s ice columns, thermoWinton / thermoIce0 with the nudging and ice-ocean fluxes (nxs_column_kernels.inl, nxs_dyn_column)
 //   k_slab                                    FE.cpp:5413-6133: thermo()'s slab loop from new ice to tracers, with meltPonds (nxs_slab_kernels.inl, nxs_dyn_slab)
 //   k_coupled_thermo, k_coupled_bins          the same loop as an OASIS build compiles it, on the attached floe-size bins (nxs_slab_fsd_kernels.inl, nxs_dyn_slab_coupled)
+//   k_thermo_forcing_blend / _ingest          externaldata.cpp:324-439, 1436: thermo()'s ten element forcing rows, ExternalData::get and InterpFromGridToMeshx (nxs_thermo_forcing_kernels.inl, nxs_dyn_thermo_forcing_*)
 //   k_fsd_init / _update / _breakup / _weld   FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870 + 5888-5896: the floe-size distribution (nxs_fsd_kernels.inl, nxs_dyn_fsd_*)
 //   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
 //
@@ -56,6 +57,7 @@
 #include "nxs_column_kernels.inl"
 #include "nxs_slab_kernels.inl"
 #include "nxs_slab_fsd_kernels.inl"
+#include "nxs_thermo_forcing_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -207,6 +209,15 @@ struct ForcingPair {       // nxs_dyn_set_forcing_pair's snapshots
     double *f_snap[6] = {};                // wind0, wind1, ocean0, ocean1, ssh0, ssh1
     bool have_pair = false;
 };
+struct ThermoForcing {     // nxs_dyn_thermo_forcing_*: both snapshots of thermo()'s ten element forcing rows, the datasets' targets, the uploaded source grid
+    std::vector<void *> tf_allocs;
+    double *tf_snap[2][TF_ROWS] = {};      // [snapshot][NXS_TF_*] [Ne] each, made when first given
+    unsigned tf_have[2] = {0, 0};          // bit k: row k of that snapshot was given on this mesh
+    double *tf_rx[TF_SETS] = {}, *tf_ry[TF_SETS] = {};   // [Ne] the element barycentres in each dataset's coordinates
+    unsigned tf_targets_have = 0;
+    double *tf_gx = nullptr, *tf_gy = nullptr, *tf_data = nullptr;   // the last ingest's pixel centres and data (they grow: tf_reserve)
+    size_t tf_gx_cap = 0, tf_gy_cap = 0, tf_data_cap = 0;
+};
 struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stress / nxs_dyn_put_coupled) and the floe-size distribution's (nxs_dyn_fsd_*)
     std::vector<void *> coupled_allocs;
     // ATTACHED is what h->dw says (tau_wi, cum_damage, conc_fsd non-NULL) and fsd_mech / fsd_cumw non-NULL; a detached buffer is kept for the next attach (no hipFree
@@ -218,7 +229,7 @@ struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stres
     size_t mech_capacity = 0;
 };
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, CoupledBuffers {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, CoupledBuffers {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -613,6 +624,7 @@ void release_halo(nxs_dyn_handle *h) {
     release_halo_fused(h);
 }
 void release_forcing_pair(nxs_dyn_handle *h) { release_group<ForcingPair>(h, h->forcing_allocs); }
+void release_thermo_forcing(nxs_dyn_handle *h) { release_group<ThermoForcing>(h, h->tf_allocs); }
 // the coupled build's buffers; their attachments are members of h->dw
 void release_coupled(nxs_dyn_handle *h) {
     release_group<CoupledBuffers>(h, h->coupled_allocs);
@@ -636,6 +648,7 @@ void release_mesh(nxs_dyn_handle *h) {
     release_smooth_patches(h);
     release_ring(h);
     release_forcing_pair(h);
+    release_thermo_forcing(h);
     release_coupled(h);
     h->no_big_cut = false;
     h->rank = 0; h->nranks = 1;   // (the partition is the mesh's: a single rank until nxs_dyn_set_halo says otherwise)
@@ -3854,5 +3867,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_column.inl"
 #include "nxs_slab.inl"
 #include "nxs_slab_fsd.inl"
+#include "nxs_thermo_forcing.inl"
 
 }  // extern "C"

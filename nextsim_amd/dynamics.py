@@ -102,6 +102,11 @@ def load_library():
     L.nxs_dyn_column_get_state.argtypes = [H, P(_abi.ColumnState)]
     L.nxs_dyn_column.argtypes = [H, C.c_int32]
     L.nxs_dyn_column_get.argtypes = [H, P(_abi.ColumnRows), P(C.c_void_p)]
+    L.nxs_dyn_thermo_forcing_pair.argtypes = [H, P(_abi.ThermoForcingRows), P(_abi.ThermoForcingRows)]
+    L.nxs_dyn_thermo_forcing_time.argtypes = [H, P(_abi.ThermoForcingTime)]
+    L.nxs_dyn_thermo_forcing_targets.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p]
+    L.nxs_dyn_thermo_forcing_ingest.argtypes = [H, C.c_int32, P(_abi.ForcingGrid), _abi.c_double_p, C.c_int32, _abi.c_int32_p, _abi.c_int32_p]
+    L.nxs_dyn_thermo_forcing_get.argtypes = [H, C.c_int32, P(_abi.ThermoForcingRows)]
     L.nxs_slab_default_config.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_config_check.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_constants.argtypes = [P(C.c_double), C.c_int32]
@@ -180,6 +185,7 @@ EXPORTS = (
     "nxs_dyn_fluxes", "nxs_dyn_fluxes_get",
     "nxs_col_default_config", "nxs_col_config_check", "nxs_col_constants", "nxs_dyn_column_configure", "nxs_dyn_column_set_forcing", "nxs_dyn_column_put",
     "nxs_dyn_column_get_state", "nxs_dyn_column", "nxs_dyn_column_get",
+    "nxs_dyn_thermo_forcing_pair", "nxs_dyn_thermo_forcing_time", "nxs_dyn_thermo_forcing_targets", "nxs_dyn_thermo_forcing_ingest", "nxs_dyn_thermo_forcing_get",
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
@@ -952,6 +958,74 @@ class FiniteElementDynamics:
         self._chk(self.L.nxs_dyn_column_get(self.h, C.byref(r), dev if want_device else None))
         if want_device:
             return out, dict(zip(_abi.COL_ROWS, (int(p or 0) for p in dev)))
+        return out
+
+    # ---- thermo()'s element forcing: both snapshots resident, ExternalData::get per step on the device (model/externaldata.cpp:324-439, 1436) ----
+    def _thermo_forcing_rows(self, rows, what: str):
+        r, keep = _abi.ThermoForcingRows(), []
+        for k, v in (rows or {}).items():
+            if k not in _abi.TF_ROWS:
+                raise KeyError(f"{what} has no row {k!r}")
+            if v is None:
+                continue
+            a = np.ascontiguousarray(v, np.float64)
+            if a.shape != (self.lm.num_elements,):
+                raise ValueError(f"{k} has shape {a.shape}, expected ({self.lm.num_elements},)")
+            r.row[_abi.TF_ROWS.index(k)] = _abi.dptr(a)
+            keep.append(a)
+        return r, keep
+
+    def thermo_forcing_pair(self, snapshot0: dict, snapshot1: dict = None):
+        """nxs_dyn_thermo_forcing_pair: {row name of _abi.TF_ROWS: [Ne]} of snapshot 0 and (optionally) 1; a row left out or None keeps that snapshot's device copy."""
+        r0, keep0 = self._thermo_forcing_rows(snapshot0, "nxs_dyn_thermo_forcing_rows")
+        r1, keep1 = self._thermo_forcing_rows(snapshot1, "nxs_dyn_thermo_forcing_rows")
+        self._chk(self.L.nxs_dyn_thermo_forcing_pair(self.h, C.byref(r0), C.byref(r1) if snapshot1 is not None else None))
+        del keep0, keep1
+
+    def thermo_forcing_time(self, rows: dict):
+        """nxs_dyn_thermo_forcing_time: {row name: dict(mode="off" | "linear" | "step" or NXS_TF_*, fcoeff0=, fcoeff1=, factor=1, bias=0)}; a row left out is OFF.
+        One asynchronous launch writes the rows nxs_dyn_fluxes / nxs_dyn_column / nxs_dyn_slab read."""
+        t = _abi.ThermoForcingTime()
+        for k in range(_abi.NXS_TF_ROWS):
+            t.factor[k] = 1.
+        for name, spec in rows.items():
+            if name not in _abi.TF_ROWS:
+                raise KeyError(f"nxs_dyn_thermo_forcing_time has no row {name!r}")
+            k = _abi.TF_ROWS.index(name)
+            mode = spec.get("mode", "linear")
+            t.mode[k] = _abi.TF_MODES[mode] if isinstance(mode, str) else int(mode)
+            t.fcoeff0[k], t.fcoeff1[k] = float(spec.get("fcoeff0", 1.)), float(spec.get("fcoeff1", 0.))
+            t.factor[k], t.bias[k] = float(spec.get("factor", 1.)), float(spec.get("bias", 0.))
+        self._chk(self.L.nxs_dyn_thermo_forcing_time(self.h, C.byref(t)))
+
+    def thermo_forcing_targets(self, set: int, RX, RY):
+        """nxs_dyn_thermo_forcing_targets: the [Ne] element barycentres in the coordinates of dataset `set` (0 .. NXS_TF_SETS - 1), resident until the mesh changes."""
+        rx, ry = np.ascontiguousarray(RX, np.float64), np.ascontiguousarray(RY, np.float64)
+        if rx.shape != (self.lm.num_elements,) or ry.shape != rx.shape:
+            raise ValueError(f"targets have shapes {rx.shape}, {ry.shape}, expected ({self.lm.num_elements},)")
+        self._chk(self.L.nxs_dyn_thermo_forcing_targets(self.h, int(set), _abi.dptr(rx), _abi.dptr(ry)))
+
+    def thermo_forcing_ingest(self, set: int, x_in, y_in, data, row, snapshot, default_value=1e8, interp=1, row_major=False):
+        """nxs_dyn_thermo_forcing_ingest: InterpFromGridToMeshx at the targets of `set`, arguments as interp.InterpFromGridToMeshx (data [M, N, N_data], or
+        [N, M, N_data] when row_major; x_in / y_in centres or contours).  Column j goes to snapshot[j] of row[j] (a name of _abi.TF_ROWS, NXS_TF_*, or -1 / None:
+        skipped).  The launch is asynchronous."""
+        f64 = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
+        x_in, y_in, data = f64(x_in), f64(y_in), f64(data)
+        if data.ndim == 2:
+            data = data[:, :, None]
+        M, N = (data.shape[1], data.shape[0]) if row_major else (data.shape[0], data.shape[1])
+        rows = np.array([-1 if r is None else _abi.TF_ROWS.index(r) if isinstance(r, str) else int(r) for r in row], np.int32)
+        snaps = np.ascontiguousarray(snapshot, np.int32)
+        if rows.shape != (data.shape[2],) or snaps.shape != rows.shape:
+            raise ValueError(f"row and snapshot must name the {data.shape[2]} columns of data")
+        g = _abi.ForcingGrid(_abi.dptr(x_in), _abi.dptr(y_in), x_in.size, y_in.size, M, N, int(interp), int(bool(row_major)), float(default_value))
+        self._chk(self.L.nxs_dyn_thermo_forcing_ingest(self.h, int(set), C.byref(g), _abi.dptr(data), data.shape[2], _abi.iptr(rows), _abi.iptr(snaps)))
+
+    def thermo_forcing_get(self, which: int, names=_abi.TF_ROWS) -> dict:
+        """nxs_dyn_thermo_forcing_get: the named rows of snapshot 0 / 1 (which = 0 / 1) or as the launches will read them (which = 2)."""
+        out = {k: np.empty(self.lm.num_elements) for k in names}
+        r, _ = self._thermo_forcing_rows(out, "nxs_dyn_thermo_forcing_rows")
+        self._chk(self.L.nxs_dyn_thermo_forcing_get(self.h, int(which), C.byref(r)))
         return out
 
     # ---- thermo()'s slab loop from new ice to tracers: sections 6 to 10 (FE.cpp:5413-6133) ----
