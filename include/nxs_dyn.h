@@ -642,6 +642,41 @@ typedef struct nxs_dyn_regrid_info {
 
 NXS_API int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regrid_info *info /* may be NULL */);
 
+/* ---- The thermodynamic state across a regrid (opt-in).  In the reference the rows of nxs_dyn_flux_state, nxs_dyn_column_state and nxs_dyn_slab_state are ordinary
+ * members of M_prognostic_variables_elt (FE.cpp:7137-7237) and pass through the same collectVariables -> ConservativeRemappingMeshToMesh -> redistributeVariables
+ * as M_conc.  With carry != 0, nxs_dyn_regrid appends one column for every such row that is PRESENT on the old mesh (given by nxs_dyn_flux_put / _column_put /
+ * _slab_put); within each kind the carried columns come before the caller's extras, columns 0 and 1 stay conc and thick.  interpTransformation and bounds are
+ * model/model_variable.cpp's:
+ *     tice0 none, tice1 enthalpy, tice2 thick (all three M_tice: -mu * si where the new mesh has no ice)
+ *     tsurf_young, sst, sss, lid_volume, pond_volume, del_vi_tend     none, unbounded
+ *     conc_upd                                                        none, [-1, 1]
+ *     freeze_onset, conc_summer, fyi_fraction                         none, [0, 1]
+ *     freeze_days, thick_summer, age_det, age                         none, >= 0
+ * Three flux rows are not interpolated by the reference and are RE-MADE on the new mesh whenever carry is on: drag_ti = drag_ti_young = drag_ice_t everywhere
+ * (assignVariables, FE.cpp:566-571) and pond_fraction = 0 (D_pond_fraction is a diagnostic: scatterFieldsElement assigns 0, FE.cpp:3012-3015).
+ * After the call the rows present on the new mesh are exactly the carried and the re-made ones; a row that was missing stays missing; the forcing rows
+ * (nxs_dyn_flux_set_atmosphere, nxs_dyn_column_set_forcing, the nxs_dyn_thermo_forcing_* pool) are missing as after nxs_dyn_set_mesh -- the reference sets
+ * interpolated = false -- and so are the output rows of nxs_dyn_fluxes / _column / _slab: the chain starts again with nxs_dyn_fluxes.  A row of a new element the
+ * remapping marked failed is NaN in the carried rows too.  The enthalpy constants use nxs_dyn_regrid_args::freezingpoint_mu; if the handle has a column
+ * configuration whose freezingpoint_mu differs, nxs_dyn_regrid answers NXS_ERR_INVALID naming both values before its first launch.  A failure before the mesh swap
+ * leaves every thermodynamic row of the old mesh as it was.
+ *   nxs_dyn_regrid_carry_thermo      the setting is the handle's and survives nxs_dyn_set_mesh; carry = 0 restores the default (every row missing after a regrid).
+ *                                    NXS_ERR_INVALID: carry != 0 with a NaN drag_ice_t
+ *   nxs_dyn_regrid_thermo_info_get   what the last nxs_dyn_regrid did (all zero before the first) */
+typedef struct nxs_dyn_regrid_thermo {
+    int32_t carry;        /* != 0: nxs_dyn_regrid carries the thermodynamic state */
+    int32_t reserved;
+    double drag_ice_t;    /* thermo.drag_ice_t (FE.cpp:566): what drag_ti and drag_ti_young become on the new mesh */
+} nxs_dyn_regrid_thermo;
+NXS_API int nxs_dyn_regrid_carry_thermo(nxs_dyn_handle *h, const nxs_dyn_regrid_thermo *o);
+typedef struct nxs_dyn_regrid_thermo_info {
+    uint32_t flux_carried, col_carried, slab_carried;   /* bit k: member k of nxs_dyn_flux_state / _column_state / _slab_state was a column */
+    uint32_t flux_remade;                               /* bit k: that member of nxs_dyn_flux_state was re-made */
+    int32_t nb_var_element;                             /* columns of the element rows, the carried ones included (= nxs_dyn_regrid_info::nb_var_element) */
+    int32_t tiled;                                      /* 1: rows wider than 31 columns went through LDS in column tiles (option "regrid_tile"); 0: staged whole, or walked in global memory */
+} nxs_dyn_regrid_thermo_info;
+NXS_API int nxs_dyn_regrid_thermo_info_get(nxs_dyn_handle *h, nxs_dyn_regrid_thermo_info *out);
+
 /* ---- The floe-size distribution on the device (#ifdef OASIS, M_num_fsd_bins > 0): the per-element loops a wave-coupled step() runs between two dynamics steps --
  * updateFSD() after update(), after thermo() and after a regrid (FE.cpp:8144-8147, 8216-8219), redistributeFSD() on every coupling step (FE.cpp:8156-8168),
  * weldingRoach() and the mechanical healing inside thermo() (FE.cpp:5783-5796, 5888-5896) -- on the bins nxs_dyn_put_coupled attached, so that a resident host no
@@ -770,8 +805,9 @@ NXS_API int nxs_dyn_fsd_weld(nxs_dyn_handle *h, double ddt, const uint8_t *freez
  *   nxs_dyn_flux_put / _get   the thermodynamic rows the fluxes read or write; NULL members as in nxs_dyn_put_state / nxs_dyn_get_state (put: the device copy is
  *                  current; get: not wanted).  sss is carried for the slab loop: specificHumidity(WATER) assigns it and never reads it (FE.cpp:4990-4993)
  *   nxs_dyn_fluxes            the launch, asynchronous on the handle's stream.  NXS_ERR_STATE: before nxs_dyn_flux_configure, before nxs_dyn_put_state and a
- *                  forcing, while an atmosphere or flux row is missing -- which is the state after nxs_dyn_set_mesh AND after nxs_dyn_regrid: the host's
- *                  regrid re-makes those rows on the new mesh, the handle does not carry them
+ *                  forcing, while an atmosphere or flux row is missing -- which is the state after nxs_dyn_set_mesh AND, by default, after nxs_dyn_regrid.
+ *                  With nxs_dyn_regrid_carry_thermo the rows of nxs_dyn_flux_state cross a regrid on the device (drag_ti, drag_ti_young and pond_fraction
+ *                  are re-made, as in the reference); the atmosphere is the host's to give again on the new mesh in either case
  *   nxs_dyn_fluxes_get        synchronised on return.  out (may be NULL): host pointers, a NULL row is skipped.  device_rows (may be NULL): receives the
  *                  NXS_FLUX_ROWS DEVICE pointers of the same rows ([Ne] each, library-owned, valid until nxs_dyn_set_mesh), for the slab loop or a host that
  *                  lives on the GPU.  In the classic category the nine _young rows are zero (FE.cpp:5266-5272).  NXS_ERR_STATE before the first nxs_dyn_fluxes */
@@ -840,8 +876,8 @@ NXS_API int nxs_dyn_fluxes_get(nxs_dyn_handle *h, const nxs_dyn_flux_rows *out /
  *   nxs_dyn_column_put / nxs_dyn_column_get_state   the rows of M_tice the fluxes do not carry (tice1, tice2); NULL members as in nxs_dyn_flux_put / _get
  *   nxs_dyn_column            the launch, asynchronous on the handle's stream; dt is thermo()'s integer argument (ddt = double(dt); BASIC divides by it as
  *                  FE.cpp:6410 does).  NXS_ERR_INVALID: dt <= 0.  NXS_ERR_STATE: before nxs_dyn_column_configure, before the first nxs_dyn_fluxes since the last
- *                  nxs_dyn_set_mesh / nxs_dyn_regrid, while a needed row is missing (again the state after set_mesh and after regrid), under WINTON without
- *                  tice1 / tice2
+ *                  nxs_dyn_set_mesh / nxs_dyn_regrid, while a needed row is missing (again the state after set_mesh and after regrid: the forcing rows
+ *                  always, tice1 / tice2 unless nxs_dyn_regrid_carry_thermo carried them), under WINTON without tice1 / tice2
  *   nxs_dyn_column_get        exactly like nxs_dyn_fluxes_get.  In the classic category the nine _young rows are zero.  NXS_ERR_STATE before the first nxs_dyn_column */
 enum { NXS_COL_THERMO_ZERO_LAYER = 0, NXS_COL_THERMO_WINTON = 1 };                 /* setup::ThermoType */
 enum { NXS_COL_QIO_BASIC = 0, NXS_COL_QIO_EXCHANGE = 1 };                          /* setup::OceanHeatfluxScheme */
@@ -974,8 +1010,9 @@ NXS_API int nxs_dyn_thermo_forcing_get(nxs_dyn_handle *h, int32_t which, const n
  * block (FE.cpp:5729-5764), redistributeThermoFSD (FE.cpp:5768-5776), the in-loop weldingRoach (FE.cpp:5779-5797), the mechanical FSD healing of 9.b
  * (FE.cpp:5883-5898): these are nxs_dyn_slab_coupled's, below.  Because FE.cpp:5729-5764 would have to touch the bins, nxs_dyn_slab answers NXS_ERR_STATE while
  * floe-size bins are attached (nxs_dyn_put_coupled with num_fsd_bins > 0): such a host calls nxs_dyn_slab_coupled.  The throw of a wrong newice_type / melt_type is NXS_ERR_INVALID at
- * configuration.  nxs_dyn_regrid does NOT carry nxs_dyn_slab_state across a regrid: nxs_dyn_set_mesh and nxs_dyn_regrid make it missing again, like tice1 /
- * tice2; the host fetches it before a regrid and puts it back after.  nxs_dyn_means_update accumulates the rows (NXS_MEANS_QA .. NXS_MEANS_SALTFLUX) where they lie.
+ * configuration.  By default nxs_dyn_regrid does NOT carry nxs_dyn_slab_state across a regrid: nxs_dyn_set_mesh and nxs_dyn_regrid make it missing again, like
+ * tice1 / tice2.  A host that has called nxs_dyn_regrid_carry_thermo finds the rows it had put on the old mesh present on the new one, remapped as the reference
+ * remaps M_prognostic_variables_elt; any other host fetches them before a regrid and puts them back after.  nxs_dyn_means_update accumulates the rows (NXS_MEANS_QA .. NXS_MEANS_SALTFLUX) where they lie.
  *   nxs_slab_default_config   model/options.cpp:329-331, 397-403, 428-449, 543-548
  *   nxs_slab_config_check     what nxs_dyn_slab_configure refuses, without a handle: newice_type outside 1 .. 4, melt_type outside 1 .. 2 (3 is the OASIS branch),
  *                  hnull, PhiF, h_young_min, meltpond_depth_to_fraction, time_relaxation_damage or deltaT_relaxation_damage <= 0 (or NaN), h_young_max <=
@@ -1263,6 +1300,9 @@ NXS_API int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t);
  *   "means_stage"  the read-modify-write of the Moorings accumulators (nxs_dyn_means_update): 1 (default) = a workgroup's rows staged through LDS and
  *                  added as one contiguous stream of 16-byte accesses; 0 = every thread walks its own row in 16-byte accesses (rows of an even number of
  *                  variables; 8-byte otherwise).  The same bits; scripts/time_means.py times both
+ *   "regrid_tile"  nxs_dyn_regrid with more than 31 element columns (a thermodynamic run with the coupled build's columns attached): 1 (default) = a workgroup's
+ *                  rows pass through LDS in tiles of up to 31 columns; 0 = every thread walks its own row in global memory.  The same bits;
+ *                  scripts/time_regrid_thermo.py times both
  *   "means_timing" 1 = nxs_dyn_means_update records events around its two launches; nxs_dyn_debug_array "means_update_ms" returns their device times
  *                  [elemental, nodal] in ms.  Default 0
  *   "slab_coupled_timing" 1 = nxs_dyn_slab_coupled records events around its two launches; nxs_dyn_debug_array "slab_coupled_ms" returns their device times

@@ -85,6 +85,16 @@ public:
         check(nxs_dyn_regrid(h_, &a, &info), "regrid");
         return info;
     }
+    // ... with the thermodynamic rows carried across (nxs_dyn_regrid_carry_thermo), and what the last regrid did with them
+    void regridCarryThermo(bool carry, double drag_ice_t) {
+        const nxs_dyn_regrid_thermo o{carry ? 1 : 0, 0, drag_ice_t};
+        check(nxs_dyn_regrid_carry_thermo(h_, &o), "regridCarryThermo");
+    }
+    nxs_dyn_regrid_thermo_info regridThermoInfo() {
+        nxs_dyn_regrid_thermo_info info{};
+        check(nxs_dyn_regrid_thermo_info_get(h_, &info), "regridThermoInfo");
+        return info;
+    }
     nxs_dyn_handle *handle() { return h_; }
 
 private:

@@ -388,6 +388,30 @@ class RegridInfo(C.Structure):   # nxs_dyn_regrid_info
                 ("set_mesh_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class RegridThermo(C.Structure):   # nxs_dyn_regrid_thermo
+    _fields_ = [("carry", C.c_int32), ("reserved", C.c_int32), ("drag_ice_t", C.c_double)]
+
+
+class RegridThermoInfo(C.Structure):   # nxs_dyn_regrid_thermo_info
+    _fields_ = [("flux_carried", C.c_uint32), ("col_carried", C.c_uint32), ("slab_carried", C.c_uint32), ("flux_remade", C.c_uint32),
+                ("nb_var_element", C.c_int32), ("tiled", C.c_int32)]
+
+
+# nxs_dyn_regrid_carry_thermo: the thermodynamic rows as columns of nxs_dyn_regrid, in column order within each kind -- (name, interpTransformation, minVal,
+# maxVal, is M_tice) of model/model_variable.cpp (the lines: thermo_carry[] of csrc/nxs_dyn.hip); None = no bound ...
+REGRID_THERMO_COLUMNS = (
+    ("tice0", "none", None, None, True), ("tsurf_young", "none", None, None, False), ("sst", "none", None, None, False), ("sss", "none", None, None, False),
+    ("lid_volume", "none", None, None, False),
+    ("conc_upd", "none", -1., 1., False), ("pond_volume", "none", None, None, False), ("del_vi_tend", "none", None, None, False),
+    ("freeze_days", "none", 0., None, False), ("freeze_onset", "none", 0., 1., False), ("conc_summer", "none", 0., 1., False),
+    ("thick_summer", "none", 0., None, False), ("fyi_fraction", "none", 0., 1., False), ("age_det", "none", 0., None, False), ("age", "none", 0., None, False),
+    ("tice2", "thick", None, None, True),
+    ("tice1", "enthalpy", None, None, True),
+)
+# ... and the rows of nxs_dyn_flux_state the reference re-makes instead (FE.cpp:566-571, 3012-3015)
+REGRID_THERMO_REMADE = ("drag_ti", "drag_ti_young", "pond_fraction")
+
+
 # enum nxs_means_var: the Moorings variables nxs_dyn_means_* accumulates, named after GridOutput::variableID
 MEANS_ELEMENTAL = ("conc", "thick", "snow", "conc_cons", "damage", "ridge_ratio", "conc_young", "h_young", "hs_young", "conc_myi", "thick_myi",
                    "dci_ridge_myi", "sigma_11", "sigma_22", "sigma_12", "sigma_n", "sigma_s", "divergence", "drag_ui", "ice_mask")

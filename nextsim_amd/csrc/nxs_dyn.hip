@@ -23,6 +23,7 @@
 //   k_thermo_forcing_blend / _ingest          externaldata.cpp:324-439, 1436: thermo()'s ten element forcing rows, ExternalData::get and InterpFromGridToMeshx (nxs_thermo_forcing_kernels.inl, nxs_dyn_thermo_forcing_*)
 //   k_fsd_init / _update / _breakup / _weld   FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870 + 5888-5896: the floe-size distribution (nxs_fsd_kernels.inl, nxs_dyn_fsd_*)
 //   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
+//   k_regrid_collect_tiled / _redistribute_tiled   the same for rows wider than 31 columns, in column tiles through LDS; k_regrid_remake_thermo   FE.cpp:566-571, 3012-3015 (nxs_dyn_regrid_carry_thermo)
 //
 // Determinism: the reference scatters element contributions into nodes in ascending element
 // order.  Here every node GATHERS over its element fan sorted ascending, which performs the same
@@ -116,7 +117,7 @@ struct MeshArrays {        // the mesh and its tables (set_mesh)
     DevMesh dm{};
     bool have_mesh = false;
 };
-struct FluxRows {          // thermo()'s atmospheric bulk fluxes: rows in the state pool -- after set_mesh / regrid every row is MISSING until it is given again
+struct FluxRows {          // thermo()'s atmospheric bulk fluxes: rows in the state pool -- after set_mesh / regrid every row is MISSING until it is given again (the state rows cross a regrid with nxs_dyn_regrid_carry_thermo)
     double *d_flux_atm[FLUX_ATM_ROWS] = {};        // tair, mslp, Qsw_in, humidity, longwave
     double *d_flux_st[FLUX_ST_ROWS] = {};          // tice0, tsurf_young, sst, sss, drag_ti, drag_ti_young, pond_fraction, lid_volume
     unsigned flux_atm_have = 0, flux_st_have = 0;  // bit k: row k was given on this mesh
@@ -338,6 +339,10 @@ struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, Pa
     hipEvent_t means_ev[3] = {nullptr, nullptr, nullptr};
     bool means_timed = false;
     int means_stage = 1;                           // option "means_stage": the rows' read-modify-write staged through LDS (1) or walked by each thread (0)
+    // nxs_dyn_regrid_carry_thermo: the handle's and kept across set_mesh; what the last nxs_dyn_regrid did with it
+    nxs_dyn_regrid_thermo regrid_thermo{};
+    nxs_dyn_regrid_thermo_info regrid_thermo_info{};
+    int regrid_tile = 1;                           // option "regrid_tile": rows wider than NXS_REGRID_STAGE_MAX columns staged in column tiles (1) or walked in global memory (0)
     // the drifters (nxs_dyn_drifters_*): the sets are the handle's and survive set_mesh; the two locators go with the mesh / with M_UM (nxs_drifters.hpp)
     nxs_drifters::State *drift = nullptr;          // made by the first nxs_dyn_drifters_set
     int update_launch[3] = {-1, -1, 0};    // the last launch of k_update: REC, FSD, threads per block (nxs_dyn_debug_array "update_launch"; -1 = none yet)
@@ -637,6 +642,11 @@ void coupled_adopt(nxs_dyn_handle *h, double **member, double **attachment, doub
 }
 // the state pool: the prognostic and work arrays, the flux and column rows, the means' accumulators, D_tau_ow, the ice diagnostics, the branch trace
 void release_state(nxs_dyn_handle *h) { release_group<StateArrays>(h, h->state_allocs); }
+// ... and the same for a row of the state pool (a thermodynamic row nxs_dyn_regrid carried across: nxs_dyn_regrid_carry_thermo)
+void state_adopt(nxs_dyn_handle *h, double **member, double *buf) {
+    h->state_allocs.push_back(buf);
+    *member = buf;
+}
 // Everything that goes with the mesh (nxs_dyn_set_mesh, nxs_dyn_regrid, nxs_dyn_destroy; never inside a step).  Kept: every option but trace_branches, the
 // parameters, the flux / column / FSD / means configurations, the drifter sets, pair_hint and flow_failed, the mailbox, the communicator, the timing sums.
 void release_mesh(nxs_dyn_handle *h) {
@@ -1890,6 +1900,27 @@ struct RegridContextGuard {   // a context made inside the call goes with it
     nxs_regrid *r = nullptr;
     ~RegridContextGuard() { if (r) (void)nxs_regrid_destroy(r); }
 };
+// nxs_dyn_regrid_carry_thermo: the rows of nxs_dyn_flux_state (group 0), nxs_dyn_column_state (1) and nxs_dyn_slab_state (2) as columns of nxs_dyn_regrid, in column
+// order within each kind.  interpTransformation, minVal / maxVal of model/model_variable.cpp: M_tice 133-162 (component 0 none, 1 enthalpy, 2 thick), M_sst 164-172,
+// M_sss 174-182, M_tsurf_young 184-192, M_lid_volume 420-427, M_conc_upd 316-328, M_pond_volume 411-418, M_del_vi_tend 402-409, M_freeze_days 378-387,
+// M_freeze_onset 389-400, M_conc_summer 354-365, M_thick_summer 367-376, M_fyi_fraction 271-282, M_age_det 284-293, M_age 295-304.  (nextsim_amd/_abi.py
+// REGRID_THERMO_COLUMNS is the same table by name.)
+enum { FLUX_ST_TICE0 = 0, FLUX_ST_TSURF_YOUNG, FLUX_ST_SST, FLUX_ST_SSS, FLUX_ST_DRAG_TI, FLUX_ST_DRAG_TI_YOUNG, FLUX_ST_POND_FRACTION, FLUX_ST_LID_VOLUME };
+struct ThermoCarry { int group, row, kind, flags; double lo, hi; };
+constexpr int TC_LO = NXS_REGRID_VAR_HAS_MIN, TC_LOHI = NXS_REGRID_VAR_HAS_MIN | NXS_REGRID_VAR_HAS_MAX;
+const ThermoCarry thermo_carry[] = {
+    {0, FLUX_ST_TICE0, NXS_TRANSFORM_NONE, NXS_REGRID_VAR_IS_TICE, 0., 0.},
+    {0, FLUX_ST_TSURF_YOUNG, NXS_TRANSFORM_NONE, 0, 0., 0.}, {0, FLUX_ST_SST, NXS_TRANSFORM_NONE, 0, 0., 0.}, {0, FLUX_ST_SSS, NXS_TRANSFORM_NONE, 0, 0., 0.},
+    {0, FLUX_ST_LID_VOLUME, NXS_TRANSFORM_NONE, 0, 0., 0.},
+    {2, 0 /* conc_upd */, NXS_TRANSFORM_NONE, TC_LOHI, -1., 1.}, {2, 1 /* pond_volume */, NXS_TRANSFORM_NONE, 0, 0., 0.}, {2, 2 /* del_vi_tend */, NXS_TRANSFORM_NONE, 0, 0., 0.},
+    {2, 3 /* freeze_days */, NXS_TRANSFORM_NONE, TC_LO, 0., 0.}, {2, 4 /* freeze_onset */, NXS_TRANSFORM_NONE, TC_LOHI, 0., 1.},
+    {2, 5 /* conc_summer */, NXS_TRANSFORM_NONE, TC_LOHI, 0., 1.}, {2, 6 /* thick_summer */, NXS_TRANSFORM_NONE, TC_LO, 0., 0.},
+    {2, 7 /* fyi_fraction */, NXS_TRANSFORM_NONE, TC_LOHI, 0., 1.}, {2, 8 /* age_det */, NXS_TRANSFORM_NONE, TC_LO, 0., 0.}, {2, 9 /* age */, NXS_TRANSFORM_NONE, TC_LO, 0., 0.},
+    {1, 1 /* tice2 */, NXS_TRANSFORM_THICK, NXS_REGRID_VAR_IS_TICE, 0., 0.},
+    {1, 0 /* tice1 */, NXS_TRANSFORM_ENTHALPY, NXS_REGRID_VAR_IS_TICE, 0., 0.},
+};
+// ... and the three the reference does not interpolate: M_drag_ti, M_drag_ti_young (assignVariables, FE.cpp:566-571), D_pond_fraction (FE.cpp:3012-3015)
+constexpr unsigned THERMO_REMADE = (1u << FLUX_ST_DRAG_TI) | (1u << FLUX_ST_DRAG_TI_YOUNG) | (1u << FLUX_ST_POND_FRACTION);
 inline double ms_since(const std::chrono::steady_clock::time_point &t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -2151,6 +2182,7 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
     }
     if (!std::strcmp(key, "pin_host")) { h->pin_host = value != 0; if (!h->pin_host) unpin_all(h); return NXS_OK; }
     if (!std::strcmp(key, "means_stage")) { h->means_stage = value != 0; return NXS_OK; }
+    if (!std::strcmp(key, "regrid_tile")) { h->regrid_tile = value != 0; return NXS_OK; }
     if (!std::strcmp(key, "drifters_timing")) {
         if (!h->drift) h->drift = nxs_drifters::create();
         nxs_drifters::set_timing(h->drift, value != 0);
@@ -3007,6 +3039,10 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
         return fail(h, NXS_ERR_STATE, "regrid: this handle has halo lists set (rank %d of %d): the reference interpolates on its root rank from gathered state, and the gather / scatter "
                                       "of a partitioned run is not done here", h->rank, h->nranks);
     if (int rc = check_mesh(h, a->new_mesh)) return rc;
+    const bool carry_thermo = h->regrid_thermo.carry != 0;
+    if (carry_thermo && h->col_configured && h->col_cfg.freezingpoint_mu != a->freezingpoint_mu)
+        return fail(h, NXS_ERR_INVALID, "regrid: freezingpoint_mu = %.17g of the call differs from freezingpoint_mu = %.17g of nxs_dyn_column_configure, whose ice temperatures "
+                                        "the enthalpy transformation carries (nxs_dyn_regrid_carry_thermo)", a->freezingpoint_mu, h->col_cfg.freezingpoint_mu);
     const nxs_dyn_mesh &nm = *a->new_mesh;
     const int Nn_old = h->dm.Nn, Ne_old = h->dm.Ne, Nn_new = nm.num_nodes, Ne_new = nm.num_elements;
     if (Nn_new < 3) return fail(h, NXS_ERR_INVALID, "regrid: a new mesh of %d nodes", Nn_new);
@@ -3052,10 +3088,38 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     if (carry_mech) for (int b = 0; b < nbins; ++b) cols.push_back(RegridCol{h->fsd_mech + (size_t)b * Ne_old, new_mech + (size_t)b * Ne_new, NXS_TRANSFORM_NONE, LOHI, 0., 1.});
     if (carry_cum && fsd_order) cols.push_back(RegridCol{h->dw.cum_damage, new_cum, NXS_TRANSFORM_NONE, LO, 0., 0.});
     if (carry_cumw) cols.push_back(RegridCol{h->fsd_cumw, new_cumw, NXS_TRANSFORM_NONE, LO, 0., 0.});
+    // nxs_dyn_regrid_carry_thermo: the rows of nxs_dyn_flux_state / _column_state / _slab_state present on the old mesh get a fresh row of the new one (the slab's
+    // ten are one block, as nxs_dyn_slab_put makes them: its kernel takes the base); the three re-made flux rows always
+    double *new_flux[FLUX_ST_ROWS] = {}, *new_col[COL_ST_ROWS] = {}, *new_slab = nullptr;
+    nxs_dyn_regrid_thermo_info tinf{};
+    if (carry_thermo) {
+        for (const ThermoCarry &c : thermo_carry) {
+            const unsigned have = c.group == 0 ? h->flux_st_have : c.group == 1 ? h->col_st_have : h->slab_st_have;
+            if (!(have & (1u << c.row))) continue;
+            (c.group == 0 ? tinf.flux_carried : c.group == 1 ? tinf.col_carried : tinf.slab_carried) |= 1u << c.row;
+        }
+        tinf.flux_remade = THERMO_REMADE;
+        for (int k = 0; k < FLUX_ST_ROWS; ++k)
+            if (((tinf.flux_carried | tinf.flux_remade) & (1u << k)) && !(new_flux[k] = mem.alloc<double>(Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for the flux rows");
+        for (int k = 0; k < COL_ST_ROWS; ++k)
+            if ((tinf.col_carried & (1u << k)) && !(new_col[k] = mem.alloc<double>(Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for the column rows");
+        if (tinf.slab_carried && !(new_slab = mem.alloc<double>((size_t)SLAB_ST_ROWS * Ne_new))) return fail(h, NXS_ERR_HIP, "regrid: no device memory for the slab rows");
+    }
+    auto carried = [&](int kind) {   // ... as columns of that kind, in the table's order, before the caller's
+        for (const ThermoCarry &c : thermo_carry) {
+            if (c.kind != kind) continue;
+            const unsigned mask = c.group == 0 ? tinf.flux_carried : c.group == 1 ? tinf.col_carried : tinf.slab_carried;
+            if (!(mask & (1u << c.row))) continue;
+            const double *src = c.group == 0 ? h->d_flux_st[c.row] : c.group == 1 ? h->d_col_st[c.row] : h->d_slab_st[c.row];
+            double *dst = c.group == 0 ? new_flux[c.row] : c.group == 1 ? new_col[c.row] : new_slab + (size_t)c.row * Ne_new;
+            cols.push_back(RegridCol{src, dst, c.kind, c.flags, c.lo, c.hi});
+        }
+    };
     // the caller's variables, kind by kind; host arrays get a device twin (up now, down after the swap)
     struct Down { double *host; const double *dev; };
     std::vector<Down> downs;
-    for (int kind = NXS_TRANSFORM_NONE; kind <= NXS_TRANSFORM_ENTHALPY; ++kind)
+    for (int kind = NXS_TRANSFORM_NONE; kind <= NXS_TRANSFORM_ENTHALPY; ++kind) {
+        carried(kind);
         for (int k = 0; k < a->num_extra; ++k) {
             const nxs_dyn_regrid_var &v = a->extra[k];
             if (v.transformation != kind) continue;
@@ -3074,8 +3138,10 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
             }
             cols.push_back(RegridCol{src, dst, v.transformation, v.flags & (NXS_REGRID_VAR_HAS_MIN | NXS_REGRID_VAR_HAS_MAX | NXS_REGRID_VAR_IS_TICE), v.min_val, v.max_val});
         }
+    }
     const int n = (int)cols.size();
     inf.nb_var_element = n;
+    tinf.nb_var_element = n;
     RegridCol *d_cols = mem.alloc<RegridCol>(n);
     double *rows_old = mem.alloc<double>((size_t)Ne_old * n), *rows_new = mem.alloc<double>((size_t)Ne_new * n);
     double *nod_old = mem.alloc<double>(6 * (size_t)Nn_old), *nod_new = mem.alloc<double>(6 * (size_t)Nn_new);
@@ -3090,11 +3156,13 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     const double enth_a = mu * NXS_SI * NXS_LF;                  // FE.cpp:2145: M_freezingpoint_mu*physical::si*physical::Lf / (physical::C*val)
     const double enth_b = 4 * mu * NXS_SI * NXS_LF / NXS_HEAT_C; // FE.cpp:2237: 4* M_freezingpoint_mu*physical::si*physical::Lf/physical::C
     const double t_noice = -mu * NXS_SI;                         // FE.cpp:2245
-    const bool stage = n <= NXS_REGRID_STAGE_MAX;
-    const size_t lds = stage ? (size_t)BLOCK * (n | 1) * sizeof(double) : 0;
+    const bool stage = n <= NXS_REGRID_STAGE_MAX, tiled = !stage && h->regrid_tile;   // (wider rows: in column tiles through the same LDS, or walked in global memory)
+    const size_t lds = stage ? (size_t)BLOCK * (n | 1) * sizeof(double) : tiled ? (size_t)BLOCK * NXS_REGRID_TILE_STRIDE * sizeof(double) : 0;
+    tinf.tiled = tiled;
 
     // ---- 1. collectVariables + gatherFieldsNode
     if (stage) hipLaunchKernelGGL(k_regrid_collect<true>, dim3(nblocks(Ne_old)), dim3(BLOCK), lds, h->stream, Ne_old, n, (const RegridCol *)d_cols, enth_a, (double)NXS_HEAT_C, rows_old);
+    else if (tiled) hipLaunchKernelGGL(k_regrid_collect_tiled, dim3(nblocks(Ne_old)), dim3(BLOCK), lds, h->stream, Ne_old, n, (const RegridCol *)d_cols, enth_a, (double)NXS_HEAT_C, rows_old);
     else hipLaunchKernelGGL(k_regrid_collect<false>, dim3(nblocks(Ne_old)), dim3(BLOCK), 0, h->stream, Ne_old, n, (const RegridCol *)d_cols, enth_a, (double)NXS_HEAT_C, rows_old);
     hipLaunchKernelGGL(k_regrid_pack_nodes, dim3(nblocks(Nn_old)), dim3(BLOCK), 0, h->stream, Nn_old, (const double *)so.VT, (const double *)so.UM, (const double *)so.UT, nod_old);
     HIPCHK(h, hipGetLastError());
@@ -3122,7 +3190,11 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     HIPCHK(h, hipSetDevice(h->device));
     const int cap_col = h->dp.young_cat ? cy_col : -1;
     if (stage) hipLaunchKernelGGL(k_regrid_redistribute<true>, dim3(nblocks(Ne_new)), dim3(BLOCK), lds, h->stream, Ne_new, n, (const RegridCol *)d_cols, enth_b, t_noice, cap_col, (const double *)rows_new);
+    else if (tiled) hipLaunchKernelGGL(k_regrid_redistribute_tiled, dim3(nblocks(Ne_new)), dim3(BLOCK), lds, h->stream, Ne_new, n, (const RegridCol *)d_cols, enth_b, t_noice, cap_col, (const double *)rows_new);
     else hipLaunchKernelGGL(k_regrid_redistribute<false>, dim3(nblocks(Ne_new)), dim3(BLOCK), 0, h->stream, Ne_new, n, (const RegridCol *)d_cols, enth_b, t_noice, cap_col, (const double *)rows_new);
+    if (carry_thermo)   // the flux rows the reference re-makes instead of interpolating
+        hipLaunchKernelGGL(k_regrid_remake_thermo, dim3(nblocks(Ne_new)), dim3(BLOCK), 0, h->stream, Ne_new, h->regrid_thermo.drag_ice_t, new_flux[FLUX_ST_DRAG_TI], new_flux[FLUX_ST_DRAG_TI_YOUNG],
+                           new_flux[FLUX_ST_POND_FRACTION]);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     inf.redistribute_ms = ms_since(t_phase); t_phase = std::chrono::steady_clock::now();
@@ -3148,6 +3220,16 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     if (carry_fsd) { coupled_adopt(h, &h->d_fsd, &h->dw.conc_fsd, new_fsd); mem.release(new_fsd); h->fsd_capacity = (size_t)nbins * Ne_new; h->dw.nbins = nbins; }
     if (carry_mech) { coupled_adopt(h, &h->d_mech, &h->fsd_mech, new_mech); mem.release(new_mech); h->mech_capacity = (size_t)nbins * Ne_new; }
     if (carry_cumw) { coupled_adopt(h, &h->d_cumw, &h->fsd_cumw, new_cumw); mem.release(new_cumw); }
+    // the thermodynamic rows: present on the new mesh exactly where they were carried or re-made; the forcing rows, every output row and the done flags are as
+    // set_mesh_impl left them (missing / false)
+    for (int k = 0; k < FLUX_ST_ROWS; ++k) if (new_flux[k]) { state_adopt(h, &h->d_flux_st[k], new_flux[k]); mem.release(new_flux[k]); }
+    for (int k = 0; k < COL_ST_ROWS; ++k) if (new_col[k]) { state_adopt(h, &h->d_col_st[k], new_col[k]); mem.release(new_col[k]); }
+    if (new_slab) {
+        state_adopt(h, &h->d_slab_st[0], new_slab); mem.release(new_slab);
+        for (int k = 1; k < SLAB_ST_ROWS; ++k) h->d_slab_st[k] = new_slab + (size_t)k * Ne_new;
+    }
+    h->flux_st_have = tinf.flux_carried | tinf.flux_remade; h->col_st_have = tinf.col_carried; h->slab_st_have = tinf.slab_carried;
+    h->regrid_thermo_info = tinf;
     if (h->drift) nxs_drifters::state_changed(h->drift);
     for (const Down &d : downs) HIPCHK(h, hipMemcpyAsync(d.host, d.dev, (size_t)Ne_new * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3156,6 +3238,20 @@ int nxs_dyn_regrid(nxs_dyn_handle *h, const nxs_dyn_regrid_args *a, nxs_dyn_regr
     if (info) *info = inf;
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_regrid"); }
+
+int nxs_dyn_regrid_carry_thermo(nxs_dyn_handle *h, const nxs_dyn_regrid_thermo *o) try {
+    if (!h || !o) return NXS_ERR_INVALID;
+    if (o->carry && !(o->drag_ice_t == o->drag_ice_t)) return fail(h, NXS_ERR_INVALID, "regrid_carry_thermo: drag_ice_t is NaN");
+    h->regrid_thermo = *o;
+    h->regrid_thermo.carry = o->carry != 0;
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_regrid_carry_thermo"); }
+
+int nxs_dyn_regrid_thermo_info_get(nxs_dyn_handle *h, nxs_dyn_regrid_thermo_info *out) try {
+    if (!h || !out) return NXS_ERR_INVALID;
+    *out = h->regrid_thermo_info;
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_regrid_thermo_info_get"); }
 
 int nxs_dyn_get_diag(nxs_dyn_handle *h, nxs_dyn_diag *dg) try {
     if (!h || !dg) return NXS_ERR_INVALID;

@@ -4480,6 +4480,94 @@ __global__ void __launch_bounds__(BLOCK) k_regrid_redistribute(int Ne, int n, co
     if (cy_col >= 0 && !failed && (conc + cyoung) > 1.) cols[cy_col].dst[e] = 1. - conc;   // FE.cpp:2253-2256
 }
 
+// ---- rows wider than NXS_REGRID_STAGE_MAX columns (a thermodynamic run with the coupled build's columns attached): the workgroup's rows pass through the same
+// 62 KB of LDS in TILES of up to NXS_REGRID_STAGE_MAX columns, the last one narrower.  The LDS row stride is the tile's odd width (NXS_REGRID_STAGE_MAX | 1)
+// whatever the tile holds, so the bank argument above stands; a tile enters / leaves global memory as runs of 8 * w contiguous bytes per row (w = the tile's
+// columns) instead of 8 bytes per lane.  Every thread reaches every barrier: threads past the end redo the last element and write nothing.  The arithmetic is
+// the text of the two kernels above.
+#define NXS_REGRID_TILE_STRIDE (NXS_REGRID_STAGE_MAX | 1)
+__global__ void __launch_bounds__(BLOCK) k_regrid_collect_tiled(int Ne, int n, const RegridCol *__restrict__ cols, double enth_a, double heat_C, double *__restrict__ rows) {
+    extern __shared__ double regrid_stage[];
+    const int e = min(blockIdx.x * BLOCK + (int)threadIdx.x, Ne - 1);
+    const int nrows = min(BLOCK, Ne - (int)blockIdx.x * BLOCK);
+    const size_t base = (size_t)blockIdx.x * BLOCK * n;
+    const double conc = cols[0].src[e], thick = cols[1].src[e];
+    double *r = regrid_stage + (size_t)threadIdx.x * NXS_REGRID_TILE_STRIDE;
+    for (int c0 = 0; c0 < n; c0 += NXS_REGRID_STAGE_MAX) {
+        const int w = min(NXS_REGRID_STAGE_MAX, n - c0);
+        for (int k = c0; k < c0 + w; ++k) {
+            double val = cols[k].src[e];
+            switch (cols[k].transformation) {
+                case NXS_TRANSFORM_CONC: val *= conc; break;                                          // FE.cpp:2139
+                case NXS_TRANSFORM_THICK: val *= thick; break;                                        // FE.cpp:2142
+                case NXS_TRANSFORM_ENTHALPY: val = (val - enth_a / (heat_C * val)) * thick; break;    // FE.cpp:2145 (Winton, 2000, eq 39)
+                default: break;
+            }
+            r[k - c0] = val;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < nrows * w; i += BLOCK) { const int q = i / w, c = i - q * w; rows[base + (size_t)q * n + c0 + c] = regrid_stage[q * NXS_REGRID_TILE_STRIDE + c]; }
+        __syncthreads();   // (the next tile overwrites the stage)
+    }
+}
+
+// ... and redistributeVariables: the clamped new M_conc / M_thick / M_conc_young and the failed mark of column 0 stay in registers from tile to tile
+__global__ void __launch_bounds__(BLOCK) k_regrid_redistribute_tiled(int Ne, int n, const RegridCol *__restrict__ cols, double enth_b, double t_noice, int cy_col,
+                                                                     const double *__restrict__ rows) {
+    extern __shared__ double regrid_stage[];
+    const int e = min(blockIdx.x * BLOCK + (int)threadIdx.x, Ne - 1);
+    const bool live = blockIdx.x * BLOCK + (int)threadIdx.x < Ne;
+    const int nrows = min(BLOCK, Ne - (int)blockIdx.x * BLOCK);
+    const size_t base = (size_t)blockIdx.x * BLOCK * n;
+    const double *r = regrid_stage + (size_t)min((int)threadIdx.x, nrows - 1) * NXS_REGRID_TILE_STRIDE;
+    bool failed = false;
+    double conc = 0., thick = 0., cyoung = 0.;
+    for (int c0 = 0; c0 < n; c0 += NXS_REGRID_STAGE_MAX) {
+        const int w = min(NXS_REGRID_STAGE_MAX, n - c0);
+        for (int i = threadIdx.x; i < nrows * w; i += BLOCK) { const int q = i / w, c = i - q * w; regrid_stage[q * NXS_REGRID_TILE_STRIDE + c] = rows[base + (size_t)q * n + c0 + c]; }
+        __syncthreads();
+        if (c0 == 0) failed = r[0] != r[0];
+        for (int k = c0; k < c0 + w; ++k) {
+            const double raw = r[k - c0];
+            double val = raw;
+            bool no_old_ice = false;
+            const int flags = cols[k].flags;
+            switch (cols[k].transformation) {
+                case NXS_TRANSFORM_CONC:                                                   // FE.cpp:2217-2223
+                    if (conc > 0) val /= conc; else no_old_ice = true;
+                    break;
+                case NXS_TRANSFORM_THICK:                                                  // FE.cpp:2224-2230
+                    if (thick > 0) val /= thick; else no_old_ice = true;
+                    break;
+                case NXS_TRANSFORM_ENTHALPY:                                               // FE.cpp:2231-2241 (Winton, 2000, eq 38)
+                    if (thick > 0) { const double enth = raw / thick; val = 0.5 * (enth - sqrt(enth * enth + enth_b)); }
+                    else no_old_ice = true;
+                    break;
+                default: break;
+            }
+            if (no_old_ice && (flags & NXS_REGRID_VAR_IS_TICE)) val = t_noice;             // FE.cpp:2243-2245
+            if (flags & NXS_REGRID_VAR_HAS_MIN) val = STD_MAX(cols[k].min_val, val);       // FE.cpp:2247
+            if (flags & NXS_REGRID_VAR_HAS_MAX) val = STD_MIN(cols[k].max_val, val);       // FE.cpp:2249
+            if (failed) val = raw;
+            if (k == 0) conc = val;
+            if (k == 1) thick = val;
+            if (k == cy_col) cyoung = val;
+            if (live) cols[k].dst[e] = val;
+        }
+        __syncthreads();   // (the next tile overwrites the stage)
+    }
+    if (live && cy_col >= 0 && !failed && (conc + cyoung) > 1.) cols[cy_col].dst[e] = 1. - conc;   // FE.cpp:2253-2256
+}
+
+// The three rows of nxs_dyn_flux_state the reference does not interpolate, on the new mesh (nxs_dyn_regrid_carry_thermo): M_drag_ti = M_drag_ti_young = drag_ice_t
+// (assignVariables, FE.cpp:566-571), D_pond_fraction = 0 (a diagnostic: scatterFieldsElement assigns 0, FE.cpp:3012-3015)
+__global__ void __launch_bounds__(BLOCK) k_regrid_remake_thermo(int Ne, double drag_ice_t, double *__restrict__ drag_ti, double *__restrict__ drag_ti_young,
+                                                                double *__restrict__ pond_fraction) {
+    const int e = blockIdx.x * BLOCK + (int)threadIdx.x;
+    if (e >= Ne) return;
+    drag_ti[e] = drag_ice_t; drag_ti_young[e] = drag_ice_t; pond_fraction[e] = 0.;
+}
+
 // gatherFieldsNode(), FE.cpp:3174-3198: [Nn][6] = VT.u, VT.v, UM.u, UM.v, UT.u, UT.v, staged like k_ice_diagnostics' rows
 __global__ void __launch_bounds__(BLOCK) k_regrid_pack_nodes(int Nn, const double *__restrict__ VT, const double *__restrict__ UM, const double *__restrict__ UT,
                                                              double *__restrict__ out) {

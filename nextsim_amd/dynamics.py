@@ -134,6 +134,8 @@ def load_library():
     L.nxs_dyn_drifters_mask.argtypes = [H, C.c_int32, C.c_double, _abi.c_int32_p, C.c_int32, P(C.c_int32)]
     L.nxs_dyn_drifters_get.argtypes = [H, C.c_int32, P(C.c_int32), _abi.c_double_p, _abi.c_double_p, _abi.c_int32_p, _abi.c_double_p, _abi.c_int32_p]
     L.nxs_dyn_regrid.argtypes = [H, P(_abi.RegridArgs), P(_abi.RegridInfo)]
+    L.nxs_dyn_regrid_carry_thermo.argtypes = [H, P(_abi.RegridThermo)]
+    L.nxs_dyn_regrid_thermo_info_get.argtypes = [H, P(_abi.RegridThermoInfo)]
     L.nxs_dyn_step.argtypes = [H]
     L.nxs_dyn_explicit_solve.argtypes = [H]
     L.nxs_dyn_update.argtypes = [H]
@@ -190,7 +192,7 @@ EXPORTS = (
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
-    "nxs_dyn_drifters_get", "nxs_dyn_regrid",
+    "nxs_dyn_drifters_get", "nxs_dyn_regrid", "nxs_dyn_regrid_carry_thermo", "nxs_dyn_regrid_thermo_info_get",
     "nxs_dyn_explicit_solve", "nxs_dyn_update", "nxs_dyn_synchronize", "nxs_dyn_step_host",
     "nxs_dyn_check_regridding", "nxs_dyn_check_fields_fast", "nxs_dyn_get_timing", "nxs_dyn_get_step_times", "nxs_dyn_get_traffic_model", "nxs_dyn_set_option",
     "nxs_dyn_debug_array", "nxs_dyn_get_branch_trace", "nxs_mesh_connectivity", "nxs_mesh_element_connectivity", "nxs_calc_cohesion",
@@ -442,6 +444,10 @@ def fsd_config_check(num_bins: int, tables: dict, attached_bins: int, **options)
 
 
 REGRID_INPUTS = ("cohesion", "time_relaxation_damage", "drag_ui", "drag_ui_young")
+# FiniteElementDynamics.regrid_carry_thermo: the thermodynamic rows as columns of a regrid, (name, kind, min, max, is_tice) in column order within each kind, and the
+# flux rows that are re-made instead
+REGRID_THERMO_COLUMNS = _abi.REGRID_THERMO_COLUMNS
+REGRID_THERMO_REMADE = _abi.REGRID_THERMO_REMADE
 
 
 def regrid_args(lm_new, previous_numbering, n_geom_vertices, inputs, extras=(), context=None, moved=None, num_nodes_old=None, num_elements_old=None,
@@ -1144,6 +1150,23 @@ class FiniteElementDynamics:
         del keep
         self.lm = lm_new
         return {k: getattr(info, k) for k, _ in _abi.RegridInfo._fields_ if k != "reserved0"}
+
+    def regrid_carry_thermo(self, carry: bool = True, drag_ice_t: float = 0.0013):
+        """nxs_dyn_regrid_carry_thermo: from now on regrid() carries every row of flux_put / column_put / slab_put that is present on the old mesh (the columns of
+        REGRID_THERMO_COLUMNS) and re-makes drag_ti = drag_ti_young = drag_ice_t, pond_fraction = 0; only the forcing is given again on the new mesh.  Survives
+        set_mesh; carry=False restores the default (every thermodynamic row missing after a regrid)."""
+        o = _abi.RegridThermo(int(bool(carry)), 0, float(drag_ice_t))
+        self._chk(self.L.nxs_dyn_regrid_carry_thermo(self.h, C.byref(o)))
+
+    def regrid_thermo_info(self) -> dict:
+        """nxs_dyn_regrid_thermo_info_get: what the last regrid() did -- the bit masks flux_carried / col_carried / slab_carried / flux_remade (bit k: row k of
+        _abi.FLUX_STATE / COL_STATE / SLAB_STATE), the same as tuples of row names under *_names, nb_var_element, tiled."""
+        i = _abi.RegridThermoInfo()
+        self._chk(self.L.nxs_dyn_regrid_thermo_info_get(self.h, C.byref(i)))
+        out = {k: getattr(i, k) for k, _ in _abi.RegridThermoInfo._fields_}
+        for k, rows in (("flux_carried", _abi.FLUX_STATE), ("col_carried", _abi.COL_STATE), ("slab_carried", _abi.SLAB_STATE), ("flux_remade", _abi.FLUX_STATE)):
+            out[k + "_names"] = tuple(name for b, name in enumerate(rows) if out[k] & (1 << b))
+        return out
 
     # ---- the Moorings time means: updateMeans / updateGridMean / resetMeshMean (FE.cpp:8518-9024, gridoutput.cpp:387-550) ----
     @staticmethod
