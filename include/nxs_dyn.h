@@ -387,8 +387,11 @@ NXS_API int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *d, cons
  * The identifiers are named after GridOutput::variableID (model/gridoutput.hpp) and cover the variables whose sources the handle holds.
  * The thermodynamic variables (NXS_MEANS_THERMO_BEGIN ..) read the rows nxs_dyn_fluxes / nxs_dyn_column / nxs_dyn_slab left on the handle: the flux, column and slab
  * state, the slab's D_* rows, the atmosphere and the column's forcing -- a host whose thermodynamics runs here fetches none of them for a time-mean Moorings file.
- * OUT OF SCOPE (the host keeps summing those itself): dmax / dmean (the FSD diagnostics of the coupled build), loaded (non-regular) grids,
- * ConservativeRemappingMeshToGrid, rotateVectors, the land-sea mask, and the coupler's means (M_cpl_out). */
+ * On a LOADED grid with interpMethod::conservative (a coupler's grid; the Moorings with moorings.use_conservative_remapping) the elemental rows go through
+ * nxs_dyn_means_to_grid_conservative and a resident nxs_gridmap (include/nxs_interp.h) instead.
+ * OUT OF SCOPE (the host keeps doing those itself): dmax / dmean (the FSD diagnostics of the coupled build), the NODAL leg on a loaded grid
+ * (InterpFromMeshToMesh2dx at gridX / gridY, the proc mask, rotateVectors), the land-sea mask (setLSM / applyLSM), and a second set of accumulators for
+ * the coupler's means (M_cpl_out) beside the Moorings'. */
 enum nxs_means_var {
     /* elemental: accumulated over the owned elements i < M_local_nelements, the rows of ghost elements stay 0 (FE.cpp:8527) */
     NXS_MEANS_CONC = 0,           /* FE.cpp:8526  D_conc */
@@ -532,6 +535,12 @@ typedef struct nxs_dyn_means_grid {
  *                  semantics (nxs_interp_mesh_to_grid_device, default value 0); transposed as gridoutput.cpp:526-537 (grid_ind = i + ncols * j) and ADDED to
  *                  the caller's grid_elemental [num_elemental][ncols * nrows] / grid_nodal [num_nodal][ncols * nrows] (nodal values times the proc mask);
  *                  then the ice-mask rule on the variables with `mask`.  Summing the ranks' grids (boost::mpi::reduce, FE.cpp:9476-9487) stays with the caller.
+ *   nxs_dyn_means_to_grid_conservative  updateGridMean()'s elemental leg on a loaded grid with interpMethod::conservative: the accumulator rows go straight from
+ *                  the device into nxs_gridmap_mesh_to_grid with missing value 0. (gridoutput.cpp:473-476 passes 0., not M_miss_val); the result is ADDED to the
+ *                  caller's grid_elemental [num_elemental][G] WITHOUT transposition (:541-545); then the ice-mask rule of :410-414 with miss_val.  `map` is a
+ *                  nxs_gridmap (nxs_interp.h) of this mesh on the handle's device -- for a partitioned run the restricted one.  NXS_ERR_STATE: the map's
+ *                  element count is not the handle's, no elemental variable is configured, a mask flag is set without NXS_MEANS_ICE_MASK.  A handle that
+ *                  never calls it allocates and launches nothing for it.
  *   nxs_dyn_means_reset    resetMeshMean(bamgmesh): zeroes both accumulators on the stream. */
 NXS_API int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c);
 NXS_API int nxs_dyn_means_set_tau_ow(nxs_dyn_handle *h, const double *tau_ow /* [Ne] D_tau_ow, NULL = detach */);
@@ -539,6 +548,8 @@ NXS_API int nxs_dyn_means_update(nxs_dyn_handle *h, double time_factor);
 NXS_API int nxs_dyn_means_get(nxs_dyn_handle *h, double *elemental /* [Ne][n_el] */, double *nodal /* [Nn][n_nod] */, const double **elemental_dev,
                               const double **nodal_dev);
 NXS_API int nxs_dyn_means_to_grid(nxs_dyn_handle *h, const nxs_dyn_means_grid *g, double *grid_elemental, double *grid_nodal);
+struct nxs_gridmap;
+NXS_API int nxs_dyn_means_to_grid_conservative(nxs_dyn_handle *h, struct nxs_gridmap *map, double miss_val, double *grid_elemental /* [n_el][G] */);
 NXS_API int nxs_dyn_means_reset(nxs_dyn_handle *h);
 
 /* ---- The drifters on the device: the three statements of checkUpdateDrifters() (FE.cpp:8403-8437) that touch the handle's arrays -- Drifters::move with

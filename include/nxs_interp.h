@@ -163,6 +163,55 @@ NXS_INTERP_API int nxs_interp_last_timing(double *ms8);
 /* test door: the device-built tables (which = 0 bucket grid offsets, 1 its lists, 2 NodalElementConnectivity, 3 ElementConnectivity; ints, -1 = NaN) */
 NXS_INTERP_API int nxs_regrid_debug_tables(nxs_regrid *r, int32_t which, int32_t *out, int64_t cap, int64_t *count);
 
+/* ---- conservative remapping between the mesh and a grid of quadrilateral cells (a coupler's grid, or a loaded Moorings grid with
+ * moorings.use_conservative_remapping), the weights resident on the device as lists.  Replaces, in a coupled run's step,
+ *
+ *   ConservativeRemappingWeights(bamgmesh_root, gridX, gridY, gridCornerX, gridCornerY, gridP, triangles, weights);     gridoutput.cpp:699
+ *   ConservativeRemappingMeshToGrid(interp_out, interp_in, nb_var, grid_size, miss_val, gridP, cornerX, cornerY, triangles, weights);  :473
+ *   ConservativeRemappingGridToMesh(interp_out, interp_in, nb_var, numElements, gridP, triangles, weights);             dataset.cpp
+ *
+ * (contrib/bamg/src/ConservativeRemapping.cpp:15-171).  nxs_gridmap_create is the first on the mesh of a regrid context AT REST (the reference
+ * builds the weights on bamgmesh_root after a regrid, where M_UM = 0): the seed of a cell is the element holding its P-point (gridX, gridY) -- the
+ * context's exact locator with default -1, as InterpFromMeshToMesh2dx(..., true, -1) at :55-61 -- and a cell whose P-point is in no element is land
+ * and gets no row, even if it overlaps the mesh; a wet cell's row is checkTriangle's walk (the code of nxs_interp_conservative_remap with four
+ * corners), its (triangle, weight) entries in the reference's push order, which is the order of every floating-point sum below.  Same predicates,
+ * tolerances, sort and operand order as the reference: lists, weights and both applications are bit-identical (tests/golden/bamg_grid_remap.npz).
+ *
+ * The stored form is the COMPACT one GridOutput keeps after gridoutput.cpp:706-735: wet rows only, gridP ascending.  (The raw output of
+ * ConservativeRemappingWeights keeps a row for every cell with gridP[land] = 0 and no entry, which makes ConservativeRemappingMeshToGrid overwrite
+ * cell 0 with 0 * (1 / area); that quirk never reaches GridOutput, which drops the empty rows, and is not reproduced.)
+ *
+ *   cornerX, cornerY [4*G]  the corners of cell c at 4*c .. 4*c+3, in order around the cell (gridCornerX / gridCornerY)
+ *   A cell is FAILED when it overlaps more than 4096 triangles or one of its polygons has more than 16 points (a cell that is not convex;
+ *   a triangle against a convex quadrilateral gives at most 13): it gets no row and is counted in nxs_gridmap_info, never truncated.
+ *   Cells are walked in chunks so that the arena of 4096-entry lists stays under 2 GiB.
+ * There is no CPU path: NXS_ERR_NO_DEVICE without a device. */
+typedef struct nxs_gridmap nxs_gridmap;
+NXS_INTERP_API int nxs_gridmap_create(nxs_regrid *r, const double *gridX, const double *gridY, const double *cornerX, const double *cornerY, int32_t G,
+                                      nxs_gridmap **out);
+NXS_INTERP_API int nxs_gridmap_destroy(nxs_gridmap *map);
+/* wet cells (rows), entries, the longest row, failed cells, the element count of the mesh and the size of the grid; any pointer may be NULL */
+NXS_INTERP_API int nxs_gridmap_info(const nxs_gridmap *map, int32_t *wet_cells, int64_t *entries, int32_t *longest_row, int32_t *failed_cells, int32_t *nels,
+                                    int32_t *grid_size);
+/* ConservativeRemappingMeshToGrid (:103-135): out [G][nb_var], in [nels][nb_var].  Every cell gets miss_val; a wet cell gets
+ * (sum_k in[tri_k] * w_k) * (1 / area(cell)), summed from 0 in list order.  flags: NXS_REGRID_IN_DEVICE / NXS_REGRID_OUT_DEVICE. */
+NXS_INTERP_API int nxs_gridmap_mesh_to_grid(nxs_gridmap *map, double *out, const double *in, int32_t nb_var, double miss_val, int32_t flags);
+/* ConservativeRemappingGridToMesh (:138-171): out [nels][nb_var], in [G][nb_var]; a gather over the transposed lists, whose rows are in the order
+ * the reference's scatter over (cell, position) reaches each triangle -- the same sums, triangle_area included.  A triangle no wet cell touches
+ * gets 0 * (1 / 0.), a NaN, as in the reference. */
+NXS_INTERP_API int nxs_gridmap_grid_to_mesh(nxs_gridmap *map, double *out, const double *in, int32_t nb_var, int32_t flags);
+/* Partitioned runs (gridoutput.cpp:691-735: the root computes, everybody filters).  export: the host lists for the caller's broadcast --
+ * gridP [rows], off [rows + 1], tris, w [entries], cornerX, cornerY [4*G], sizes from nxs_gridmap_info, any pointer may be NULL; import: a map out of
+ * such lists on `device`; restrict: the entries of local triangles (local_of_root [nels of the map], -1 = not here), renumbered, rows left empty
+ * dropped -- a new map on a mesh of nels_local elements. */
+NXS_INTERP_API int nxs_gridmap_export(nxs_gridmap *map, int32_t *gridP, int32_t *off, int32_t *tris, double *w, double *cornerX, double *cornerY);
+NXS_INTERP_API int nxs_gridmap_import(int32_t device, int32_t nels, int32_t G, int32_t rows, const int32_t *gridP, const int32_t *off, const int32_t *tris,
+                                      const double *w, const double *cornerX, const double *cornerY, nxs_gridmap **out);
+NXS_INTERP_API int nxs_gridmap_restrict(nxs_gridmap *map, const int32_t *local_of_root, int32_t nels_local, nxs_gridmap **out);
+/* test door: build the weights in chunks of `cells` cells (0 = as many as the arena allows); *last_chunks (may be NULL) = the chunks the last build took */
+NXS_INTERP_API int nxs_gridmap_debug_chunk(int32_t cells, int32_t *last_chunks);
+
+
 #ifdef __cplusplus
 }
 #endif

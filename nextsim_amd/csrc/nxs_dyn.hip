@@ -3492,6 +3492,36 @@ int nxs_dyn_means_to_grid(nxs_dyn_handle *h, const nxs_dyn_means_grid *g, double
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_means_to_grid"); }
 
+// updateGridMean()'s elemental leg on a loaded grid with interpMethod::conservative (gridoutput.cpp:470-476, 541-545, 410-414)
+int nxs_dyn_means_to_grid_conservative(nxs_dyn_handle *h, struct nxs_gridmap *map, double miss_val, double *grid_elemental) try {
+    if (!h || !map) return NXS_ERR_INVALID;
+    if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "means_to_grid_conservative needs set_mesh and put_state");
+    const int n_el = (int)h->means_ids[0].size();
+    if (!n_el) return fail(h, NXS_ERR_STATE, "means_to_grid_conservative: no elemental variable is configured (nxs_dyn_means_configure)");
+    bool any_mask = false;
+    for (unsigned char m : h->means_mask[0]) any_mask = any_mask || m;
+    if (any_mask && h->means_ice_mask_col < 0) return fail(h, NXS_ERR_STATE, "means_to_grid_conservative: a variable has `mask` set but NXS_MEANS_ICE_MASK is not among the elemental ids");
+    int32_t map_nels = 0, G32 = 0;
+    if (int rc = nxs_gridmap_info(map, nullptr, nullptr, nullptr, nullptr, &map_nels, &G32)) return fail(h, rc, "means_to_grid_conservative: %s", nxs_interp_last_error());
+    if (map_nels != h->dm.Ne) return fail(h, NXS_ERR_STATE, "means_to_grid_conservative: the map is on a mesh of %d elements, the handle's has %d", map_nels, h->dm.Ne);
+    if (!grid_elemental) return fail(h, NXS_ERR_INVALID, "means_to_grid_conservative: grid_elemental is NULL");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // the accumulators are complete before the application, which runs on the interpolation's own stream
+    if (h->res_ready || h->flow_ready) { int rc = resident_error(h); if (rc) return rc; }
+    const size_t G = (size_t)G32;
+    std::vector<double> out(G * n_el);
+    if (int rc = nxs_gridmap_mesh_to_grid(map, out.data(), h->d_means[0], n_el, 0., NXS_REGRID_IN_DEVICE)) return fail(h, rc, "means_to_grid_conservative: %s", nxs_interp_last_error());
+    for (int nv = 0; nv < n_el; ++nv)
+        for (size_t j = 0; j < G; ++j) grid_elemental[nv * G + j] += out[n_el * j + nv];
+    if (h->means_ice_mask_col >= 0) {
+        const double *ice = grid_elemental + (size_t)h->means_ice_mask_col * G;
+        for (int nv = 0; nv < n_el; ++nv)
+            if (h->means_mask[0][nv])
+                for (size_t i = 0; i < G; ++i) if (ice[i] <= 0. && grid_elemental[nv * G + i] != miss_val) grid_elemental[nv * G + i] = 0.;
+    }
+    return NXS_OK;
+} catch (...) { return dyn_caught(h, "nxs_dyn_means_to_grid_conservative"); }
+
 // test door: the branch trace of updateSigmaDamage (option "trace_branches"), 4 words per element
 // ---- the drifters: checkMoveDrifters / checkUpdateDrifters (FE.cpp:8375-8437), Drifters::move / updateConc / maskXY (drifters.cpp:468-579); the kernels live next to
 // the exact point locator (nxs_drifters.inl), this file hands them the handle's own device arrays

@@ -1066,6 +1066,296 @@ extern "C" int nxs_regrid_debug_tables(nxs_regrid *rg, int32_t which, int32_t *o
 } catch (...) { return entry_caught("nxs_regrid_debug_tables"); }
 
 // ---------------------------------------------------------------------------------------------------------
+// Conservative remapping between the mesh and a grid of quadrilateral cells, the weights resident as lists (nxs_gridmap_*):
+// ConservativeRemappingWeights / MeshToGrid / GridToMesh, contrib/bamg/src/ConservativeRemapping.cpp:15-171
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+#include "nxs_gridmap_kernels.inl"
+int g_gridmap_chunk = 0;        // test door (nxs_gridmap_debug_chunk): cells per chunk of the weights build, 0 = as many as the arena allows
+int g_gridmap_last_chunks = 0;  // chunks the last nxs_gridmap_create of the process took
+}  // namespace
+
+struct nxs_gridmap {
+    int device = 0, nels = 0, G = 0, rows = 0, longest = 0, failed = 0;
+    long long n = 0;                       // entries
+    std::vector<double> cornerX, cornerY;  // [4 G], host (nxs_gridmap_export; the device copies are only needed while the map is made)
+    DevBuf<int> dgridP, doff, dtris;       // the forward lists: row i is cell gridP[i], entries off[i] .. off[i + 1]
+    DevBuf<double> dw, drarea;             // weights; 1 / area(cell) per row
+    DevBuf<int> drow_of_cell;              // [G] row of a cell, -1 = land
+    DevBuf<int> dt_off, dt_pos, dcell;     // the transposed lists: per triangle the indices of its entries, ascending; the cell of every entry
+};
+
+namespace {
+
+// everything derived from the forward lists (already on the device) and the corners: 1 / area, row_of_cell, the transposed lists
+int gridmap_finish(nxs_gridmap *g, const double *dcx, const double *dcy) {
+    const int rows = g->rows, nels = g->nels, n = (int)g->n;
+    DevBuf<int> cursor;
+    if (g->drarea.alloc(rows) || g->drow_of_cell.alloc(g->G) || g->dt_off.alloc((size_t)nels + 1) || g->dt_pos.alloc(n) || g->dcell.alloc(n) || cursor.alloc(nels))
+        return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+    if (hipMemsetAsync(g->drow_of_cell.p, 0xff, (size_t)g->G * sizeof(int), S()) != hipSuccess || hipMemsetAsync(g->dt_off.p, 0, ((size_t)nels + 1) * sizeof(int), S()) != hipSuccess ||
+        hipMemsetAsync(cursor.p, 0, (size_t)nels * sizeof(int), S()) != hipSuccess)
+        return fail(NXS_ERR_HIP, "hipMemset failed");
+    if (rows > 0)
+        hipLaunchKernelGGL(gridmap::k_gridmap_rows, dim3((rows + 255) / 256), dim3(256), 0, S(), rows, (const int *)g->dgridP.p, dcx, dcy, g->drarea.p, g->drow_of_cell.p);
+    if (n > 0) {
+        hipLaunchKernelGGL(gridmap::k_gridmap_t_count, dim3((n + 255) / 256), dim3(256), 0, S(), n, (const int *)g->dtris.p, g->dt_off.p);
+        if (regrid_tables::exclusive_scan(g->dt_off.p, nels + 1, S()) != hipSuccess) return fail(NXS_ERR_HIP, "scan of the transposed lists failed");
+        hipLaunchKernelGGL(gridmap::k_gridmap_t_fill, dim3((n + 255) / 256), dim3(256), 0, S(), n, rows, (const int *)g->dtris.p, (const int *)g->doff.p, (const int *)g->dgridP.p,
+                           (const int *)g->dt_off.p, cursor.p, g->dt_pos.p, g->dcell.p);
+        hipLaunchKernelGGL(regrid_tables::k_rows_sort, dim3((nels + 255) / 256), dim3(256), 0, S(), nels, (const int *)g->dt_off.p, g->dt_pos.p, 0);
+    }
+    if (hipStreamSynchronize(S()) != hipSuccess) return fail(NXS_ERR_HIP, "grid map kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+// a map out of host lists (nxs_gridmap_import, nxs_gridmap_restrict): checked, uploaded, finished
+int gridmap_from_host(int device, int nels, int G, int rows, const int32_t *gridP, const int32_t *off, const int32_t *tris, const double *w, const double *cornerX,
+                      const double *cornerY, int failed, nxs_gridmap **out) {
+    if (nels < 1 || G < 1 || rows < 0 || rows > G) return fail(NXS_ERR_INVALID, "bad sizes");
+    if (off[0] != 0) return fail(NXS_ERR_INVALID, "off[0] must be 0");
+    int longest = 0;
+    for (int i = 0; i < rows; ++i) {
+        if (gridP[i] < 0 || gridP[i] >= G || (i > 0 && gridP[i] <= gridP[i - 1])) return fail(NXS_ERR_INVALID, "gridP[%d] out of range or not ascending", i);
+        if (off[i + 1] <= off[i]) return fail(NXS_ERR_INVALID, "row %d is empty or off is not ascending", i);
+        longest = std::max(longest, off[i + 1] - off[i]);
+    }
+    const int n = off[rows];
+    for (int e = 0; e < n; ++e)
+        if (tris[e] < 0 || tris[e] >= nels) return fail(NXS_ERR_INVALID, "tris[%d] out of range", e);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NXS_ERR_NO_DEVICE, "no HIP device visible: the grid map has no CPU path");
+    if (device < 0 || device >= ndev) return fail(NXS_ERR_INVALID, "device %d out of range", device);
+    if (hipSetDevice(device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    std::unique_ptr<nxs_gridmap> g(new nxs_gridmap());
+    g->device = device; g->nels = nels; g->G = G; g->rows = rows; g->n = n; g->longest = longest; g->failed = failed;
+    g->cornerX.assign(cornerX, cornerX + 4 * (size_t)G); g->cornerY.assign(cornerY, cornerY + 4 * (size_t)G);
+    DevBuf<double> dcx, dcy;
+    if (g->dgridP.upload(gridP, rows) || g->doff.upload(off, (size_t)rows + 1) || g->dtris.upload(tris, n) || g->dw.upload(w, n) || dcx.upload(cornerX, 4 * (size_t)G) ||
+        dcy.upload(cornerY, 4 * (size_t)G))
+        return fail(NXS_ERR_HIP, "device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));
+    if (int rc = gridmap_finish(g.get(), dcx.p, dcy.p)) return rc;
+    *out = g.release();
+    return NXS_OK;
+}
+
+struct GridmapHost { std::vector<int32_t> gridP, off, tris; std::vector<double> w; };
+int gridmap_download(nxs_gridmap *g, GridmapHost &h) {
+    h.gridP.resize(g->rows); h.off.resize((size_t)g->rows + 1); h.tris.resize(g->n); h.w.resize(g->n);
+    if (copy_sync(h.off.data(), g->doff.p, h.off.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+        (g->rows > 0 && copy_sync(h.gridP.data(), g->dgridP.p, h.gridP.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (g->n > 0 && (copy_sync(h.tris.data(), g->dtris.p, h.tris.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+                      copy_sync(h.w.data(), g->dw.p, h.w.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)))
+        return fail(NXS_ERR_HIP, "copy back failed");
+    return 0;
+}
+
+}  // namespace
+
+// ConservativeRemappingWeights on the context's mesh (at rest: the reference builds it on bamgmesh_root after a regrid, where M_UM = 0)
+extern "C" int nxs_gridmap_create(nxs_regrid *rg, const double *gridX, const double *gridY, const double *cornerX, const double *cornerY, int32_t G,
+                                  nxs_gridmap **out) try {
+    if (!out) return fail(NXS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!rg || !gridX || !gridY || !cornerX || !cornerY) return fail(NXS_ERR_INVALID, "NULL argument");
+    if (G < 1) return fail(NXS_ERR_INVALID, "the grid has no cell");
+    if (hipSetDevice(rg->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    for (double &v : g_ms) v = 0.;
+    Tick whole(6);
+    if (int rc = regrid_connectivity(rg, nullptr, 0, nullptr)) return rc;
+    Locator *locp = nullptr;
+    if (int rc = regrid_locator(rg, false, &locp)) return rc;
+    std::unique_ptr<nxs_gridmap> g(new nxs_gridmap());
+    g->device = rg->device; g->nels = rg->nels; g->G = G;
+    g->cornerX.assign(cornerX, cornerX + 4 * (size_t)G); g->cornerY.assign(cornerY, cornerY + 4 * (size_t)G);
+    DevBuf<double> dgx, dgy, dcx, dcy;
+    DevBuf<int> dseed, dcells, dcount, dfailed;
+    if (dgx.upload(gridX, G) || dgy.upload(gridY, G) || dcx.upload(cornerX, 4 * (size_t)G) || dcy.upload(cornerY, 4 * (size_t)G) || dseed.alloc(G) || dfailed.alloc(1))
+        return fail(NXS_ERR_HIP, "device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));
+    InterpDev loc = locp->d;
+    loc.isdefault = 1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    struct Events { hipEvent_t &a, &b; ~Events() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } events{e0, e1};
+    (void)hipEventRecord(e0, S());
+    hipLaunchKernelGGL(gridmap::k_gridmap_seed, dim3((G + 255) / 256), dim3(256), 0, S(), loc, (int)G, (const double *)dgx.p, (const double *)dgy.p, dseed.p);
+    std::vector<int> seed(G), wet;
+    if (copy_sync(seed.data(), dseed.p, (size_t)G * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "seed kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    for (int c = 0; c < G; ++c) if (seed[c] >= 0) wet.push_back(c);
+    const int nwet = (int)wet.size();
+    // the walk, in chunks of cells whose arena of kMaxVisitBig-entry lists stays under 2 GiB; every chunk is compacted into a piece of its own
+    const size_t K = (size_t)nxs_remap::kMaxVisitBig, per_cell = K * (sizeof(int) + sizeof(double)) + (K + 1) * sizeof(nxs_remap::Frame);
+    int chunk = (int)std::min<size_t>((size_t)std::max(nwet, 1), ((size_t)2 << 30) / per_cell - 1);
+    if (g_gridmap_chunk > 0) chunk = std::min(chunk, g_gridmap_chunk);
+    struct Piece { DevBuf<int> t; DevBuf<double> w; int n = 0; };
+    std::vector<std::unique_ptr<Piece>> pieces;
+    std::vector<int> count(nwet);
+    DevBuf<int> arena_t;
+    DevBuf<double> arena_w;
+    DevBuf<nxs_remap::Frame> arena_s;
+    const nxs_remap::OldMesh m{rg->nels, rg->nods, rg->dtrio.p, rg->dxo.p, rg->dyo.p, rg->dnec.p, rg->nec_width, rg->dec.p};
+    if (memset_sync(dfailed.p, 0, sizeof(int)) != hipSuccess) return fail(NXS_ERR_HIP, "hipMemset failed");
+    long long total = 0;
+    int nchunks = 0;
+    if (nwet > 0) {
+        if (dcells.upload(wet.data(), nwet) || dcount.alloc((size_t)chunk + 1) || arena_t.alloc(chunk * K) || arena_w.alloc(chunk * K) || arena_s.alloc(chunk * (K + 1)))
+            return fail(NXS_ERR_HIP, "weights build: %d cells per chunk need %zu MB of lists", chunk, chunk * per_cell >> 20);
+        for (int c0 = 0; c0 < nwet; c0 += chunk, ++nchunks) {
+            const int nc = std::min(chunk, nwet - c0);
+            if (hipMemsetAsync(dcount.p, 0, ((size_t)nc + 1) * sizeof(int), S()) != hipSuccess) return fail(NXS_ERR_HIP, "hipMemset failed");
+            hipLaunchKernelGGL(gridmap::k_gridmap_walk, dim3((nc + 63) / 64), dim3(64), 0, S(), m, nc, (const int *)dcells.p + c0, (const int *)dseed.p, (const double *)dcx.p,
+                               (const double *)dcy.p, arena_t.p, arena_w.p, arena_s.p, dcount.p, dfailed.p);
+            if (copy_sync(count.data() + c0, dcount.p, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(NXS_ERR_HIP, "weights kernel failed: %s", hipGetErrorString(hipGetLastError()));
+            if (regrid_tables::exclusive_scan(dcount.p, nc + 1, S()) != hipSuccess) return fail(NXS_ERR_HIP, "scan of the row lengths failed");
+            std::unique_ptr<Piece> p(new Piece());
+            for (int i = 0; i < nc; ++i) p->n += count[c0 + i];
+            if (p->n > 0) {
+                if (p->t.alloc(p->n) || p->w.alloc(p->n)) return fail(NXS_ERR_HIP, "device allocation failed");
+                hipLaunchKernelGGL(gridmap::k_gridmap_compact, dim3((nc + 3) / 4), dim3(256), 0, S(), nc, (const int *)dcount.p, (const int *)arena_t.p, (const double *)arena_w.p,
+                                   p->t.p, p->w.p);
+            }
+            total += p->n;
+            pieces.push_back(std::move(p));
+        }
+    }
+    g_gridmap_last_chunks = nchunks;
+    if (total > 0x7fffffffll) return fail(NXS_ERR_INVALID, "the lists have %lld entries (int offsets)", total);
+    if (copy_sync(&g->failed, dfailed.p, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "weights kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    // the rows: wet cells that were not failed, in cell order; the scan across the chunks
+    std::vector<int> gridP, off(1, 0);
+    for (int i = 0; i < nwet; ++i)
+        if (count[i] > 0) { gridP.push_back(wet[i]); off.push_back(off.back() + count[i]); g->longest = std::max(g->longest, count[i]); }
+    g->rows = (int)gridP.size(); g->n = total;
+    if (g->dtris.alloc(total) || g->dw.alloc(total) || g->dgridP.upload(gridP.data(), gridP.size()) || g->doff.upload(off.data(), off.size()))
+        return fail(NXS_ERR_HIP, "device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));
+    size_t base = 0;
+    for (const auto &p : pieces) {
+        if (p->n > 0 && (hipMemcpyAsync(g->dtris.p + base, p->t.p, (size_t)p->n * sizeof(int), hipMemcpyDeviceToDevice, S()) != hipSuccess ||
+                         hipMemcpyAsync(g->dw.p + base, p->w.p, (size_t)p->n * sizeof(double), hipMemcpyDeviceToDevice, S()) != hipSuccess))
+            return fail(NXS_ERR_HIP, "device copy failed");
+        base += p->n;
+    }
+    if (int rc = gridmap_finish(g.get(), dcx.p, dcy.p)) return rc;
+    (void)hipEventRecord(e1, S());
+    if (hipStreamSynchronize(S()) != hipSuccess) return fail(NXS_ERR_HIP, "grid map kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    g_ms[4] += ms;
+    *out = g.release();
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_create"); }
+
+extern "C" int nxs_gridmap_destroy(nxs_gridmap *g) try {
+    if (!g) return NXS_OK;
+    (void)hipSetDevice(g->device);
+    delete g;
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_destroy"); }
+
+extern "C" int nxs_gridmap_info(const nxs_gridmap *g, int32_t *wet_cells, int64_t *entries, int32_t *longest_row, int32_t *failed_cells, int32_t *nels,
+                                int32_t *grid_size) try {
+    if (!g) return fail(NXS_ERR_INVALID, "NULL argument");
+    if (wet_cells) *wet_cells = g->rows;
+    if (entries) *entries = g->n;
+    if (longest_row) *longest_row = g->longest;
+    if (failed_cells) *failed_cells = g->failed;
+    if (nels) *nels = g->nels;
+    if (grid_size) *grid_size = g->G;
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_info"); }
+
+// ConservativeRemappingMeshToGrid (:103-135).  flags: NXS_REGRID_IN_DEVICE = `in` is a device pointer ([nels][nb_var]), NXS_REGRID_OUT_DEVICE = `out` is ([G][nb_var])
+extern "C" int nxs_gridmap_mesh_to_grid(nxs_gridmap *g, double *out, const double *in, int32_t nb_var, double miss_val, int32_t flags) try {
+    if (!g || !out || !in) return fail(NXS_ERR_INVALID, "NULL argument");
+    if (nb_var < 1) return fail(NXS_ERR_INVALID, "nb_var must be positive");
+    if (hipSetDevice(g->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    const bool in_dev = flags & NXS_REGRID_IN_DEVICE, out_dev = flags & NXS_REGRID_OUT_DEVICE;
+    const long long total = (long long)g->G * nb_var;
+    DevBuf<double> din, dout;
+    if ((!in_dev && din.upload(in, (size_t)g->nels * nb_var)) || (!out_dev && dout.alloc((size_t)total)))
+        return fail(NXS_ERR_HIP, "device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));
+    double *outp = out_dev ? out : dout.p;
+    hipLaunchKernelGGL(gridmap::k_gridmap_to_grid, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, S(), total, (int)nb_var, (const int *)g->drow_of_cell.p, (const int *)g->doff.p,
+                       (const int *)g->dtris.p, (const double *)g->dw.p, (const double *)g->drarea.p, in_dev ? in : (const double *)din.p, miss_val, outp);
+    if (hipStreamSynchronize(S()) != hipSuccess) return fail(NXS_ERR_HIP, "mesh-to-grid kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!out_dev && copy_sync(out, dout.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_mesh_to_grid"); }
+
+// ConservativeRemappingGridToMesh (:138-171) as a gather.  flags as above: `in` [G][nb_var], `out` [nels][nb_var]
+extern "C" int nxs_gridmap_grid_to_mesh(nxs_gridmap *g, double *out, const double *in, int32_t nb_var, int32_t flags) try {
+    if (!g || !out || !in) return fail(NXS_ERR_INVALID, "NULL argument");
+    if (nb_var < 1) return fail(NXS_ERR_INVALID, "nb_var must be positive");
+    if (hipSetDevice(g->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    const bool in_dev = flags & NXS_REGRID_IN_DEVICE, out_dev = flags & NXS_REGRID_OUT_DEVICE;
+    const long long total = (long long)g->nels * nb_var;
+    DevBuf<double> din, dout;
+    if ((!in_dev && din.upload(in, (size_t)g->G * nb_var)) || (!out_dev && dout.alloc((size_t)total)))
+        return fail(NXS_ERR_HIP, "device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));
+    double *outp = out_dev ? out : dout.p;
+    hipLaunchKernelGGL(gridmap::k_gridmap_to_mesh, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, S(), total, (int)nb_var, (const int *)g->dt_off.p, (const int *)g->dt_pos.p,
+                       (const int *)g->dcell.p, (const double *)g->dw.p, in_dev ? in : (const double *)din.p, outp);
+    if (hipStreamSynchronize(S()) != hipSuccess) return fail(NXS_ERR_HIP, "grid-to-mesh kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!out_dev && copy_sync(out, dout.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_grid_to_mesh"); }
+
+// the host form of the lists for the caller's broadcast; sizes from nxs_gridmap_info; any pointer may be NULL
+extern "C" int nxs_gridmap_export(nxs_gridmap *g, int32_t *gridP, int32_t *off, int32_t *tris, double *w, double *cornerX, double *cornerY) try {
+    if (!g) return fail(NXS_ERR_INVALID, "NULL argument");
+    if (hipSetDevice(g->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    GridmapHost h;
+    if (int rc = gridmap_download(g, h)) return rc;
+    if (gridP) std::copy(h.gridP.begin(), h.gridP.end(), gridP);
+    if (off) std::copy(h.off.begin(), h.off.end(), off);
+    if (tris) std::copy(h.tris.begin(), h.tris.end(), tris);
+    if (w) std::copy(h.w.begin(), h.w.end(), w);
+    if (cornerX) std::copy(g->cornerX.begin(), g->cornerX.end(), cornerX);
+    if (cornerY) std::copy(g->cornerY.begin(), g->cornerY.end(), cornerY);
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_export"); }
+
+extern "C" int nxs_gridmap_import(int32_t device, int32_t nels, int32_t G, int32_t rows, const int32_t *gridP, const int32_t *off, const int32_t *tris, const double *w,
+                                  const double *cornerX, const double *cornerY, nxs_gridmap **out) try {
+    if (!out) return fail(NXS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!off || !cornerX || !cornerY || (rows > 0 && (!gridP || !tris || !w))) return fail(NXS_ERR_INVALID, "NULL argument");
+    return gridmap_from_host(device, nels, G, rows, gridP, off, tris, w, cornerX, cornerY, 0, out);
+} catch (...) { return entry_caught("nxs_gridmap_import"); }
+
+// gridoutput.cpp:706-735: the entries of local triangles, renumbered; rows left empty dropped
+extern "C" int nxs_gridmap_restrict(nxs_gridmap *g, const int32_t *local_of_root, int32_t nels_local, nxs_gridmap **out) try {
+    if (!out) return fail(NXS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!g || !local_of_root) return fail(NXS_ERR_INVALID, "NULL argument");
+    if (nels_local < 1) return fail(NXS_ERR_INVALID, "nels_local must be positive");
+    for (int t = 0; t < g->nels; ++t)
+        if (local_of_root[t] >= nels_local) return fail(NXS_ERR_INVALID, "local_of_root[%d] = %d is not below nels_local", t, local_of_root[t]);
+    if (hipSetDevice(g->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    GridmapHost h, r;
+    if (int rc = gridmap_download(g, h)) return rc;
+    r.off.push_back(0);
+    for (int i = 0; i < g->rows; ++i) {
+        for (int k = h.off[i]; k < h.off[i + 1]; ++k) {
+            const int loc = local_of_root[h.tris[k]];
+            if (loc >= 0) { r.tris.push_back(loc); r.w.push_back(h.w[k]); }
+        }
+        if ((int)r.tris.size() > r.off.back()) { r.gridP.push_back(h.gridP[i]); r.off.push_back((int32_t)r.tris.size()); }
+    }
+    return gridmap_from_host(g->device, nels_local, g->G, (int)r.gridP.size(), r.gridP.data(), r.off.data(), r.tris.data(), r.w.data(), g->cornerX.data(), g->cornerY.data(),
+                             g->failed, out);
+} catch (...) { return entry_caught("nxs_gridmap_restrict"); }
+
+// test door: the weights build in chunks of `cells` cells (0 = as many as the 2 GiB arena allows); *last_chunks = the chunks the last build took
+extern "C" int nxs_gridmap_debug_chunk(int32_t cells, int32_t *last_chunks) try {
+    if (cells < 0) return fail(NXS_ERR_INVALID, "cells must not be negative");
+    g_gridmap_chunk = cells;
+    if (last_chunks) *last_chunks = g_gridmap_last_chunks;
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_debug_chunk"); }
+
+// ---------------------------------------------------------------------------------------------------------
 // Structured grid -> mesh nodes: the forcing ingest (InterpFromGridToMeshx, called at externaldata.cpp:1436)
 // ---------------------------------------------------------------------------------------------------------
 namespace {

@@ -12,6 +12,11 @@
 //      the floating-point sum), so it is replayed with an explicit stack of (triangle, stage, i, j) frames.
 // Every floating-point expression below keeps the reference's operand order; std::sort on <= 16 points is
 // libstdc++'s insertion sort (bits/stl_algo.h __insertion_sort / __unguarded_linear_insert), replayed here.
+//
+// The cell has NC corners, a template parameter: 3 for the new triangle of a regrid (the forms without a suffix, which
+// oracle/remap_host.cpp and k_remap use), 4 for the quadrilateral cell of a coupling grid (ConservativeRemappingWeights, :15-100, through
+// nxs_gridmap_create).  A triangle against a convex quadrilateral gives at most 3 + 4 + 6 = 13 points; more than kMaxPoints (a cell that
+// is not convex) fails the cell.
 #ifndef NXS_REMAP_CORE_INL
 #define NXS_REMAP_CORE_INL
 
@@ -23,7 +28,7 @@ namespace nxs_remap {
 
 constexpr int kMaxVisit = 96;   // old triangles one new triangle may overlap, fast path (lists in per-thread scratch);
 constexpr int kMaxVisitBig = 4096;  // second pass for the few that exceed it (lists in global memory); reference: unbounded
-constexpr int kMaxPoints = 16;  // 3 nodes + 3 corners + 6 intersections <= 12
+constexpr int kMaxPoints = 16;  // 3 nodes + NC corners + 2*NC intersections: <= 12 (NC = 3), <= 13 (NC = 4, convex)
 
 struct OldMesh {
     int nels, nods;
@@ -78,32 +83,37 @@ NXS_HD inline double polygon_area(Pt *p, int n) {
     return fabs(twice) * 0.5;
 }
 
-// Is (qx, qy) inside the triangle (tx, ty)?  The reference's test (ConservativeRemapping.cpp:463-514), with its tolerances: a point
+// Is (qx, qy) inside the polygon (tx, ty) of NV vertices -- the triangle, or the cell?  The reference's test (ConservativeRemapping.cpp:463-514), with its tolerances: a point
 // within 1 mm (in both coordinates) of a corner, or with an edge cross product inside the band of +-1e-8, is "on the boundary" and
 // gets the answer the caller asks for (`boundary_counts`); cross products of both signs mean outside.
-NXS_HD inline bool inside3(const double *tx, const double *ty, double qx, double qy, bool boundary_counts) {
+template <int NV>
+NXS_HD inline bool inside_n(const double *tx, const double *ty, double qx, double qy, bool boundary_counts) {
     const double corner_tol = 1.e-3, band = 1e-8;
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < NV; ++k)
         if (fabs(qx - tx[k]) < corner_tol && fabs(qy - ty[k]) < corner_tol) return boundary_counts;
     int left = 0, right = 0;
-    for (int k = 0; k < 3; ++k) {
-        const int k1 = (k + 1) % 3;
+    for (int k = 0; k < NV; ++k) {
+        const int k1 = (k + 1) % NV;
         const double turn = (tx[k1] - tx[k]) * (qy - ty[k]) - (ty[k1] - ty[k]) * (qx - tx[k]);
         if (turn > band) ++left;
         else if (turn < -band) ++right;
     }
     if (left > 0 && right > 0) return false;
-    return (left + right < 3) ? boundary_counts : true;
+    return (left + right < NV) ? boundary_counts : true;
+}
+NXS_HD inline bool inside3(const double *tx, const double *ty, double qx, double qy, bool boundary_counts) {
+    return inside_n<3>(tx, ty, qx, qy, boundary_counts);
 }
 
-// The proper crossings of the segment (x0, y0) -> (x1, y1) with the three edges of the cell, appended to pts in edge order (edge k
+// The proper crossings of the segment (x0, y0) -> (x1, y1) with the NC edges of the cell, appended to pts in edge order (edge k
 // runs from corner k-1 to corner k).  Parametric form of ConservativeRemapping.cpp:518-553: with d the segment and e the edge,
 // D = -e.x*d.y + d.x*e.y (edges with |D| < 1e-6 are taken as parallel), both parameters strictly inside (0, 1), the point taken on
 // the segment as start + t*d.  Every product and sum in the reference's operand order.
-NXS_HD inline bool intersect3(double x1, double y1, double x0, double y0, const double *cx, const double *cy, Pt *pts, int &npts) {
+template <int NC>
+NXS_HD inline bool intersect_n(double x1, double y1, double x0, double y0, const double *cx, const double *cy, Pt *pts, int &npts) {
     bool crossed = false;
     const double dx = x1 - x0, dy = y1 - y0;
-    for (int k = 0, from = 2; k < 3; from = k++) {
+    for (int k = 0, from = NC - 1; k < NC; from = k++) {
         const double ex = cx[k] - cx[from], ey = cy[k] - cy[from];
         const double D = -ex * dy + dx * ey;
         if (fabs(D) < 1e-6) continue;
@@ -118,11 +128,15 @@ NXS_HD inline bool intersect3(double x1, double y1, double x0, double y0, const 
     }
     return crossed;
 }
+NXS_HD inline bool intersect3(double x1, double y1, double x0, double y0, const double *cx, const double *cy, Pt *pts, int &npts) {
+    return intersect_n<3>(x1, y1, x0, y0, cx, cy, pts, npts);
+}
 
 // What checkTriangle computes for ONE old triangle against the cell, independent of the recursion:
 // bits 0-2 inCell[i]; bit 3 "returned early" (all nodes in the cell, or the whole cell in the triangle);
 // bits 4-6 edge (i, prev) intersects the cell and is followed.  *weight = the area it stores.
-NXS_HD inline int classify(const OldMesh &m, int t, const double *cx, const double *cy, double *weight, int *overflow) {
+template <int NC>
+NXS_HD inline int classify_n(const OldMesh &m, int t, const double *cx, const double *cy, double *weight, int *overflow) {
     Pt pts[kMaxPoints];
     int np = 0, bits = 0;
     double X[3], Y[3];
@@ -130,24 +144,27 @@ NXS_HD inline int classify(const OldMesh &m, int t, const double *cx, const doub
         const int node = m.tri[3 * t + i];
         X[i] = m.x[node];
         Y[i] = m.y[node];
-        if (inside3(cx, cy, X[i], Y[i], false)) {
+        if (inside_n<NC>(cx, cy, X[i], Y[i], false)) {
             bits |= 1 << i;
             pts[np].x = X[i]; pts[np].y = Y[i]; ++np;
         }
     }
     if ((bits & 7) == 7) { *weight = polygon_area(pts, np); return bits | 8; }
     int counter = 0;
-    for (int c = 0; c < 3; ++c)
-        if (inside3(X, Y, cx[c], cy[c], true)) { pts[np].x = cx[c]; pts[np].y = cy[c]; ++np; ++counter; }
-    if (counter == 3) { *weight = polygon_area(pts, np); return bits | 8; }
+    for (int c = 0; c < NC; ++c)
+        if (inside_n<3>(X, Y, cx[c], cy[c], true)) { pts[np].x = cx[c]; pts[np].y = cy[c]; ++np; ++counter; }
+    if (counter == NC) { *weight = polygon_area(pts, np); return bits | 8; }
     int prev = 2;
     for (int i = 0; i < 3; prev = i++) {
         if ((bits >> i & 1) && (bits >> prev & 1)) continue;
-        if (intersect3(X[i], Y[i], X[prev], Y[prev], cx, cy, pts, np)) bits |= 16 << i;
+        if (intersect_n<NC>(X[i], Y[i], X[prev], Y[prev], cx, cy, pts, np)) bits |= 16 << i;
     }
     if (np > kMaxPoints) { *overflow = 1; np = kMaxPoints; }
     *weight = polygon_area(pts, np);
     return bits;
+}
+NXS_HD inline int classify(const OldMesh &m, int t, const double *cx, const double *cy, double *weight, int *overflow) {
+    return classify_n<3>(m, t, cx, cy, weight, overflow);
 }
 
 struct Frame {
@@ -155,12 +172,13 @@ struct Frame {
     unsigned char bits, stage, i, j;
 };
 
-// One new triangle: corners (cx, cy), the old triangle `seed` that holds its barycentre, `same` = the three
-// vertices are those of the seed (ConservativeRemapping.cpp:263-289).  Fills tris/w in the reference's
-// push order and returns their number, or -1 on capacity overflow (cap entries in tris / w, cap + 1 frames).
-NXS_HD inline int collect(const OldMesh &m, const double *cx, const double *cy, int seed, bool same, int *tris, double *w, Frame *stack,
-                          int cap = kMaxVisit) {
-    if (same) {
+// One cell: corners (cx, cy), the old triangle `seed` that holds its P-point (the barycentre of a new triangle), `same` = the three
+// vertices are those of the seed (ConservativeRemapping.cpp:263-289; a triangle's shortcut only).  Fills tris/w in the reference's
+// push order and returns their number, or -1 on overflow: more than cap triangles (cap entries in tris / w, cap + 1 frames) or more
+// than kMaxPoints points in one polygon.
+template <int NC>
+NXS_HD inline int collect_n(const OldMesh &m, const double *cx, const double *cy, int seed, bool same, int *tris, double *w, Frame *stack, int cap) {
+    if (NC == 3 && same) {
         Pt p[3] = {{cx[0], cy[0]}, {cx[1], cy[1]}, {cx[2], cy[2]}};
         tris[0] = seed;
         w[0] = polygon_area(p, 3);
@@ -174,7 +192,7 @@ NXS_HD inline int collect(const OldMesh &m, const double *cx, const double *cy, 
     };
     auto enter = [&](int t) {  // checkTriangle's prologue: plant the flag, reserve the weight slot
         tris[n] = t;
-        const int bits = classify(m, t, cx, cy, &w[n], &overflow);
+        const int bits = classify_n<NC>(m, t, cx, cy, &w[n], &overflow);
         ++n;
         stack[sp].t = t; stack[sp].bits = (unsigned char)bits; stack[sp].stage = 1; stack[sp].i = 0; stack[sp].j = 0;
         ++sp;
@@ -232,17 +250,55 @@ NXS_HD inline int collect(const OldMesh &m, const double *cx, const double *cy, 
     }
     return overflow ? -1 : n;
 }
+NXS_HD inline int collect(const OldMesh &m, const double *cx, const double *cy, int seed, bool same, int *tris, double *w, Frame *stack,
+                          int cap = kMaxVisit) {
+    return collect_n<3>(m, cx, cy, seed, same, tris, w, stack, cap);
+}
 
-// ConservativeRemappingMeshToGrid with num_corners == 3 (ConservativeRemapping.cpp:97-131), one cell
-NXS_HD inline void apply(const double *in, int nb_var, const double *cx, const double *cy, const int *tris, const double *w, int n, double *out) {
-    Pt p[3] = {{cx[0], cy[0]}, {cx[1], cy[1]}, {cx[2], cy[2]}};
-    const double r_cell_area = 1. / polygon_area(p, 3);
+// 1 / area(cell) as ConservativeRemappingMeshToGrid takes it (ConservativeRemapping.cpp:116-122): the corners through the same sort and shoelace sum
+template <int NC>
+NXS_HD inline double r_cell_area_n(const double *cx, const double *cy) {
+    Pt p[NC];
+    for (int c = 0; c < NC; ++c) { p[c].x = cx[c]; p[c].y = cy[c]; }
+    return 1. / polygon_area(p, NC);
+}
+
+// ConservativeRemappingMeshToGrid (ConservativeRemapping.cpp:97-131), one cell of NC corners; the form without a suffix is num_corners == 3
+template <int NC>
+NXS_HD inline void apply_n(const double *in, int nb_var, const double *cx, const double *cy, const int *tris, const double *w, int n, double *out) {
+    const double r_cell_area = r_cell_area_n<NC>(cx, cy);
     for (int var = 0; var < nb_var; ++var) {
         double v = 0.;
         for (int k = 0; k < n; ++k) v += in[(long long)tris[k] * nb_var + var] * w[k];
         v *= r_cell_area;
         out[var] = v;
     }
+}
+NXS_HD inline void apply(const double *in, int nb_var, const double *cx, const double *cy, const int *tris, const double *w, int n, double *out) {
+    apply_n<3>(in, nb_var, cx, cy, tris, w, n, out);
+}
+
+// The two applications of weights kept as lists (nxs_gridmap), one output value each.
+// mesh -> grid (ConservativeRemapping.cpp:125-133): variable `var` of one wet cell, its row of n (triangle, weight) entries in push order
+NXS_HD inline double grid_value(const double *in, int nb_var, int var, const int *tris, const double *w, int n, double r_cell_area) {
+    double v = 0.;
+    for (int k = 0; k < n; ++k) v += in[(long long)tris[k] * nb_var + var] * w[k];
+    v *= r_cell_area;
+    return v;
+}
+// grid -> mesh (ConservativeRemapping.cpp:145-170) as a gather: variable `var` of one triangle; pos[0..n) = its entries' indices in the forward
+// lists, ascending -- the order in which the reference's scatter over (cell, position) reaches this triangle; cell[p] = gridP of entry p's row.
+// A triangle without an entry gets 0 * (1 / 0.), a NaN, as in the reference.
+NXS_HD inline double mesh_value(const double *in, int nb_var, int var, const int *pos, int n, const int *cell, const double *w) {
+    double v = 0., triangle_area = 0.;
+    for (int k = 0; k < n; ++k) {
+        const int p = pos[k];
+        triangle_area += w[p];
+        v += in[(long long)cell[p] * nb_var + var] * w[p];
+    }
+    const double r_triangle_area = 1. / triangle_area;
+    v *= r_triangle_area;
+    return v;
 }
 
 // nodes_old == nodes_new after sorting (ConservativeRemapping.cpp:263-289).  previous_numbering may be

@@ -125,6 +125,7 @@ def load_library():
     L.nxs_dyn_means_update.argtypes = [H, C.c_double]
     L.nxs_dyn_means_get.argtypes = [H, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
     L.nxs_dyn_means_to_grid.argtypes = [H, P(_abi.MeansGrid), _abi.c_double_p, _abi.c_double_p]
+    L.nxs_dyn_means_to_grid_conservative.argtypes = [H, C.c_void_p, C.c_double, _abi.c_double_p]
     L.nxs_dyn_means_reset.argtypes = [H]
     L.nxs_dyn_drifters_set.argtypes = [H, C.c_int32, C.c_int32, _abi.c_double_p, _abi.c_double_p, _abi.c_int32_p]
     L.nxs_dyn_drifters_clear.argtypes = [H, C.c_int32]
@@ -190,7 +191,7 @@ EXPORTS = (
     "nxs_dyn_thermo_forcing_pair", "nxs_dyn_thermo_forcing_time", "nxs_dyn_thermo_forcing_targets", "nxs_dyn_thermo_forcing_ingest", "nxs_dyn_thermo_forcing_get",
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
-    "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_reset",
+    "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_to_grid_conservative", "nxs_dyn_means_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
     "nxs_dyn_drifters_get", "nxs_dyn_regrid", "nxs_dyn_regrid_carry_thermo", "nxs_dyn_regrid_thermo_info_get",
     "nxs_dyn_explicit_solve", "nxs_dyn_update", "nxs_dyn_synchronize", "nxs_dyn_step_host",
@@ -199,7 +200,9 @@ EXPORTS = (
 )
 INTERP_EXPORTS = ("nxs_interp_mesh_to_mesh_2d", "nxs_interp_mesh_to_grid", "nxs_interp_mesh_to_grid_device", "nxs_interp_conservative_remap", "nxs_interp_grid_to_mesh",
                   "nxs_interp_last_error", "nxs_interp_last_info", "nxs_mesh_convex_completion", "nxs_mesh_convex_completion_mode", "nxs_regrid_create", "nxs_regrid_destroy",
-                  "nxs_regrid_interp_nodes", "nxs_regrid_remap_elements", "nxs_interp_last_timing", "nxs_regrid_debug_tables")
+                  "nxs_regrid_interp_nodes", "nxs_regrid_remap_elements", "nxs_interp_last_timing", "nxs_regrid_debug_tables", "nxs_gridmap_create", "nxs_gridmap_destroy",
+                  "nxs_gridmap_info", "nxs_gridmap_mesh_to_grid", "nxs_gridmap_grid_to_mesh", "nxs_gridmap_export", "nxs_gridmap_import", "nxs_gridmap_restrict",
+                  "nxs_gridmap_debug_chunk")
 
 
 def selftest_quotients(n: int, seed: int = 1, mode: int = 0, device: int = 0) -> int:
@@ -1234,6 +1237,18 @@ class FiniteElementDynamics:
         g = _abi.MeansGrid(float(xmin), float(ymax), float(mooring_spacing), float(miss_val), int(ncols), int(nrows))
         self._chk(self.L.nxs_dyn_means_to_grid(self.h, C.byref(g), _abi.dptr(grid_elemental) if n_el else None, _abi.dptr(grid_nodal) if n_nod else None))
         return (grid_elemental if n_el else None), (grid_nodal if n_nod else None)
+
+    def means_to_grid_conservative(self, gridmap, miss_val=-1e14, grid_elemental=None):
+        """updateGridMean()'s elemental leg on a loaded grid with conservative remapping: the accumulator rows through `gridmap` (interp.GridMap of this
+        mesh) with missing value 0., ADDED to grid_elemental [n_el, G] (made of zeros when None) without transposition, then the ice-mask rule."""
+        n_el = getattr(self, "_means_n", (0, 0))[0]
+        G = gridmap.info()["grid_size"]
+        if grid_elemental is None:
+            grid_elemental = np.zeros((max(n_el, 1), G))
+        if n_el and (grid_elemental.shape != (n_el, G) or grid_elemental.dtype != np.float64 or not grid_elemental.flags.c_contiguous):
+            raise ValueError(f"grid array has shape {grid_elemental.shape}, expected a C-contiguous float64 ({n_el}, {G})")
+        self._chk(self.L.nxs_dyn_means_to_grid_conservative(self.h, gridmap.h, float(miss_val), _abi.dptr(grid_elemental)))
+        return grid_elemental
 
     def means_reset(self):
         """resetMeshMean(bamgmesh): both accumulators to zero, on the stream."""

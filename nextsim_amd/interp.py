@@ -306,6 +306,148 @@ class Regrid:
         return out[:n.value]
 
 
+class GridMap:
+    """Conservative remapping between a mesh and a grid of quadrilateral cells with the weights resident on the device (include/nxs_interp.h,
+    nxs_gridmap_*): ConservativeRemappingWeights / MeshToGrid / GridToMesh of contrib/bamg.  Made by weights() from a Regrid context of the mesh at
+    rest, by import_() from exported lists, or by restrict() from another map."""
+
+    IN_DEVICE, OUT_DEVICE = 1, 2
+
+    def __init__(self, handle):
+        self.L = _declare_gridmap()
+        self.h = handle
+
+    @classmethod
+    def weights(cls, regrid, gridX, gridY, cornerX, cornerY):
+        """ConservativeRemappingWeights: gridX, gridY [G] the P-points, cornerX, cornerY [G, 4] the corners in order around each cell."""
+        L = _declare_gridmap()
+        f64 = lambda a: np.ascontiguousarray(a, np.float64).ravel()  # noqa: E731
+        gx, gy, cx, cy = f64(gridX), f64(gridY), f64(cornerX), f64(cornerY)
+        if gy.size != gx.size or cx.size != 4 * gx.size or cy.size != 4 * gx.size:
+            raise ValueError("gridX, gridY [G] and cornerX, cornerY [G, 4] expected")
+        h = C.c_void_p()
+        rc = L.nxs_gridmap_create(regrid.h, _abi.dptr(gx), _abi.dptr(gy), _abi.dptr(cx), _abi.dptr(cy), gx.size, C.byref(h))
+        if rc:
+            raise NxsError(rc, (L.nxs_interp_last_error() or b"").decode())
+        return cls(h)
+
+    @classmethod
+    def import_(cls, lists, device=0):
+        """A map out of what export() returned (after the caller's broadcast)."""
+        L = _declare_gridmap()
+        i32 = lambda a: np.ascontiguousarray(a, np.int32).ravel()  # noqa: E731
+        f64 = lambda a: np.ascontiguousarray(a, np.float64).ravel()  # noqa: E731
+        gp, off, tr, w, cx, cy = i32(lists["gridP"]), i32(lists["off"]), i32(lists["tris"]), f64(lists["w"]), f64(lists["cornerX"]), f64(lists["cornerY"])
+        if off.size != gp.size + 1 or tr.size != w.size or (off.size and off[-1] != tr.size) or cx.size != 4 * int(lists["grid_size"]) or cy.size != cx.size:
+            raise ValueError("inconsistent lists")
+        h = C.c_void_p()
+        rc = L.nxs_gridmap_import(device, int(lists["nels"]), int(lists["grid_size"]), gp.size, _abi.iptr(gp), _abi.iptr(off), _abi.iptr(tr), _abi.dptr(w),
+                                  _abi.dptr(cx), _abi.dptr(cy), C.byref(h))
+        if rc:
+            raise NxsError(rc, (L.nxs_interp_last_error() or b"").decode())
+        return cls(h)
+
+    def _chk(self, rc):
+        if rc:
+            raise NxsError(rc, (self.L.nxs_interp_last_error() or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.nxs_gridmap_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        wet, lng, failed, nels, G = (C.c_int32() for _ in range(5))
+        n = C.c_int64()
+        self._chk(self.L.nxs_gridmap_info(self.h, C.byref(wet), C.byref(n), C.byref(lng), C.byref(failed), C.byref(nels), C.byref(G)))
+        return {"wet": wet.value, "entries": n.value, "longest": lng.value, "failed": failed.value, "nels": nels.value, "grid_size": G.value}
+
+    def export(self):
+        """The host lists: gridP [rows], off [rows + 1], tris, w [entries], cornerX, cornerY [G, 4], with nels and grid_size."""
+        i = self.info()
+        gp, off, tr = np.empty(i["wet"], np.int32), np.empty(i["wet"] + 1, np.int32), np.empty(i["entries"], np.int32)
+        w, cx, cy = np.empty(i["entries"]), np.empty((i["grid_size"], 4)), np.empty((i["grid_size"], 4))
+        self._chk(self.L.nxs_gridmap_export(self.h, _abi.iptr(gp), _abi.iptr(off), _abi.iptr(tr), _abi.dptr(w), _abi.dptr(cx), _abi.dptr(cy)))
+        return {"gridP": gp, "off": off, "tris": tr, "w": w, "cornerX": cx, "cornerY": cy, "nels": i["nels"], "grid_size": i["grid_size"]}
+
+    def restrict(self, local_of_root, nels_local):
+        """The map of a partition: local_of_root [nels] = the local number of every triangle, -1 = not here (gridoutput.cpp:706-735)."""
+        lor = np.ascontiguousarray(local_of_root, np.int32).ravel()
+        if lor.size != self.info()["nels"]:
+            raise ValueError("local_of_root has one entry per triangle of the map's mesh")
+        h = C.c_void_p()
+        self._chk(self.L.nxs_gridmap_restrict(self.h, _abi.iptr(lor), int(nels_local), C.byref(h)))
+        return GridMap(h)
+
+    def _apply(self, fn, rows_in, rows_out, data, in_device, out_device, out, extra):
+        flags = 0
+        if in_device is not None:
+            dptr, nv = in_device
+            src = C.c_void_p(dptr); flags |= self.IN_DEVICE
+        else:
+            data = np.ascontiguousarray(data, np.float64)
+            if data.ndim == 1:
+                data = data[:, None]
+            if data.shape[0] != rows_in:
+                raise ValueError(f"data has {data.shape[0]} rows, expected {rows_in}")
+            nv = data.shape[1]
+            src = C.c_void_p(data.ctypes.data)
+        if out_device is not None:
+            out = None
+            dst = C.c_void_p(out_device); flags |= self.OUT_DEVICE
+        else:
+            out = _result_array(out, (rows_out, nv))
+            dst = C.c_void_p(out.ctypes.data)
+        self._chk(fn(self.h, dst, src, nv, *extra, flags))
+        return out
+
+    def mesh_to_grid(self, data, miss_val=0., in_device=None, out_device=None, out=None):
+        """ConservativeRemappingMeshToGrid: data [nels, nb_var] -> [G, nb_var].  in_device = (device pointer, nb_var) instead of `data`; out_device = a device pointer."""
+        i = self.info()
+        return self._apply(self.L.nxs_gridmap_mesh_to_grid, i["nels"], i["grid_size"], data, in_device, out_device, out, (float(miss_val),))
+
+    def grid_to_mesh(self, data, in_device=None, out_device=None, out=None):
+        """ConservativeRemappingGridToMesh: data [G, nb_var] -> [nels, nb_var]."""
+        i = self.info()
+        return self._apply(self.L.nxs_gridmap_grid_to_mesh, i["grid_size"], i["nels"], data, in_device, out_device, out, ())
+
+
+def _declare_gridmap():
+    L = _lib()
+    if not hasattr(L, "_gridmap_declared"):
+        D, I, V = _abi.c_double_p, _abi.c_int32_p, C.c_void_p
+        P32, P64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        L.nxs_gridmap_create.argtypes = [V, D, D, D, D, C.c_int32, C.POINTER(V)]
+        L.nxs_gridmap_destroy.argtypes = [V]
+        L.nxs_gridmap_info.argtypes = [V, P32, P64, P32, P32, P32, P32]
+        L.nxs_gridmap_mesh_to_grid.argtypes = [V, V, V, C.c_int32, C.c_double, C.c_int32]
+        L.nxs_gridmap_grid_to_mesh.argtypes = [V, V, V, C.c_int32, C.c_int32]
+        L.nxs_gridmap_export.argtypes = [V, I, I, I, D, D, D]
+        L.nxs_gridmap_import.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, I, I, I, D, D, D, C.POINTER(V)]
+        L.nxs_gridmap_restrict.argtypes = [V, I, C.c_int32, C.POINTER(V)]
+        L.nxs_gridmap_debug_chunk.argtypes = [C.c_int32, P32]
+        for n in ("create", "destroy", "info", "mesh_to_grid", "grid_to_mesh", "export", "import", "restrict", "debug_chunk"):
+            getattr(L, "nxs_gridmap_" + n).restype = C.c_int
+        L._gridmap_declared = True
+    return L
+
+
+def gridmap_debug_chunk(cells=0):
+    """Test door: build the weights in chunks of `cells` cells (0 = the default); returns the chunks the last build took."""
+    L = _declare_gridmap()
+    last = C.c_int32(0)
+    rc = L.nxs_gridmap_debug_chunk(int(cells), C.byref(last))
+    if rc:
+        raise NxsError(rc, (L.nxs_interp_last_error() or b"").decode())
+    return last.value
+
+
 TRIANGLE, BILINEAR, NEAREST = 0, 1, 2
 
 
