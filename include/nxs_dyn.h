@@ -1005,6 +1005,87 @@ NXS_API int nxs_dyn_thermo_forcing_ingest(nxs_dyn_handle *h, int32_t set, const 
                                           const int32_t *snapshot);
 NXS_API int nxs_dyn_thermo_forcing_get(nxs_dyn_handle *h, int32_t which, const nxs_dyn_thermo_forcing_rows *out);
 
+/* ---- Nesting on the device: nestingIce() (FE.cpp:4878-4908) and nestingDynamics() (FE.cpp:4915-4958), the two statements FiniteElement::step() runs between
+ * thermo() and the dynamics under nesting.use_nesting (FE.cpp:8172-8192).  Per entry x += (fNudge*(time_step/nudge_time)*(target - x)), with target =
+ * ExternalData::get of the nesting dataset (externaldata.cpp:366-438, the semantics of nxs_dyn_thermo_forcing_time) evaluated in the same kernel from both resident
+ * snapshots, and fNudge = 1. - std::min(1., dist/nudge_scale) (NXS_NUDGE_LINEAR) or std::exp(-dist/nudge_scale) (NXS_NUDGE_EXPONENTIAL).  All M_num_elements and
+ * M_num_nodes are updated, ghosts included; nothing is exchanged, so both calls work on a handle with halo lists.  Nothing runs unless these entry points are
+ * called: no allocation at nxs_dyn_set_mesh, no launch in nxs_dyn_step.
+ * IN PLACE: between two steps M_sigma / M_damage are current either in their arrays or in the 4-double records the sub-step loop left behind;
+ * nxs_dyn_nesting_dynamics nudges them where they are (no unpack now, no pack in the next step).  Under EVP / mEVP the records hold no damage: M_damage is nudged in
+ * its array.  M_VT is nudged in the array nxs_dyn_get_state reads.
+ *   nxs_nesting_config_check    what nxs_dyn_nesting_configure refuses, without a handle (the text: nxs_dyn_last_error(NULL)): nudge_function other than
+ *                  NXS_NUDGE_LINEAR / _EXPONENTIAL (the reference throws, FE.cpp:4886-4888); nudge_timescale, nudge_scale not finite or <= 0; dtime_step not finite
+ *   nxs_dyn_nesting_configure   the configuration is the handle's and survives nxs_dyn_set_mesh.  time_step is the model's int, dtime_step its double: the element
+ *                  rows and all of nestingIce use (double)time_step / nudge_timescale, M_VT dtime_step / nudge_timescale (FE.cpp:4954-4955); both quotients are
+ *                  formed once, here.  nudge_scale = M_nudge_lengthscale * M_res_root_mesh
+ *   nxs_dyn_nesting_pair        host rows of snapshot 0 (s0) and 1 (s1, may be NULL) of a nesting interval: [Ne] element rows in the order of forcingNesting()
+ *                  (FE.cpp:11062-11111), [Nn] nodal rows (FE.cpp:11113-11121).  A NULL row means "not given".  The rows go with the mesh: gone after
+ *                  nxs_dyn_set_mesh and nxs_dyn_regrid.  NXS_ERR_STATE before nxs_dyn_set_mesh
+ *   nxs_dyn_nesting_time        per DATASET (NXS_NEST_DS_*: the five of FE.cpp:822-827 without the ocean one) mode NXS_TF_LINEAR / NXS_TF_STEP (NXS_TF_OFF: a
+ *                  dataset that is not read), fcoeff0, fcoeff1, M_factor, M_bias_correction.  The handle's; no launch.  NXS_ERR_INVALID: an unknown mode
+ *   nxs_dyn_nesting_ice         one launch on the handle's stream: M_conc, M_thick, M_snow_thick, and M_conc_young, M_h_young, M_hs_young when the handle's
+ *                  ice_cat_type is YOUNG_ICE (only then are the young-ice rows required).  NXS_ERR_STATE: no configuration, no time, no state, a dataset OFF that
+ *                  is read, a required row (both snapshots under LINEAR, snapshot 0 under STEP) missing on this mesh -- the message names the row
+ *   nxs_dyn_nesting_dynamics    one launch: M_sigma[0..2], M_damage, M_ridge_ratio per element, M_VT per node.  As above; NXS_ERR_STATE also when the configuration's
+ *                  nest_dynamic_vars is 0
+ *   nxs_dyn_nesting_get         which = 0 / 1: the snapshots back to the host (NULL rows are skipped; a missing row that is asked for is NXS_ERR_STATE).  The
+ *                  tests' door */
+enum { NXS_NEST_DIST = 0, NXS_NEST_THICK, NXS_NEST_CONC, NXS_NEST_SNOW_THICK, NXS_NEST_H_YOUNG, NXS_NEST_CONC_YOUNG, NXS_NEST_HS_YOUNG,
+       NXS_NEST_SIGMA1, NXS_NEST_SIGMA2, NXS_NEST_SIGMA3, NXS_NEST_DAMAGE, NXS_NEST_RIDGE_RATIO };
+#define NXS_NEST_ELEMENT_ROWS 12
+enum { NXS_NEST_DIST_NODES = 0, NXS_NEST_VT1, NXS_NEST_VT2 };
+#define NXS_NEST_NODE_ROWS 3
+enum { NXS_NEST_DS_DISTANCE_ELEMENTS = 0, NXS_NEST_DS_ICE_ELEMENTS, NXS_NEST_DS_DYNAMICS_ELEMENTS, NXS_NEST_DS_DISTANCE_NODES, NXS_NEST_DS_NODES };
+#define NXS_NEST_DATASETS 5
+enum { NXS_NUDGE_LINEAR = 0, NXS_NUDGE_EXPONENTIAL = 1 };
+typedef struct nxs_dyn_nesting_config {
+    int32_t nudge_function;             /* NXS_NUDGE_LINEAR / NXS_NUDGE_EXPONENTIAL (nesting.nudge_function) */
+    int32_t nest_dynamic_vars;          /* nesting.nest_dynamic_vars: nxs_dyn_nesting_dynamics may be called */
+    int32_t time_step;                  /* the model's int time_step (s) */
+    int32_t reserved0;
+    double nudge_timescale;             /* M_nudge_timescale (s) */
+    double nudge_scale;                 /* M_nudge_lengthscale * M_res_root_mesh (m) */
+    double dtime_step;                  /* the model's double dtime_step (s) */
+} nxs_dyn_nesting_config;
+typedef struct nxs_dyn_nesting_rows {
+    double *element[NXS_NEST_ELEMENT_ROWS];   /* [Ne] each, indexed by NXS_NEST_* (read by _pair, written by _get) */
+    double *node[NXS_NEST_NODE_ROWS];         /* [Nn] each, indexed by NXS_NEST_DIST_NODES .. NXS_NEST_VT2 */
+} nxs_dyn_nesting_rows;
+/* (a struct TAG only, as nxs_dyn_thermo_forcing_time) */
+struct nxs_dyn_nesting_time {
+    int32_t mode[NXS_NEST_DATASETS];    /* NXS_TF_OFF / _LINEAR / _STEP per NXS_NEST_DS_* */
+    int32_t reserved0;
+    double fcoeff0[NXS_NEST_DATASETS];
+    double fcoeff1[NXS_NEST_DATASETS];
+    double factor[NXS_NEST_DATASETS];
+    double bias[NXS_NEST_DATASETS];
+};
+
+NXS_API int nxs_nesting_config_check(const nxs_dyn_nesting_config *c);
+NXS_API int nxs_dyn_nesting_configure(nxs_dyn_handle *h, const nxs_dyn_nesting_config *c);
+NXS_API int nxs_dyn_nesting_pair(nxs_dyn_handle *h, const nxs_dyn_nesting_rows *s0, const nxs_dyn_nesting_rows *s1 /* may be NULL */);
+NXS_API int nxs_dyn_nesting_time(nxs_dyn_handle *h, const struct nxs_dyn_nesting_time *t);
+NXS_API int nxs_dyn_nesting_ice(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_nesting_dynamics(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_nesting_get(nxs_dyn_handle *h, int32_t which, const nxs_dyn_nesting_rows *out);
+
+/* ---- Slab-ocean diffusion on the device: diffuse() (FE.cpp:2760-2815) for M_sst and M_sss, the first thing update() does whenever thermo.diffusivity_sst / _sss > 0
+ * (FE.cpp:3938-3939).  One explicit Jacobi step over bamgmesh->ElementConnectivity: v[e] += f0 + f1 + f2 with fj = factor*(old[n_j] - old[e]), or 0. where the
+ * element has no neighbour across edge j; every flux reads the OLD row.  An element without any neighbour still executes v += 0. + 0. + 0. (-0.0 becomes +0.0).
+ * Neither explicitSolve() nor the element loop of update() reads or writes M_sst / M_sss, so nxs_dyn_diffuse right before nxs_dyn_step gives the reference's bits.
+ *   nxs_dyn_diffusion_configure  factor = diffusivity * dtime_step / std::pow(dx, 2.) is formed here, on the host (FE.cpp:2775).  A diffusivity <= 0 switches that
+ *                  field off (FE.cpp:2762).  The handle's; survives nxs_dyn_set_mesh.  NXS_ERR_INVALID: a non-finite argument, dx <= 0
+ *   nxs_dyn_diffuse              works in place on the sst / sss rows of nxs_dyn_flux_state (their device addresses do not change): two launches -- {sst, sss}
+ *                  packed into one [Ne] array of 16-byte pairs, then per element one index load and three gathers.  Both fields off: nothing is launched.  The
+ *                  element-to-element table (ints [Ne][3], -1 on the boundary; debug array "diffuse_table", [3 Ne]) and the packed copy are made by the first call
+ *                  after a mesh change and go with the mesh.  NXS_ERR_STATE: not configured, before nxs_dyn_set_mesh, sst or sss never put on this mesh, a
+ *                  handle with halo lists (the reference diffuses on its root rank from gathered fields; no element-row exchange exists here)
+ *   nxs_dyn_flux_device_rows     the DEVICE addresses of the eight rows of nxs_dyn_flux_state in its member order; NULL for a row never put on this mesh */
+NXS_API int nxs_dyn_diffusion_configure(nxs_dyn_handle *h, double diffusivity_sst, double diffusivity_sss, double dx, double dtime_step);
+NXS_API int nxs_dyn_diffuse(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_flux_device_rows(nxs_dyn_handle *h, const double **device_rows /* [8] */);
+
 /* ---- The rest of thermo()'s slab loop on the device: FE.cpp:5413-6133 as a default (non-OASIS) build compiles it -- the assimilation flux (FE.cpp:5415-5425),
  * section 6: new ice over open water and lateral melt (FE.cpp:5434-5646; newice_type 1 .. 4, type 3 with windSpeedElement, FE.cpp:6359-6370; melt_type 1, 2), the
  * freeze-days block (FE.cpp:5649-5682), the new concentration and thickness with Winton's (38), (39), (26) (FE.cpp:5685-5711), the limit block (FE.cpp:5714-5728),

@@ -311,6 +311,28 @@ class ForcingGrid(C.Structure):   # nxs_dyn_forcing_grid
     _fields_ = [("x_in", c_double_p), ("y_in", c_double_p)] + [(k, C.c_int32) for k in ("x_rows", "y_rows", "M", "N", "interp", "row_major")] + [("default_value", C.c_double)]
 
 
+# ---- nesting and the slab ocean's diffusion on the device (include/nxs_dyn.h, nxs_dyn_nesting_* / nxs_dyn_diffuse)
+NEST_ELEMENT_ROWS = ("dist", "thick", "conc", "snow_thick", "h_young", "conc_young", "hs_young", "sigma1", "sigma2", "sigma3", "damage", "ridge_ratio")   # NXS_NEST_*
+NEST_NODE_ROWS = ("dist_nodes", "VT1", "VT2")
+NEST_DATASETS = ("distance_elements", "ice_elements", "dynamics_elements", "distance_nodes", "nodes")   # NXS_NEST_DS_*
+NXS_NEST_ELEMENT_ROWS, NXS_NEST_NODE_ROWS, NXS_NEST_DATASETS = 12, 3, 5
+NXS_NUDGE_LINEAR, NXS_NUDGE_EXPONENTIAL = 0, 1
+NUDGE_FUNCTIONS = {"linear": NXS_NUDGE_LINEAR, "exponential": NXS_NUDGE_EXPONENTIAL}
+assert (len(NEST_ELEMENT_ROWS), len(NEST_NODE_ROWS), len(NEST_DATASETS)) == (NXS_NEST_ELEMENT_ROWS, NXS_NEST_NODE_ROWS, NXS_NEST_DATASETS)
+
+
+class NestingConfig(C.Structure):   # nxs_dyn_nesting_config
+    _fields_ = [(k, C.c_int32) for k in ("nudge_function", "nest_dynamic_vars", "time_step", "reserved0")] + [(k, C.c_double) for k in ("nudge_timescale", "nudge_scale", "dtime_step")]
+
+
+class NestingRows(C.Structure):   # nxs_dyn_nesting_rows
+    _fields_ = [("element", c_double_p * NXS_NEST_ELEMENT_ROWS), ("node", c_double_p * NXS_NEST_NODE_ROWS)]
+
+
+class NestingTime(C.Structure):   # struct nxs_dyn_nesting_time
+    _fields_ = [("mode", C.c_int32 * NXS_NEST_DATASETS), ("reserved0", C.c_int32)] + [(k, C.c_double * NXS_NEST_DATASETS) for k in ("fcoeff0", "fcoeff1", "factor", "bias")]
+
+
 # ---- thermo()'s slab loop from new ice to tracers (include/nxs_dyn.h, nxs_slab_* / nxs_dyn_slab_* / nxs_dyn_slab)
 SLAB_CONSTANTS = ("cmin", "hmin", "rhow", "cpw", "rhoi", "rhos", "Lf", "C", "ki", "si", "days_in_sec")   # NXS_SLAB_CONST_*
 SLAB_CONFIG_INTS = ("newice_type", "melt_type", "use_assim_flux", "temp_dep_healing", "use_meltponds", "reset_by_date", "include_young_ice", "equal_melting")

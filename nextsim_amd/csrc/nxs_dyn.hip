@@ -21,6 +21,7 @@
 //   k_slab                                    FE.cpp:5413-6133: thermo()'s slab loop from new ice to tracers, with meltPonds (nxs_slab_kernels.inl, nxs_dyn_slab)
 //   k_coupled_thermo, k_coupled_bins          the same loop as an OASIS build compiles it, on the attached floe-size bins (nxs_slab_fsd_kernels.inl, nxs_dyn_slab_coupled)
 //   k_thermo_forcing_blend / _ingest          externaldata.cpp:324-439, 1436: thermo()'s ten element forcing rows, ExternalData::get and InterpFromGridToMeshx (nxs_thermo_forcing_kernels.inl, nxs_dyn_thermo_forcing_*)
+//   k_nesting_ice / _dynamics, k_diffuse(_pack) FE.cpp:4878-4958, 2760-2815: nestingIce, nestingDynamics and diffuse of M_sst / M_sss, in place (nxs_nesting_kernels.inl, nxs_dyn_nesting_*, nxs_dyn_diffuse)
 //   k_fsd_init / _update / _breakup / _weld   FE.cpp:7562-7576, 4674-4732, 4268-4483, 4737-4870 + 5888-5896: the floe-size distribution (nxs_fsd_kernels.inl, nxs_dyn_fsd_*)
 //   k_regrid_collect / _redistribute / _pack_nodes / _unpack_nodes   FE.cpp:2120-2151, 2196-2258, 3174-3198, 3280-3293: interpFields around the two interpolations (nxs_dyn_regrid)
 //   k_regrid_collect_tiled / _redistribute_tiled   the same for rows wider than 31 columns, in column tiles through LDS; k_regrid_remake_thermo   FE.cpp:566-571, 3012-3015 (nxs_dyn_regrid_carry_thermo)
@@ -59,6 +60,7 @@
 #include "nxs_slab_kernels.inl"
 #include "nxs_slab_fsd_kernels.inl"
 #include "nxs_thermo_forcing_kernels.inl"
+#include "nxs_nesting_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -219,6 +221,17 @@ struct ThermoForcing {     // nxs_dyn_thermo_forcing_*: both snapshots of thermo
     double *tf_gx = nullptr, *tf_gy = nullptr, *tf_data = nullptr;   // the last ingest's pixel centres and data (they grow: tf_reserve)
     size_t tf_gx_cap = 0, tf_gy_cap = 0, tf_data_cap = 0;
 };
+struct Nesting {           // nxs_dyn_nesting_*: both snapshots of a nesting interval, made when first given
+    std::vector<void *> nest_allocs;
+    double *nest_el[2][NEST_EL_ROWS] = {};   // [snapshot][NXS_NEST_*] [Ne] each
+    double *nest_nd[2][NEST_ND_ROWS] = {};   // [snapshot][NXS_NEST_DIST_NODES ..] [Nn] each
+    unsigned nest_el_have[2] = {0, 0}, nest_nd_have[2] = {0, 0};   // bit k: row k of that snapshot was given on this mesh
+};
+struct Diffusion {         // nxs_dyn_diffuse: the element-to-element table and the packed OLD copy, made by the first call on this mesh
+    std::vector<void *> diff_allocs;
+    int *d_diff_ec = nullptr;              // [Ne][3] bamgmesh->ElementConnectivity, 0-based, -1 on the boundary
+    double *d_diff_old = nullptr;          // [Ne] pairs {sst, sss}
+};
 struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stress / nxs_dyn_put_coupled) and the floe-size distribution's (nxs_dyn_fsd_*)
     std::vector<void *> coupled_allocs;
     // ATTACHED is what h->dw says (tau_wi, cum_damage, conc_fsd non-NULL) and fsd_mech / fsd_cumw non-NULL; a detached buffer is kept for the next attach (no hipFree
@@ -230,7 +243,7 @@ struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stres
     size_t mech_capacity = 0;
 };
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, CoupledBuffers {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, Nesting, Diffusion, CoupledBuffers {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -330,6 +343,14 @@ struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, Pa
                           // (the large patches of k_substep_resident_big: one workgroup per CU, nothing else fills its wait), 0 never, 1 wherever built
     bool res_ovl = false; // what the tables of the resident loop were built for
     size_t res_lds = 0;
+    // nesting (nxs_dyn_nesting_*) and the slab ocean's diffusion (nxs_dyn_diffuse): the configurations and the datasets' time are the handle's and survive set_mesh;
+    // the snapshots and the table are Nesting / Diffusion
+    nxs_dyn_nesting_config nest_cfg{};
+    bool nest_configured = false, nest_timed = false;
+    double nest_q = 0., nest_qvt = 0.;             // (double)time_step / nudge_timescale, dtime_step / nudge_timescale: formed once (nxs_dyn_nesting_configure)
+    NestTime nest_time[NEST_DATASETS] = {};        // nxs_dyn_nesting_time
+    bool diff_configured = false, diff_on[2] = {false, false};   // [0] sst, [1] sss
+    double diff_factor[2] = {0., 0.};              // diffusivity * dtime_step / std::pow(dx, 2.)
     // the Moorings time means (nxs_dyn_means_*): the configuration is the handle's and survives set_mesh; the buffers are in the state pool (StateArrays)
     std::vector<int> means_ids[2];                 // [0] elemental, [1] nodal: NXS_MEANS_* in column order
     std::vector<unsigned char> means_mask[2];      // Variable::mask per column
@@ -630,6 +651,8 @@ void release_halo(nxs_dyn_handle *h) {
 }
 void release_forcing_pair(nxs_dyn_handle *h) { release_group<ForcingPair>(h, h->forcing_allocs); }
 void release_thermo_forcing(nxs_dyn_handle *h) { release_group<ThermoForcing>(h, h->tf_allocs); }
+void release_nesting(nxs_dyn_handle *h) { release_group<Nesting>(h, h->nest_allocs); }
+void release_diffusion(nxs_dyn_handle *h) { release_group<Diffusion>(h, h->diff_allocs); }
 // the coupled build's buffers; their attachments are members of h->dw
 void release_coupled(nxs_dyn_handle *h) {
     release_group<CoupledBuffers>(h, h->coupled_allocs);
@@ -659,6 +682,8 @@ void release_mesh(nxs_dyn_handle *h) {
     release_ring(h);
     release_forcing_pair(h);
     release_thermo_forcing(h);
+    release_nesting(h);
+    release_diffusion(h);
     release_coupled(h);
     h->no_big_cut = false;
     h->rank = 0; h->nranks = 1;   // (the partition is the mesh's: a single rank until nxs_dyn_set_halo says otherwise)
@@ -3607,6 +3632,8 @@ int nxs_dyn_get_branch_trace(nxs_dyn_handle *h, uint64_t *out, int64_t num_words
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_get_branch_trace"); }
 
+static int diffusion_ensure(nxs_dyn_handle *h);   // nxs_nesting.inl
+
 // debug / test door: copy a named work array to the host (n doubles)
 int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_t n) try {
     if (!h || !name || !out) return NXS_ERR_INVALID;
@@ -3661,6 +3688,15 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
         HIPCHK(h, hipMemcpyAsync(&v, h->dw.shape_range, sizeof v, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         out[0] = (double)v;
+        return NXS_OK;
+    }
+    if (!std::strcmp(name, "diffuse_table")) {   // [3 Ne] the element-to-element table of nxs_dyn_diffuse as doubles (0-based, -1 on the boundary); built if it is not there yet
+        if (n != 3 * Ne) return fail(h, NXS_ERR_INVALID, "debug_array diffuse_table has %lld entries, caller asked %lld", (long long)(3 * Ne), (long long)n);
+        if (int rc = diffusion_ensure(h)) return rc;
+        std::vector<int> v(3 * (size_t)Ne);
+        HIPCHK(h, hipMemcpyAsync(v.data(), h->d_diff_ec, v.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < v.size(); ++i) out[i] = (double)v[i];
         return NXS_OK;
     }
     if (!std::strcmp(name, "slab_branches")) {   // [Ne] the NXS_SLAB_BR_* word of every element from the last nxs_dyn_slab, as doubles
@@ -3994,5 +4030,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_slab.inl"
 #include "nxs_slab_fsd.inl"
 #include "nxs_thermo_forcing.inl"
+#include "nxs_nesting.inl"
 
 }  // extern "C"

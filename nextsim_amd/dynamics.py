@@ -107,6 +107,16 @@ def load_library():
     L.nxs_dyn_thermo_forcing_targets.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p]
     L.nxs_dyn_thermo_forcing_ingest.argtypes = [H, C.c_int32, P(_abi.ForcingGrid), _abi.c_double_p, C.c_int32, _abi.c_int32_p, _abi.c_int32_p]
     L.nxs_dyn_thermo_forcing_get.argtypes = [H, C.c_int32, P(_abi.ThermoForcingRows)]
+    L.nxs_nesting_config_check.argtypes = [P(_abi.NestingConfig)]
+    L.nxs_dyn_nesting_configure.argtypes = [H, P(_abi.NestingConfig)]
+    L.nxs_dyn_nesting_pair.argtypes = [H, P(_abi.NestingRows), P(_abi.NestingRows)]
+    L.nxs_dyn_nesting_time.argtypes = [H, P(_abi.NestingTime)]
+    L.nxs_dyn_nesting_ice.argtypes = [H]
+    L.nxs_dyn_nesting_dynamics.argtypes = [H]
+    L.nxs_dyn_nesting_get.argtypes = [H, C.c_int32, P(_abi.NestingRows)]
+    L.nxs_dyn_diffusion_configure.argtypes = [H, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.nxs_dyn_diffuse.argtypes = [H]
+    L.nxs_dyn_flux_device_rows.argtypes = [H, P(C.c_void_p)]
     L.nxs_slab_default_config.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_config_check.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_constants.argtypes = [P(C.c_double), C.c_int32]
@@ -189,6 +199,8 @@ EXPORTS = (
     "nxs_col_default_config", "nxs_col_config_check", "nxs_col_constants", "nxs_dyn_column_configure", "nxs_dyn_column_set_forcing", "nxs_dyn_column_put",
     "nxs_dyn_column_get_state", "nxs_dyn_column", "nxs_dyn_column_get",
     "nxs_dyn_thermo_forcing_pair", "nxs_dyn_thermo_forcing_time", "nxs_dyn_thermo_forcing_targets", "nxs_dyn_thermo_forcing_ingest", "nxs_dyn_thermo_forcing_get",
+    "nxs_nesting_config_check", "nxs_dyn_nesting_configure", "nxs_dyn_nesting_pair", "nxs_dyn_nesting_time", "nxs_dyn_nesting_ice", "nxs_dyn_nesting_dynamics",
+    "nxs_dyn_nesting_get", "nxs_dyn_diffusion_configure", "nxs_dyn_diffuse", "nxs_dyn_flux_device_rows",
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_to_grid_conservative", "nxs_dyn_means_reset",
@@ -388,6 +400,22 @@ def slab_config_check(**options) -> int:
     """What slab_configure would answer for the defaults changed by `options` (nxs_slab_config_check, host only): 0 or NXS_ERR_INVALID."""
     c = _slab_config(options)
     return load_library().nxs_slab_config_check(C.byref(c))
+
+
+def _nesting_config(nudge_function="linear", nudge_timescale=86400., nudge_scale=1., nest_dynamic_vars=False, time_step=0, dtime_step=None) -> "_abi.NestingConfig":
+    c = _abi.NestingConfig()
+    c.nudge_function = _abi.NUDGE_FUNCTIONS[nudge_function] if isinstance(nudge_function, str) else int(nudge_function)
+    c.nest_dynamic_vars, c.time_step = int(bool(nest_dynamic_vars)), int(time_step)
+    c.nudge_timescale, c.nudge_scale = float(nudge_timescale), float(nudge_scale)
+    c.dtime_step = float(time_step if dtime_step is None else dtime_step)
+    return c
+
+
+def nesting_config_check(**options):
+    """What nesting_configure would answer for `options` (nxs_nesting_config_check, host only): (0 or NXS_ERR_INVALID, the message)."""
+    L = load_library()
+    rc = L.nxs_nesting_config_check(C.byref(_nesting_config(**options)))
+    return rc, (L.nxs_dyn_last_error(None) or b"").decode() if rc else ""
 
 
 def slab_coupled_config_check(coupled_melt_type: int, attached_bins: int, **options) -> int:
@@ -1037,6 +1065,85 @@ class FiniteElementDynamics:
         self._chk(self.L.nxs_dyn_thermo_forcing_get(self.h, int(which), C.byref(r)))
         return out
 
+    # ---- nesting: nestingIce / nestingDynamics on the device (FE.cpp:4878-4958), both snapshots of a nesting interval resident ----
+    def nesting_configure(self, **options):
+        """nxs_dyn_nesting_configure: nudge_function ("linear" | "exponential"), nudge_timescale (s), nudge_scale (= M_nudge_lengthscale * M_res_root_mesh),
+        nest_dynamic_vars, time_step (the model's int) and dtime_step (its double; time_step by default).  Survives set_mesh."""
+        self._chk(self.L.nxs_dyn_nesting_configure(self.h, C.byref(_nesting_config(**options))))
+
+    def _nesting_rows(self, rows):
+        r, keep = _abi.NestingRows(), []
+        for k, v in (rows or {}).items():
+            if k not in _abi.NEST_ELEMENT_ROWS + _abi.NEST_NODE_ROWS:
+                raise KeyError(f"nxs_dyn_nesting_rows has no row {k!r}")
+            if v is None:
+                continue
+            nodal = k in _abi.NEST_NODE_ROWS
+            n = self.lm.num_nodes if nodal else self.lm.num_elements
+            a = np.ascontiguousarray(v, np.float64)
+            if a.shape != (n,):
+                raise ValueError(f"{k} has shape {a.shape}, expected ({n},)")
+            if nodal:
+                r.node[_abi.NEST_NODE_ROWS.index(k)] = _abi.dptr(a)
+            else:
+                r.element[_abi.NEST_ELEMENT_ROWS.index(k)] = _abi.dptr(a)
+            keep.append(a)
+        return r, keep
+
+    def nesting_pair(self, snapshot0: dict, snapshot1: dict = None):
+        """nxs_dyn_nesting_pair: {row name of _abi.NEST_ELEMENT_ROWS ([Ne]) or _abi.NEST_NODE_ROWS ([Nn])} of snapshot 0 and (optionally) 1; a row left out or None
+        is not given.  The rows go with the mesh."""
+        r0, keep0 = self._nesting_rows(snapshot0)
+        r1, keep1 = self._nesting_rows(snapshot1)
+        self._chk(self.L.nxs_dyn_nesting_pair(self.h, C.byref(r0), C.byref(r1) if snapshot1 is not None else None))
+        del keep0, keep1
+
+    def nesting_time(self, datasets: dict):
+        """nxs_dyn_nesting_time: {dataset name of _abi.NEST_DATASETS: dict(mode="linear" | "step" | "off" or NXS_TF_*, fcoeff0=, fcoeff1=, factor=1, bias=0)}; a dataset
+        left out is OFF.  No launch: nesting_ice / nesting_dynamics evaluate the targets."""
+        t = _abi.NestingTime()
+        for k in range(_abi.NXS_NEST_DATASETS):
+            t.factor[k] = 1.
+        for name, spec in datasets.items():
+            if name not in _abi.NEST_DATASETS:
+                raise KeyError(f"nxs_dyn_nesting_time has no dataset {name!r}")
+            k = _abi.NEST_DATASETS.index(name)
+            mode = spec.get("mode", "linear")
+            t.mode[k] = _abi.TF_MODES[mode] if isinstance(mode, str) else int(mode)
+            t.fcoeff0[k], t.fcoeff1[k] = float(spec.get("fcoeff0", 1.)), float(spec.get("fcoeff1", 0.))
+            t.factor[k], t.bias[k] = float(spec.get("factor", 1.)), float(spec.get("bias", 0.))
+        self._chk(self.L.nxs_dyn_nesting_time(self.h, C.byref(t)))
+
+    def nesting_ice(self):
+        """nxs_dyn_nesting_ice: one launch; M_conc, M_thick, M_snow_thick (and the young-ice trio) relaxed towards the outer model.  Asynchronous."""
+        self._chk(self.L.nxs_dyn_nesting_ice(self.h))
+
+    def nesting_dynamics(self):
+        """nxs_dyn_nesting_dynamics: one launch; M_sigma, M_damage, M_ridge_ratio and M_VT, where they are current on the device.  Asynchronous."""
+        self._chk(self.L.nxs_dyn_nesting_dynamics(self.h))
+
+    def nesting_get(self, which: int, names=_abi.NEST_ELEMENT_ROWS + _abi.NEST_NODE_ROWS) -> dict:
+        """nxs_dyn_nesting_get: the named rows of snapshot 0 / 1."""
+        out = {k: np.empty(self.lm.num_nodes if k in _abi.NEST_NODE_ROWS else self.lm.num_elements) for k in names}
+        r, _ = self._nesting_rows(out)
+        self._chk(self.L.nxs_dyn_nesting_get(self.h, int(which), C.byref(r)))
+        return out
+
+    # ---- the slab ocean's horizontal diffusion: diffuse() for M_sst and M_sss (FE.cpp:2760-2815) ----
+    def diffusion_configure(self, diffusivity_sst: float, diffusivity_sss: float, dx: float, dtime_step: float):
+        """nxs_dyn_diffusion_configure: a diffusivity <= 0 switches that field off.  Survives set_mesh."""
+        self._chk(self.L.nxs_dyn_diffusion_configure(self.h, float(diffusivity_sst), float(diffusivity_sss), float(dx), float(dtime_step)))
+
+    def diffuse(self):
+        """nxs_dyn_diffuse: one Jacobi step on the sst / sss rows of flux_put, in place; call it right before step().  Asynchronous."""
+        self._chk(self.L.nxs_dyn_diffuse(self.h))
+
+    def flux_device_rows(self) -> dict:
+        """nxs_dyn_flux_device_rows: {row name of _abi.FLUX_STATE: device address, 0 for a row never put on this mesh}."""
+        dev = (C.c_void_p * len(_abi.FLUX_STATE))()
+        self._chk(self.L.nxs_dyn_flux_device_rows(self.h, dev))
+        return dict(zip(_abi.FLUX_STATE, (int(p or 0) for p in dev)))
+
     # ---- thermo()'s slab loop from new ice to tracers: sections 6 to 10 (FE.cpp:5413-6133) ----
     def slab_configure(self, **options):
         """nxs_dyn_slab_configure: the defaults of slab_default_config() changed by keywords named after nxs_dyn_slab_config's members.  Survives set_mesh."""
@@ -1332,7 +1439,7 @@ class FiniteElementDynamics:
         n = {"rlmass": Nn, "node_mass": Nn, "C_bu": Nn, "grad_ssh": 2 * Nn, "fcor": Nn, "VTM": 2 * Nn,
              "shape": 6 * Ne, "emass": Ne, "ecbu": Ne, "force": 6 * Ne, "volume": Ne, "expC": Ne,
              "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn, "drag_ui": Ne, "drag_ui_young": Ne, "slab_branches": Ne, "slab_fsd_branches": Ne,
-             "means_update_ms": 2, "slab_coupled_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3}[name]
+             "means_update_ms": 2, "slab_coupled_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3, "diffuse_table": 3 * Ne}[name]
         out = np.empty(n)
         self._chk(self.L.nxs_dyn_debug_array(self.h, name.encode(), _abi.dptr(out), n))
         return out
