@@ -1005,6 +1005,92 @@ NXS_API int nxs_dyn_thermo_forcing_ingest(nxs_dyn_handle *h, int32_t set, const 
                                           const int32_t *snapshot);
 NXS_API int nxs_dyn_thermo_forcing_get(nxs_dyn_handle *h, int32_t which, const nxs_dyn_thermo_forcing_rows *out);
 
+/* ---- The dynamics' nodal forcing on the device: both snapshots of M_wind, M_ocean and M_ssh made FROM THE SOURCE GRID without the host's transformData,
+ * wrap and InterpFromGridToMeshx (ExternalData::loadDataset, model/externaldata.cpp:461-940), and a time blend with coefficients per dataset.  Everything here
+ * is additive: a handle that never calls these entry points allocates and launches nothing new, and nxs_dyn_set_forcing / _pair / _time keep their bits.
+ *
+ * THE PROJECTION.  nxs_mapx_polar holds the derived constants forward_mapx reads for a north-aspect "Polar Stereographic Ellipsoid" map;
+ * nxs_mapx_polar_north (host only) forms them from what an .mpp file holds -- init_polar_stereographic_ellipsoid (contrib/mapx/src/polar_stereographic.c:89-134)
+ * and the tail of reinit_mapx (contrib/mapx/src/mapx.c:1011-1064: the rotation matrix, x0 / y0 from the centre, u0 / v0), operand for operand; lat1 == 999 means
+ * lat0, as there; false easting / northing and maximum_error are 0, as new_mapx leaves them for such a file.  NXS_ERR_INVALID: out NULL, lat0 != 90.
+ * nxs_mapx_forward runs forward_mapx on n points: device >= 0 on that device (one launch, arrays copied there and back), device < 0 the same source on the host.
+ * NXS_ERR_INVALID: a NULL argument, n < 0.  nxs_mapx_constants is a TEST DOOR like nxs_dyn_physical_constants: mapx_Re_km and PI of contrib/mapx/include/mapx.h
+ * as compiled into the kernels, in the order NXS_MAPX_CONST_*.
+ *
+ * THE INGEST.  nxs_dyn_forcing_targets gives the [Nn] node positions in the coordinates of dataset `set` (convertTargetXY's output: the projection of the targets
+ * stays the host's); resident until the mesh changes.  nxs_dyn_forcing_ingest takes the data of one InterpFromGridToMeshx call, [M][N][N_data] (or [N][M][N_data]
+ * with row_major), UNTRANSFORMED AND WITHOUT THE WRAP, uploads them and runs on the device, in the reference's order:
+ *   transformData (externaldata.cpp:944-1288) for the column pairs `vectors` names: the east/north branch (:1155-1204) where east_west_oriented, the mean over the
+ *     row beside a row at 90N (:1206-1243; y[0] == 90. or y[M-1] == 90. of the pixel centres, the last wins), the rotation by cos / sin(-rotation_angle) as the
+ *     host computed them (:1246-1261) where `rotate`.  A pair is two COLUMNS of data (variable j of snapshot fstep is column fstep*nb_var + j in loadDataset's
+ *     call), so two snapshots of one vector are two pairs.  vectors == NULL: no transform.
+ *   interpolateDataset's wrap (:1315-1373): cyclic_x appends column N = column 0 and x[N-1] + (x[N-1] - x[N-2]) to the centres, cyclic_y the same with a row; the
+ *     corner cell when both are set holds 0., as the reference's zero-initialised vector does.
+ *   InterpFromGridToMeshx at the nodes (:1436): the arithmetic of nxs_interp_grid_to_mesh, the same bits.  Column j goes to snapshot snapshot[j] (0 or 1) of row
+ *     row[j] (NXS_NF_*); row[j] = -1 skips the column.  The rows ARE the snapshots nxs_dyn_set_forcing_pair owns (V at offset Nn of the [2*Nn] vector), made here
+ *     when the pair was never given; the two routes mix per half-row, and nxs_dyn_set_forcing_time / _time_rows see a pair once all ten half-rows have been given on
+ *     this mesh by either route.
+ *   The host arrays are free on return; the launches are asynchronous.  NXS_ERR_INVALID: a NULL argument (vectors may be NULL), a set out of range, M or N < 2,
+ *   N_data outside 1 .. NXS_NF_MAX_COLUMNS, axes that are neither centres nor contours, an unknown interpolation, a row outside -1 .. NXS_NF_ROWS - 1, a snapshot
+ *   other than 0 / 1, two columns for one snapshot of one row, contours or row_major data with a cyclic axis; with vectors: n_pairs outside 0 .. NXS_NF_MAX_VECTORS, a pair naming a
+ *   column out of range, skipped or named twice, row_major != 0, lat / lon NULL while a pair is east_west_oriented, is_wav_dir (the wave-direction branch) or
+ *   gridded_rotation_angle without `rotate` (the OASIS branch) -- neither is built.  NXS_ERR_STATE: before nxs_dyn_set_mesh, before nxs_dyn_forcing_targets of that
+ *   set on this mesh.
+ * nxs_dyn_set_forcing_time_rows is nxs_dyn_set_forcing_time with its own mode (NXS_TF_OFF / _LINEAR / _STEP), coefficients, M_factor and M_bias_correction per group
+ * {wind, ocean, ssh} (the reference's atmosphere and ocean are different datasets with different ftime_ranges): LINEAR writes factor*(fcoeff0*d0 + fcoeff1*d1) + bias
+ * -- nxs_dyn_set_forcing_time's expression, the same bits --, STEP factor*d0 + bias without reading d1, OFF leaves the vector alone.  One asynchronous launch.
+ * NXS_ERR_INVALID: h or t NULL, an unknown mode.  NXS_ERR_STATE: before nxs_dyn_set_mesh, a LINEAR group without both snapshots, a STEP group without snapshot 0.
+ * The step's forcing counts as given once wind, ocean and ssh have been written this way (or by the older calls) AND the element depth is there.
+ * nxs_dyn_set_element_depth uploads the constant [Ne] row alone, so a host on this route never needs nxs_dyn_set_forcing_pair.
+ * nxs_dyn_forcing_get (tests, a restart writer) returns the named half-rows of snapshot `which` (0 / 1), [Nn] each; NULL rows are skipped, a missing row that is
+ * asked for is NXS_ERR_STATE.  nxs_dyn_debug_array "nf_grid" returns the last ingest's grid data after transform and wrap, [cM][cN][N_data].
+ * MEMORY: the snapshots stay nxs_dyn_set_forcing_pair's (10 * 8 B * Nn); the targets (2 * 8 B * Nn per set) and the uploaded grid are a pool of their own that
+ * goes with the mesh: nxs_dyn_set_mesh and nxs_dyn_regrid drop it. */
+typedef struct nxs_mapx_polar {
+    double lon0, Rg, m1, t1, eccentricity, scale, lat1;
+    double T00, T01, T10, T11, u0, v0, false_easting, false_northing;
+} nxs_mapx_polar;
+enum { NXS_MAPX_CONST_RE_KM = 0, NXS_MAPX_CONST_PI, NXS_MAPX_CONST_COUNT };
+NXS_API int nxs_mapx_constants(double *out, int32_t count);
+NXS_API int nxs_mapx_polar_north(double lat0, double lon0, double lat1, double rotation, double scale, double center_lat, double center_lon, double equatorial_radius,
+                                 double eccentricity, nxs_mapx_polar *out);
+NXS_API int nxs_mapx_forward(const nxs_mapx_polar *map, int64_t n, const double *lat, const double *lon, double *x, double *y, int32_t device);
+
+enum { NXS_NF_WIND_U = 0, NXS_NF_WIND_V, NXS_NF_OCEAN_U, NXS_NF_OCEAN_V, NXS_NF_SSH };
+#define NXS_NF_ROWS 5
+#define NXS_NF_SETS 4
+#define NXS_NF_MAX_COLUMNS 32
+#define NXS_NF_MAX_VECTORS 4
+enum { NXS_NF_GROUP_WIND = 0, NXS_NF_GROUP_OCEAN, NXS_NF_GROUP_SSH };
+#define NXS_NF_GROUPS 3
+typedef struct nxs_dyn_forcing_vectors {   /* dataset->vectorial_variables and what transformData reads beside them */
+    int32_t n_pairs;
+    int32_t component0[NXS_NF_MAX_VECTORS], component1[NXS_NF_MAX_VECTORS];   /* the two columns of data of each pair */
+    int32_t east_west_oriented[NXS_NF_MAX_VECTORS];
+    int32_t is_wav_dir[NXS_NF_MAX_VECTORS];                                   /* wavDirOptions.isWavDir: not built */
+    int32_t gridded_rotation_angle;                                           /* grid.gridded_rotation_angle (#ifdef OASIS): not built */
+    int32_t latlon_per_point;              /* 0: lat[M], lon[N] (a regular lat-lon grid); else lat[M*N], lon[M*N] */
+    int32_t rotate;                        /* dataset->rotation_angle != 0. */
+    const double *lat, *lon;               /* degrees; may be NULL when no pair is east_west_oriented */
+    nxs_mapx_polar map;                    /* the model's projection (Environment::nextsimMppfile) */
+    double cos_m_diff_angle, sin_m_diff_angle;   /* std::cos(-rotation_angle), std::sin(-rotation_angle) */
+} nxs_dyn_forcing_vectors;
+typedef struct nxs_dyn_forcing_rows { double *row[NXS_NF_ROWS]; } nxs_dyn_forcing_rows;   /* [Nn] each, indexed by NXS_NF_* */
+/* (a struct TAG only, as nxs_dyn_thermo_forcing_time) */
+struct nxs_dyn_forcing_time_rows {
+    int32_t mode[NXS_NF_GROUPS];           /* NXS_TF_OFF / _LINEAR / _STEP per NXS_NF_GROUP_* */
+    double fcoeff0[NXS_NF_GROUPS];         /* |t - ftime_range[1]| / fdt of the group's dataset (LINEAR) */
+    double fcoeff1[NXS_NF_GROUPS];         /* |t - ftime_range[0]| / fdt */
+    double factor[NXS_NF_GROUPS];          /* M_factor */
+    double bias[NXS_NF_GROUPS];            /* M_bias_correction */
+};
+NXS_API int nxs_dyn_forcing_targets(nxs_dyn_handle *h, int32_t set, const double *RX, const double *RY);
+NXS_API int nxs_dyn_forcing_ingest(nxs_dyn_handle *h, int32_t set, const nxs_dyn_forcing_grid *g, int32_t cyclic_x, int32_t cyclic_y, const double *data, int32_t N_data,
+                                   const int32_t *row, const int32_t *snapshot, const nxs_dyn_forcing_vectors *vectors /* may be NULL */);
+NXS_API int nxs_dyn_set_forcing_time_rows(nxs_dyn_handle *h, const struct nxs_dyn_forcing_time_rows *t);
+NXS_API int nxs_dyn_set_element_depth(nxs_dyn_handle *h, const double *depth);
+NXS_API int nxs_dyn_forcing_get(nxs_dyn_handle *h, int32_t which, const nxs_dyn_forcing_rows *out);
+
 /* ---- Nesting on the device: nestingIce() (FE.cpp:4878-4908) and nestingDynamics() (FE.cpp:4915-4958), the two statements FiniteElement::step() runs between
  * thermo() and the dynamics under nesting.use_nesting (FE.cpp:8172-8192).  Per entry x += (fNudge*(time_step/nudge_time)*(target - x)), with target =
  * ExternalData::get of the nesting dataset (externaldata.cpp:366-438, the semantics of nxs_dyn_thermo_forcing_time) evaluated in the same kernel from both resident

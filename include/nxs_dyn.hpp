@@ -32,6 +32,16 @@ public:
     void setForcingTime(double fcoeff0, double fcoeff1, const double *factor = nullptr, const double *bias = nullptr) {
         check(nxs_dyn_set_forcing_time(h_, fcoeff0, fcoeff1, factor, bias), "set_forcing_time");
     }
+    // the same snapshots made on the device from a dataset's source grid: transformData, the cyclic wrap, InterpFromGridToMeshx at the nodes (externaldata.cpp:461-940);
+    // the time blend with coefficients per dataset; M_element_depth alone
+    void forcingTargets(int set, const double *RX, const double *RY) { check(nxs_dyn_forcing_targets(h_, set, RX, RY), "forcing_targets"); }
+    void forcingIngest(int set, const nxs_dyn_forcing_grid &g, bool cyclic_x, bool cyclic_y, const double *data, int N_data, const int32_t *row, const int32_t *snapshot,
+                       const nxs_dyn_forcing_vectors *vectors = nullptr) {
+        check(nxs_dyn_forcing_ingest(h_, set, &g, cyclic_x ? 1 : 0, cyclic_y ? 1 : 0, data, N_data, row, snapshot, vectors), "forcing_ingest");
+    }
+    void setForcingTimeRows(const struct nxs_dyn_forcing_time_rows &t) { check(nxs_dyn_set_forcing_time_rows(h_, &t), "set_forcing_time_rows"); }
+    void setElementDepth(const double *depth) { check(nxs_dyn_set_element_depth(h_, depth), "set_element_depth"); }
+    void forcingGet(int which, const nxs_dyn_forcing_rows &out) { check(nxs_dyn_forcing_get(h_, which, &out), "forcing_get"); }
     void setOption(const char *key, long long value) { check(nxs_dyn_set_option(h_, key, value), "set_option"); }
     void getDiag(nxs_dyn_diag &d) { check(nxs_dyn_get_diag(h_, &d), "get_diag"); }
     // the coupled build's terms (#ifdef OASIS): M_tau_wi into explicitSolve(), M_cum_damage / M_conc_fsd through the sub-steps and update()

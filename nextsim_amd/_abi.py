@@ -311,6 +311,31 @@ class ForcingGrid(C.Structure):   # nxs_dyn_forcing_grid
     _fields_ = [("x_in", c_double_p), ("y_in", c_double_p)] + [(k, C.c_int32) for k in ("x_rows", "y_rows", "M", "N", "interp", "row_major")] + [("default_value", C.c_double)]
 
 
+# ---- the dynamics' nodal forcing on the device (include/nxs_dyn.h, nxs_mapx_* / nxs_dyn_forcing_*)
+NF_ROWS = ("wind_u", "wind_v", "ocean_u", "ocean_v", "ssh")   # NXS_NF_*
+NF_GROUPS = ("wind", "ocean", "ssh")                          # NXS_NF_GROUP_*
+NXS_NF_ROWS, NXS_NF_SETS, NXS_NF_MAX_COLUMNS, NXS_NF_MAX_VECTORS, NXS_NF_GROUPS = 5, 4, 32, 4, 3
+MAPX_POLAR_FIELDS = ("lon0", "Rg", "m1", "t1", "eccentricity", "scale", "lat1", "T00", "T01", "T10", "T11", "u0", "v0", "false_easting", "false_northing")
+
+
+class MapxPolar(C.Structure):   # nxs_mapx_polar
+    _fields_ = [(k, C.c_double) for k in MAPX_POLAR_FIELDS]
+
+
+class ForcingVectors(C.Structure):   # nxs_dyn_forcing_vectors
+    _fields_ = ([("n_pairs", C.c_int32)] + [(k, C.c_int32 * NXS_NF_MAX_VECTORS) for k in ("component0", "component1", "east_west_oriented", "is_wav_dir")]
+                + [(k, C.c_int32) for k in ("gridded_rotation_angle", "latlon_per_point", "rotate")] + [("lat", c_double_p), ("lon", c_double_p), ("map", MapxPolar),
+                                                                                                        ("cos_m_diff_angle", C.c_double), ("sin_m_diff_angle", C.c_double)])
+
+
+class ForcingRows(C.Structure):   # nxs_dyn_forcing_rows
+    _fields_ = [("row", c_double_p * NXS_NF_ROWS)]
+
+
+class ForcingTimeRows(C.Structure):   # struct nxs_dyn_forcing_time_rows
+    _fields_ = [("mode", C.c_int32 * NXS_NF_GROUPS)] + [(k, C.c_double * NXS_NF_GROUPS) for k in ("fcoeff0", "fcoeff1", "factor", "bias")]
+
+
 # ---- nesting and the slab ocean's diffusion on the device (include/nxs_dyn.h, nxs_dyn_nesting_* / nxs_dyn_diffuse)
 NEST_ELEMENT_ROWS = ("dist", "thick", "conc", "snow_thick", "h_young", "conc_young", "hs_young", "sigma1", "sigma2", "sigma3", "damage", "ridge_ratio")   # NXS_NEST_*
 NEST_NODE_ROWS = ("dist_nodes", "VT1", "VT2")

@@ -61,6 +61,7 @@
 #include "nxs_slab_fsd_kernels.inl"
 #include "nxs_thermo_forcing_kernels.inl"
 #include "nxs_nesting_kernels.inl"
+#include "nxs_nodal_forcing_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -149,6 +150,8 @@ struct StateArrays : FluxRows, ColumnRows, SlabRows {   // the prognostic and wo
     DevState ds{};
     DevWork dw{};                          // (tau_wi, tau_sum, cum_damage, conc_fsd: attachments of CoupledBuffers; trace: option "trace_branches")
     bool have_state = false, have_forcing = false;
+    bool have_depth = false;               // M_element_depth was given on this mesh (set_forcing, set_forcing_pair, set_element_depth)
+    unsigned live_forcing = 0;             // bit NXS_NF_GROUP_*: nxs_dyn_set_forcing_time_rows has written that vector on this mesh
     int sig_loc = 0;                       // where M_sigma / M_damage are current: 0 = the state arrays, 1 = the records in S4a (left there by
                                            // the fused sub-step loop; k_update works on them, the arrays follow on demand: ensure_arrays)
     int trace_branches = 0;                // option "trace_branches": the per-loop kernels keep the branch trace of updateSigmaDamage (dw.trace: gone with the pool, so off again)
@@ -211,6 +214,7 @@ struct ForcingPair {       // nxs_dyn_set_forcing_pair's snapshots
     std::vector<void *> forcing_allocs;
     double *f_snap[6] = {};                // wind0, wind1, ocean0, ocean1, ssh0, ssh1
     bool have_pair = false;
+    unsigned f_have = 0;                   // bit s*NXS_NF_ROWS + NXS_NF_*: that half-row of snapshot s was given on this mesh (set_forcing_pair: all; nxs_dyn_forcing_ingest)
 };
 struct ThermoForcing {     // nxs_dyn_thermo_forcing_*: both snapshots of thermo()'s ten element forcing rows, the datasets' targets, the uploaded source grid
     std::vector<void *> tf_allocs;
@@ -220,6 +224,14 @@ struct ThermoForcing {     // nxs_dyn_thermo_forcing_*: both snapshots of thermo
     unsigned tf_targets_have = 0;
     double *tf_gx = nullptr, *tf_gy = nullptr, *tf_data = nullptr;   // the last ingest's pixel centres and data (they grow: tf_reserve)
     size_t tf_gx_cap = 0, tf_gy_cap = 0, tf_data_cap = 0;
+};
+struct NodalForcing {      // nxs_dyn_forcing_*: the datasets' node targets and the uploaded source grid (the snapshots are ForcingPair's)
+    std::vector<void *> nf_allocs;
+    double *nf_rx[NF_SETS] = {}, *nf_ry[NF_SETS] = {};   // [Nn] the nodes in each dataset's coordinates
+    unsigned nf_targets_have = 0;
+    double *nf_gx = nullptr, *nf_gy = nullptr, *nf_data = nullptr, *nf_lat = nullptr, *nf_lon = nullptr;   // the last ingest's pixel centres, data and lat / lon (they grow: nf_reserve)
+    size_t nf_gx_cap = 0, nf_gy_cap = 0, nf_data_cap = 0, nf_lat_cap = 0, nf_lon_cap = 0;
+    size_t nf_grid_cells = 0;              // doubles of nf_data the last ingest left behind (debug array "nf_grid"); 0: none
 };
 struct Nesting {           // nxs_dyn_nesting_*: both snapshots of a nesting interval, made when first given
     std::vector<void *> nest_allocs;
@@ -243,7 +255,7 @@ struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stres
     size_t mech_capacity = 0;
 };
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, Nesting, Diffusion, CoupledBuffers {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, CoupledBuffers {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -651,6 +663,7 @@ void release_halo(nxs_dyn_handle *h) {
 }
 void release_forcing_pair(nxs_dyn_handle *h) { release_group<ForcingPair>(h, h->forcing_allocs); }
 void release_thermo_forcing(nxs_dyn_handle *h) { release_group<ThermoForcing>(h, h->tf_allocs); }
+void release_nodal_forcing(nxs_dyn_handle *h) { release_group<NodalForcing>(h, h->nf_allocs); }
 void release_nesting(nxs_dyn_handle *h) { release_group<Nesting>(h, h->nest_allocs); }
 void release_diffusion(nxs_dyn_handle *h) { release_group<Diffusion>(h, h->diff_allocs); }
 // the coupled build's buffers; their attachments are members of h->dw
@@ -682,6 +695,7 @@ void release_mesh(nxs_dyn_handle *h) {
     release_ring(h);
     release_forcing_pair(h);
     release_thermo_forcing(h);
+    release_nodal_forcing(h);
     release_nesting(h);
     release_diffusion(h);
     release_coupled(h);
@@ -2945,6 +2959,7 @@ int nxs_dyn_set_forcing(nxs_dyn_handle *h, const nxs_dyn_forcing *f) try {
     HIPCHK(h, hipMemcpyAsync(h->ds.depth, f->element_depth, Ne * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_forcing = true;
+    h->have_depth = true;
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_set_forcing"); }
 
@@ -2962,6 +2977,8 @@ int nxs_dyn_set_forcing_pair(nxs_dyn_handle *h, const nxs_dyn_forcing *f0, const
     HIPCHK(h, hipMemcpyAsync(h->ds.depth, f0->element_depth, Ne * sizeof(double), hipMemcpyHostToDevice, h->stream));  // a "constant" dataset
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_pair = true;
+    h->f_have = (1u << (2 * NF_ROWS)) - 1u;
+    h->have_depth = true;
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_set_forcing_pair"); }
 
@@ -3699,6 +3716,13 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
         for (size_t i = 0; i < v.size(); ++i) out[i] = (double)v[i];
         return NXS_OK;
     }
+    if (!std::strcmp(name, "nf_grid")) {   // [cM][cN][N_data] the grid data of the last nxs_dyn_forcing_ingest after transformData and the wrap
+        if (!h->nf_grid_cells) return fail(h, NXS_ERR_STATE, "debug_array nf_grid: no nxs_dyn_forcing_ingest on this mesh");
+        if (n != (int64_t)h->nf_grid_cells) return fail(h, NXS_ERR_INVALID, "debug_array nf_grid has %lld entries, caller asked %lld", (long long)h->nf_grid_cells, (long long)n);
+        HIPCHK(h, hipMemcpyAsync(out, h->nf_data, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return NXS_OK;
+    }
     if (!std::strcmp(name, "slab_branches")) {   // [Ne] the NXS_SLAB_BR_* word of every element from the last nxs_dyn_slab, as doubles
         if (n != Ne) return fail(h, NXS_ERR_INVALID, "debug_array slab_branches has %lld entries, caller asked %lld", (long long)Ne, (long long)n);
         if (!h->slab_done) return fail(h, NXS_ERR_STATE, "debug_array slab_branches: no nxs_dyn_slab on this mesh");
@@ -4031,5 +4055,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_slab_fsd.inl"
 #include "nxs_thermo_forcing.inl"
 #include "nxs_nesting.inl"
+#include "nxs_nodal_forcing.inl"
 
 }  // extern "C"

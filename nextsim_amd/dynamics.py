@@ -9,6 +9,7 @@ library or GPU is an error, never a fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -107,6 +108,14 @@ def load_library():
     L.nxs_dyn_thermo_forcing_targets.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p]
     L.nxs_dyn_thermo_forcing_ingest.argtypes = [H, C.c_int32, P(_abi.ForcingGrid), _abi.c_double_p, C.c_int32, _abi.c_int32_p, _abi.c_int32_p]
     L.nxs_dyn_thermo_forcing_get.argtypes = [H, C.c_int32, P(_abi.ThermoForcingRows)]
+    L.nxs_mapx_constants.argtypes = [P(C.c_double), C.c_int32]
+    L.nxs_mapx_polar_north.argtypes = [C.c_double] * 9 + [P(_abi.MapxPolar)]
+    L.nxs_mapx_forward.argtypes = [P(_abi.MapxPolar), C.c_int64, _abi.c_double_p, _abi.c_double_p, _abi.c_double_p, _abi.c_double_p, C.c_int32]
+    L.nxs_dyn_forcing_targets.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p]
+    L.nxs_dyn_forcing_ingest.argtypes = [H, C.c_int32, P(_abi.ForcingGrid), C.c_int32, C.c_int32, _abi.c_double_p, C.c_int32, _abi.c_int32_p, _abi.c_int32_p, P(_abi.ForcingVectors)]
+    L.nxs_dyn_set_forcing_time_rows.argtypes = [H, P(_abi.ForcingTimeRows)]
+    L.nxs_dyn_set_element_depth.argtypes = [H, _abi.c_double_p]
+    L.nxs_dyn_forcing_get.argtypes = [H, C.c_int32, P(_abi.ForcingRows)]
     L.nxs_nesting_config_check.argtypes = [P(_abi.NestingConfig)]
     L.nxs_dyn_nesting_configure.argtypes = [H, P(_abi.NestingConfig)]
     L.nxs_dyn_nesting_pair.argtypes = [H, P(_abi.NestingRows), P(_abi.NestingRows)]
@@ -179,6 +188,59 @@ def load_library():
     return L
 
 
+def mapx_constants() -> dict:
+    """nxs_mapx_constants: mapx_Re_km and PI of contrib/mapx/include/mapx.h as the kernels hold them."""
+    out = (C.c_double * 2)()
+    rc = load_library().nxs_mapx_constants(out, 2)
+    if rc:
+        raise NxsError(rc, "nxs_mapx_constants")
+    return {"Re_km": out[0], "PI": out[1]}
+
+
+def mapx_polar_north(lat0=90., lon0=0., lat1=60., rotation=-45., scale=0.001, center_lat=90., center_lon=135., equatorial_radius=6378.273, eccentricity=0.081816153) -> "_abi.MapxPolar":
+    """nxs_mapx_polar_north: the constants of forward_mapx from what an .mpp file holds (the defaults are the model's own map, rotation -45)."""
+    L = load_library()
+    m = _abi.MapxPolar()
+    rc = L.nxs_mapx_polar_north(lat0, lon0, lat1, rotation, scale, center_lat, center_lon, equatorial_radius, eccentricity, C.byref(m))
+    if rc:
+        raise NxsError(rc, (L.nxs_dyn_last_error(None) or b"").decode())
+    return m
+
+
+def mapx_forward(m, lat, lon, device: int = -1):
+    """nxs_mapx_forward: forward_mapx of every (lat, lon) in degrees; device < 0 runs the same source on the host."""
+    L = load_library()
+    lat, lon = np.ascontiguousarray(lat, np.float64).ravel(), np.ascontiguousarray(lon, np.float64).ravel()
+    if lat.shape != lon.shape:
+        raise ValueError("lat and lon differ in length")
+    x, y = np.empty(lat.size), np.empty(lat.size)
+    rc = L.nxs_mapx_forward(C.byref(m), lat.size, _abi.dptr(lat), _abi.dptr(lon), _abi.dptr(x), _abi.dptr(y), int(device))
+    if rc:
+        raise NxsError(rc, (L.nxs_dyn_last_error(None) or b"").decode())
+    return x, y
+
+
+def forcing_vectors(pairs=(), lat=None, lon=None, map=None, rotation_angle=0., per_point=False, is_wav_dir=(), gridded_rotation_angle=False):
+    """nxs_dyn_forcing_vectors from pairs = [(column0, column1, east_west_oriented), ...]; cos / sin(-rotation_angle) are taken here, as transformData takes them.
+    Returns the struct and what must outlive the call."""
+    v = _abi.ForcingVectors()
+    v.n_pairs = len(pairs)
+    for k, (j0, j1, ew) in enumerate(pairs[:_abi.NXS_NF_MAX_VECTORS]):
+        v.component0[k], v.component1[k], v.east_west_oriented[k] = int(j0), int(j1), int(bool(ew))
+    for k in is_wav_dir:
+        v.is_wav_dir[k] = 1
+    v.gridded_rotation_angle, v.latlon_per_point, v.rotate = int(bool(gridded_rotation_angle)), int(bool(per_point)), int(rotation_angle != 0.)
+    keep = [None if a is None else np.ascontiguousarray(a, np.float64).ravel() for a in (lat, lon)]
+    if keep[0] is not None:
+        v.lat = _abi.dptr(keep[0])
+    if keep[1] is not None:
+        v.lon = _abi.dptr(keep[1])
+    if map is not None:
+        v.map = map
+    v.cos_m_diff_angle, v.sin_m_diff_angle = math.cos(-rotation_angle), math.sin(-rotation_angle)
+    return v, keep
+
+
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _abi.c_double_p, _abi.c_double_p)
 
 # every symbol include/nxs_dyn.h declares
@@ -199,6 +261,8 @@ EXPORTS = (
     "nxs_col_default_config", "nxs_col_config_check", "nxs_col_constants", "nxs_dyn_column_configure", "nxs_dyn_column_set_forcing", "nxs_dyn_column_put",
     "nxs_dyn_column_get_state", "nxs_dyn_column", "nxs_dyn_column_get",
     "nxs_dyn_thermo_forcing_pair", "nxs_dyn_thermo_forcing_time", "nxs_dyn_thermo_forcing_targets", "nxs_dyn_thermo_forcing_ingest", "nxs_dyn_thermo_forcing_get",
+    "nxs_mapx_constants", "nxs_mapx_polar_north", "nxs_mapx_forward", "nxs_dyn_forcing_targets", "nxs_dyn_forcing_ingest", "nxs_dyn_set_forcing_time_rows", "nxs_dyn_set_element_depth",
+    "nxs_dyn_forcing_get",
     "nxs_nesting_config_check", "nxs_dyn_nesting_configure", "nxs_dyn_nesting_pair", "nxs_dyn_nesting_time", "nxs_dyn_nesting_ice", "nxs_dyn_nesting_dynamics",
     "nxs_dyn_nesting_get", "nxs_dyn_diffusion_configure", "nxs_dyn_diffuse", "nxs_dyn_flux_device_rows",
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
@@ -1063,6 +1127,75 @@ class FiniteElementDynamics:
         out = {k: np.empty(self.lm.num_elements) for k in names}
         r, _ = self._thermo_forcing_rows(out, "nxs_dyn_thermo_forcing_rows")
         self._chk(self.L.nxs_dyn_thermo_forcing_get(self.h, int(which), C.byref(r)))
+        return out
+
+    # ---- the dynamics' nodal forcing: both snapshots of M_wind, M_ocean, M_ssh made on the device from the source grid (model/externaldata.cpp:461-940) ----
+    def forcing_targets(self, set: int, RX, RY):
+        """nxs_dyn_forcing_targets: the [Nn] node positions in the coordinates of dataset `set` (0 .. NXS_NF_SETS - 1), resident until the mesh changes."""
+        rx, ry = np.ascontiguousarray(RX, np.float64), np.ascontiguousarray(RY, np.float64)
+        if rx.shape != (self.lm.num_nodes,) or ry.shape != rx.shape:
+            raise ValueError(f"targets have shapes {rx.shape}, {ry.shape}, expected ({self.lm.num_nodes},)")
+        self._chk(self.L.nxs_dyn_forcing_targets(self.h, int(set), _abi.dptr(rx), _abi.dptr(ry)))
+
+    def forcing_ingest(self, set: int, x_in, y_in, data, row, snapshot, default_value=1e8, interp=1, row_major=False, cyclic_x=False, cyclic_y=False, vectors=None):
+        """nxs_dyn_forcing_ingest: transformData, the cyclic wrap and InterpFromGridToMeshx at the targets of `set` on the device.  data [M, N, N_data] (or
+        [N, M, N_data] when row_major) untransformed and without the wrap; column j goes to snapshot[j] of row[j] (a name of _abi.NF_ROWS, NXS_NF_*, or -1 / None:
+        skipped).  vectors: None, or a dict as forcing_vectors() takes it.  The launches are asynchronous."""
+        f64 = lambda a: np.ascontiguousarray(a, np.float64)  # noqa: E731
+        x_in, y_in, data = f64(x_in), f64(y_in), f64(data)
+        if data.ndim == 2:
+            data = data[:, :, None]
+        M, N = (data.shape[1], data.shape[0]) if row_major else (data.shape[0], data.shape[1])
+        rows = np.array([-1 if r is None else _abi.NF_ROWS.index(r) if isinstance(r, str) else int(r) for r in row], np.int32)
+        snaps = np.ascontiguousarray(snapshot, np.int32)
+        if rows.shape != (data.shape[2],) or snaps.shape != rows.shape:
+            raise ValueError(f"row and snapshot must name the {data.shape[2]} columns of data")
+        g = _abi.ForcingGrid(_abi.dptr(x_in), _abi.dptr(y_in), x_in.size, y_in.size, M, N, int(interp), int(bool(row_major)), float(default_value))
+        v, keep = forcing_vectors(**vectors) if vectors is not None else (None, None)
+        self._chk(self.L.nxs_dyn_forcing_ingest(self.h, int(set), C.byref(g), int(bool(cyclic_x)), int(bool(cyclic_y)), _abi.dptr(data), data.shape[2], _abi.iptr(rows),
+                                                _abi.iptr(snaps), C.byref(v) if v is not None else None))
+        self._nf_grid_shape = (M + int(bool(cyclic_y)), N + int(bool(cyclic_x)), data.shape[2])
+        del keep
+
+    def set_forcing_time_rows(self, groups: dict):
+        """nxs_dyn_set_forcing_time_rows: {"wind" | "ocean" | "ssh": dict(mode="linear" | "step" | "off" or NXS_TF_*, fcoeff0=, fcoeff1=, factor=1, bias=0)}; a group
+        left out is OFF.  One asynchronous launch writes M_wind / M_ocean / M_ssh as the step reads them."""
+        t = _abi.ForcingTimeRows()
+        for k in range(_abi.NXS_NF_GROUPS):
+            t.factor[k] = 1.
+        for name, spec in groups.items():
+            if name not in _abi.NF_GROUPS:
+                raise KeyError(f"nxs_dyn_set_forcing_time_rows has no group {name!r}")
+            k = _abi.NF_GROUPS.index(name)
+            mode = spec.get("mode", "linear")
+            t.mode[k] = _abi.TF_MODES[mode] if isinstance(mode, str) else int(mode)
+            t.fcoeff0[k], t.fcoeff1[k] = float(spec.get("fcoeff0", 1.)), float(spec.get("fcoeff1", 0.))
+            t.factor[k], t.bias[k] = float(spec.get("factor", 1.)), float(spec.get("bias", 0.))
+        self._chk(self.L.nxs_dyn_set_forcing_time_rows(self.h, C.byref(t)))
+
+    def set_element_depth(self, depth):
+        """nxs_dyn_set_element_depth: M_element_depth ([Ne], a constant dataset) alone."""
+        a = np.ascontiguousarray(depth, np.float64)
+        if a.shape != (self.lm.num_elements,):
+            raise ValueError(f"element_depth has shape {a.shape}, expected ({self.lm.num_elements},)")
+        self._chk(self.L.nxs_dyn_set_element_depth(self.h, _abi.dptr(a)))
+
+    def forcing_get(self, which: int, names=_abi.NF_ROWS) -> dict:
+        """nxs_dyn_forcing_get: the named [Nn] half-rows of snapshot 0 / 1."""
+        out = {k: np.empty(self.lm.num_nodes) for k in names}
+        r = _abi.ForcingRows()
+        for k, a in out.items():
+            r.row[_abi.NF_ROWS.index(k)] = _abi.dptr(a)
+        self._chk(self.L.nxs_dyn_forcing_get(self.h, int(which), C.byref(r)))
+        return out
+
+    def forcing_grid(self) -> np.ndarray:
+        """debug array "nf_grid": the last forcing_ingest's grid data after transformData and the wrap, [cM, cN, N_data]."""
+        shape = getattr(self, "_nf_grid_shape", None)
+        if shape is None:
+            raise NxsError(-2, "forcing_grid before forcing_ingest")
+        out = np.empty(shape)
+        self._chk(self.L.nxs_dyn_debug_array(self.h, b"nf_grid", _abi.dptr(out), out.size))
         return out
 
     # ---- nesting: nestingIce / nestingDynamics on the device (FE.cpp:4878-4958), both snapshots of a nesting interval resident ----
