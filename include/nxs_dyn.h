@@ -25,6 +25,7 @@
  *   #ifdef OASIS: M_tau_wi in explicitSolve()   nxs_dyn_set_wave_stress (FE.cpp:10353-10354, 10408-10414, 10509-10518)
  *   #ifdef OASIS: M_cum_damage, M_conc_fsd      nxs_dyn_put_coupled / nxs_dyn_get_coupled (FE.cpp:4233-4238, 3991-3994)
  *   updateMeans(M_moorings, time_factor)        nxs_dyn_means_update    (FE.cpp:8518-9024; configure / get / to_grid / reset beside it)
+ *   M_moorings.updateGridMean() on a loaded grid nxs_dyn_means_points_update (gridoutput.cpp:387-415, 470-485; set / lsm / get / reset beside it)
  *   interpFields() + assignVariables()          nxs_dyn_regrid          (FE.cpp:3071-3154, 2120-2151, 2196-2258, 3161-3297, 553-572)
  *   #ifdef OASIS: initFsd / updateFSD / redistributeFSD / weldingRoach   nxs_fsd_bins, nxs_dyn_fsd_* (FE.cpp:7408-7576, 4674-4732, 4268-4483, 4737-4870, 5888-5896)
  *   thermo(): OWBulkFluxes + IABulkFluxes       nxs_dyn_fluxes, nxs_dyn_flux_* (FE.cpp:5214-5277, 5032-5159, 6148-6353, 4966-5019, 6359-6389, 6454-6535)
@@ -389,9 +390,10 @@ NXS_API int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *d, cons
  * state, the slab's D_* rows, the atmosphere and the column's forcing -- a host whose thermodynamics runs here fetches none of them for a time-mean Moorings file.
  * On a LOADED grid with interpMethod::conservative (a coupler's grid; the Moorings with moorings.use_conservative_remapping) the elemental rows go through
  * nxs_dyn_means_to_grid_conservative and a resident nxs_gridmap (include/nxs_interp.h) instead.
- * OUT OF SCOPE (the host keeps doing those itself): dmax / dmean (the FSD diagnostics of the coupled build), the NODAL leg on a loaded grid
- * (InterpFromMeshToMesh2dx at gridX / gridY, the proc mask, rotateVectors), the land-sea mask (setLSM / applyLSM), and a second set of accumulators for
- * the coupler's means (M_cpl_out) beside the Moorings'. */
+ * On a LOADED grid without conservative remapping (moorings.grid_type=from_file) both legs, the proc mask, rotateVectors, the grid accumulators and the
+ * land-sea mask are nxs_dyn_means_points_* below.
+ * OUT OF SCOPE (the host keeps doing those itself): dmax / dmean (the FSD diagnostics of the coupled build), rotateVectors and the land-sea mask on the
+ * REGULAR grid of nxs_dyn_means_to_grid, and a second set of accumulators for the coupler's means (M_cpl_out) beside the Moorings'. */
 enum nxs_means_var {
     /* elemental: accumulated over the owned elements i < M_local_nelements, the rows of ghost elements stay 0 (FE.cpp:8527) */
     NXS_MEANS_CONC = 0,           /* FE.cpp:8526  D_conc */
@@ -551,6 +553,67 @@ NXS_API int nxs_dyn_means_to_grid(nxs_dyn_handle *h, const nxs_dyn_means_grid *g
 struct nxs_gridmap;
 NXS_API int nxs_dyn_means_to_grid_conservative(nxs_dyn_handle *h, struct nxs_gridmap *map, double miss_val, double *grid_elemental /* [n_el][G] */);
 NXS_API int nxs_dyn_means_reset(nxs_dyn_handle *h);
+
+/* ---- The Moorings means on a LOADED grid (moorings.grid_type=from_file: the TOPAZ / NEMO / any curvilinear grid): GridOutput::updateGridMean() through the
+ * M_grid.loaded, non-conservative branch of updateGridMeanWorker (model/gridoutput.cpp:387-415, 470-485, 511-545), setLSM / applyLSM (:558-574, :639-651),
+ * rotateVectors (:578-623), resetGridMean (:627-635).  The G grid points, their rotation, the land-sea mask and the grid accumulators (data_grid) live on the
+ * handle; one launch locates every grid point ONCE in the mesh displaced by the device's M_UM -- the reference's three InterpFromMeshToMesh2dx calls
+ * (elemental variables, nodal variables, proc mask; isdefault = true, default 0.) see the same mesh and the same points, so they find the same triangle -- and
+ * does the gather, the rotation, the product with the proc mask ("found in an owned element"), the accumulation and the ice-mask rule for that point.
+ * The locator is the drifters' (exact, bamg's integer plane); the points, the mask and the accumulators do not depend on the mesh and SURVIVE nxs_dyn_set_mesh and
+ * nxs_dyn_regrid: the reference calls updateGridMean just before a regrid and goes on adding after it.  A handle that never calls these functions allocates
+ * and launches nothing for them.
+ * OUT OF SCOPE: reading and projecting the grid file (initArbitraryGrid), the NetCDF writer, M_cpl_out's accumulators and the OASIS put, dmax / dmean, the
+ * reduction over ranks (FE.cpp:9476-9487: ranks fetch with apply_lsm = 0, sum, and mask themselves). */
+enum nxs_means_rotation {
+    NXS_MEANS_ROTATE_NONE = 0,        /* M_false_easting && thetaName == "": rotateVectors returns at once */
+    NXS_MEANS_ROTATE_NORTH_EAST = 1,  /* !M_false_easting: cos / sin(rotation_angle - gridLON[i] * PI / 180) */
+    NXS_MEANS_ROTATE_GRID_THETA = 2   /* M_false_easting with a theta variable: cos / sin(rotation_angle - gridTheta[i]) */
+};
+#define NXS_MEANS_MAX_PAIRS (NXS_MEANS_MAX_VARS / 2)
+
+typedef struct nxs_dyn_means_points {
+    int32_t G;                 /* M_grid_size; 0 removes the object */
+    int32_t rotation;          /* enum nxs_means_rotation */
+    const double *gridX;       /* [G] projected coordinates (forward_mapx stays the caller's, or nxs_mapx_forward) */
+    const double *gridY;       /* [G] */
+    const double *gridLON;     /* [G] degrees; NXS_MEANS_ROTATE_NORTH_EAST */
+    const double *gridTheta;   /* [G] radians; NXS_MEANS_ROTATE_GRID_THETA */
+    double rotation_angle;     /* radians: mapNextsim->rotation * PI / 180 */
+    double miss_val;           /* M_miss_val */
+    int32_t n_pairs;           /* M_vectorial_variables.size(), <= NXS_MEANS_MAX_PAIRS */
+    int32_t pair_first[NXS_MEANS_MAX_PAIRS];    /* components_Id.first: a column of the configured nodal list */
+    int32_t pair_second[NXS_MEANS_MAX_PAIRS];   /* components_Id.second */
+} nxs_dyn_means_points;
+
+/*   nxs_dyn_means_points_set     everything is copied.  cosang / sinang (gridoutput.cpp:602-614) are evaluated here, once, on the host with std::cos / std::sin of
+ *                  the reference's own expressions and uploaded; the device does the four products and two sums of :617-618 without contraction, so the rotation is
+ *                  bit for bit.  A new set replaces the previous one (mask and accumulators included).  G == 0 or p == NULL removes the object and frees its
+ *                  memory.  nxs_dyn_means_configure with other list sizes drops the accumulators; they are made again, zeroed, at the new sizes by the next
+ *                  nxs_dyn_means_points_update / _get / _reset.  NXS_ERR_INVALID: G < 0, a NULL coordinate array, a non-finite coordinate, an unknown rotation
+ *                  mode or its angle array missing (or holding a non-finite value), n_pairs outside 0 .. NXS_MEANS_MAX_PAIRS, a pair index outside the
+ *                  configured nodal list.
+ *   nxs_dyn_means_points_lsm     setLSM.  lsm_in == NULL: computed on the handle's own mesh AT REST (M_UM = 0): 1 where the point lies in any triangle, ghosts
+ *                  included, else 0 (needs nxs_dyn_set_mesh).  lsm_in != NULL: [G] uploaded (a partitioned run's root computes it on the root mesh, which no
+ *                  handle holds).  lsm_out ([G], may be NULL) receives it.  Without this call there is no mask (M_use_lsm = false).
+ *   nxs_dyn_means_points_update  updateGridMean(): asynchronous on the handle's stream.  Per grid point: the isdefault box test of InterpFromMeshToMesh2dx.cpp:92
+ *                  against the displaced mesh's OWN box (the rank's, as the reference's per-rank call), the exact location; data_grid[nv][j] += the accumulator
+ *                  row of the found element (P0; ghost elements included, their rows are 0), 0. when none holds the point; the nodal variables P1 in the operand
+ *                  order of :157-159 (0. when not found), rotateVectors per pair in list order with the skip interp_out[first] == miss_val, then
+ *                  data_grid[nv][j] += value * proc_mask (a NaN times 0 stays a NaN); the ice-mask rule of :404-414, nodal variables first.
+ *                  NXS_ERR_STATE: before nxs_dyn_set_mesh / nxs_dyn_put_state, without points, nothing configured, a pair index outside the nodal list as
+ *                  configured NOW.
+ *   nxs_dyn_means_points_get     synchronised on return.  grid_elemental [num_elemental][G], grid_nodal [num_nodal][G] host arrays (either may be NULL), NOT
+ *                  transposed (:541-545).  apply_lsm != 0 with a mask present: applyLSM on the copy handed out (miss_val where the mask is 0); the resident rows
+ *                  stay as they are.  *elemental_dev / *nodal_dev (either may be NULL) receive the DEVICE pointers of the resident rows (library-owned, valid
+ *                  until nxs_dyn_means_points_set / nxs_dyn_means_configure; NULL for an empty list).
+ *   nxs_dyn_means_points_reset   resetGridMean(): the grid accumulators to zero, on the stream. */
+NXS_API int nxs_dyn_means_points_set(nxs_dyn_handle *h, const nxs_dyn_means_points *p);
+NXS_API int nxs_dyn_means_points_lsm(nxs_dyn_handle *h, const int32_t *lsm_in /* [G] or NULL */, int32_t *lsm_out /* [G] or NULL */);
+NXS_API int nxs_dyn_means_points_update(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_means_points_get(nxs_dyn_handle *h, int32_t apply_lsm, double *grid_elemental /* [n_el][G] */, double *grid_nodal /* [n_nod][G] */,
+                                     const double **elemental_dev, const double **nodal_dev);
+NXS_API int nxs_dyn_means_points_reset(nxs_dyn_handle *h);
 
 /* ---- The drifters on the device: the three statements of checkUpdateDrifters() (FE.cpp:8403-8437) that touch the handle's arrays -- Drifters::move with
  * M_UT and the reset of M_UT (checkMoveDrifters, FE.cpp:8375-8397), Drifters::updateConc on the mesh displaced by M_UM, Drifters::maskXY.  drifters.cpp's file
@@ -1486,7 +1549,8 @@ NXS_API int nxs_dyn_get_traffic_model(nxs_dyn_handle *h, nxs_dyn_traffic *t);
  *   "slab_coupled_timing" 1 = nxs_dyn_slab_coupled records events around its two launches; nxs_dyn_debug_array "slab_coupled_ms" returns their device times
  *                  [k_coupled_thermo, k_coupled_bins] in ms.  Default 0
  *   "drifters_timing" 1 = the nxs_dyn_drifters_* calls record events around their launches and wait for them; nxs_dyn_debug_array "drifters_ms" returns the device
- *                  times [locator build, move kernels, conc kernel, mask kernels] of the last of each in ms.  Default 0
+ *                  times [locator build, move kernels, conc kernel, mask kernels] of the last of each in ms.  nxs_dyn_means_points_update is timed by the
+ *                  same option: "means_points_ms" returns [its locator build (0: the locator was current), its kernel].  Default 0
  *   "ipc_delay", "halo_one_directional"   test doors of the exchange protocols, see NXS_DELAY_* above */
 NXS_API int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value);
 

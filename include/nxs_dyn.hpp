@@ -89,6 +89,15 @@ public:
         check(nxs_dyn_drifters_get(h_, set, &n, x, y, id, conc, found), "drifters_get");
         return n;
     }
+    // The Moorings means on a LOADED grid (moorings.grid_type=from_file): GridOutput::updateGridMean / setLSM / applyLSM / resetGridMean (gridoutput.cpp:387-415,
+    // 470-485, 558-651) on the device-resident accumulators.  The grid, its mask and its accumulators survive setMesh and regrid.
+    void meansPointsSet(const nxs_dyn_means_points *p) { check(nxs_dyn_means_points_set(h_, p), "means_points_set"); }       // NULL or G == 0: removed
+    void meansPointsSetLSM(const int32_t *lsm_in = nullptr, int32_t *lsm_out = nullptr) { check(nxs_dyn_means_points_lsm(h_, lsm_in, lsm_out), "means_points_lsm"); }
+    void meansPointsUpdateGridMean() { check(nxs_dyn_means_points_update(h_), "means_points_update"); }
+    void meansPointsGet(bool apply_lsm, double *grid_elemental, double *grid_nodal, const double **elemental_dev = nullptr, const double **nodal_dev = nullptr) {
+        check(nxs_dyn_means_points_get(h_, apply_lsm ? 1 : 0, grid_elemental, grid_nodal, elemental_dev, nodal_dev), "means_points_get");
+    }
+    void meansPointsResetGridMean() { check(nxs_dyn_means_points_reset(h_), "means_points_reset"); }
     // interpFields() + assignVariables() on the device-resident state (FE.cpp:3071-3154, 553-572): the handle goes on with a.new_mesh; forcing is the next setForcing
     nxs_dyn_regrid_info regrid(const nxs_dyn_regrid_args &a) {
         nxs_dyn_regrid_info info{};

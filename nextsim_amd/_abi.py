@@ -489,6 +489,17 @@ class MeansGrid(C.Structure):   # nxs_dyn_means_grid
                 ("ncols", C.c_int32), ("nrows", C.c_int32)]
 
 
+NXS_MEANS_ROTATE_NONE, NXS_MEANS_ROTATE_NORTH_EAST, NXS_MEANS_ROTATE_GRID_THETA = range(3)   # enum nxs_means_rotation
+MEANS_ROTATION = {"none": NXS_MEANS_ROTATE_NONE, "north_east": NXS_MEANS_ROTATE_NORTH_EAST, "grid_theta": NXS_MEANS_ROTATE_GRID_THETA}
+NXS_MEANS_MAX_PAIRS = NXS_MEANS_MAX_VARS // 2
+
+
+class MeansPoints(C.Structure):   # nxs_dyn_means_points
+    _fields_ = [("G", C.c_int32), ("rotation", C.c_int32), ("gridX", c_double_p), ("gridY", c_double_p), ("gridLON", c_double_p), ("gridTheta", c_double_p),
+                ("rotation_angle", C.c_double), ("miss_val", C.c_double), ("n_pairs", C.c_int32), ("pair_first", C.c_int32 * NXS_MEANS_MAX_PAIRS),
+                ("pair_second", C.c_int32 * NXS_MEANS_MAX_PAIRS)]
+
+
 NXS_DRIFTER_SETS = 8   # include/nxs_dyn.h: drifter sets per handle (nxs_dyn_drifters_*)
 
 ICE_DIAG = ("D_conc", "D_thick", "D_snow_thick", "D_sigma0", "D_sigma1", "D_divergence")

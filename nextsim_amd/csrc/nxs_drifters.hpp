@@ -13,6 +13,8 @@
 #include <cstdint>
 #include <string>
 
+#include "nxs_means_points_body.inl"   // nxs_mp::Args
+
 namespace nxs_drifters {
 
 struct MeshView {
@@ -39,6 +41,11 @@ int move(State *s, hipStream_t st, const MeshView &m, const double *UT, const do
 int conc(State *s, hipStream_t st, const MeshView &m, const double *UM, const double *conc, int set, const double *bbox, double *conc_host, std::string &err);
 int mask(State *s, hipStream_t st, int set, double conc_lim, const int32_t *keepers, int32_t n_keepers, int32_t *n_left, std::string &err);
 int get(State *s, hipStream_t st, int set, int32_t *n, double *x, double *y, int32_t *id, double *conc, int32_t *found, std::string &err);
+
+// the Moorings means on a loaded grid (nxs_dyn_means_points_*, nxs_means_points_kernels.inl): they use the two locators above and build none of their own
+int means_points_update(State *s, hipStream_t st, const MeshView &m, const double *UM, const nxs_mp::Args &a, std::string &err);   // one launch, asynchronous
+int means_points_lsm(State *s, hipStream_t st, const MeshView &m, int G, const double *gx, const double *gy, int *lsm /* device, [G] */, std::string &err);
+bool means_points_timing(const State *s, double ms[2]);   // of the last means_points_update: its locator build (0: the locator was current), its kernel [ms]
 
 }  // namespace nxs_drifters
 #endif

@@ -194,7 +194,9 @@ struct State {
     double own_box[2][4] = {};
     bool timing = false, timed = false;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms[4] = {0, 0, 0, 0};
+    double ms[5] = {0, 0, 0, 0, 0};    // [4] the launch of nxs_means_points_kernels.inl
+    double mp_ms[2] = {0, 0};          // the last nxs_dyn_means_points_update: its locator build (0: none was needed), its kernel
+    unsigned builds = 0;               // locator builds so far
 };
 
 namespace {
@@ -308,6 +310,7 @@ int build_locator(State *s, hipStream_t st, const MeshView &m, const double *UM,
     d.isdefault = 1; d.defaultvalue = 0.;
     for (int k = 0; k < 4; ++k) L.bbox[k] = box[k];
     L.valid = true;
+    ++s->builds;
     return NXS_OK;
 }
 

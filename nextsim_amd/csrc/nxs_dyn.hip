@@ -254,8 +254,20 @@ struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stres
     unsigned char *d_freezing = nullptr;
     size_t mech_capacity = 0;
 };
+struct MeansPoints {       // nxs_dyn_means_points_*: a loaded grid, its rotation, its land-sea mask and the grid accumulators (data_grid).  NOT the mesh's: release_mesh leaves them
+    std::vector<void *> mp_allocs;
+    bool mp_set = false;
+    int mp_G = 0, mp_n_pairs = 0;
+    int mp_first[NXS_MEANS_MAX_PAIRS] = {}, mp_second[NXS_MEANS_MAX_PAIRS] = {};
+    double mp_miss_val = 0.;
+    double *mp_gx = nullptr, *mp_gy = nullptr, *mp_cos = nullptr, *mp_sin = nullptr;   // [G]; cos / sin NULL: NXS_MEANS_ROTATE_NONE
+    double *mp_grid[2] = {nullptr, nullptr};   // [n_el][G], [n_nod][G]
+    int mp_grid_n[2] = {0, 0};                 // the list sizes the accumulators were made for
+    bool mp_have_lsm = false;                  // M_use_lsm
+    std::vector<int32_t> mp_lsm;               // [G] M_lsm (applyLSM works on the copy nxs_dyn_means_points_get hands out)
+};
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, CoupledBuffers {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, CoupledBuffers, MeansPoints {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -666,6 +678,8 @@ void release_thermo_forcing(nxs_dyn_handle *h) { release_group<ThermoForcing>(h,
 void release_nodal_forcing(nxs_dyn_handle *h) { release_group<NodalForcing>(h, h->nf_allocs); }
 void release_nesting(nxs_dyn_handle *h) { release_group<Nesting>(h, h->nest_allocs); }
 void release_diffusion(nxs_dyn_handle *h) { release_group<Diffusion>(h, h->diff_allocs); }
+// the loaded grid of the Moorings with its accumulators: nxs_dyn_means_points_set (a new grid, or none) and nxs_dyn_destroy -- not release_mesh
+void release_means_points(nxs_dyn_handle *h) { release_group<MeansPoints>(h, h->mp_allocs); }
 // the coupled build's buffers; their attachments are members of h->dw
 void release_coupled(nxs_dyn_handle *h) {
     release_group<CoupledBuffers>(h, h->coupled_allocs);
@@ -2068,6 +2082,7 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     if (h->comm && h->rccl.CommDestroy) h->rccl.CommDestroy(h->comm);
     ipc_release(h);
     release_mesh(h);
+    release_means_points(h);
     if (!h->reg_key.empty()) nxs_reg::table_for(h->reg_key).remove((uint64_t)(uintptr_t)h);
     unpin_all(h);
     if (h->h_send) (void)hipHostFree(h->h_send);
@@ -3362,6 +3377,8 @@ int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) tr
     HIPCHK(h, hipSetDevice(h->device));
     if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));
     means_drop_buffers(h);
+    for (int k = 0; k < 2; ++k)   // the grid accumulators of a loaded grid (nxs_dyn_means_points_*) are made again by their next call when a list changes its size
+        if (h->mp_grid_n[k] != (int)ids[k].size()) { pool_free_one(h->mp_allocs, h->mp_grid[k]); h->mp_grid[k] = nullptr; h->mp_grid_n[k] = 0; }
     for (int k = 0; k < 2; ++k) { h->means_ids[k] = ids[k]; h->means_mask[k] = mask[k]; }
     h->means_ice_mask_col = ice_col;
     if (h->have_mesh) { int rc = means_make_buffers(h); if (rc) return rc; }
@@ -3690,6 +3707,11 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
     if (!std::strcmp(name, "drifters_ms")) {   // [4] device time of the last locator build, move kernels, conc kernel, mask kernels with option "drifters_timing" 1
         if (n != 4) return fail(h, NXS_ERR_INVALID, "debug_array drifters_ms has 4 entries");
         if (!h->drift || !nxs_drifters::timing(h->drift, out)) return fail(h, NXS_ERR_STATE, "debug_array drifters_ms: no timed nxs_dyn_drifters_* call (option drifters_timing)");
+        return NXS_OK;
+    }
+    if (!std::strcmp(name, "means_points_ms")) {   // [2] device time of the last nxs_dyn_means_points_update with option "drifters_timing" 1: its locator build (0: none), its kernel
+        if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array means_points_ms has 2 entries");
+        if (!h->drift || !nxs_drifters::means_points_timing(h->drift, out)) return fail(h, NXS_ERR_STATE, "debug_array means_points_ms: no timed nxs_dyn_means_points_update (option drifters_timing)");
         return NXS_OK;
     }
     if (!std::strcmp(name, "means_update_ms")) {   // [2] device time of the last nxs_dyn_means_update with option "means_timing" 1: the elemental launch, the nodal launch
@@ -4056,5 +4078,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_thermo_forcing.inl"
 #include "nxs_nesting.inl"
 #include "nxs_nodal_forcing.inl"
+#include "nxs_means_points.inl"
 
 }  // extern "C"

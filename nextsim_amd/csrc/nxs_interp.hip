@@ -1413,3 +1413,5 @@ extern "C" int nxs_interp_grid_to_mesh(double *data_mesh, const double *x_in, in
 // The drifters of a dynamics handle (nxs_dyn_drifters_*): kernels that share locate() with k_interp, and the locator built from device coordinates
 // ---------------------------------------------------------------------------------------------------------
 #include "nxs_drifters.inl"
+// The Moorings means on a loaded grid (nxs_dyn_means_points_*): one more consumer of locate() and of the drifters' locators
+#include "nxs_means_points_kernels.inl"

@@ -146,6 +146,11 @@ def load_library():
     L.nxs_dyn_means_to_grid.argtypes = [H, P(_abi.MeansGrid), _abi.c_double_p, _abi.c_double_p]
     L.nxs_dyn_means_to_grid_conservative.argtypes = [H, C.c_void_p, C.c_double, _abi.c_double_p]
     L.nxs_dyn_means_reset.argtypes = [H]
+    L.nxs_dyn_means_points_set.argtypes = [H, P(_abi.MeansPoints)]
+    L.nxs_dyn_means_points_lsm.argtypes = [H, _abi.c_int32_p, _abi.c_int32_p]
+    L.nxs_dyn_means_points_update.argtypes = [H]
+    L.nxs_dyn_means_points_get.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
+    L.nxs_dyn_means_points_reset.argtypes = [H]
     L.nxs_dyn_drifters_set.argtypes = [H, C.c_int32, C.c_int32, _abi.c_double_p, _abi.c_double_p, _abi.c_int32_p]
     L.nxs_dyn_drifters_clear.argtypes = [H, C.c_int32]
     L.nxs_dyn_drifters_mesh_bbox.argtypes = [H, C.c_int32, _abi.c_double_p]
@@ -268,6 +273,7 @@ EXPORTS = (
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_to_grid_conservative", "nxs_dyn_means_reset",
+    "nxs_dyn_means_points_set", "nxs_dyn_means_points_lsm", "nxs_dyn_means_points_update", "nxs_dyn_means_points_get", "nxs_dyn_means_points_reset",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
     "nxs_dyn_drifters_get", "nxs_dyn_regrid", "nxs_dyn_regrid_carry_thermo", "nxs_dyn_regrid_thermo_info_get",
     "nxs_dyn_explicit_solve", "nxs_dyn_update", "nxs_dyn_synchronize", "nxs_dyn_step_host",
@@ -1494,6 +1500,66 @@ class FiniteElementDynamics:
         """resetMeshMean(bamgmesh): both accumulators to zero, on the stream."""
         self._chk(self.L.nxs_dyn_means_reset(self.h))
 
+    # ---- the Moorings means on a loaded grid: updateGridMean / setLSM / applyLSM / rotateVectors / resetGridMean (gridoutput.cpp:387-415, 470-485, 558-651) ----
+    def means_points_set(self, gridX=None, gridY=None, miss_val=-1e14, rotation="none", gridLON=None, gridTheta=None, rotation_angle=0., pairs=()):
+        """The loaded grid of the Moorings on the handle: projected coordinates gridX / gridY [G], the rotation mode ("none", "north_east" with gridLON in
+        degrees, "grid_theta" with gridTheta in radians) with rotation_angle in radians, and the vectorial variables as pairs of columns of the configured nodal
+        list.  Everything is copied; the grid, its mask and its accumulators survive set_mesh and regrid.  No coordinates (or empty ones) remove the object."""
+        if gridX is None or np.size(gridX) == 0:
+            self._chk(self.L.nxs_dyn_means_points_set(self.h, None))
+            self._points_G = 0
+            return
+        x, y = np.ascontiguousarray(gridX, np.float64).ravel(), np.ascontiguousarray(gridY, np.float64).ravel()
+        if x.shape != y.shape:
+            raise ValueError("gridX and gridY differ in length")
+        p = _abi.MeansPoints()
+        p.G, p.rotation = x.size, _abi.MEANS_ROTATION[rotation] if isinstance(rotation, str) else int(rotation)
+        p.gridX, p.gridY = _abi.dptr(x), _abi.dptr(y)
+        keep = []
+        for name, a in (("gridLON", gridLON), ("gridTheta", gridTheta)):
+            if a is not None:
+                a = np.ascontiguousarray(a, np.float64).ravel()
+                if a.shape != x.shape:
+                    raise ValueError(f"{name} has {a.size} entries, the grid {x.size}")
+                keep.append(a)
+                setattr(p, name, _abi.dptr(a))
+        p.rotation_angle, p.miss_val = float(rotation_angle), float(miss_val)
+        pairs = list(pairs)
+        p.n_pairs = len(pairs)
+        for k, (first, second) in enumerate(pairs[:_abi.NXS_MEANS_MAX_PAIRS]):
+            p.pair_first[k], p.pair_second[k] = int(first), int(second)
+        self._chk(self.L.nxs_dyn_means_points_set(self.h, C.byref(p)))
+        self._points_G = int(x.size)
+
+    def means_points_lsm(self, lsm=None) -> np.ndarray:
+        """setLSM: computed on the handle's own mesh at rest (1 where a grid point lies in any triangle, ghosts included) or, given, uploaded.  Returns it."""
+        G = getattr(self, "_points_G", 0)
+        out = np.empty(G, np.int32)
+        given = None if lsm is None else np.ascontiguousarray(lsm, np.int32).ravel()
+        if given is not None and given.size != G:
+            raise ValueError(f"lsm has {given.size} entries, the grid {G}")
+        self._chk(self.L.nxs_dyn_means_points_lsm(self.h, _abi.iptr(given) if given is not None else None, _abi.iptr(out)))
+        return out
+
+    def means_points_update(self):
+        """updateGridMean() on the loaded grid: one launch on the handle's stream that locates every grid point once in the mesh displaced by M_UM."""
+        self._chk(self.L.nxs_dyn_means_points_update(self.h))
+
+    def means_points_get(self, apply_lsm: bool = False, want_host: bool = True):
+        """(elemental [n_el, G] or None, nodal [n_nod, G] or None, device pointer of the elemental rows, of the nodal rows); apply_lsm: applyLSM on the copy."""
+        n_el, n_nod = getattr(self, "_means_n", (0, 0))
+        G = getattr(self, "_points_G", 0)
+        el = np.empty((n_el, G)) if want_host and n_el else None
+        nod = np.empty((n_nod, G)) if want_host and n_nod else None
+        de, dn = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.nxs_dyn_means_points_get(self.h, int(bool(apply_lsm)), _abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None,
+                                                  C.byref(de), C.byref(dn)))
+        return el, nod, de.value, dn.value
+
+    def means_points_reset(self):
+        """resetGridMean(): the grid accumulators to zero, on the stream."""
+        self._chk(self.L.nxs_dyn_means_points_reset(self.h))
+
     # ---- the drifters: checkMoveDrifters / checkUpdateDrifters (FE.cpp:8375-8437), Drifters::move / updateConc / maskXY (drifters.cpp:468-579) ----
     @staticmethod
     def _bbox(bbox):
@@ -1572,7 +1638,7 @@ class FiniteElementDynamics:
         n = {"rlmass": Nn, "node_mass": Nn, "C_bu": Nn, "grad_ssh": 2 * Nn, "fcor": Nn, "VTM": 2 * Nn,
              "shape": 6 * Ne, "emass": Ne, "ecbu": Ne, "force": 6 * Ne, "volume": Ne, "expC": Ne,
              "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn, "drag_ui": Ne, "drag_ui_young": Ne, "slab_branches": Ne, "slab_fsd_branches": Ne,
-             "means_update_ms": 2, "slab_coupled_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3, "diffuse_table": 3 * Ne}[name]
+             "means_update_ms": 2, "means_points_ms": 2, "slab_coupled_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3, "diffuse_table": 3 * Ne}[name]
         out = np.empty(n)
         self._chk(self.L.nxs_dyn_debug_array(self.h, name.encode(), _abi.dptr(out), n))
         return out
