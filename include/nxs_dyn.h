@@ -31,6 +31,7 @@
  *   thermo(): OWBulkFluxes + IABulkFluxes       nxs_dyn_fluxes, nxs_dyn_flux_* (FE.cpp:5214-5277, 5032-5159, 6148-6353, 4966-5019, 6359-6389, 6454-6535)
  *   thermo(): thermoWinton / thermoIce0 columns nxs_dyn_column, nxs_dyn_column_* (FE.cpp:5306-5411, 6396-6448, 6633-6962)
  *   thermo(): the slab loop from new ice to tracers nxs_dyn_slab, nxs_dyn_slab_*, nxs_slab_* (FE.cpp:5413-6133, 6538-6627)
+ *   thermo() under OceanType::COUPLED + the receive nxs_dyn_ocean_coupled_*, nxs_gridmap_receive_rows (FE.cpp:5150-5157, 5348-5358, 5826-5841; externaldata.cpp:163-236)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -867,8 +868,9 @@ NXS_API int nxs_dyn_fsd_weld(nxs_dyn_handle *h, double ddt, const uint8_t *freez
  * blended by nxs_dyn_set_forcing_time) -- all resident --, the atmosphere and the thermodynamic rows below, and writes 25 rows for the slab loop, D_tau_ow into
  * the row nxs_dyn_means_update reads (so no nxs_dyn_means_set_tau_ow) and M_drag_ui / M_drag_ti and their _young twins IN PLACE (the next call and the next step
  * read them: no upload of drag_ui / drag_ui_young through nxs_dyn_put_state).
- * OUT OF SCOPE: the #ifdef AEROBULK branch of OWBulkFluxes (a Fortran library; only the `nextsim` formula is built), the OceanType::COUPLED term
- * Qow += Qsw * M_qsrml (FE.cpp:5153-5154), and thermo() from FE.cpp:5279 on (the slab loop), which consumes the rows of nxs_dyn_fluxes_get.
+ * While a coupled ocean is attached (nxs_dyn_ocean_coupled_attach, below) Qow += Qsw * M_qsrml replaces Qow += Qsw (FE.cpp:5150-5157); NXS_FLUX_QSW_OW stays the
+ * total short wave.  OUT OF SCOPE: the #ifdef AEROBULK branch of OWBulkFluxes (a Fortran library; only the `nextsim` formula is built), and thermo() from
+ * FE.cpp:5279 on (the slab loop), which consumes the rows of nxs_dyn_fluxes_get.
  *   nxs_flux_default_config   model/options.cpp:388-438; humidity from the dew point, long wave from Qlw_in
  *   nxs_flux_config_check     what nxs_dyn_flux_configure refuses, without a handle (so without a device): alb_scheme outside 1..4, zref_wind, zref_temp or
  *                  limiting_lengthscale <= 0 (or NaN), an unknown humidity or long-wave source; NXS_ERR_INVALID, the text in nxs_dyn_last_error(NULL)
@@ -937,8 +939,11 @@ NXS_API int nxs_dyn_fluxes_get(nxs_dyn_handle *h, const nxs_dyn_flux_rows *out /
  * M_tice[0], M_tsurf_young, M_sst, M_sss (the device copies of nxs_dyn_flux_state: ONE copy that both launches use), M_tair (nxs_dyn_flux_set_atmosphere), and under
  * EXCHANGE M_VT and M_ocean at the element's three nodes.  It writes NXS_COL_ROWS rows for sections 6 to 10 and, IN PLACE, M_tice[0] (under WINTON also M_tice[1],
  * M_tice[2]) and in the young-ice category M_tsurf_young, M_h_young, M_hs_young -- the last two are rows of nxs_dyn_state, so the next nxs_dyn_step reads them.
+ * While a coupled ocean is attached (nxs_dyn_ocean_coupled_attach, below) the launch runs the reference's OceanType::COUPLED branch (FE.cpp:5348-5358) whatever
+ * ocean_type was configured: Qdw = Fdw = 0 and M_sst, M_sss are reset IN PLACE to the received ocean_temp, ocean_salt before iceOceanHeatflux and freezingPoint read
+ * them; the configuration itself still refuses NXS_COL_OCEAN_COUPLED (the coupled ocean is an attachment, not an option).
  * OUT OF SCOPE: thermo() from FE.cpp:5413 on (the assimilation flux, new ice, lateral melt, redistributeThermoFSD, meltPonds, the slab ocean, healing, diagnostics,
- * tracers), OceanType::COUPLED (#ifdef OASIS), Winton's LOG(WARNING) and assert.
+ * tracers), Winton's LOG(WARNING) and assert.
  *   nxs_col_default_config    model/options.cpp:112, 291-293, 383-420; snowfall from precip*snowfr, the constant mixed layer depth
  *   nxs_col_config_check      what nxs_dyn_column_configure refuses, without a handle: an unknown enum value, snow_cond, constant_mld, nudge_timeT or nudge_timeS
  *                  <= 0 (or NaN), the coupled ocean; NXS_ERR_INVALID, the text in nxs_dyn_last_error(NULL)
@@ -956,7 +961,7 @@ NXS_API int nxs_dyn_fluxes_get(nxs_dyn_handle *h, const nxs_dyn_flux_rows *out /
 enum { NXS_COL_THERMO_ZERO_LAYER = 0, NXS_COL_THERMO_WINTON = 1 };                 /* setup::ThermoType */
 enum { NXS_COL_QIO_BASIC = 0, NXS_COL_QIO_EXCHANGE = 1 };                          /* setup::OceanHeatfluxScheme */
 enum { NXS_COL_FREEZINGPOINT_LINEAR = 0, NXS_COL_FREEZINGPOINT_UNESCO = 1 };       /* setup::FreezingPointType */
-enum { NXS_COL_OCEAN_CONSTANT = 0, NXS_COL_OCEAN_NUDGED = 1, NXS_COL_OCEAN_COUPLED = 7 };   /* setup::OceanType: CONSTANT, any nudged dataset (TOPAZ4R = 1 ...), COUPLED (refused) */
+enum { NXS_COL_OCEAN_CONSTANT = 0, NXS_COL_OCEAN_NUDGED = 1, NXS_COL_OCEAN_COUPLED = 7 };   /* setup::OceanType: CONSTANT, any nudged dataset (TOPAZ4R = 1 ...), COUPLED (refused as an option: nxs_dyn_ocean_coupled_attach) */
 enum { NXS_COL_SNOWFALL_PRECIP_SNOWFR = 0 /* M_precip*M_snowfr */, NXS_COL_SNOWFALL_SNOWFALL = 1 /* M_snowfall */, NXS_COL_SNOWFALL_PRECIP_TAIR = 2 /* M_precip where M_tair < 0 */ };
 enum { NXS_COL_MLD_CONSTANT = 0 /* ideal_simul.constant_mld */, NXS_COL_MLD_ROW = 1 /* M_mld */ };
 enum { NXS_COL_CONST_RHOW = 0, NXS_COL_CONST_CPW, NXS_COL_CONST_RHOI, NXS_COL_CONST_RHOS, NXS_COL_CONST_LF, NXS_COL_CONST_C, NXS_COL_CONST_KI, NXS_COL_CONST_SI,
@@ -1235,6 +1240,56 @@ NXS_API int nxs_dyn_diffusion_configure(nxs_dyn_handle *h, double diffusivity_ss
 NXS_API int nxs_dyn_diffuse(nxs_dyn_handle *h);
 NXS_API int nxs_dyn_flux_device_rows(nxs_dyn_handle *h, const double **device_rows /* [8] */);
 
+/* ---- A coupled ocean on the device: thermo() under OceanType::COUPLED (the reference's #ifdef OASIS, a neXtSIM-NEMO run).  The coupled ocean is ATTACHED to a
+ * handle, the way the wave terms are; nxs_dyn_column_configure keeps refusing NXS_COL_OCEAN_COUPLED, and a handle that never calls these entry points allocates
+ * nothing, launches nothing new and keeps its bits.  Each coupling step the reference runs ExternalData::check_and_reload for ocean_cpl_elements and
+ * wave_cpl_elements (externaldata.cpp:163-236, 461-514, 1291-1493; dataset.cpp:2828-3031, 3219-3393): receiveCouplingData, ConservativeRemappingGridToMesh, get.
+ * Here that is ONE launch (nxs_gridmap_receive_rows, include/nxs_interp.h) from the fields on the exchange grid to the [Ne] device rows thermo() reads -- no host
+ * remap and no [Ne] upload.  The five rows:
+ *   NXS_OC_OCEAN_TEMP, NXS_OC_OCEAN_SALT, NXS_OC_MLD   M_ocean_temp, M_ocean_salt, M_mld: the SAME device rows nxs_dyn_column_set_forcing and
+ *                  nxs_dyn_thermo_forcing_time fill -- whichever came last wins, and the have-bits are set as after an upload
+ *   NXS_OC_QSRML, NXS_OC_WLBK   M_qsrml (I_FrcQsr) and M_wlbk (I_wlbk): two rows of the attachment's own, in a pool that goes with the mesh
+ * While a coupled ocean is attached with OCEAN_TEMP, OCEAN_SALT and QSRML configured, nxs_dyn_fluxes, nxs_dyn_column, nxs_dyn_slab and nxs_dyn_slab_coupled run
+ * the reference's COUPLED statements (FE.cpp:5150-5157, 5348-5358, 5826-5841; see each of them above), nxs_dyn_column answers NXS_ERR_STATE unless
+ * freezingpoint_type is UNESCO (FE.cpp:1244-1248: the reference overrides the option silently; a host that passes M_freezingpoint_type passes UNESCO), a needed
+ * received row that is missing on this mesh is NXS_ERR_STATE naming the row, and nxs_dyn_diffuse answers NXS_ERR_STATE (FE.cpp:3934-3940).
+ *   nxs_ocean_coupled_default_config   the reference's receive with coupler.rcv_first_layer_depth off and no wave model: I_SST, I_SSS, I_FrcQsr in that order,
+ *                  a = 1, b = 0 (dataset.cpp), factor = 1, bias = 0.  (I_MLD: a = 1, b = 0; I_wlbk: a = 2, b = 0.)
+ *   nxs_ocean_coupled_config_check     what the attach refuses in a configuration, without a handle: n_fields outside 1 .. NXS_OC_ROWS, an unknown row, a row twice
+ *   nxs_dyn_ocean_coupled_attach   cfg names the rows that are received, in the order the fields arrive, with a, b, factor, bias per FIELD.  map is BORROWED (the
+ *                  caller destroys it after the detach or the next nxs_dyn_set_mesh); NULL for a host that only uses _put_rows; otherwise its element count
+ *                  must be the handle's (a partitioned run passes the nxs_gridmap_restrict-ed map): NXS_ERR_INVALID naming both sizes.  cfg == NULL DETACHES:
+ *                  the two rows are freed and the handle is again the library without this section.  NXS_ERR_STATE before nxs_dyn_set_mesh.  nxs_dyn_set_mesh
+ *                  and nxs_dyn_regrid DROP the attachment and the two rows: the map belonged to the old mesh, and the host builds new weights at rest as
+ *                  FE.cpp:8037-8049 does.  nxs_dyn_regrid_carry_thermo still carries sst / sss as before
+ *   nxs_dyn_ocean_coupled_receive  fields[k], k < n_fields: the [G] field of cfg.row[k] on the map's grid, host pointers or, with NXS_REGRID_IN_DEVICE, device
+ *                  pointers.  One launch on the handle's stream: receive -> fluxes -> column needs no host synchronisation (host fields are uploaded on the
+ *                  stream first and the call waits for those uploads).  A triangle no wet cell touches receives NaN, as in the reference.  NXS_ERR_STATE: not
+ *                  attached, attached without a map
+ *   nxs_dyn_ocean_coupled_put_rows the same five rows from host [Ne] arrays, a NULL row is skipped: the way in for a host that remapped itself.  NXS_ERR_INVALID
+ *                  for a row the configuration does not name
+ *   nxs_dyn_ocean_coupled_get      synchronised; [Ne] host rows, a NULL row is skipped, a row asked for that was never given on this mesh is NXS_ERR_STATE.
+ *                  device_rows (may be NULL) [NXS_OC_ROWS]: the device addresses, NULL for a missing row -- device_rows[NXS_OC_WLBK] is what a host hands
+ *                  nxs_dyn_fsd_breakup(..., NXS_FSD_WLBK_ON_DEVICE, ...)
+ * OUT OF SCOPE: the nodal half of the receive (I_Uocn, I_Vocn, I_SSH, I_tauwix / y go through FromMeshToMeshQuick on a triangulated source, the gridTheta
+ * rotation of transformData; those rows keep nxs_dyn_set_forcing_pair / nxs_dyn_set_wave_stress), ocean_turning_angle = 0 (a parameter the host sets), the
+ * outgoing side (M_cpl_out, the reduction over ranks, the OASIS put), OASIS itself, reading and projecting the exchange grid file, dmax / dmean, AEROBULK. */
+enum { NXS_OC_OCEAN_TEMP = 0, NXS_OC_OCEAN_SALT = 1, NXS_OC_QSRML = 2, NXS_OC_MLD = 3, NXS_OC_WLBK = 4, NXS_OC_ROWS = 5 };
+typedef struct nxs_dyn_ocean_coupled_config {
+    int32_t n_fields;                  /* fields of one receive, 1 .. NXS_OC_ROWS */
+    int32_t row[NXS_OC_ROWS];          /* row[k]: the NXS_OC_* row field k goes to; no row twice */
+    double a[NXS_OC_ROWS], b[NXS_OC_ROWS];            /* receiveCouplingData: t = field; t *= a; t += b (per field k) */
+    double factor[NXS_OC_ROWS], bias[NXS_OC_ROWS];    /* ExternalData::get: M_factor * x + M_bias_correction (per field k) */
+} nxs_dyn_ocean_coupled_config;
+typedef struct nxs_dyn_ocean_coupled_rows { double *row[NXS_OC_ROWS]; } nxs_dyn_ocean_coupled_rows;   /* [Ne] each, indexed by NXS_OC_* */
+struct nxs_gridmap;   /* include/nxs_interp.h */
+NXS_API int nxs_ocean_coupled_default_config(nxs_dyn_ocean_coupled_config *c);
+NXS_API int nxs_ocean_coupled_config_check(const nxs_dyn_ocean_coupled_config *c);
+NXS_API int nxs_dyn_ocean_coupled_attach(nxs_dyn_handle *h, struct nxs_gridmap *map /* may be NULL */, const nxs_dyn_ocean_coupled_config *c /* NULL: detach */);
+NXS_API int nxs_dyn_ocean_coupled_receive(nxs_dyn_handle *h, const double *const *fields, int32_t flags);
+NXS_API int nxs_dyn_ocean_coupled_put_rows(nxs_dyn_handle *h, const nxs_dyn_ocean_coupled_rows *rows);
+NXS_API int nxs_dyn_ocean_coupled_get(nxs_dyn_handle *h, const nxs_dyn_ocean_coupled_rows *out /* may be NULL */, const double **device_rows /* [NXS_OC_ROWS], may be NULL */);
+
 /* ---- The rest of thermo()'s slab loop on the device: FE.cpp:5413-6133 as a default (non-OASIS) build compiles it -- the assimilation flux (FE.cpp:5415-5425),
  * section 6: new ice over open water and lateral melt (FE.cpp:5434-5646; newice_type 1 .. 4, type 3 with windSpeedElement, FE.cpp:6359-6370; melt_type 1, 2), the
  * freeze-days block (FE.cpp:5649-5682), the new concentration and thickness with Winton's (38), (39), (26) (FE.cpp:5685-5711), the limit block (FE.cpp:5714-5728),
@@ -1360,8 +1415,9 @@ NXS_API int nxs_dyn_slab_get(nxs_dyn_handle *h, const nxs_dyn_slab_rows *out /* 
  * Two launches on the handle's stream: the loop (the bins are read as a stream, four intermediates of thermo() are left as rows), then a thread per element with
  * its bins in registers (builds for 2 / 6 / 12 / 16 bins like nxs_dyn_fsd_*).  distinguish_mech_fsd, welding_type, welding_kappa, debug_fsd and the tables are
  * nxs_dyn_fsd_configure's: one copy of each.  nxs_dyn_slab and its refusals are unchanged.
- * OUT OF SCOPE, each needs the coupled ocean's received fields, which no entry point carries: the OceanType::COUPLED guards (FE.cpp:5826-5841: M_sst and M_sss
- * are updated as by a slab ocean), their counterpart in the column (FE.cpp:5348-5358), M_qsrml (FE.cpp:5150-5156).
+ * While a coupled ocean is attached (nxs_dyn_ocean_coupled_attach, below) nxs_dyn_slab and nxs_dyn_slab_coupled -- one slab_element -- skip the two stores of
+ * FE.cpp:5829 and 5841: M_sst and M_sss are NOT advanced, delsss still feeds D_delS, and section 9's Tbot = freezingPoint(M_sss) sees the received salinity.
+ * OUT OF SCOPE: the outgoing side of the coupling (M_cpl_out's accumulators, the reduction over ranks, the OASIS put).
  *   nxs_slab_coupled_config_check   HOST ONLY: nxs_slab_config_check with the configuration's melt_type replaced by `melt_type` (1, 2, 3); 3 needs attached_bins >=
  *                  1 (the throw of FE.cpp:5595).  NXS_ERR_INVALID, the text in nxs_dyn_last_error(NULL)
  *   nxs_dyn_slab_coupled_configure  the melt type of nxs_dyn_slab_coupled, on top of nxs_dyn_slab_configure (NXS_ERR_STATE before it); nothing else is

@@ -114,6 +114,12 @@ public:
         check(nxs_dyn_regrid_thermo_info_get(h_, &info), "regridThermoInfo");
         return info;
     }
+    // A coupled ocean (OceanType::COUPLED, #ifdef OASIS): the receive of ocean_cpl_elements / wave_cpl_elements onto the device rows thermo() reads, and the
+    // COUPLED statements of thermo() (FE.cpp:5150-5157, 5348-5358, 5826-5841) for as long as it is attached.  cfg == nullptr detaches.
+    void oceanCoupledAttach(struct nxs_gridmap *map, const nxs_dyn_ocean_coupled_config *cfg) { check(nxs_dyn_ocean_coupled_attach(h_, map, cfg), "ocean_coupled_attach"); }
+    void oceanCoupledReceive(const double *const *fields, int32_t flags = 0) { check(nxs_dyn_ocean_coupled_receive(h_, fields, flags), "ocean_coupled_receive"); }
+    void oceanCoupledPutRows(const nxs_dyn_ocean_coupled_rows &rows) { check(nxs_dyn_ocean_coupled_put_rows(h_, &rows), "ocean_coupled_put_rows"); }
+    void oceanCoupledGet(const nxs_dyn_ocean_coupled_rows *out, const double **device_rows = nullptr) { check(nxs_dyn_ocean_coupled_get(h_, out, device_rows), "ocean_coupled_get"); }
     nxs_dyn_handle *handle() { return h_; }
 
 private:

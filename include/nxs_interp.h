@@ -200,6 +200,29 @@ NXS_INTERP_API int nxs_gridmap_mesh_to_grid(nxs_gridmap *map, double *out, const
  * the reference's scatter over (cell, position) reaches each triangle -- the same sums, triangle_area included.  A triangle no wet cell touches
  * gets 0 * (1 / 0.), a NaN, as in the reference. */
 NXS_INTERP_API int nxs_gridmap_grid_to_mesh(nxs_gridmap *map, double *out, const double *in, int32_t nb_var, int32_t flags);
+/* The coupler's receive of element variables (ExternalData::check_and_reload of ocean_cpl_elements / wave_cpl_elements, externaldata.cpp:163-236, 461-514,
+ * 1291-1493; dataset.cpp:2828-3031, 3219-3393) in ONE launch: per variable v < n_var (1 .. NXS_GRIDMAP_MAX_RECEIVE)
+ *   receiveCouplingData      t = fields[v][c]; t *= a[v]; t += b[v]           (two roundings; a = 1, b = 0 for I_SST, I_SSS, I_FrcQsr, I_MLD, a = 2 for I_wlbk)
+ *   interpolateDataset       ConservativeRemappingGridToMesh of the transformed fields, as nxs_gridmap_grid_to_mesh: from 0, in the scatter's (cell, position)
+ *                            order, triangle_area summed alongside, times 1. / triangle_area; a triangle no wet cell touches gets 0 * (1 / 0.), a NaN
+ *   ExternalData::get        out_rows[v][t] = factor[v] * x + bias[v]         (the "coupled" step branch, externaldata.cpp:434, 438: always evaluated, so a -0.
+ *                            becomes +0. under factor 1 and bias 0)
+ * fields[v] is an [G] array of its own, as OASIS delivers one 2-D field per get_2d; out_rows[v] an [nels] row of its own.  One thread per triangle walks the
+ * triangle's transposed list once for all variables: the bits are those of nxs_gridmap_grid_to_mesh on the interleaved, transformed input followed by
+ * factor * x + bias.  reduced_nodes_ind is empty for this interpolation method (DataSet::loadGrid builds it only in its FromMeshToMesh2dx / FromMeshToMeshQuick branch,
+ * dataset.cpp:10321-10690; the ConservativeRemapping branch from :10692 leaves it empty), so every
+ * cell of the field is read as delivered; nb_forcing_step = 1; there is no cyclic axis.
+ * flags: NXS_REGRID_IN_DEVICE = fields[] are device pointers, NXS_REGRID_OUT_DEVICE = out_rows[] are (the arrays `fields` and `out_rows` themselves are host
+ * arrays of pointers).  stream: a hipStream_t of the map's device, or NULL for the library's own.  With a stream and device rows out the call is ASYNCHRONOUS on
+ * that stream (host fields are uploaded on it first, and the call waits for the uploads only); otherwise it returns when the rows are written.  The map's
+ * lists are complete when nxs_gridmap_create / _import / _restrict return (they synchronise): a launch on any stream may follow without a fence. */
+#define NXS_GRIDMAP_MAX_RECEIVE 5
+NXS_INTERP_API int nxs_gridmap_receive_rows(nxs_gridmap *map, int32_t n_var, const double *const *fields, const double *a, const double *b, const double *factor,
+                                            const double *bias, double *const *out_rows, int32_t flags, void *stream);
+/* test door: how nxs_gridmap_receive_rows reads the cell and weight of an entry -- 1 (the default: the faster of the two on the 2 km mesh) through
+ * copies of both in transposed order, so that a triangle's walk is contiguous (12 bytes per entry more, made by the first receive on a map, which waits for
+ * them once), 0 through the index list of the transposed lists, as nxs_gridmap_grid_to_mesh does.  The same bits.  *previous (may be NULL) = the mode before */
+NXS_INTERP_API int nxs_gridmap_debug_receive_lists(int32_t mode, int32_t *previous);
 /* Partitioned runs (gridoutput.cpp:691-735: the root computes, everybody filters).  export: the host lists for the caller's broadcast --
  * gridP [rows], off [rows + 1], tris, w [entries], cornerX, cornerY [4*G], sizes from nxs_gridmap_info, any pointer may be NULL; import: a map out of
  * such lists on `device`; restrict: the entries of local triangles (local_of_root [nels of the map], -1 = not here), renumbered, rows left empty

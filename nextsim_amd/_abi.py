@@ -290,6 +290,37 @@ def column_config_struct(base: "ColumnConfig", **options) -> ColumnConfig:
 
 
 # ---- thermo()'s element forcing on the device (include/nxs_dyn.h, nxs_dyn_thermo_forcing_*)
+OC_ROWS = ("ocean_temp", "ocean_salt", "qsrml", "mld", "wlbk")   # NXS_OC_*: the rows a coupled ocean delivers (nxs_dyn_ocean_coupled_*)
+NXS_OC_ROWS = 5
+NXS_GRIDMAP_MAX_RECEIVE = 5
+assert len(OC_ROWS) == NXS_OC_ROWS
+
+
+class OceanCoupledConfig(C.Structure):   # nxs_dyn_ocean_coupled_config
+    _fields_ = [("n_fields", C.c_int32), ("row", C.c_int32 * NXS_OC_ROWS), ("a", C.c_double * NXS_OC_ROWS), ("b", C.c_double * NXS_OC_ROWS),
+                ("factor", C.c_double * NXS_OC_ROWS), ("bias", C.c_double * NXS_OC_ROWS)]
+
+
+class OceanCoupledRows(C.Structure):   # nxs_dyn_ocean_coupled_rows
+    _fields_ = [("row", c_double_p * NXS_OC_ROWS)]
+
+
+def ocean_coupled_config_struct(rows, a=None, b=None, factor=None, bias=None) -> OceanCoupledConfig:
+    """rows: the names (OC_ROWS) or numbers of the received rows in the order the fields arrive; a, b, factor, bias: per field, a scalar or a sequence (default 1, 0,
+    1, 0).  Nothing is checked here: that is nxs_ocean_coupled_config_check's."""
+    c = OceanCoupledConfig()
+    rows = list(rows)
+    c.n_fields = len(rows)
+    for k, r in enumerate(rows[:NXS_OC_ROWS]):
+        c.row[k] = OC_ROWS.index(r) if isinstance(r, str) else int(r)
+    for name, v, dflt in (("a", a, 1.), ("b", b, 0.), ("factor", factor, 1.), ("bias", bias, 0.)):
+        vals = np.broadcast_to(np.asarray(dflt if v is None else v, np.float64), (len(rows),)) if len(rows) else np.zeros(0)
+        arr = getattr(c, name)
+        for k in range(NXS_OC_ROWS):
+            arr[k] = float(vals[k]) if k < len(rows) else dflt
+    return c
+
+
 TF_ROWS = FLUX_ATMOSPHERE + COL_FORCING   # NXS_TF_*: tair .. longwave are d_flux_atm's rows, precip .. mld d_col_forcing's
 NXS_TF_ROWS = 10
 NXS_TF_SETS = 4

@@ -93,10 +93,17 @@ int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt) try {   // thermo()'s slab loo
     if (!h->col_configured) return fail(h, NXS_ERR_STATE, "column before nxs_dyn_column_configure");
     if (!h->have_mesh || !h->have_state || !h->flux_done) return fail(h, NXS_ERR_STATE, "column before nxs_dyn_fluxes on this mesh (its rows, and tice0, tsurf_young, sst, sss, are the column's inputs)");
     const nxs_dyn_column_config &g = h->col_cfg;
+    const bool coupled = ocean_coupled_on(h);   // the reference's OceanType::COUPLED, FE.cpp:5348-5358: the configuration's ocean_type is not consulted
+    if (coupled && g.freezingpoint_type != NXS_COL_FREEZINGPOINT_UNESCO)
+        return fail(h, NXS_ERR_STATE, "column: a coupled ocean is attached and freezingpoint_type is not UNESCO (FE.cpp:1246: the reference overrides the option when coupled to an ocean)");
+    if (coupled)
+        for (int k = 2; k <= 3; ++k)
+            if (!(h->col_forcing_have & (1u << k)))
+                return fail(h, NXS_ERR_STATE, "column: a coupled ocean is attached and %s is missing on this mesh (nxs_dyn_ocean_coupled_receive / _put_rows)", k == 2 ? "ocean_temp" : "ocean_salt");
     unsigned need = 0;   // bits of nxs_dyn_column_forcing: precip, snow, ocean_temp, ocean_salt, mld
     if (g.snowfall_source != NXS_COL_SNOWFALL_SNOWFALL) need |= 1u << 0;
     if (g.snowfall_source != NXS_COL_SNOWFALL_PRECIP_TAIR) need |= 1u << 1;
-    if (g.ocean_type != NXS_COL_OCEAN_CONSTANT) need |= (1u << 2) | (1u << 3);
+    if (g.ocean_type != NXS_COL_OCEAN_CONSTANT || coupled) need |= (1u << 2) | (1u << 3);
     if (g.mld_source == NXS_COL_MLD_ROW) need |= 1u << 4;
     if ((h->col_forcing_have & need) != need)
         return fail(h, NXS_ERR_STATE, "column: a forcing row is missing on this mesh (nxs_dyn_column_set_forcing after set_mesh / regrid; needed 0x%x, present 0x%x)", need, h->col_forcing_have);
@@ -109,7 +116,7 @@ int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt) try {   // thermo()'s slab loo
     const size_t Ne = h->dm.Ne;
     if (!h->d_col_out) { if (int rc = dev_alloc(h, h->state_allocs, &h->d_col_out, (size_t)COL_ROWS * Ne)) return rc; }
     ColDev c{};
-    c.thermo_type = g.thermo_type; c.qio_type = g.qio_type; c.freezingpoint_type = g.freezingpoint_type; c.ocean_type = g.ocean_type;
+    c.thermo_type = g.thermo_type; c.qio_type = g.qio_type; c.freezingpoint_type = g.freezingpoint_type; c.ocean_type = coupled ? (int)NXS_COL_OCEAN_COUPLED : g.ocean_type;
     c.snowfall_source = g.snowfall_source; c.mld_source = g.mld_source; c.flooding = g.flooding != 0; c.young_cat = h->dp.young_cat ? 1 : 0;
     c.mu = g.freezingpoint_mu; c.ks = g.snow_cond; c.Csens_io = g.Csens_io; c.constant_mld = g.constant_mld; c.timeT = g.nudge_timeT; c.timeS = g.nudge_timeS;
     c.Qdw_const = g.Qdw_const; c.Fdw_const = g.Fdw_const; c.dt = double(dt);
@@ -118,7 +125,7 @@ int nxs_dyn_column(nxs_dyn_handle *h, int32_t dt) try {   // thermo()'s slab loo
     const double *any = h->d_flux_atm[0];
     const ColArrays a{h->dm.Ne, h->dm.Nn, h->dm.t0, h->dm.t1, h->dm.t2, h->ds.VT, h->ds.ocean, h->d_flux_atm[0], fo[0] ? fo[0] : any, fo[1] ? fo[1] : any, fo[2] ? fo[2] : any,
                        fo[3] ? fo[3] : any, fo[4] ? fo[4] : any, h->d_flux_out, h->ds.conc, h->ds.thick, h->ds.snow, h->ds.cyoung, h->ds.hyoung, h->ds.hsyoung,
-                       st[0], h->d_col_st[0], h->d_col_st[1], st[1], st[2], st[3], h->d_col_out};
+                       st[0], h->d_col_st[0], h->d_col_st[1], st[1], st[2], st[3], h->d_col_out, coupled ? st[2] : nullptr, coupled ? st[3] : nullptr};
     LAUNCH(h, k_column, h->dm.Ne, a, c);
     HIPCHK(h, hipGetLastError());
     h->col_done = true;

@@ -6,7 +6,8 @@
 // [Ne] and a thread touches entry e of it; only the EXCHANGE scheme gathers M_VT and M_ocean at the three nodes.  No LDS, no atomics.  Operand order is the
 // reference's, divisions stay divisions, the build is uncontracted (-ffp-contract=off).  The only library calls are sqrt (Winton's (21) and (38), the UNESCO
 // freezing point) and hypot (EXCHANGE).  Where the reference makes a transient NaN (0 / 0 in (26) or (39) of a layer that has gone) the kernel makes the same one.
-// NOT here: Winton's LOG(WARNING) when everything sublimates and its assert(Msurf >= 0); the OceanType::COUPLED branch (#ifdef OASIS); thermo() from FE.cpp:5413 on.
+// NOT here: Winton's LOG(WARNING) when everything sublimates and its assert(Msurf >= 0); thermo() from FE.cpp:5413 on.  The OceanType::COUPLED branch (#ifdef OASIS,
+// FE.cpp:5348-5358) runs while a coupled ocean is attached (nxs_dyn_ocean_coupled_attach): the host then passes NXS_COL_OCEAN_COUPLED, whatever was configured.
 
 // physical::, model/constants.hpp (rhow, rhoi, rhos, Lf, C and si are nxs_dyn_kernels.inl's)
 #define NXS_CPW 4186.84
@@ -35,6 +36,7 @@ struct ColArrays {
     double *tice0, *tice1, *tice2, *tsurf_young;                // in place
     const double *sst, *sss;
     double *out;                                                // [COL_ROWS][Ne]
+    double *sst_reset, *sss_reset;                              // the same two rows, writable: OceanType::COUPLED resets them (NULL otherwise)
 };
 
 // freezingPoint, FE.cpp:6432-6448
@@ -265,12 +267,19 @@ __global__ void __launch_bounds__(BLOCK) k_column(ColArrays a, ColDev c) {
     tmp_snowfall = STD_MAX(0., tmp_snowfall);
     double mld = c.constant_mld;
     if (c.mld_source == NXS_COL_MLD_ROW) mld = a.mld[e];
-    const double sst = a.sst[e], sss = a.sss[e];
+    double sst = a.sst[e], sss = a.sss[e];
     // the flux due to nudging, FE.cpp:5343-5366
     double Qdw, Fdw;
     if (c.ocean_type == NXS_COL_OCEAN_CONSTANT) {
         Qdw = c.Qdw_const;
         Fdw = c.Fdw_const;
+    } else if (c.ocean_type == NXS_COL_OCEAN_COUPLED) {   // FE.cpp:5348-5358: no nudging, M_sst and M_sss are reset to the values received (an attached coupled ocean)
+        Qdw = 0;
+        Fdw = 0;
+        sst = a.ocean_temp[e];
+        sss = a.ocean_salt[e];
+        a.sst_reset[e] = sst;
+        a.sss_reset[e] = sss;
     } else {
         Qdw = -(sst - a.ocean_temp[e]) * mld * NXS_RHOW * NXS_CPW / c.timeT;
         const double delS = sss - a.ocean_salt[e];

@@ -244,6 +244,15 @@ struct Diffusion {         // nxs_dyn_diffuse: the element-to-element table and 
     int *d_diff_ec = nullptr;              // [Ne][3] bamgmesh->ElementConnectivity, 0-based, -1 on the boundary
     double *d_diff_old = nullptr;          // [Ne] pairs {sst, sss}
 };
+struct OceanCoupled {      // nxs_dyn_ocean_coupled_*: the attachment of a coupled ocean and the two received rows that are no column forcing (ocean_temp, ocean_salt, mld: d_col_forcing)
+    std::vector<void *> oc_allocs;
+    bool oc_attached = false;
+    struct nxs_gridmap *oc_map = nullptr;  // borrowed; NULL: a host that only uses nxs_dyn_ocean_coupled_put_rows
+    nxs_dyn_ocean_coupled_config oc_cfg{};
+    unsigned oc_rows = 0;                  // bit NXS_OC_*: that row is configured
+    double *d_oc_qsrml = nullptr, *d_oc_wlbk = nullptr;   // [Ne] M_qsrml, M_wlbk, made when first given
+    unsigned oc_have = 0;                  // bit NXS_OC_QSRML / NXS_OC_WLBK: that row was given on this mesh
+};
 struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stress / nxs_dyn_put_coupled) and the floe-size distribution's (nxs_dyn_fsd_*)
     std::vector<void *> coupled_allocs;
     // ATTACHED is what h->dw says (tau_wi, cum_damage, conc_fsd non-NULL) and fsd_mech / fsd_cumw non-NULL; a detached buffer is kept for the next attach (no hipFree
@@ -267,7 +276,7 @@ struct MeansPoints {       // nxs_dyn_means_points_*: a loaded grid, its rotatio
     std::vector<int32_t> mp_lsm;               // [G] M_lsm (applyLSM works on the copy nxs_dyn_means_points_get hands out)
 };
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, CoupledBuffers, MeansPoints {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, CoupledBuffers, MeansPoints {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -678,6 +687,13 @@ void release_thermo_forcing(nxs_dyn_handle *h) { release_group<ThermoForcing>(h,
 void release_nodal_forcing(nxs_dyn_handle *h) { release_group<NodalForcing>(h, h->nf_allocs); }
 void release_nesting(nxs_dyn_handle *h) { release_group<Nesting>(h, h->nest_allocs); }
 void release_diffusion(nxs_dyn_handle *h) { release_group<Diffusion>(h, h->diff_allocs); }
+// the coupled ocean: its two rows and the attachment itself -- the map was the old mesh's (FE.cpp:8037-8049: new weights after a regrid)
+void release_ocean_coupled(nxs_dyn_handle *h) { release_group<OceanCoupled>(h, h->oc_allocs); }
+// thermo() runs its OceanType::COUPLED branches (FE.cpp:5150-5157, 5348-5358, 5826-5841): a coupled ocean is attached with ocean_temp, ocean_salt and qsrml configured
+inline bool ocean_coupled_on(const nxs_dyn_handle *h) {
+    const unsigned need = (1u << NXS_OC_OCEAN_TEMP) | (1u << NXS_OC_OCEAN_SALT) | (1u << NXS_OC_QSRML);
+    return h->oc_attached && (h->oc_rows & need) == need;
+}
 // the loaded grid of the Moorings with its accumulators: nxs_dyn_means_points_set (a new grid, or none) and nxs_dyn_destroy -- not release_mesh
 void release_means_points(nxs_dyn_handle *h) { release_group<MeansPoints>(h, h->mp_allocs); }
 // the coupled build's buffers; their attachments are members of h->dw
@@ -712,6 +728,7 @@ void release_mesh(nxs_dyn_handle *h) {
     release_nodal_forcing(h);
     release_nesting(h);
     release_diffusion(h);
+    release_ocean_coupled(h);
     release_coupled(h);
     h->no_big_cut = false;
     h->rank = 0; h->nranks = 1;   // (the partition is the mesh's: a single rank until nxs_dyn_set_halo says otherwise)
@@ -4078,6 +4095,7 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_thermo_forcing.inl"
 #include "nxs_nesting.inl"
 #include "nxs_nodal_forcing.inl"
+#include "nxs_ocean_coupled.inl"
 #include "nxs_means_points.inl"
 
 }  // extern "C"

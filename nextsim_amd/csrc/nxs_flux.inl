@@ -88,6 +88,8 @@ int nxs_dyn_fluxes(nxs_dyn_handle *h) try {   // thermo()'s "fluxes" timer, FE.c
         return fail(h, NXS_ERR_STATE, "fluxes: an atmosphere row is missing on this mesh (nxs_dyn_flux_set_atmosphere; mask of the rows present 0x%x)", h->flux_atm_have);
     if (h->flux_st_have != (1u << FLUX_ST_ROWS) - 1)
         return fail(h, NXS_ERR_STATE, "fluxes: a flux row is missing on this mesh (nxs_dyn_flux_put after set_mesh / regrid; mask of the rows present 0x%x)", h->flux_st_have);
+    if (ocean_coupled_on(h) && !(h->oc_have & (1u << NXS_OC_QSRML)))
+        return fail(h, NXS_ERR_STATE, "fluxes: a coupled ocean is attached and qsrml is missing on this mesh (nxs_dyn_ocean_coupled_receive / _put_rows; FE.cpp:5150-5157)");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = launch_gave_up(h)) return rc;
     const size_t Ne = h->dm.Ne;
@@ -102,7 +104,7 @@ int nxs_dyn_fluxes(nxs_dyn_handle *h) try {   // thermo()'s "fluxes" timer, FE.c
     double *const *at = h->d_flux_atm, *const *st = h->d_flux_st;
     const FluxArrays a{h->dm.Ne, h->dm.Nn, h->dp.young_cat, h->dm.t0, h->dm.t1, h->dm.t2, h->ds.wind, at[0], at[1], at[2], at[3], at[4],
                        h->ds.conc, h->ds.snow, h->ds.cyoung, h->ds.hsyoung, st[0], st[1], st[2], st[6], st[7],
-                       h->ds.drag_ui, st[4], h->ds.drag_ui_young, st[5], h->d_flux_out, h->d_tau_ow};
+                       h->ds.drag_ui, st[4], h->ds.drag_ui_young, st[5], h->d_flux_out, h->d_tau_ow, ocean_coupled_on(h) ? h->d_oc_qsrml : nullptr};
     LAUNCH(h, k_fluxes, h->dm.Ne, a, c);
     HIPCHK(h, hipGetLastError());
     h->tau_ow_attached = true;   // D_tau_ow is the handle's own now: taux / tauy / taumod of nxs_dyn_means_update need no upload

@@ -81,6 +81,7 @@ struct FluxArrays {
     double *drag_ui, *drag_ti, *drag_ui_young, *drag_ti_young;   // updated in place
     double *out;                                            // [FLUX_ROWS][Ne], row FLUX_TAU_OW unused:
     double *tau_ow;                                         // D_tau_ow is the row the Moorings means read
+    const double *qsrml;                                    // [Ne] M_qsrml of an attached coupled ocean (nxs_dyn_ocean_coupled_*), NULL without one
 };
 
 struct FluxAtm { double mslp, tair, sphuma, rhoair, wspeed, Qsw_in, Qlw_in; };
@@ -243,7 +244,8 @@ __global__ void __launch_bounds__(BLOCK) k_fluxes(FluxArrays a, FluxDev c) {
         const double Qlw_out = NXS_EPS * NXS_SIGMA_SB * pow(sst + NXS_TFRWK, 4.);
         const double Qlw = Qlw_out - at.Qlw_in;
         double Qow = Qlw + Qsh + Qlh;
-        Qow += Qsw;
+        if (a.qsrml) Qow += Qsw * a.qsrml[e];   // OceanType::COUPLED, FE.cpp:5150-5157: the short wave the ocean's first layer absorbs
+        else Qow += Qsw;
         a.out[FLUX_QOW * n + e] = Qow; a.out[FLUX_QLW_OW * n + e] = Qlw; a.out[FLUX_QSW_OW * n + e] = Qsw; a.out[FLUX_QLH_OW * n + e] = Qlh;
         a.out[FLUX_QSH_OW * n + e] = Qsh; a.out[FLUX_EVAP * n + e] = evap;
         a.tau_ow[e] = at.rhoair * drag_ocean_m;

@@ -103,4 +103,35 @@ __global__ void __launch_bounds__(256) k_gridmap_to_mesh(long long total, int nb
     out[gid] = nxs_remap::mesh_value(in, nb_var, var, t_pos + lo, t_off[t + 1] - lo, cell, w);
 }
 
+// The coupler's receive (nxs_gridmap_receive_rows): up to kMaxReceive element variables, each an [G] field of its own in and an [Ne] row of its own out.
+// One thread per triangle: its transposed list is walked ONCE for all variables (k_gridmap_to_mesh walks it once per variable), the transform t * a + b is
+// applied as a cell is gathered, factor * x + bias as the row is stored -- consecutive threads store consecutive entries of every row.  Same sums in the same
+// order as k_gridmap_to_mesh on the interleaved, transformed input (nxs_remap::receive_values); no atomics.  PERM: cell / w are copies in transposed order.
+constexpr int kMaxReceive = 5;
+struct ReceiveArgs {
+    const double *field[kMaxReceive];
+    double *out[kMaxReceive];
+    nxs_remap::ReceiveCoef co[kMaxReceive];
+};
+template <int NV, bool PERM>
+__global__ void __launch_bounds__(256) k_gridmap_receive(int nels, const int *__restrict__ t_off, const int *__restrict__ t_pos, const int *__restrict__ cell,
+                                                         const double *__restrict__ w, ReceiveArgs r) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nels) return;
+    const int lo = t_off[t];
+    double v[NV];
+    nxs_remap::receive_values<NV>(r.field, r.co, PERM ? nullptr : t_pos, lo, t_off[t + 1] - lo, cell, w, v);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) r.out[i][t] = v[i];
+}
+// cell / w in transposed order, for PERM: one thread per entry
+__global__ void __launch_bounds__(256) k_gridmap_permute(int n, const int *__restrict__ t_pos, const int *__restrict__ cell, const double *__restrict__ w,
+                                                         int *__restrict__ cell_t, double *__restrict__ w_t) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const int p = t_pos[k];
+    cell_t[k] = cell[p];
+    w_t[k] = w[p];
+}
+
 }  // namespace gridmap

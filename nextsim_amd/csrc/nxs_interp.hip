@@ -1073,6 +1073,7 @@ namespace {
 #include "nxs_gridmap_kernels.inl"
 int g_gridmap_chunk = 0;        // test door (nxs_gridmap_debug_chunk): cells per chunk of the weights build, 0 = as many as the arena allows
 int g_gridmap_last_chunks = 0;  // chunks the last nxs_gridmap_create of the process took
+int g_gridmap_receive_lists = 1;  // nxs_gridmap_debug_receive_lists: 0 = the receive walks cell / w through t_pos, 1 (the faster on the 2 km mesh: DESIGN 6n) = through copies in transposed order
 }  // namespace
 
 struct nxs_gridmap {
@@ -1083,6 +1084,10 @@ struct nxs_gridmap {
     DevBuf<double> dw, drarea;             // weights; 1 / area(cell) per row
     DevBuf<int> drow_of_cell;              // [G] row of a cell, -1 = land
     DevBuf<int> dt_off, dt_pos, dcell;     // the transposed lists: per triangle the indices of its entries, ascending; the cell of every entry
+    DevBuf<int> dcell_t;                   // nxs_gridmap_receive_rows: copies of cell and w in transposed
+    DevBuf<double> dw_t;                   // order, made by the first call on the map (12 bytes per entry; not under nxs_gridmap_debug_receive_lists(0))
+    DevBuf<double> dstage;                 // ... with host fields: where they are uploaded, [n_var][G]; it only grows
+    size_t stage_cap = 0;
 };
 
 namespace {
@@ -1300,6 +1305,69 @@ extern "C" int nxs_gridmap_grid_to_mesh(nxs_gridmap *g, double *out, const doubl
     if (!out_dev && copy_sync(out, dout.p, (size_t)total * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
     return NXS_OK;
 } catch (...) { return entry_caught("nxs_gridmap_grid_to_mesh"); }
+
+// The coupler's receive: receiveCouplingData's transform, ConservativeRemappingGridToMesh and ExternalData::get's factor / bias in one launch on `stream`
+// (dataset.cpp:2828-3031, ConservativeRemapping.cpp:138-171, externaldata.cpp:434-438).  fields [n_var] of [G], out_rows [n_var] of [nels]
+extern "C" int nxs_gridmap_receive_rows(nxs_gridmap *g, int32_t n_var, const double *const *fields, const double *a, const double *b, const double *factor,
+                                        const double *bias, double *const *out_rows, int32_t flags, void *stream) try {
+    if (!g || !fields || !a || !b || !factor || !bias || !out_rows) return fail(NXS_ERR_INVALID, "receive_rows: NULL argument");
+    if (n_var < 1 || n_var > gridmap::kMaxReceive) return fail(NXS_ERR_INVALID, "receive_rows: n_var = %d (1 .. %d)", n_var, gridmap::kMaxReceive);
+    for (int v = 0; v < n_var; ++v)
+        if (!fields[v] || !out_rows[v]) return fail(NXS_ERR_INVALID, "receive_rows: %s %d is NULL", fields[v] ? "output row" : "field", v);
+    if (hipSetDevice(g->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    const bool in_dev = flags & NXS_REGRID_IN_DEVICE, out_dev = flags & NXS_REGRID_OUT_DEVICE;
+    const hipStream_t st = stream ? (hipStream_t)stream : S();
+    const size_t G = (size_t)g->G, nels = (size_t)g->nels;
+    const bool perm = g_gridmap_receive_lists == 1 && g->n > 0;
+    if (perm && !g->dcell_t.p) {
+        if (g->dcell_t.alloc(g->n) || g->dw_t.alloc(g->n)) return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        hipLaunchKernelGGL(gridmap::k_gridmap_permute, dim3((unsigned)((g->n + 255) / 256)), dim3(256), 0, st, (int)g->n, (const int *)g->dt_pos.p, (const int *)g->dcell.p,
+                           (const double *)g->dw.p, g->dcell_t.p, g->dw_t.p);
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "permuting the lists failed: %s", hipGetErrorString(hipGetLastError()));   // (once: a later call may come on another stream)
+    }
+    gridmap::ReceiveArgs r{};
+    DevBuf<double> dout;
+    if (!in_dev) {   // the fields go up on the same stream; the host arrays are the caller's again on return
+        if (g->stage_cap < (size_t)n_var * G) {
+            if (g->dstage.alloc((size_t)n_var * G)) { g->stage_cap = 0; return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError())); }
+            g->stage_cap = (size_t)n_var * G;
+        }
+        for (int v = 0; v < n_var; ++v)
+            if (hipMemcpyAsync(g->dstage.p + (size_t)v * G, fields[v], G * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return fail(NXS_ERR_HIP, "upload failed");
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "upload failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (!out_dev && dout.alloc((size_t)n_var * nels)) return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+    for (int v = 0; v < n_var; ++v) {
+        r.field[v] = in_dev ? fields[v] : g->dstage.p + (size_t)v * G;
+        r.out[v] = out_dev ? out_rows[v] : dout.p + (size_t)v * nels;
+        r.co[v] = nxs_remap::ReceiveCoef{a[v], b[v], factor[v], bias[v]};
+    }
+    const dim3 grid((unsigned)((nels + 255) / 256)), block(256);
+    const int *t_off = g->dt_off.p, *t_pos = g->dt_pos.p, *cell = perm ? g->dcell_t.p : g->dcell.p;
+    const double *w = perm ? g->dw_t.p : g->dw.p;
+#define NXS_RECEIVE(NV)                                                                                                             \
+    case NV:                                                                                                                        \
+        if (perm) hipLaunchKernelGGL((gridmap::k_gridmap_receive<NV, true>), grid, block, 0, st, (int)nels, t_off, t_pos, cell, w, r);  \
+        else hipLaunchKernelGGL((gridmap::k_gridmap_receive<NV, false>), grid, block, 0, st, (int)nels, t_off, t_pos, cell, w, r);      \
+        break;
+    switch (n_var) { NXS_RECEIVE(1) NXS_RECEIVE(2) NXS_RECEIVE(3) NXS_RECEIVE(4) NXS_RECEIVE(5) }
+#undef NXS_RECEIVE
+    if (hipGetLastError() != hipSuccess) return fail(NXS_ERR_HIP, "receive kernel launch failed");
+    if (stream && out_dev) return NXS_OK;   // asynchronous on the caller's stream
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "receive kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!out_dev)
+        for (int v = 0; v < n_var; ++v)
+            if (copy_sync(out_rows[v], dout.p + (size_t)v * nels, nels * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_receive_rows"); }
+
+// test door: how nxs_gridmap_receive_rows reads cell / w -- 0 through t_pos, 1 through copies in transposed order; *previous (may be NULL) = the mode before
+extern "C" int nxs_gridmap_debug_receive_lists(int32_t mode, int32_t *previous) try {
+    if (mode != 0 && mode != 1) return fail(NXS_ERR_INVALID, "mode must be 0 or 1");
+    if (previous) *previous = g_gridmap_receive_lists;
+    g_gridmap_receive_lists = mode;
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_debug_receive_lists"); }
 
 // the host form of the lists for the caller's broadcast; sizes from nxs_gridmap_info; any pointer may be NULL
 extern "C" int nxs_gridmap_export(nxs_gridmap *g, int32_t *gridP, int32_t *off, int32_t *tris, double *w, double *cornerX, double *cornerY) try {

@@ -202,6 +202,7 @@ int nxs_dyn_diffuse(nxs_dyn_handle *h) try {
     if (multi_rank(h) || h->have_halo)
         return fail(h, NXS_ERR_STATE, "diffuse: this handle has halo lists set (rank %d of %d): the reference diffuses on its root rank from gathered fields, and the gather / scatter "
                                       "of a partitioned run is not done here", h->rank, h->nranks);
+    if (ocean_coupled_on(h)) return fail(h, NXS_ERR_STATE, "diffuse: a coupled ocean is attached (nxs_dyn_ocean_coupled_attach): the reference does not diffuse M_sst / M_sss when coupled to an ocean (FE.cpp:3934-3940)");
     if (!h->diff_on[0] && !h->diff_on[1]) return NXS_OK;   // "nothing to do" (FE.cpp:2762-2767)
     double *sst = h->d_flux_st[2], *sss = h->d_flux_st[3];
     if (!(h->flux_st_have & (1u << 2))) return fail(h, NXS_ERR_STATE, "diffuse: sst was never put on this mesh (nxs_dyn_flux_put after set_mesh / regrid)");

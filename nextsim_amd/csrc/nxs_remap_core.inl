@@ -301,6 +301,33 @@ NXS_HD inline double mesh_value(const double *in, int nb_var, int var, const int
     return v;
 }
 
+// The coupler's receive of NV element variables at once (nxs_gridmap_receive_rows), one triangle: receiveCouplingData's t = f[c]; t *= a; t += b per gathered
+// cell (dataset.cpp:2828-3031), mesh_value's sums for every variable over ONE walk of the triangle's list with one triangle_area, then ExternalData::get's
+// factor * x + bias (externaldata.cpp:434-438).  field[v] is an [G] array of its own; pos == nullptr: cell / w are already in transposed order (entry k itself).
+struct ReceiveCoef { double a, b, factor, bias; };
+template <int NV>
+NXS_HD inline void receive_values(const double *const *field, const ReceiveCoef *co, const int *pos, int lo, int n, const int *cell, const double *w, double *out) {
+    double v[NV], triangle_area = 0.;
+    for (int i = 0; i < NV; ++i) v[i] = 0.;
+    for (int k = lo; k < lo + n; ++k) {
+        const int p = pos ? pos[k] : k;
+        const double wp = w[p];
+        const int c = cell[p];
+        triangle_area += wp;
+        for (int i = 0; i < NV; ++i) {
+            double t = field[i][c];
+            t *= co[i].a;
+            t += co[i].b;
+            v[i] += t * wp;
+        }
+    }
+    const double r_triangle_area = 1. / triangle_area;
+    for (int i = 0; i < NV; ++i) {
+        v[i] *= r_triangle_area;
+        out[i] = co[i].factor * v[i] + co[i].bias;
+    }
+}
+
 // nodes_old == nodes_new after sorting (ConservativeRemapping.cpp:263-289).  previous_numbering may be
 // NULL (no vertex survived); the ">" (not ">=") against the number of geometric vertices is the reference's.
 NXS_HD inline bool same_triangle(const OldMesh &m, int seed, const int *new_tri, const double *previous_numbering, int n_geom) {

@@ -141,7 +141,7 @@ static int slab_launch_args(nxs_dyn_handle *h, bool coupled, int32_t dt, const n
               (g.include_young_ice && g.reset_by_date ? SF_YOUNG_IN_MYI_RESET : 0) /* FE.cpp:5649-5650 */ | (g.equal_melting ? SF_EQUAL_MELTING : 0) |
               (young ? SF_YOUNG_CAT : 0) | (winton ? SF_WINTON : 0) | (cg.mld_source == NXS_COL_MLD_ROW ? SF_MLD_ROW : 0) |
               (clock->first_step_of_day ? SF_FIRST_STEP : 0) | (clock->last_step_of_day ? SF_LAST_STEP : 0) | (clock->fyi_reset_now ? SF_FYI_RESET : 0) |
-              (clock->myi_reset_now ? SF_MYI_RESET : 0) | (clock->onset_reset_now ? SF_ONSET_RESET : 0);
+              (clock->myi_reset_now ? SF_MYI_RESET : 0) | (clock->onset_reset_now ? SF_ONSET_RESET : 0) | (ocean_coupled_on(h) ? SF_OCEAN_COUPLED : 0);
     c.rh0 = 1. / g.hnull; c.rPhiF = 1. / g.PhiF;   // FE.cpp:5184-5185
     c.PhiF = g.PhiF; c.PhiM = g.PhiM; c.h_young_min = g.h_young_min;
     c.h_young_max_sharp = .5 * (g.h_young_min + g.h_young_max);   // FE.cpp:1198

@@ -34,7 +34,8 @@ static_assert(SLAB_ROWS == NXS_SLAB_ROWS && (int)SLAB_QASSIM == (int)NXS_SLAB_QA
 // the switches of the configuration and the clock: one word, uniform
 enum { SF_ASSIM = 1 << 0, SF_HEALING = 1 << 1, SF_PONDS = 1 << 2, SF_RESET_BY_DATE = 1 << 3, SF_YOUNG_IN_MYI_RESET = 1 << 4 /* age.include_young_ice && age.reset_by_date:
        FE.cpp:5649-5650 */, SF_EQUAL_MELTING = 1 << 5, SF_YOUNG_CAT = 1 << 6, SF_WINTON = 1 << 7, SF_MLD_ROW = 1 << 8,
-       SF_FIRST_STEP = 1 << 9, SF_LAST_STEP = 1 << 10, SF_FYI_RESET = 1 << 11, SF_MYI_RESET = 1 << 12, SF_ONSET_RESET = 1 << 13 /* nxs_dyn_slab_clock */ };
+       SF_FIRST_STEP = 1 << 9, SF_LAST_STEP = 1 << 10, SF_FYI_RESET = 1 << 11, SF_MYI_RESET = 1 << 12, SF_ONSET_RESET = 1 << 13 /* nxs_dyn_slab_clock */,
+       SF_OCEAN_COUPLED = 1 << 14 /* OceanType::COUPLED: a coupled ocean is attached (nxs_dyn_ocean_coupled_attach), M_sst and M_sss are not advanced */ };
 
 struct SlabDev {
     int newice_type, melt_type;
@@ -419,7 +420,8 @@ __device__ __forceinline__ void slab_element(const SlabArrays &a, const SlabDev 
     }
     const double Qdw = K[COL_QDW * n], Fdw = K[COL_FDW * n];
     double Qow_mean = Qow * old_ow_fraction;
-    sst = sst - ddt * (Qio_mean + Qow_mean - Qdw + Qassm) / (NXS_RHOW * NXS_CPW * mld);
+    const bool ocean_coupled = (c.flags & SF_OCEAN_COUPLED) != 0;   // FE.cpp:5826-5828, 5838-5840
+    if (!ocean_coupled) sst = sst - ddt * (Qio_mean + Qow_mean - Qdw + Qassm) / (NXS_RHOW * NXS_CPW * mld);
     double denominator = (mld * NXS_RHOW - del_vi * NXS_RHOI - (del_vs_mlt * NXS_RHOS + (emp - Fdw) * ddt));
     if (!(denominator > 1. * NXS_RHOW)) {
         br |= NXS_SLAB_BR_DENOM_CLAMP;
@@ -429,8 +431,10 @@ __device__ __forceinline__ void slab_element(const SlabArrays &a, const SlabDev 
     const double si_eff = STD_MIN(sss, NXS_SI);
     if (sss < NXS_SI) br |= NXS_SLAB_BR_SSS_BELOW_SI;
     const double delsss = ((sss - si_eff) * NXS_RHOI * del_vi + sss * (del_vs_mlt * NXS_RHOS + (emp - Fdw) * ddt)) / denominator;
-    sss += delsss;
-    a.sst[e] = sst; a.sss[e] = sss;
+    if (!ocean_coupled) {
+        sss += delsss;
+        a.sst[e] = sst; a.sss[e] = sss;
+    }
     if (thick > old_vol) {
         br |= NXS_SLAB_BR_RIDGE;
         ridge *= old_vol / thick;

@@ -126,6 +126,12 @@ def load_library():
     L.nxs_dyn_diffusion_configure.argtypes = [H, C.c_double, C.c_double, C.c_double, C.c_double]
     L.nxs_dyn_diffuse.argtypes = [H]
     L.nxs_dyn_flux_device_rows.argtypes = [H, P(C.c_void_p)]
+    L.nxs_ocean_coupled_default_config.argtypes = [P(_abi.OceanCoupledConfig)]
+    L.nxs_ocean_coupled_config_check.argtypes = [P(_abi.OceanCoupledConfig)]
+    L.nxs_dyn_ocean_coupled_attach.argtypes = [H, C.c_void_p, P(_abi.OceanCoupledConfig)]
+    L.nxs_dyn_ocean_coupled_receive.argtypes = [H, P(C.c_void_p), C.c_int32]
+    L.nxs_dyn_ocean_coupled_put_rows.argtypes = [H, P(_abi.OceanCoupledRows)]
+    L.nxs_dyn_ocean_coupled_get.argtypes = [H, P(_abi.OceanCoupledRows), P(C.c_void_p)]
     L.nxs_slab_default_config.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_config_check.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_constants.argtypes = [P(C.c_double), C.c_int32]
@@ -270,6 +276,8 @@ EXPORTS = (
     "nxs_dyn_forcing_get",
     "nxs_nesting_config_check", "nxs_dyn_nesting_configure", "nxs_dyn_nesting_pair", "nxs_dyn_nesting_time", "nxs_dyn_nesting_ice", "nxs_dyn_nesting_dynamics",
     "nxs_dyn_nesting_get", "nxs_dyn_diffusion_configure", "nxs_dyn_diffuse", "nxs_dyn_flux_device_rows",
+    "nxs_ocean_coupled_default_config", "nxs_ocean_coupled_config_check", "nxs_dyn_ocean_coupled_attach", "nxs_dyn_ocean_coupled_receive", "nxs_dyn_ocean_coupled_put_rows",
+    "nxs_dyn_ocean_coupled_get",
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_to_grid_conservative", "nxs_dyn_means_reset",
@@ -284,7 +292,7 @@ INTERP_EXPORTS = ("nxs_interp_mesh_to_mesh_2d", "nxs_interp_mesh_to_grid", "nxs_
                   "nxs_interp_last_error", "nxs_interp_last_info", "nxs_mesh_convex_completion", "nxs_mesh_convex_completion_mode", "nxs_regrid_create", "nxs_regrid_destroy",
                   "nxs_regrid_interp_nodes", "nxs_regrid_remap_elements", "nxs_interp_last_timing", "nxs_regrid_debug_tables", "nxs_gridmap_create", "nxs_gridmap_destroy",
                   "nxs_gridmap_info", "nxs_gridmap_mesh_to_grid", "nxs_gridmap_grid_to_mesh", "nxs_gridmap_export", "nxs_gridmap_import", "nxs_gridmap_restrict",
-                  "nxs_gridmap_debug_chunk")
+                  "nxs_gridmap_debug_chunk", "nxs_gridmap_receive_rows", "nxs_gridmap_debug_receive_lists")
 
 
 def selftest_quotients(n: int, seed: int = 1, mode: int = 0, device: int = 0) -> int:
@@ -486,6 +494,22 @@ def nesting_config_check(**options):
     L = load_library()
     rc = L.nxs_nesting_config_check(C.byref(_nesting_config(**options)))
     return rc, (L.nxs_dyn_last_error(None) or b"").decode() if rc else ""
+
+
+def ocean_coupled_default_config() -> dict:
+    """nxs_ocean_coupled_default_config: the rows of the reference's receive (coupler.rcv_first_layer_depth off, no wave model) and their coefficients."""
+    c = _abi.OceanCoupledConfig()
+    rc = load_library().nxs_ocean_coupled_default_config(C.byref(c))
+    if rc:
+        raise NxsError(rc, "nxs_ocean_coupled_default_config")
+    n = c.n_fields
+    return {"rows": tuple(_abi.OC_ROWS[c.row[k]] for k in range(n)), "a": list(c.a[:n]), "b": list(c.b[:n]), "factor": list(c.factor[:n]), "bias": list(c.bias[:n])}
+
+
+def ocean_coupled_config_check(rows, **coef) -> int:
+    """nxs_ocean_coupled_config_check: 0, or the status nxs_dyn_ocean_coupled_attach would return for this configuration (the text: nxs_dyn_last_error(NULL))."""
+    c = _abi.ocean_coupled_config_struct(rows, **coef)
+    return load_library().nxs_ocean_coupled_config_check(C.byref(c))
 
 
 def slab_coupled_config_check(coupled_melt_type: int, attached_bins: int, **options) -> int:
@@ -1276,6 +1300,74 @@ class FiniteElementDynamics:
     def diffuse(self):
         """nxs_dyn_diffuse: one Jacobi step on the sst / sss rows of flux_put, in place; call it right before step().  Asynchronous."""
         self._chk(self.L.nxs_dyn_diffuse(self.h))
+
+    # ---- a coupled ocean: thermo() under OceanType::COUPLED, and the receive of its element fields (include/nxs_dyn.h, nxs_dyn_ocean_coupled_*) ----
+    def ocean_coupled_attach(self, gridmap=None, rows=None, **coef):
+        """nxs_dyn_ocean_coupled_attach.  gridmap: an interp.GridMap of this handle's mesh (borrowed: keep it alive), or None for a host that only uses
+        ocean_coupled_put_rows.  rows: the received rows in the order the fields arrive (names of _abi.OC_ROWS; default: ocean_coupled_default_config()); a, b,
+        factor, bias: per field.  While attached with ocean_temp, ocean_salt and qsrml, fluxes / column / slab / slab_coupled run the COUPLED branch."""
+        if rows is None:
+            d = ocean_coupled_default_config()
+            rows = d.pop("rows")
+            coef = dict(d, **coef)
+        c = _abi.ocean_coupled_config_struct(rows, **coef)
+        self._chk(self.L.nxs_dyn_ocean_coupled_attach(self.h, gridmap.h if gridmap is not None else None, C.byref(c)))
+        self._oc_map, self._oc_fields = gridmap, c.n_fields
+
+    def ocean_coupled_detach(self):
+        """nxs_dyn_ocean_coupled_attach(h, NULL, NULL): the handle is again the library without a coupled ocean."""
+        self._chk(self.L.nxs_dyn_ocean_coupled_attach(self.h, None, None))
+        self._oc_map = None
+
+    def ocean_coupled_receive(self, fields, device: bool = False):
+        """nxs_dyn_ocean_coupled_receive: fields = one [G] array per configured row, in the configured order -- or, with device=True, one device address each.  One
+        launch on the handle's stream."""
+        n = len(fields)
+        ptrs = (C.c_void_p * max(n, 1))()
+        keep = []
+        for k, f in enumerate(fields):
+            if device:
+                ptrs[k] = int(f)
+            else:
+                a = np.ascontiguousarray(f, np.float64).ravel()
+                G = self._oc_map.info()["grid_size"] if getattr(self, "_oc_map", None) is not None else a.size
+                if a.size != G:
+                    raise ValueError(f"field {k} has {a.size} cells, the map's grid has {G}")
+                keep.append(a)
+                ptrs[k] = a.ctypes.data
+        if n != getattr(self, "_oc_fields", n):
+            raise ValueError(f"{n} fields given, the attached configuration receives {self._oc_fields}")
+        self._chk(self.L.nxs_dyn_ocean_coupled_receive(self.h, ptrs, 1 if device else 0))   # NXS_REGRID_IN_DEVICE
+        del keep
+
+    def ocean_coupled_put_rows(self, **rows):
+        """ocean_temp, ocean_salt, qsrml, mld, wlbk: [Ne] host rows; a row left out or None is skipped."""
+        r = _abi.OceanCoupledRows()
+        keep = []
+        for k, v in rows.items():
+            if k not in _abi.OC_ROWS:
+                raise KeyError(f"nxs_dyn_ocean_coupled_rows has no row {k!r}")
+            if v is None:
+                continue
+            a = np.ascontiguousarray(v, np.float64)
+            if a.shape != (self.lm.num_elements,):
+                raise ValueError(f"{k} has shape {a.shape}, expected ({self.lm.num_elements},)")
+            r.row[_abi.OC_ROWS.index(k)] = _abi.dptr(a)
+            keep.append(a)
+        self._chk(self.L.nxs_dyn_ocean_coupled_put_rows(self.h, C.byref(r)))
+        del keep
+
+    def ocean_coupled_get(self, names=(), want_device: bool = False):
+        """The named rows of _abi.OC_ROWS as host arrays (synchronised); with want_device also {name: device pointer} of the five rows, 0 for a missing one."""
+        out = {k: np.empty(self.lm.num_elements) for k in names}
+        r = _abi.OceanCoupledRows()
+        for k, v in out.items():
+            r.row[_abi.OC_ROWS.index(k)] = _abi.dptr(v)
+        dev = (C.c_void_p * _abi.NXS_OC_ROWS)()
+        self._chk(self.L.nxs_dyn_ocean_coupled_get(self.h, C.byref(r), dev if want_device else None))
+        if want_device:
+            return out, dict(zip(_abi.OC_ROWS, (int(p or 0) for p in dev)))
+        return out
 
     def flux_device_rows(self) -> dict:
         """nxs_dyn_flux_device_rows: {row name of _abi.FLUX_STATE: device address, 0 for a row never put on this mesh}."""

@@ -418,6 +418,51 @@ class GridMap:
         return self._apply(self.L.nxs_gridmap_grid_to_mesh, i["grid_size"], i["nels"], data, in_device, out_device, out, ())
 
 
+    def receive_rows(self, fields, a=1., b=0., factor=1., bias=0., in_device=False, out_device=None, stream=None):
+        """nxs_gridmap_receive_rows: the coupler's receive of up to five element variables in one launch.  fields: one [G] array per variable (in_device: one
+        device address each); a, b, factor, bias: per variable (scalars are broadcast).  Returns [n_var, nels] rows -- or, with out_device (one device address
+        of an [nels] row per variable), None.  stream: a hipStream_t as an int (asynchronous when the rows stay on the device), None for the library's own."""
+        i = self.info()
+        n = len(fields)
+        co = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (n,))) for v in (a, b, factor, bias)]
+        src, dst, keep, flags = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))(), [], 0
+        for k, f in enumerate(fields):
+            if in_device:
+                src[k] = int(f)
+            else:
+                arr = np.ascontiguousarray(f, np.float64).ravel()
+                if arr.size != i["grid_size"]:
+                    raise ValueError(f"field {k} has {arr.size} cells, expected {i['grid_size']}")
+                keep.append(arr)
+                src[k] = arr.ctypes.data
+        flags |= self.IN_DEVICE if in_device else 0
+        out = None
+        if out_device is not None:
+            if len(out_device) != n:
+                raise ValueError("one output row per field expected")
+            for k, p in enumerate(out_device):
+                dst[k] = int(p)
+            flags |= self.OUT_DEVICE
+        else:
+            out = np.empty((n, i["nels"]))
+            for k in range(n):
+                dst[k] = out[k].ctypes.data
+        self._chk(self.L.nxs_gridmap_receive_rows(self.h, n, src, _abi.dptr(co[0]), _abi.dptr(co[1]), _abi.dptr(co[2]), _abi.dptr(co[3]), dst, flags,
+                                                  C.c_void_p(int(stream)) if stream else None))
+        del keep
+        return out
+
+
+def gridmap_debug_receive_lists(mode: int) -> int:
+    """Test door: 0 = receive_rows reads cell and weight through the index list, 1 = through copies in transposed order.  Returns the mode before."""
+    L = _declare_gridmap()
+    prev = C.c_int32(0)
+    rc = L.nxs_gridmap_debug_receive_lists(int(mode), C.byref(prev))
+    if rc:
+        raise NxsError(rc, (L.nxs_interp_last_error() or b"").decode())
+    return prev.value
+
+
 def _declare_gridmap():
     L = _lib()
     if not hasattr(L, "_gridmap_declared"):
@@ -432,7 +477,9 @@ def _declare_gridmap():
         L.nxs_gridmap_import.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, I, I, I, D, D, D, C.POINTER(V)]
         L.nxs_gridmap_restrict.argtypes = [V, I, C.c_int32, C.POINTER(V)]
         L.nxs_gridmap_debug_chunk.argtypes = [C.c_int32, P32]
-        for n in ("create", "destroy", "info", "mesh_to_grid", "grid_to_mesh", "export", "import", "restrict", "debug_chunk"):
+        L.nxs_gridmap_receive_rows.argtypes = [V, C.c_int32, C.POINTER(V), D, D, D, D, C.POINTER(V), C.c_int32, V]
+        L.nxs_gridmap_debug_receive_lists.argtypes = [C.c_int32, P32]
+        for n in ("create", "destroy", "info", "mesh_to_grid", "grid_to_mesh", "export", "import", "restrict", "debug_chunk", "receive_rows", "debug_receive_lists"):
             getattr(L, "nxs_gridmap_" + n).restype = C.c_int
         L._gridmap_declared = True
     return L
