@@ -393,8 +393,9 @@ NXS_API int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *d, cons
  * nxs_dyn_means_to_grid_conservative and a resident nxs_gridmap (include/nxs_interp.h) instead.
  * On a LOADED grid without conservative remapping (moorings.grid_type=from_file) both legs, the proc mask, rotateVectors, the grid accumulators and the
  * land-sea mask are nxs_dyn_means_points_* below.
- * OUT OF SCOPE (the host keeps doing those itself): dmax / dmean (the FSD diagnostics of the coupled build), rotateVectors and the land-sea mask on the
- * REGULAR grid of nxs_dyn_means_to_grid, and a second set of accumulators for the coupler's means (M_cpl_out) beside the Moorings'. */
+ * dmax / dmean (NXS_MEANS_FSD_BEGIN ..), the floe-size diagnostics of the coupled build, need nxs_dyn_fsd_diag_configure below.  The coupler's means (M_cpl_out)
+ * are a second set of accumulators beside these: nxs_dyn_cpl_out_* below.
+ * OUT OF SCOPE (the host keeps doing those itself): rotateVectors and the land-sea mask on the REGULAR grid of nxs_dyn_means_to_grid. */
 enum nxs_means_var {
     /* elemental: accumulated over the owned elements i < M_local_nelements, the rows of ghost elements stay 0 (FE.cpp:8527) */
     NXS_MEANS_CONC = 0,           /* FE.cpp:8526  D_conc */
@@ -482,6 +483,10 @@ enum nxs_means_var {
     NXS_MEANS_TSURF = 188,               /* FE.cpp:8551  D_tsurf of updateIceDiagnostics (FE.cpp:7875-7883) */
     NXS_MEANS_WSPEED = 189,              /* FE.cpp:8865  windSpeedElement(i) (FE.cpp:6359-6370) of the wind the step reads */
     NXS_MEANS_THERMO_END = 190,
+    /* elemental, the floe-size diagnostics of the coupled build (updateIceDiagnostics, FE.cpp:7902-7951): nxs_dyn_fsd_diag_configure */
+    NXS_MEANS_DMAX = 192,                /* FE.cpp:8883  D_dmax */
+    NXS_MEANS_DMEAN = 193,               /* FE.cpp:8887  D_dmean */
+    NXS_MEANS_FSD_END = 194,
     /* nodal: accumulated over all M_num_nodes, ghosts included */
     NXS_MEANS_VT_X = 64,          /* FE.cpp:8931  M_VT[i] */
     NXS_MEANS_VT_Y = 65,          /* FE.cpp:8936  M_VT[i + M_num_nodes] */
@@ -498,6 +503,7 @@ enum nxs_means_var {
 };
 #define NXS_MEANS_NODAL_BEGIN 64
 #define NXS_MEANS_THERMO_BEGIN 128
+#define NXS_MEANS_FSD_BEGIN 192
 #define NXS_MEANS_MAX_VARS 24   /* entries per list (the list travels to the kernel by value; a workgroup stages 256 rows of it in LDS) */
 
 typedef struct nxs_dyn_means_config {
@@ -518,7 +524,7 @@ typedef struct nxs_dyn_means_grid {
 
 /*   nxs_dyn_means_configure  the two lists (copied).  The configuration survives nxs_dyn_set_mesh: the accumulators are re-sized and zeroed there, which is
  *                  resetMeshMean(bamgmesh, regrid = true, ...).  The elemental list takes the ids below NXS_MEANS_ELEMENTAL_END and those of NXS_MEANS_THERMO_BEGIN
- *                  .. NXS_MEANS_THERMO_END - 1, in any mixture.  NXS_ERR_INVALID: an unknown id, an elemental id in the nodal list or the reverse, more than
+ *                  .. NXS_MEANS_THERMO_END - 1 and of NXS_MEANS_FSD_BEGIN .. NXS_MEANS_FSD_END - 1, in any mixture.  NXS_ERR_INVALID: an unknown id, an elemental id in the nodal list or the reverse, more than
  *                  NXS_MEANS_MAX_VARS entries, a mask flag without NXS_MEANS_ICE_MASK among the elemental ids.  A refused configuration leaves the previous one.
  *   nxs_dyn_means_set_tau_ow  D_tau_ow ([Ne], written by the thermodynamics): the one input of taux / tauy / taumod that is not the handle's; uploaded like
  *                  a forcing member, NULL detaches.  nxs_dyn_set_mesh detaches it (the size changes).
@@ -564,7 +570,8 @@ NXS_API int nxs_dyn_means_reset(nxs_dyn_handle *h);
  * The locator is the drifters' (exact, bamg's integer plane); the points, the mask and the accumulators do not depend on the mesh and SURVIVE nxs_dyn_set_mesh and
  * nxs_dyn_regrid: the reference calls updateGridMean just before a regrid and goes on adding after it.  A handle that never calls these functions allocates
  * and launches nothing for them.
- * OUT OF SCOPE: reading and projecting the grid file (initArbitraryGrid), the NetCDF writer, M_cpl_out's accumulators and the OASIS put, dmax / dmean, the
+ * M_cpl_out's accumulators on its exchange grid: nxs_dyn_cpl_out_* below, whose nodal leg is this section's launch on that set's rows.
+ * OUT OF SCOPE: reading and projecting the grid file (initArbitraryGrid), the NetCDF writer, the OASIS put, the
  * reduction over ranks (FE.cpp:9476-9487: ranks fetch with apply_lsm = 0, sum, and mask themselves). */
 enum nxs_means_rotation {
     NXS_MEANS_ROTATE_NONE = 0,        /* M_false_easting && thetaName == "": rotateVectors returns at once */
@@ -615,6 +622,51 @@ NXS_API int nxs_dyn_means_points_update(nxs_dyn_handle *h);
 NXS_API int nxs_dyn_means_points_get(nxs_dyn_handle *h, int32_t apply_lsm, double *grid_elemental /* [n_el][G] */, double *grid_nodal /* [n_nod][G] */,
                                      const double **elemental_dev, const double **nodal_dev);
 NXS_API int nxs_dyn_means_points_reset(nxs_dyn_handle *h);
+
+/* ---- The coupler's outgoing fields: M_cpl_out, the second GridOutput of a coupled build.  FiniteElement::step() runs, every time step ("coupler put",
+ * FE.cpp:8226-8266): updateIceDiagnostics(); updateMeans(M_cpl_out, cpl_time_factor); and, when a coupling step ends, M_cpl_out.updateGridMean(bamgmesh,
+ * M_local_nelements, M_UM), the reduction over ranks, OASIS3::put_2d per variable, resetMeshMean(bamgmesh), resetGridMean() -- and updateGridMean once more in
+ * front of every regrid (FE.cpp:8012-8052).  Here that is a SECOND accumulator set on the handle beside the Moorings' (the two do not see each other), the
+ * exchange grid's accumulators (data_grid) on the device, and one put that chains the conservative elemental leg (nxs_gridmap_send_rows, include/nxs_interp.h)
+ * and the nodal leg of nxs_dyn_means_points_update (exact locator in the mesh displaced by M_UM, P1 gather, rotateVectors, proc mask) on the handle's stream:
+ * nothing crosses PCIe but the fields the host asks for.  A handle that never configures this set allocates and launches nothing for it.
+ *
+ *   nxs_dyn_cpl_out_configure  the struct and the id space of nxs_dyn_means_configure.  A set `mask` flag is NXS_ERR_INVALID: initOASIS sets none
+ *                  (FE.cpp:7596-7684) and the ice-mask rule is not built for this set.  The configuration survives nxs_dyn_set_mesh / nxs_dyn_regrid: the mesh
+ *                  accumulators are made again, zeroed, there (resetMeshMean(regrid = true)).  Other list sizes drop the grid accumulators (made again, zeroed,
+ *                  by the next put / reset_grid).  Both lists empty frees everything of the set, the attached grid included.
+ *   nxs_dyn_cpl_out_update     updateMeans(M_cpl_out, time_factor): the kernels of nxs_dyn_means_update with this set's tables and destinations; its refusals, with
+ *                  "cpl_out_update" in the message; asynchronous.  time_factor is the host's (pcpt == 0) ? 1 : dtime_step / (double)cpl_time_step (FE.cpp:8230).
+ *   nxs_dyn_cpl_out_get / nxs_dyn_cpl_out_reset   as nxs_dyn_means_get / nxs_dyn_means_reset (resetMeshMean(bamgmesh)) on this set.
+ *   nxs_dyn_cpl_out_attach_grid  `map`: the nxs_gridmap of THIS mesh on the exchange grid (a partitioned run: the restricted one, which gives this rank's
+ *                  partial sums); borrowed, and dropped by nxs_dyn_set_mesh / nxs_dyn_regrid like the ocean attachment (FE.cpp:8033: new weights after a regrid)
+ *                  -- attach the new map again.  `points`: the P-points, the rotation and the pairs of the nodal variables, copied, cos / sin evaluated on the
+ *                  host as nxs_dyn_means_points_set does; needed only when the set has nodal variables (else may be NULL).  The grid accumulators data_grid
+ *                  ([n_el][G], [n_nod][G]) are NOT the mesh's: they survive nxs_dyn_set_mesh / nxs_dyn_regrid (the reference puts before a regrid and adds
+ *                  again after it) and a new attach on a grid of the same size.  NXS_ERR_INVALID: G of map and points differ, what nxs_dyn_means_points_set
+ *                  refuses; NXS_ERR_STATE: the map's element count is not the handle's, nothing configured, nodal variables without points.
+ *   nxs_dyn_cpl_out_put        M_cpl_out.updateGridMean() (gridoutput.cpp:387-415) on the handle's stream: the elemental leg, then the nodal leg (n_el = 0, no ice
+ *                  mask).  grid_elemental [n_el][G] / grid_nodal [n_nod][G] host arrays (either may be NULL) are copied AFTER the launches and the call is
+ *                  synchronised only then; with both NULL it is asynchronous and *elemental_dev / *nodal_dev (either may be NULL) are what a host hands to its
+ *                  reduction over ranks (FE.cpp:8236-8247 stays the caller's) and to OASIS.  flags & NXS_CPL_OUT_RESET queues resetMeshMean + resetGridMean behind
+ *                  the copies (FE.cpp:8262-8263); without a host array that is NXS_ERR_INVALID: the values would be gone.
+ *   nxs_dyn_cpl_out_reset_grid resetGridMean() alone. */
+#define NXS_CPL_OUT_RESET 1
+NXS_API int nxs_dyn_cpl_out_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c);
+NXS_API int nxs_dyn_cpl_out_update(nxs_dyn_handle *h, double time_factor);
+NXS_API int nxs_dyn_cpl_out_get(nxs_dyn_handle *h, double *elemental /* [Ne][n_el] */, double *nodal /* [Nn][n_nod] */, const double **elemental_dev,
+                                const double **nodal_dev);
+NXS_API int nxs_dyn_cpl_out_reset(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_cpl_out_attach_grid(nxs_dyn_handle *h, struct nxs_gridmap *map, const nxs_dyn_means_points *points);
+NXS_API int nxs_dyn_cpl_out_put(nxs_dyn_handle *h, double *grid_elemental /* [n_el][G] */, double *grid_nodal /* [n_nod][G] */, const double **elemental_dev,
+                                const double **nodal_dev, int32_t flags);
+NXS_API int nxs_dyn_cpl_out_reset_grid(nxs_dyn_handle *h);
+/* The three options of D_dmax / D_dmean (FE.cpp:1387, 1410-1411; defaults 0.1, 1000, 10: options.cpp:510-518): wave_coupling.dmax_c_threshold,
+ * fsd_unbroken_floe_size, fsd_min_floe_size.  NXS_MEANS_DMAX / NXS_MEANS_DMEAN are the block of updateIceDiagnostics at FE.cpp:7902-7951 (+ * / min max only: bit
+ * for bit) on M_conc_mech_fsd (nxs_dyn_fsd_put) with the bin limits and centres of nxs_dyn_fsd_configure and D_conc = M_conc (+ M_conc_young).  Without bins
+ * attached (M_num_fsd_bins == 0) both accumulate 0; with bins but M_conc_mech_fsd, the FSD configuration or this one missing, the update is NXS_ERR_STATE naming
+ * the variable.  NXS_ERR_INVALID: a value that is not finite. */
+NXS_API int nxs_dyn_fsd_diag_configure(nxs_dyn_handle *h, double dmax_c_threshold, double fsd_unbroken_floe_size, double fsd_min_floe_size);
 
 /* ---- The drifters on the device: the three statements of checkUpdateDrifters() (FE.cpp:8403-8437) that touch the handle's arrays -- Drifters::move with
  * M_UT and the reset of M_UT (checkMoveDrifters, FE.cpp:8375-8397), Drifters::updateConc on the mesh displaced by M_UM, Drifters::maskXY.  drifters.cpp's file
@@ -1273,7 +1325,8 @@ NXS_API int nxs_dyn_flux_device_rows(nxs_dyn_handle *h, const double **device_ro
  *                  nxs_dyn_fsd_breakup(..., NXS_FSD_WLBK_ON_DEVICE, ...)
  * OUT OF SCOPE: the nodal half of the receive (I_Uocn, I_Vocn, I_SSH, I_tauwix / y go through FromMeshToMeshQuick on a triangulated source, the gridTheta
  * rotation of transformData; those rows keep nxs_dyn_set_forcing_pair / nxs_dyn_set_wave_stress), ocean_turning_angle = 0 (a parameter the host sets), the
- * outgoing side (M_cpl_out, the reduction over ranks, the OASIS put), OASIS itself, reading and projecting the exchange grid file, dmax / dmean, AEROBULK. */
+ * reduction over ranks and the OASIS put of the outgoing side (its accumulators and grid: nxs_dyn_cpl_out_*), OASIS itself, reading and projecting the exchange
+ * grid file, AEROBULK. */
 enum { NXS_OC_OCEAN_TEMP = 0, NXS_OC_OCEAN_SALT = 1, NXS_OC_QSRML = 2, NXS_OC_MLD = 3, NXS_OC_WLBK = 4, NXS_OC_ROWS = 5 };
 typedef struct nxs_dyn_ocean_coupled_config {
     int32_t n_fields;                  /* fields of one receive, 1 .. NXS_OC_ROWS */
@@ -1417,7 +1470,7 @@ NXS_API int nxs_dyn_slab_get(nxs_dyn_handle *h, const nxs_dyn_slab_rows *out /* 
  * nxs_dyn_fsd_configure's: one copy of each.  nxs_dyn_slab and its refusals are unchanged.
  * While a coupled ocean is attached (nxs_dyn_ocean_coupled_attach, below) nxs_dyn_slab and nxs_dyn_slab_coupled -- one slab_element -- skip the two stores of
  * FE.cpp:5829 and 5841: M_sst and M_sss are NOT advanced, delsss still feeds D_delS, and section 9's Tbot = freezingPoint(M_sss) sees the received salinity.
- * OUT OF SCOPE: the outgoing side of the coupling (M_cpl_out's accumulators, the reduction over ranks, the OASIS put).
+ * The outgoing side of the coupling (M_cpl_out's accumulators and exchange grid) is nxs_dyn_cpl_out_*.  OUT OF SCOPE: the reduction over ranks, the OASIS put.
  *   nxs_slab_coupled_config_check   HOST ONLY: nxs_slab_config_check with the configuration's melt_type replaced by `melt_type` (1, 2, 3); 3 needs attached_bins >=
  *                  1 (the throw of FE.cpp:5595).  NXS_ERR_INVALID, the text in nxs_dyn_last_error(NULL)
  *   nxs_dyn_slab_coupled_configure  the melt type of nxs_dyn_slab_coupled, on top of nxs_dyn_slab_configure (NXS_ERR_STATE before it); nothing else is

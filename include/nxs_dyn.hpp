@@ -98,6 +98,22 @@ public:
         check(nxs_dyn_means_points_get(h_, apply_lsm ? 1 : 0, grid_elemental, grid_nodal, elemental_dev, nodal_dev), "means_points_get");
     }
     void meansPointsResetGridMean() { check(nxs_dyn_means_points_reset(h_), "means_points_reset"); }
+    // The coupler's outgoing fields, M_cpl_out: updateMeans(M_cpl_out, cpl_time_factor), M_cpl_out.updateGridMean, resetMeshMean, resetGridMean (FE.cpp:8012-8052,
+    // 8226-8266) on a second accumulator set; the exchange grid's accumulators survive setMesh and regrid, the map is attached again after either.
+    void cplOutConfigure(const nxs_dyn_means_config &c) { check(nxs_dyn_cpl_out_configure(h_, &c), "cpl_out_configure"); }
+    void cplOutUpdateMeans(double cpl_time_factor) { check(nxs_dyn_cpl_out_update(h_, cpl_time_factor), "cpl_out_update"); }
+    void cplOutGet(double *elemental, double *nodal, const double **elemental_dev = nullptr, const double **nodal_dev = nullptr) {
+        check(nxs_dyn_cpl_out_get(h_, elemental, nodal, elemental_dev, nodal_dev), "cpl_out_get");
+    }
+    void cplOutResetMeshMean() { check(nxs_dyn_cpl_out_reset(h_), "cpl_out_reset"); }
+    void cplOutAttachGrid(struct nxs_gridmap *map, const nxs_dyn_means_points *points = nullptr) { check(nxs_dyn_cpl_out_attach_grid(h_, map, points), "cpl_out_attach_grid"); }
+    void cplOutUpdateGridMean(double *grid_elemental, double *grid_nodal, const double **elemental_dev = nullptr, const double **nodal_dev = nullptr, int32_t flags = 0) {
+        check(nxs_dyn_cpl_out_put(h_, grid_elemental, grid_nodal, elemental_dev, nodal_dev, flags), "cpl_out_put");
+    }
+    void cplOutResetGridMean() { check(nxs_dyn_cpl_out_reset_grid(h_), "cpl_out_reset_grid"); }
+    void fsdDiagConfigure(double dmax_c_threshold = 0.1, double fsd_unbroken_floe_size = 1000., double fsd_min_floe_size = 10.) {
+        check(nxs_dyn_fsd_diag_configure(h_, dmax_c_threshold, fsd_unbroken_floe_size, fsd_min_floe_size), "fsd_diag_configure");
+    }
     // interpFields() + assignVariables() on the device-resident state (FE.cpp:3071-3154, 553-572): the handle goes on with a.new_mesh; forcing is the next setForcing
     nxs_dyn_regrid_info regrid(const nxs_dyn_regrid_args &a) {
         nxs_dyn_regrid_info info{};

@@ -219,6 +219,15 @@ NXS_INTERP_API int nxs_gridmap_grid_to_mesh(nxs_gridmap *map, double *out, const
 #define NXS_GRIDMAP_MAX_RECEIVE 5
 NXS_INTERP_API int nxs_gridmap_receive_rows(nxs_gridmap *map, int32_t n_var, const double *const *fields, const double *a, const double *b, const double *factor,
                                             const double *bias, double *const *out_rows, int32_t flags, void *stream);
+/* The coupler's put of element variables: GridOutput::updateGridMean's conservative elemental leg (gridoutput.cpp:473, 545) with the grid accumulators left
+ * where they are.  in [nels][n_var] (the interleaved mesh accumulators), data_grid [n_var][G] (one [G] row per variable, as OASIS takes one 2-D field per put_2d):
+ * per cell and variable  v = 0; v += in[tri*n_var+var]*w in list order; v *= 1 / area(cell); data_grid[var][c] += v  (ConservativeRemapping.cpp:128-132), and a
+ * cell without a row adds 0. -- the reference passes 0., not its missing value, there; the += is kept on such a cell too (a -0. becomes +0.).  One thread per
+ * cell walks the cell's list once for all variables (lists longer than 12 variables in column tiles of 12): the bits are those of nxs_gridmap_mesh_to_grid with
+ * miss_val 0., transposed and added.  No transposition on the host, no atomics.  A restricted map (nxs_gridmap_restrict) gives this rank's partial sums.
+ * flags: NXS_REGRID_IN_DEVICE = `in` is a device pointer, NXS_REGRID_OUT_DEVICE = `data_grid` is (a host data_grid is uploaded, added to and copied back).
+ * stream as for nxs_gridmap_receive_rows: with a stream and both arrays on the device the call is ASYNCHRONOUS on it. */
+NXS_INTERP_API int nxs_gridmap_send_rows(nxs_gridmap *map, int32_t n_var, const double *in, double *data_grid, int32_t flags, void *stream);
 /* test door: how nxs_gridmap_receive_rows reads the cell and weight of an entry -- 1 (the default: the faster of the two on the 2 km mesh) through
  * copies of both in transposed order, so that a triangle's walk is contiguous (12 bytes per entry more, made by the first receive on a map, which waits for
  * them once), 0 through the index list of the transposed lists, as nxs_gridmap_grid_to_mesh does.  The same bits.  *previous (may be NULL) = the mode before */

@@ -508,6 +508,12 @@ NXS_MEANS_MAX_VARS = 24
 MEANS_ID = {k: i for i, k in enumerate(MEANS_ELEMENTAL)}
 MEANS_ID.update({k: NXS_MEANS_NODAL_BEGIN + i for i, k in enumerate(MEANS_NODAL)})
 MEANS_ID.update({k: NXS_MEANS_THERMO_BEGIN + i for i, k in enumerate(MEANS_THERMO)})
+# the floe-size diagnostics of the coupled build (D_dmax, D_dmean: nxs_dyn_fsd_diag_configure), a third elemental range with names of its own
+MEANS_FSD = ("dmax", "dmean")
+NXS_MEANS_FSD_BEGIN = 192
+NXS_MEANS_FSD_END = 194
+MEANS_FSD_ID = {k: NXS_MEANS_FSD_BEGIN + i for i, k in enumerate(MEANS_FSD)}
+NXS_CPL_OUT_RESET = 1   # nxs_dyn_cpl_out_put: resetMeshMean + resetGridMean behind the copies
 
 
 class MeansConfig(C.Structure):   # nxs_dyn_means_config

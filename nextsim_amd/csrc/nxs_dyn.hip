@@ -275,8 +275,26 @@ struct MeansPoints {       // nxs_dyn_means_points_*: a loaded grid, its rotatio
     bool mp_have_lsm = false;                  // M_use_lsm
     std::vector<int32_t> mp_lsm;               // [G] M_lsm (applyLSM works on the copy nxs_dyn_means_points_get hands out)
 };
+struct CplOut {            // nxs_dyn_cpl_out_*: the coupler's means (M_cpl_out), a second accumulator set beside the Moorings' -- the MESH side: gone with the mesh (release_mesh), the
+                           // accumulators made again, zeroed, at the new sizes by set_mesh / regrid; the borrowed map was the old mesh's (FE.cpp:8033)
+    std::vector<void *> cpl_allocs;
+    double *d_cpl[2] = {nullptr, nullptr};     // [Ne][n_el], [Nn][n_nod] interleaved like d_means
+    struct nxs_gridmap *cpl_map = nullptr;     // borrowed (nxs_dyn_cpl_out_attach_grid)
+};
+struct CplOutGrid {        // ... and the exchange grid's side: the P-points, cos / sin, the pairs and data_grid.  NOT the mesh's: release_mesh leaves it (the reference puts
+                           // before a regrid and goes on adding after it)
+    std::vector<void *> cplg_allocs;
+    int cpl_G = 0;                             // the grid the accumulators are for; 0: none attached yet
+    bool cpl_points = false;                   // the P-points were given
+    int cpl_n_pairs = 0;
+    int cpl_first[NXS_MEANS_MAX_PAIRS] = {}, cpl_second[NXS_MEANS_MAX_PAIRS] = {};
+    double cpl_miss_val = 0.;
+    double *cpl_gx = nullptr, *cpl_gy = nullptr, *cpl_cos = nullptr, *cpl_sin = nullptr;   // [G]; cos / sin NULL: NXS_MEANS_ROTATE_NONE
+    double *cpl_grid[2] = {nullptr, nullptr};  // data_grid [n_el][G], [n_nod][G]
+    int cpl_grid_n[2] = {0, 0};                // the list sizes the accumulators were made for
+};
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, CoupledBuffers, MeansPoints {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, CoupledBuffers, MeansPoints, CplOut, CplOutGrid {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -392,6 +410,12 @@ struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, Pa
     int means_timing = 0;                          // option "means_timing": events around the two launches of nxs_dyn_means_update (nxs_dyn_debug_array "means_update_ms")
     hipEvent_t means_ev[3] = {nullptr, nullptr, nullptr};
     bool means_timed = false;
+    // the coupler's means (nxs_dyn_cpl_out_*): the configuration is the handle's and survives set_mesh; the buffers are CplOut's and CplOutGrid's
+    std::vector<int> cpl_ids[2];
+    MeansTable cpl_tab[2] = {};
+    // nxs_dyn_fsd_diag_configure: dmax_c_threshold, fsd_unbroken_floe_size, fsd_min_floe_size (NXS_MEANS_DMAX / NXS_MEANS_DMEAN of either set)
+    double fsd_diag[3] = {0., 0., 0.};
+    bool fsd_diag_configured = false;
     int means_stage = 1;                           // option "means_stage": the rows' read-modify-write staged through LDS (1) or walked by each thread (0)
     // nxs_dyn_regrid_carry_thermo: the handle's and kept across set_mesh; what the last nxs_dyn_regrid did with it
     nxs_dyn_regrid_thermo regrid_thermo{};
@@ -696,6 +720,10 @@ inline bool ocean_coupled_on(const nxs_dyn_handle *h) {
 }
 // the loaded grid of the Moorings with its accumulators: nxs_dyn_means_points_set (a new grid, or none) and nxs_dyn_destroy -- not release_mesh
 void release_means_points(nxs_dyn_handle *h) { release_group<MeansPoints>(h, h->mp_allocs); }
+// the coupler's means: the mesh accumulators and the borrowed map go with the mesh; the exchange grid with its accumulators at nxs_dyn_cpl_out_configure with two
+// empty lists and nxs_dyn_destroy -- not at release_mesh
+void release_cpl_out(nxs_dyn_handle *h) { release_group<CplOut>(h, h->cpl_allocs); }
+void release_cpl_out_grid(nxs_dyn_handle *h) { release_group<CplOutGrid>(h, h->cplg_allocs); }
 // the coupled build's buffers; their attachments are members of h->dw
 void release_coupled(nxs_dyn_handle *h) {
     release_group<CoupledBuffers>(h, h->coupled_allocs);
@@ -729,6 +757,7 @@ void release_mesh(nxs_dyn_handle *h) {
     release_nesting(h);
     release_diffusion(h);
     release_ocean_coupled(h);
+    release_cpl_out(h);
     release_coupled(h);
     h->no_big_cut = false;
     h->rank = 0; h->nranks = 1;   // (the partition is the mesh's: a single rank until nxs_dyn_set_halo says otherwise)
@@ -1802,6 +1831,19 @@ static int means_make_buffers(nxs_dyn_handle *h) {
     }
     return NXS_OK;
 }
+// the coupler's set (nxs_dyn_cpl_out_*): its accumulators at the current mesh's sizes, zeroed, in a pool of their own.  No proc-mask column: its nodal leg on the
+// grid is nxs_drifters::means_points_update, which forms the mask per point.  A handle without a configured set allocates nothing
+static int cpl_out_make_buffers(nxs_dyn_handle *h) {
+    const size_t len[2] = {(size_t)h->dm.Ne, (size_t)h->dm.Nn};
+    for (int k = 0; k < 2; ++k) {
+        const size_t n = h->cpl_ids[k].size();
+        if (!n) continue;
+        int rc = dev_alloc(h, h->cpl_allocs, &h->d_cpl[k], len[k] * n);
+        if (rc) return rc;
+        HIPCHK(h, hipMemsetAsync(h->d_cpl[k], 0, len[k] * n * sizeof(double), h->stream));
+    }
+    return NXS_OK;
+}
 // the source fields an elemental / a nodal list needs (MS_* / MN_*): each is loaded once per element / node
 static unsigned means_sources(int kind, const std::vector<int> &ids, bool young_cat) {
     unsigned src = 0;
@@ -1869,18 +1911,34 @@ static const MeansThermoVar means_thermo_var[NXS_MEANS_THERMO_END - NXS_MEANS_TH
 static_assert(NXS_MEANS_SST == NXS_MEANS_THERMO_BEGIN && NXS_MEANS_T1 == NXS_MEANS_THERMO_BEGIN + 6 && NXS_MEANS_CONC_UPD == NXS_MEANS_THERMO_BEGIN + 8 &&
               NXS_MEANS_QA == NXS_MEANS_THERMO_BEGIN + 18 && NXS_MEANS_FWFLUX_ICE == NXS_MEANS_THERMO_BEGIN + 41 && NXS_MEANS_TAIR == NXS_MEANS_THERMO_BEGIN + 46 &&
               NXS_MEANS_PRECIP == NXS_MEANS_THERMO_BEGIN + 54 && NXS_MEANS_TSURF == NXS_MEANS_THERMO_BEGIN + 60 && NXS_MEANS_WSPEED + 1 == NXS_MEANS_THERMO_END &&
-              NXS_MEANS_THERMO_END <= 256, "means_thermo_var is in the order of enum nxs_means_var; MeansTable::id is an unsigned char");
+              NXS_MEANS_FSD_END <= 256, "means_thermo_var is in the order of enum nxs_means_var; MeansTable::id is an unsigned char");
 
 static bool means_is_thermo(int id) { return id >= NXS_MEANS_THERMO_BEGIN && id < NXS_MEANS_THERMO_END; }
+static bool means_is_fsd_diag(int id) { return id >= NXS_MEANS_FSD_BEGIN && id < NXS_MEANS_FSD_END; }
 
 // The by-value table of the thermodynamic columns of the elemental list, with every refusal of nxs_dyn_means_update about them; *src gains the MS_* bits of the
 // computed variables.  Returns NXS_OK with *any = false for a list without such a column.
-static int means_thermo_table(nxs_dyn_handle *h, bool young, MeansThermo *th, unsigned *src, bool *any) {
+static int means_thermo_table(nxs_dyn_handle *h, const char *who, const std::vector<int> &ids, bool young, MeansThermo *th, nxs_fsd_diag::Args *fd, unsigned *src, bool *any) {
     *th = MeansThermo{};
     *any = false;
-    const std::vector<int> &ids = h->means_ids[0];
+    *fd = nxs_fsd_diag::Args{};
     for (size_t k = 0; k < ids.size(); ++k) {
         th->row[k] = h->ds.conc;   // (a column that reads no row: the kernel's unconditional load has a valid address)
+        if (means_is_fsd_diag(ids[k])) {   // D_dmax / D_dmean (FE.cpp:7902-7951): M_num_fsd_bins == 0 accumulates 0; with bins, everything the block reads must be there
+            *any = true;
+            const char *name = ids[k] == NXS_MEANS_DMAX ? "dmax" : "dmean";
+            *src |= MS_FSDDIAG | MS_CONC | (young ? MS_CYOUNG : 0);
+            if (!h->dw.conc_fsd || h->dw.nbins == 0) continue;
+            if (!h->fsd_mech) return fail(h, NXS_ERR_STATE, "%s: %s is configured with %d bins attached but reads M_conc_mech_fsd: attach it with nxs_dyn_fsd_put", who, name, h->dw.nbins);
+            if (!h->fsd_configured || h->fsd_cfg.n != h->dw.nbins)
+                return fail(h, NXS_ERR_STATE, "%s: %s is configured with %d bins attached but nxs_dyn_fsd_configure has %d (the bin limits and centres are its)", who, name, h->dw.nbins,
+                            h->fsd_configured ? h->fsd_cfg.n : 0);
+            if (!h->fsd_diag_configured) return fail(h, NXS_ERR_STATE, "%s: %s is configured before nxs_dyn_fsd_diag_configure (dmax_c_threshold, fsd_unbroken_floe_size, fsd_min_floe_size)", who, name);
+            fd->mech = h->fsd_mech; fd->stride = h->dm.Ne; fd->nb = h->dw.nbins;
+            fd->dmax_c_threshold = h->fsd_diag[0]; fd->unbroken_floe_size = h->fsd_diag[1]; fd->min_floe_size = h->fsd_diag[2];
+            for (int b = 0; b < fd->nb; ++b) { fd->up[b] = h->fsd_cfg.up[b]; fd->centres[b] = h->fsd_cfg.centres[b]; }
+            continue;
+        }
         if (!means_is_thermo(ids[k])) continue;
         *any = true;
         const MeansThermoVar &v = means_thermo_var[ids[k] - NXS_MEANS_THERMO_BEGIN];
@@ -1888,48 +1946,48 @@ static int means_thermo_table(nxs_dyn_handle *h, bool young, MeansThermo *th, un
         const unsigned bit = 1u << v.row;
         switch (v.from) {
             case MF_FLUX_ST:
-                if (!(h->flux_st_have & bit)) return fail(h, NXS_ERR_STATE, "means_update: %s is configured but its row was never given on this mesh (nxs_dyn_flux_put)", v.name);
+                if (!(h->flux_st_have & bit)) return fail(h, NXS_ERR_STATE, "%s: %s is configured but its row was never given on this mesh (nxs_dyn_flux_put)", who, v.name);
                 th->row[k] = h->d_flux_st[v.row];
                 break;
             case MF_COL_ST:
                 if ((h->col_configured && h->col_cfg.thermo_type != NXS_COL_THERMO_WINTON) || !(h->col_st_have & bit))
-                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured without WINTON rows (tice1 / tice2: nxs_dyn_column_put under NXS_COL_THERMO_WINTON)", v.name);
+                    return fail(h, NXS_ERR_STATE, "%s: %s is configured without WINTON rows (tice1 / tice2: nxs_dyn_column_put under NXS_COL_THERMO_WINTON)", who, v.name);
                 th->row[k] = h->d_col_st[v.row];
                 break;
             case MF_SLAB_ST:
-                if (!(h->slab_st_have & bit)) return fail(h, NXS_ERR_STATE, "means_update: %s is configured but its row was never given on this mesh (nxs_dyn_slab_put)", v.name);
+                if (!(h->slab_st_have & bit)) return fail(h, NXS_ERR_STATE, "%s: %s is configured but its row was never given on this mesh (nxs_dyn_slab_put)", who, v.name);
                 th->row[k] = h->d_slab_st[v.row];
                 break;
             case MF_SLAB_OUT:
                 if (!h->slab_done || !h->d_slab_out)
-                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but reads a row of the slab before the first nxs_dyn_slab / nxs_dyn_slab_coupled on this mesh", v.name);
+                    return fail(h, NXS_ERR_STATE, "%s: %s is configured but reads a row of the slab before the first nxs_dyn_slab / nxs_dyn_slab_coupled on this mesh", who, v.name);
                 th->row[k] = h->d_slab_out + (size_t)v.row * h->dm.Ne;
                 break;
             case MF_ATM: {
                 if (v.row >= 3 && !h->flux_configured)
-                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured before nxs_dyn_flux_configure (which row it is follows from the configured source)", v.name);
+                    return fail(h, NXS_ERR_STATE, "%s: %s is configured before nxs_dyn_flux_configure (which row it is follows from the configured source)", who, v.name);
                 const int id = ids[k], hs = h->flux_cfg.humidity_source, ls = h->flux_cfg.longwave_source;
                 if ((id == NXS_MEANS_SPHUMA && hs != NXS_FLUX_HUM_SPHUMA) || (id == NXS_MEANS_MIXRAT && hs != NXS_FLUX_HUM_MIXRAT) || (id == NXS_MEANS_D2M && hs != NXS_FLUX_HUM_DEWPOINT))
-                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but the humidity row is %s (humidity_source = %d)", v.name,
+                    return fail(h, NXS_ERR_STATE, "%s: %s is configured but the humidity row is %s (humidity_source = %d)", who, v.name,
                                 hs == NXS_FLUX_HUM_SPHUMA ? "sphuma" : hs == NXS_FLUX_HUM_MIXRAT ? "mixrat" : "d2m", hs);
                 if ((id == NXS_MEANS_QLW_IN && ls != NXS_FLUX_LW_QLW_IN) || (id == NXS_MEANS_TCC && ls != NXS_FLUX_LW_TCC))
-                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but the long-wave row is %s (longwave_source = %d)", v.name, ls == NXS_FLUX_LW_TCC ? "tcc" : "Qlw_in", ls);
+                    return fail(h, NXS_ERR_STATE, "%s: %s is configured but the long-wave row is %s (longwave_source = %d)", who, v.name, ls == NXS_FLUX_LW_TCC ? "tcc" : "Qlw_in", ls);
                 if (!(h->flux_atm_have & bit))
-                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but its row was never given on this mesh (nxs_dyn_flux_set_atmosphere)", v.name);
+                    return fail(h, NXS_ERR_STATE, "%s: %s is configured but its row was never given on this mesh (nxs_dyn_flux_set_atmosphere)", who, v.name);
                 th->row[k] = h->d_flux_atm[v.row];
                 break;
             }
             case MF_COL_FORCING: {
                 if (v.row == 1) {
                     if (!h->col_configured)
-                        return fail(h, NXS_ERR_STATE, "means_update: %s is configured before nxs_dyn_column_configure (which row it is follows from the configured source)", v.name);
+                        return fail(h, NXS_ERR_STATE, "%s: %s is configured before nxs_dyn_column_configure (which row it is follows from the configured source)", who, v.name);
                     const int ss = h->col_cfg.snowfall_source;
                     if (ss != (ids[k] == NXS_MEANS_SNOWFALL ? NXS_COL_SNOWFALL_SNOWFALL : NXS_COL_SNOWFALL_PRECIP_SNOWFR))
-                        return fail(h, NXS_ERR_STATE, "means_update: %s is configured but the snow row is %s (snowfall_source = %d)", v.name,
+                        return fail(h, NXS_ERR_STATE, "%s: %s is configured but the snow row is %s (snowfall_source = %d)", who, v.name,
                                     ss == NXS_COL_SNOWFALL_SNOWFALL ? "snowfall" : ss == NXS_COL_SNOWFALL_PRECIP_SNOWFR ? "snowfr" : "not read", ss);
                 }
                 if (!(h->col_forcing_have & bit))
-                    return fail(h, NXS_ERR_STATE, "means_update: %s is configured but its row was never given on this mesh (nxs_dyn_column_set_forcing)", v.name);
+                    return fail(h, NXS_ERR_STATE, "%s: %s is configured but its row was never given on this mesh (nxs_dyn_column_set_forcing)", who, v.name);
                 th->row[k] = h->d_col_forcing[v.row];
                 break;
             }
@@ -1937,17 +1995,17 @@ static int means_thermo_table(nxs_dyn_handle *h, bool young, MeansThermo *th, un
                 if (v.op == MT_DRAG_TI) {
                     const unsigned need = 1u << 4 | (young ? 1u << 5 : 0);
                     if ((h->flux_st_have & need) != need)
-                        return fail(h, NXS_ERR_STATE, "means_update: drag_ti is configured but drag_ti%s was never given on this mesh (nxs_dyn_flux_put)", young ? " / drag_ti_young" : "");
+                        return fail(h, NXS_ERR_STATE, "%s: drag_ti is configured but drag_ti%s was never given on this mesh (nxs_dyn_flux_put)", who, young ? " / drag_ti_young" : "");
                     th->drag_ti = h->d_flux_st[4]; th->drag_ti_young = h->d_flux_st[5];
                     if (young) *src |= MS_CONC | MS_CYOUNG;
                 } else if (v.op == MT_TSURF) {
                     const unsigned need = 1u << 0 | 1u << 2 | (young ? 1u << 1 : 0);
                     if ((h->flux_st_have & need) != need)
-                        return fail(h, NXS_ERR_STATE, "means_update: tsurf is configured but tice0, sst%s were not all given on this mesh (nxs_dyn_flux_put)", young ? ", tsurf_young" : "");
+                        return fail(h, NXS_ERR_STATE, "%s: tsurf is configured but tice0, sst%s were not all given on this mesh (nxs_dyn_flux_put)", who, young ? ", tsurf_young" : "");
                     th->tice0 = h->d_flux_st[0]; th->tsurf_young = h->d_flux_st[1]; th->sst = h->d_flux_st[2];
                     *src |= MS_CONC | (young ? MS_CYOUNG : 0);
                 } else if (!h->have_forcing)
-                    return fail(h, NXS_ERR_STATE, "means_update: wspeed is configured before a forcing (the wind: nxs_dyn_set_forcing)");
+                    return fail(h, NXS_ERR_STATE, "%s: wspeed is configured before a forcing (the wind: nxs_dyn_set_forcing)", who);
                 break;
         }
     }
@@ -2100,6 +2158,7 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     ipc_release(h);
     release_mesh(h);
     release_means_points(h);
+    release_cpl_out_grid(h);
     if (!h->reg_key.empty()) nxs_reg::table_for(h->reg_key).remove((uint64_t)(uintptr_t)h);
     unpin_all(h);
     if (h->h_send) (void)hipHostFree(h->h_send);
@@ -2458,6 +2517,7 @@ static int set_mesh_impl(nxs_dyn_handle *h, const nxs_dyn_mesh *m, RegridAdopt *
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if ((rc = upload_patches(h))) return rc;
     if ((rc = means_make_buffers(h))) return rc;   // resetMeshMean(bamgmesh, regrid = true, ...): the configured accumulators at the new sizes, zeroed
+    if ((rc = cpl_out_make_buffers(h))) return rc;   // ... and M_cpl_out's (FE.cpp:8033)
     h->have_mesh = true;
     return NXS_OK;
 }
@@ -3368,28 +3428,41 @@ int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *dg, const doubl
 } catch (...) { return dyn_caught(h, "nxs_dyn_ice_diagnostics"); }
 
 // ---- the Moorings time means: updateMeans (FE.cpp:8518-9024), updateGridMean on the regular grid (gridoutput.cpp:387-550), resetMeshMean
-int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) try {
-    if (!h || !c) return NXS_ERR_INVALID;
+// the two lists of a nxs_dyn_means_config, checked (nxs_dyn_means_configure, nxs_dyn_cpl_out_configure: one id space); `who` names the entry in the message
+static int means_parse_config(nxs_dyn_handle *h, const char *who, const nxs_dyn_means_config *c, std::vector<int> (&ids)[2], std::vector<unsigned char> (&mask)[2], int *ice_col,
+                              bool *any_mask) {
     if (c->num_elemental < 0 || c->num_nodal < 0 || c->num_elemental > NXS_MEANS_MAX_VARS || c->num_nodal > NXS_MEANS_MAX_VARS)
-        return fail(h, NXS_ERR_INVALID, "means_configure: %d elemental and %d nodal variables (0..%d each)", c->num_elemental, c->num_nodal, NXS_MEANS_MAX_VARS);
-    if ((c->num_elemental > 0 && !c->elemental_ids) || (c->num_nodal > 0 && !c->nodal_ids)) return fail(h, NXS_ERR_INVALID, "means_configure: an id list is NULL");
-    std::vector<int> ids[2] = {std::vector<int>(c->elemental_ids, c->elemental_ids + c->num_elemental), std::vector<int>(c->nodal_ids, c->nodal_ids + c->num_nodal)};
-    std::vector<unsigned char> mask[2] = {std::vector<unsigned char>(ids[0].size(), 0), std::vector<unsigned char>(ids[1].size(), 0)};
+        return fail(h, NXS_ERR_INVALID, "%s: %d elemental and %d nodal variables (0..%d each)", who, c->num_elemental, c->num_nodal, NXS_MEANS_MAX_VARS);
+    if ((c->num_elemental > 0 && !c->elemental_ids) || (c->num_nodal > 0 && !c->nodal_ids)) return fail(h, NXS_ERR_INVALID, "%s: an id list is NULL", who);
+    ids[0].assign(c->elemental_ids, c->elemental_ids + c->num_elemental);
+    ids[1].assign(c->nodal_ids, c->nodal_ids + c->num_nodal);
+    mask[0].assign(ids[0].size(), 0);
+    mask[1].assign(ids[1].size(), 0);
     if (c->elemental_mask) for (size_t k = 0; k < ids[0].size(); ++k) mask[0][k] = c->elemental_mask[k] ? 1 : 0;
     if (c->nodal_mask) for (size_t k = 0; k < ids[1].size(); ++k) mask[1][k] = c->nodal_mask[k] ? 1 : 0;
-    int ice_col = -1;
-    bool any_mask = false;
+    *ice_col = -1;
+    *any_mask = false;
     for (size_t k = 0; k < ids[0].size(); ++k) {
-        if ((ids[0][k] < 0 || ids[0][k] >= NXS_MEANS_ELEMENTAL_END) && !means_is_thermo(ids[0][k]))
-            return fail(h, NXS_ERR_INVALID, "means_configure: elemental_ids[%d] = %d is not an elemental NXS_MEANS_* id", (int)k, ids[0][k]);
-        if (ids[0][k] == NXS_MEANS_ICE_MASK && ice_col < 0) ice_col = (int)k;
-        any_mask = any_mask || mask[0][k];
+        if ((ids[0][k] < 0 || ids[0][k] >= NXS_MEANS_ELEMENTAL_END) && !means_is_thermo(ids[0][k]) && !means_is_fsd_diag(ids[0][k]))
+            return fail(h, NXS_ERR_INVALID, "%s: elemental_ids[%d] = %d is not an elemental NXS_MEANS_* id", who, (int)k, ids[0][k]);
+        if (ids[0][k] == NXS_MEANS_ICE_MASK && *ice_col < 0) *ice_col = (int)k;
+        *any_mask = *any_mask || mask[0][k];
     }
     for (size_t k = 0; k < ids[1].size(); ++k) {
         if (ids[1][k] < NXS_MEANS_NODAL_BEGIN || ids[1][k] >= NXS_MEANS_NODAL_END)
-            return fail(h, NXS_ERR_INVALID, "means_configure: nodal_ids[%d] = %d is not a nodal NXS_MEANS_* id", (int)k, ids[1][k]);
-        any_mask = any_mask || mask[1][k];
+            return fail(h, NXS_ERR_INVALID, "%s: nodal_ids[%d] = %d is not a nodal NXS_MEANS_* id", who, (int)k, ids[1][k]);
+        *any_mask = *any_mask || mask[1][k];
     }
+    return NXS_OK;
+}
+
+int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) try {
+    if (!h || !c) return NXS_ERR_INVALID;
+    std::vector<int> ids[2];
+    std::vector<unsigned char> mask[2];
+    int ice_col = -1;
+    bool any_mask = false;
+    if (int rc = means_parse_config(h, "means_configure", c, ids, mask, &ice_col, &any_mask)) return rc;
     if (any_mask && ice_col < 0) return fail(h, NXS_ERR_INVALID, "means_configure: a variable has `mask` set but NXS_MEANS_ICE_MASK is not among the elemental ids");
     HIPCHK(h, hipSetDevice(h->device));
     if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3417,59 +3490,68 @@ int nxs_dyn_means_set_tau_ow(nxs_dyn_handle *h, const double *tau_ow) try {
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_means_set_tau_ow"); }
 
-int nxs_dyn_means_update(nxs_dyn_handle *h, double time_factor) try {
-    if (!h) return NXS_ERR_INVALID;
-    if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "means_update needs set_mesh and put_state");
-    if (h->means_ids[0].empty() && h->means_ids[1].empty()) return fail(h, NXS_ERR_STATE, "means_update: no variable is configured (nxs_dyn_means_configure)");
-    for (int id : h->means_ids[1]) {
+// updateMeans(set, time_factor) for ONE accumulator set -- the Moorings' (nxs_dyn_means_update) or the coupler's (nxs_dyn_cpl_out_update): the refusals (`who`
+// names the entry in the message), the two by-value tables, one launch over the owned elements and one over the nodes.  timed: the Moorings' events (option
+// "means_timing").  The one statement of the launch logic: both entries run the SAME kernels with their own lists, tables and destinations.
+static int means_update_set(nxs_dyn_handle *h, const char *who, const std::vector<int> *ids /* [2] */, MeansTable *tab /* [2] */, double *const *dst /* [2] */, double time_factor,
+                            bool timed) {
+    for (int id : ids[1]) {
         if ((id == NXS_MEANS_TAUWIX || id == NXS_MEANS_TAUWIY) && !wave_attached(h))
-            return fail(h, NXS_ERR_STATE, "means_update: tauwix / tauwiy are configured but no wave stress is attached (nxs_dyn_set_wave_stress)");
+            return fail(h, NXS_ERR_STATE, "%s: tauwix / tauwiy are configured but no wave stress is attached (nxs_dyn_set_wave_stress)", who);
         if ((id == NXS_MEANS_TAUX || id == NXS_MEANS_TAUY || id == NXS_MEANS_TAUMOD) && !h->tau_ow_attached)
-            return fail(h, NXS_ERR_STATE, "means_update: taux / tauy / taumod are configured but no D_tau_ow is attached (nxs_dyn_means_set_tau_ow)");
+            return fail(h, NXS_ERR_STATE, "%s: taux / tauy / taumod are configured but no D_tau_ow is attached (nxs_dyn_means_set_tau_ow)", who);
     }
     const int young = h->dp.young_cat ? 1 : 0;
     MeansThermo th;
+    nxs_fsd_diag::Args fd;
     unsigned thermo_src = 0;
     bool thermo = false;
-    if (int rc = means_thermo_table(h, young != 0, &th, &thermo_src, &thermo)) return rc;
+    if (int rc = means_thermo_table(h, who, ids[0], young != 0, &th, &fd, &thermo_src, &thermo)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     // (the opt-in one-launch loops can give up half-way: never a mean of a half-made step without an error -- as nxs_dyn_ice_diagnostics; the default path stays asynchronous)
     if (int rc = launch_gave_up(h)) return rc;
     for (int k = 0; k < 2; ++k) {
-        MeansTable &t = h->means_tab[k];
+        MeansTable &t = tab[k];
         t = MeansTable{};
-        t.n = (int)h->means_ids[k].size();
-        t.src = means_sources(k, h->means_ids[k], young != 0) | (k ? 0 : thermo_src);
-        for (int q = 0; q < t.n; ++q) t.id[q] = (unsigned char)(h->means_ids[k][q] - (k ? NXS_MEANS_NODAL_BEGIN : 0));
+        t.n = (int)ids[k].size();
+        t.src = means_sources(k, ids[k], young != 0) | (k ? 0 : thermo_src);
+        for (int q = 0; q < t.n; ++q) t.id[q] = (unsigned char)(ids[k][q] - (k ? NXS_MEANS_NODAL_BEGIN : 0));
     }
     const bool stage = h->means_stage != 0;
-    if (h->means_timing) HIPCHK(h, hipEventRecord(h->means_ev[0], h->stream));
-    if (h->means_tab[0].n > 0 && h->dm.Neo > 0) {
-        const MeansTable &t = h->means_tab[0];
+    if (timed) HIPCHK(h, hipEventRecord(h->means_ev[0], h->stream));
+    if (tab[0].n > 0 && h->dm.Neo > 0) {
+        const MeansTable &t = tab[0];
         const double *S4 = h->sig_loc ? (const double *)h->ds.S4a : (const double *)nullptr;
-        if (thermo) {   // the list names a thermodynamic variable: the same kernel with their table
+        if (thermo) {   // the list names a thermodynamic variable (or dmax / dmean): the same kernel with their tables
             if (stage) hipLaunchKernelGGL(k_means_elements_thermo<true>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), (size_t)BLOCK * t.n * sizeof(double), h->stream, h->dm, h->ds,
-                                          (const double *)h->dw.D_del, young, S4, t, th, time_factor, h->d_means[0]);
+                                          (const double *)h->dw.D_del, young, S4, t, th, fd, time_factor, dst[0]);
             else hipLaunchKernelGGL(k_means_elements_thermo<false>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->dw.D_del, young, S4,
-                                    t, th, time_factor, h->d_means[0]);
+                                    t, th, fd, time_factor, dst[0]);
         } else if (stage) hipLaunchKernelGGL(k_means_elements<true>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), (size_t)BLOCK * t.n * sizeof(double), h->stream, h->dm, h->ds,
-                                      (const double *)h->dw.D_del, young, S4, t, time_factor, h->d_means[0]);
+                                      (const double *)h->dw.D_del, young, S4, t, time_factor, dst[0]);
         else hipLaunchKernelGGL(k_means_elements<false>, dim3(nblocks(h->dm.Neo)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->dw.D_del, young, S4, t,
-                                time_factor, h->d_means[0]);
+                                time_factor, dst[0]);
         HIPCHK(h, hipGetLastError());
     }
-    if (h->means_timing) HIPCHK(h, hipEventRecord(h->means_ev[1], h->stream));
-    if (h->means_tab[1].n > 0) {
-        const MeansTable &t = h->means_tab[1];
+    if (timed) HIPCHK(h, hipEventRecord(h->means_ev[1], h->stream));
+    if (tab[1].n > 0) {
+        const MeansTable &t = tab[1];
         if (stage) hipLaunchKernelGGL(k_means_nodes<true>, dim3(nblocks(h->dm.Nn)), dim3(BLOCK), (size_t)BLOCK * t.n * sizeof(double), h->stream, h->dm, h->ds,
                                       (const double *)h->dw.D_tau_a, (const double *)h->dw.D_tau_w, h->dw.tau_wi, (const double *)h->d_tau_ow,
-                                      (const double *)h->dw.surface, t, time_factor, h->d_means[1]);
+                                      (const double *)h->dw.surface, t, time_factor, dst[1]);
         else hipLaunchKernelGGL(k_means_nodes<false>, dim3(nblocks(h->dm.Nn)), dim3(BLOCK), 0, h->stream, h->dm, h->ds, (const double *)h->dw.D_tau_a,
-                                (const double *)h->dw.D_tau_w, h->dw.tau_wi, (const double *)h->d_tau_ow, (const double *)h->dw.surface, t, time_factor, h->d_means[1]);
+                                (const double *)h->dw.D_tau_w, h->dw.tau_wi, (const double *)h->d_tau_ow, (const double *)h->dw.surface, t, time_factor, dst[1]);
         HIPCHK(h, hipGetLastError());
     }
-    if (h->means_timing) { HIPCHK(h, hipEventRecord(h->means_ev[2], h->stream)); h->means_timed = true; }
+    if (timed) { HIPCHK(h, hipEventRecord(h->means_ev[2], h->stream)); h->means_timed = true; }
     return NXS_OK;
+}
+
+int nxs_dyn_means_update(nxs_dyn_handle *h, double time_factor) try {
+    if (!h) return NXS_ERR_INVALID;
+    if (!h->have_mesh || !h->have_state) return fail(h, NXS_ERR_STATE, "means_update needs set_mesh and put_state");
+    if (h->means_ids[0].empty() && h->means_ids[1].empty()) return fail(h, NXS_ERR_STATE, "means_update: no variable is configured (nxs_dyn_means_configure)");
+    return means_update_set(h, "means_update", h->means_ids, h->means_tab, h->d_means, time_factor, h->means_timing != 0);
 } catch (...) { return dyn_caught(h, "nxs_dyn_means_update"); }
 
 int nxs_dyn_means_get(nxs_dyn_handle *h, double *elemental, double *nodal, const double **elemental_dev, const double **nodal_dev) try {
@@ -4097,5 +4179,6 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_nodal_forcing.inl"
 #include "nxs_ocean_coupled.inl"
 #include "nxs_means_points.inl"
+#include "nxs_cpl_out.inl"
 
 }  // extern "C"

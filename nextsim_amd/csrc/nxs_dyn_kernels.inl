@@ -3198,6 +3198,7 @@ __global__ void __launch_bounds__(BLOCK) k_ghost_ring_move(DevMesh m, DevState s
 }
 
 #include "nxs_wind_speed.inl"   // wind_speed_element: k_fluxes, k_slab and the Moorings mean `wspeed` share it
+#include "nxs_fsd_diag_body.inl"   // D_dmax / D_dmean: the Moorings / coupler means `dmax`, `dmean`
 
 // The arithmetic of updateIceDiagnostics() (FE.cpp:7860-7905) that k_ice_diagnostics and the Moorings means (k_means_elements) share -- one statement of it,
 // so that the two give the same bits: the principal stresses, and the divergence of M_VT on the mesh displaced by M_UM (shapeCoeff, FE.cpp:1951-1964).
@@ -3253,7 +3254,8 @@ struct MeansTable {
     unsigned char id[NXS_MEANS_MAX_VARS];     // NXS_MEANS_* (nodal ids minus NXS_MEANS_NODAL_BEGIN)
 };
 enum { MS_CONC = 1, MS_THICK = 2, MS_SNOW = 4, MS_SIGMA = 8 /* + damage when it lives in the records */, MS_DAMAGE = 16, MS_RIDGE = 32, MS_CYOUNG = 64, MS_HYOUNG = 128,
-       MS_HSYOUNG = 256, MS_CMYI = 512, MS_TMYI = 1024, MS_DEL = 2048, MS_DRAG = 4096, MS_DRAGY = 8192, MS_DIV = 16384 };
+       MS_HSYOUNG = 256, MS_CMYI = 512, MS_TMYI = 1024, MS_DEL = 2048, MS_DRAG = 4096, MS_DRAGY = 8192, MS_DIV = 16384,
+       MS_FSDDIAG = 32768 /* D_dmax / D_dmean (nxs_fsd_diag_body.inl): the thermodynamic build only */ };
 enum { MN_VT = 1, MN_WIND = 2, MN_TAUA = 4, MN_TAUW = 8, MN_TAUWI = 16, MN_GATHER = 32 };
 
 // The thermodynamic variables (NXS_MEANS_THERMO_BEGIN ..): some sixty sources do not fit the MS_* word, and nearly all of them are `row[e] * tf` of a row that lies
@@ -3275,7 +3277,7 @@ struct MeansThermo {
     unsigned char op[NXS_MEANS_MAX_VARS];     // MT_* per column (ignored where the id is below NXS_MEANS_THERMO_BEGIN)
 };
 
-struct MeansElem { double conc, thick, snow, damage, ridge, s0, s1, s2, cy, hy, hsy, cmyi, tmyi, del, drag, dragy, div, sn, ss; };
+struct MeansElem { double conc, thick, snow, damage, ridge, s0, s1, s2, cy, hy, hsy, cmyi, tmyi, del, drag, dragy, div, sn, ss, dmax, dmean; };
 
 // the increment of one elemental variable (already multiplied by time_factor where the reference multiplies)
 __device__ __forceinline__ double means_elem_value(int id, const MeansElem &f, int young_cat, double tf) {
@@ -3342,9 +3344,11 @@ __device__ __forceinline__ void means_add_staged(double *__restrict__ acc, size_
 // Elemental pass: one thread per OWNED element (ghost rows are not touched: FE.cpp:8527 loops i < M_local_nelements).
 // STAGE: the increments of a workgroup go to LDS ([BLOCK][n], dynamic) and are added to the rows as one stream; else every thread walks its own row.
 // THERMO: the list names a thermodynamic variable and `th` is its table; without, nothing of `th` is compiled in and the kernel is the one it was.
+// The same build takes NXS_MEANS_DMAX / NXS_MEANS_DMEAN (FE.cpp:8883-8889): `fd` is the table of updateIceDiagnostics' FSD block, run once per element behind
+// the wave-uniform MS_FSDDIAG bit.
 template <bool STAGE, bool THERMO>
 __device__ __forceinline__ void means_elements_body(const DevMesh &m, const DevState &s, const double *__restrict__ D_del, int young_cat, const double *__restrict__ S4,
-                                                    const MeansTable &t, const MeansThermo &th, double tf, double *__restrict__ acc) {
+                                                    const MeansTable &t, const MeansThermo &th, const nxs_fsd_diag::Args &fd, double tf, double *__restrict__ acc) {
     extern __shared__ double means_stage[];
     const int e = min(blockIdx.x * BLOCK + (int)threadIdx.x, m.Neo - 1);  // (threads past the end redo the last owned element: every thread reaches the barrier)
     const bool live = blockIdx.x * BLOCK + (int)threadIdx.x < m.Neo;
@@ -3374,10 +3378,14 @@ __device__ __forceinline__ void means_elements_body(const DevMesh &m, const DevS
     }
     if (src & MS_SIGMA) ice_diag_sigma(f.s0, f.s1, f.s2, f.sn, f.ss);
     if (src & MS_DIV) f.div = ice_diag_divergence(m, s, e);
+    if constexpr (THERMO) { if (src & MS_FSDDIAG) nxs_fsd_diag::diag(fd, e, young_cat ? f.conc + f.cy : f.conc, f.dmax, f.dmean); }
     const int n = t.n;
     // the increment of column k, x its row's entry: the id is the list's, so the branch is wave-uniform
     auto value_of = [&](int k, double x) -> double {
-        if constexpr (THERMO) { if (t.id[k] >= NXS_MEANS_THERMO_BEGIN) return means_thermo_value(th, k, x, e, f, m, s, young_cat, tf); }
+        if constexpr (THERMO) {
+            if (t.id[k] >= NXS_MEANS_FSD_BEGIN) return (t.id[k] == NXS_MEANS_DMAX ? f.dmax : f.dmean) * tf;   // FE.cpp:8883-8889
+            if (t.id[k] >= NXS_MEANS_THERMO_BEGIN) return means_thermo_value(th, k, x, e, f, m, s, young_cat, tf);
+        }
         return means_elem_value(t.id[k], f, young_cat, tf);
     };
     auto value = [&](int k) -> double {
@@ -3417,12 +3425,12 @@ __device__ __forceinline__ void means_elements_body(const DevMesh &m, const DevS
 template <bool STAGE>
 __global__ void __launch_bounds__(BLOCK) k_means_elements(DevMesh m, DevState s, const double *__restrict__ D_del, int young_cat, const double *__restrict__ S4,
                                                           MeansTable t, double tf, double *__restrict__ acc) {
-    means_elements_body<STAGE, false>(m, s, D_del, young_cat, S4, t, MeansThermo{}, tf, acc);
+    means_elements_body<STAGE, false>(m, s, D_del, young_cat, S4, t, MeansThermo{}, nxs_fsd_diag::Args{}, tf, acc);
 }
 template <bool STAGE>
 __global__ void __launch_bounds__(BLOCK) k_means_elements_thermo(DevMesh m, DevState s, const double *__restrict__ D_del, int young_cat, const double *__restrict__ S4,
-                                                                 MeansTable t, MeansThermo th, double tf, double *__restrict__ acc) {
-    means_elements_body<STAGE, true>(m, s, D_del, young_cat, S4, t, th, tf, acc);
+                                                                 MeansTable t, MeansThermo th, nxs_fsd_diag::Args fd, double tf, double *__restrict__ acc) {
+    means_elements_body<STAGE, true>(m, s, D_del, young_cat, S4, t, th, fd, tf, acc);
 }
 
 // hypot for the Moorings stresses (FE.cpp:8980, 8996).  The reference calls the host C library's, which rounds correctly in all but rare cases; OCML's is allowed a

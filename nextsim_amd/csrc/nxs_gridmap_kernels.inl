@@ -92,6 +92,34 @@ __global__ void __launch_bounds__(256) k_gridmap_to_grid(long long total, int nb
     out[gid] = nxs_remap::grid_value(in, nb_var, var, tris + lo, w + lo, off[row + 1] - lo, r_area[row]);
 }
 
+// The coupler's put (nxs_gridmap_send_rows): GridOutput::updateGridMean's conservative elemental leg with the grid accumulators on the device -- per cell
+// ConservativeRemapping.cpp:128-132 and gridoutput.cpp:545: v = 0; v += in[tri*nb_var+var]*w in list order; v *= r_cell_area; data_grid[var][c] += v, and a dry
+// cell adds the 0. the reference passes as its missing value there (the += is kept: it turns a -0. of the accumulator into +0.).  One thread per grid cell, all G
+// of them; a wet cell walks its list ONCE for the nv <= NV variables col0 .. (k_gridmap_to_grid walks it once per variable and writes [G][nb_var]).  A triangle's
+// nb_var accumulators are consecutive doubles; consecutive threads store consecutive entries of each [G] row.  No atomics, no LDS; the NV sums stay in registers
+// (builds for 4, 8 and 12; longer lists come in column tiles of 12).  Gather- and latency-bound: the row lengths differ from lane to lane and every entry is a
+// dependent load through tris[], so the wavefront runs as long as its longest row -- not bandwidth-bound.
+constexpr int kSendTile = 12;
+template <int NV>
+__global__ void __launch_bounds__(256) k_gridmap_send(int G, int nb_var, int col0, int nv, const int *__restrict__ row_of_cell, const int *__restrict__ off,
+                                                      const int *__restrict__ tris, const double *__restrict__ w, const double *__restrict__ r_area,
+                                                      const double *__restrict__ in, double *__restrict__ data_grid) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= G) return;
+    const int row = row_of_cell[c];
+    double v[NV];
+    if (row < 0) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) v[i] = 0.;
+    } else {
+        const int lo = off[row];
+        nxs_remap::grid_values<NV>(in, nb_var, col0, nv, tris + lo, w + lo, off[row + 1] - lo, r_area[row], v);
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        if (i < nv) data_grid[(size_t)(col0 + i) * G + c] += v[i];
+}
+
 // ConservativeRemappingGridToMesh (:138-171) as a gather over the transposed lists: one thread per (triangle, variable)
 __global__ void __launch_bounds__(256) k_gridmap_to_mesh(long long total, int nb_var, const int *__restrict__ t_off, const int *__restrict__ t_pos,
                                                          const int *__restrict__ cell, const double *__restrict__ w, const double *__restrict__ in,

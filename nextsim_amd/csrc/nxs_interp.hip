@@ -1361,6 +1361,38 @@ extern "C" int nxs_gridmap_receive_rows(nxs_gridmap *g, int32_t n_var, const dou
     return NXS_OK;
 } catch (...) { return entry_caught("nxs_gridmap_receive_rows"); }
 
+// The coupler's put: GridOutput::updateGridMean's conservative elemental leg (gridoutput.cpp:473, 545; ConservativeRemapping.cpp:103-135), ADDED to the [n_var][G]
+// rows of data_grid.  in [nels][n_var].  Column tiles of gridmap::kSendTile; the builds for at most 4, 8 and 12 variables
+extern "C" int nxs_gridmap_send_rows(nxs_gridmap *g, int32_t n_var, const double *in, double *data_grid, int32_t flags, void *stream) try {
+    if (!g || !in || !data_grid) return fail(NXS_ERR_INVALID, "send_rows: NULL argument");
+    if (n_var < 1) return fail(NXS_ERR_INVALID, "send_rows: n_var = %d must be positive", n_var);
+    if (hipSetDevice(g->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    const bool in_dev = flags & NXS_REGRID_IN_DEVICE, out_dev = flags & NXS_REGRID_OUT_DEVICE;
+    const hipStream_t st = stream ? (hipStream_t)stream : S();
+    const size_t G = (size_t)g->G, nels = (size_t)g->nels;
+    DevBuf<double> din, dout;
+    if ((!in_dev && din.alloc(nels * n_var)) || (!out_dev && dout.alloc(G * n_var))) return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+    if ((!in_dev && hipMemcpyAsync(din.p, in, nels * n_var * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) ||
+        (!out_dev && hipMemcpyAsync(dout.p, data_grid, G * n_var * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess))
+        return fail(NXS_ERR_HIP, "upload failed");
+    const double *inp = in_dev ? in : (const double *)din.p;
+    double *outp = out_dev ? data_grid : dout.p;
+    const dim3 grid((unsigned)((G + 255) / 256)), block(256);
+    for (int col0 = 0; col0 < n_var; col0 += gridmap::kSendTile) {
+        const int nv = std::min<int>(gridmap::kSendTile, n_var - col0);
+#define NXS_SEND(NV)                                                                                                                                                   \
+        hipLaunchKernelGGL((gridmap::k_gridmap_send<NV>), grid, block, 0, st, (int)G, (int)n_var, col0, nv, (const int *)g->drow_of_cell.p, (const int *)g->doff.p, \
+                           (const int *)g->dtris.p, (const double *)g->dw.p, (const double *)g->drarea.p, inp, outp)
+        if (nv <= 4) NXS_SEND(4); else if (nv <= 8) NXS_SEND(8); else NXS_SEND(12);
+#undef NXS_SEND
+    }
+    if (hipGetLastError() != hipSuccess) return fail(NXS_ERR_HIP, "send kernel launch failed");
+    if (stream && in_dev && out_dev) return NXS_OK;   // asynchronous on the caller's stream
+    if (!out_dev && hipMemcpyAsync(data_grid, dout.p, G * n_var * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "send kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_gridmap_send_rows"); }
+
 // test door: how nxs_gridmap_receive_rows reads cell / w -- 0 through t_pos, 1 through copies in transposed order; *previous (may be NULL) = the mode before
 extern "C" int nxs_gridmap_debug_receive_lists(int32_t mode, int32_t *previous) try {
     if (mode != 0 && mode != 1) return fail(NXS_ERR_INVALID, "mode must be 0 or 1");

@@ -21,44 +21,52 @@ static int mp_ensure_grids(nxs_dyn_handle *h) {
     return NXS_OK;
 }
 
+// what nxs_dyn_means_points_set and nxs_dyn_cpl_out_attach_grid refuse in a set of points (G > 0); `who` names the entry, n_nod is the nodal list the pairs index
+static int mp_check_points(nxs_dyn_handle *h, const char *who, const nxs_dyn_means_points *p, int n_nod) {
+    if (!p->gridX || !p->gridY) return fail(h, NXS_ERR_INVALID, "%s: gridX or gridY is NULL", who);
+    if (p->rotation != NXS_MEANS_ROTATE_NONE && p->rotation != NXS_MEANS_ROTATE_NORTH_EAST && p->rotation != NXS_MEANS_ROTATE_GRID_THETA)
+        return fail(h, NXS_ERR_INVALID, "%s: rotation = %d is not an nxs_means_rotation mode", who, p->rotation);
+    if (p->rotation == NXS_MEANS_ROTATE_NORTH_EAST && !p->gridLON) return fail(h, NXS_ERR_INVALID, "%s: NXS_MEANS_ROTATE_NORTH_EAST needs gridLON", who);
+    if (p->rotation == NXS_MEANS_ROTATE_GRID_THETA && !p->gridTheta) return fail(h, NXS_ERR_INVALID, "%s: NXS_MEANS_ROTATE_GRID_THETA needs gridTheta", who);
+    if (p->n_pairs < 0 || p->n_pairs > NXS_MEANS_MAX_PAIRS) return fail(h, NXS_ERR_INVALID, "%s: n_pairs = %d (0..%d)", who, p->n_pairs, NXS_MEANS_MAX_PAIRS);
+    for (int k = 0; k < p->n_pairs; ++k)
+        if (p->pair_first[k] < 0 || p->pair_first[k] >= n_nod || p->pair_second[k] < 0 || p->pair_second[k] >= n_nod)
+            return fail(h, NXS_ERR_INVALID, "%s: pair %d names the columns %d and %d, the configured nodal list has %d", who, k, p->pair_first[k], p->pair_second[k], n_nod);
+    for (int i = 0; i < p->G; ++i)
+        if (!std::isfinite(p->gridX[i]) || !std::isfinite(p->gridY[i])) return fail(h, NXS_ERR_INVALID, "%s: the coordinate of grid point %d is not finite", who, i);
+    return NXS_OK;
+}
+// cosang / sinang: gridoutput.cpp:602-614, evaluated on the host, once, with the reference's own expressions (both left empty under NXS_MEANS_ROTATE_NONE)
+static int mp_angles(nxs_dyn_handle *h, const char *who, const nxs_dyn_means_points *p, std::vector<double> &cs, std::vector<double> &sn) {
+    if (p->rotation == NXS_MEANS_ROTATE_NONE) return NXS_OK;
+    const size_t G = (size_t)p->G;
+    const double PI = NXS_MAPX_PI;   // contrib/mapx/include/mapx.h:47, the PI gridoutput.cpp sees
+    const double rotation_angle = p->rotation_angle;
+    cs.resize(G); sn.resize(G);
+    for (size_t i = 0; i < G; ++i) {
+        if (p->rotation == NXS_MEANS_ROTATE_NORTH_EAST) {
+            cs[i] = std::cos(rotation_angle - p->gridLON[i]*PI/180);
+            sn[i] = std::sin(rotation_angle - p->gridLON[i]*PI/180);
+        } else {
+            cs[i] = std::cos(rotation_angle - p->gridTheta[i]);
+            sn[i] = std::sin(rotation_angle - p->gridTheta[i]);
+        }
+        if (!std::isfinite(cs[i]) || !std::isfinite(sn[i])) return fail(h, NXS_ERR_INVALID, "%s: the angle of grid point %d is not finite", who, (int)i);
+    }
+    return NXS_OK;
+}
+
 int nxs_dyn_means_points_set(nxs_dyn_handle *h, const nxs_dyn_means_points *p) try {
     if (!h) return NXS_ERR_INVALID;
     if (p && p->G < 0) return fail(h, NXS_ERR_INVALID, "means_points_set: G = %d < 0", p->G);
-    if (p && p->G > 0) {
-        if (!p->gridX || !p->gridY) return fail(h, NXS_ERR_INVALID, "means_points_set: gridX or gridY is NULL");
-        if (p->rotation != NXS_MEANS_ROTATE_NONE && p->rotation != NXS_MEANS_ROTATE_NORTH_EAST && p->rotation != NXS_MEANS_ROTATE_GRID_THETA)
-            return fail(h, NXS_ERR_INVALID, "means_points_set: rotation = %d is not an nxs_means_rotation mode", p->rotation);
-        if (p->rotation == NXS_MEANS_ROTATE_NORTH_EAST && !p->gridLON) return fail(h, NXS_ERR_INVALID, "means_points_set: NXS_MEANS_ROTATE_NORTH_EAST needs gridLON");
-        if (p->rotation == NXS_MEANS_ROTATE_GRID_THETA && !p->gridTheta) return fail(h, NXS_ERR_INVALID, "means_points_set: NXS_MEANS_ROTATE_GRID_THETA needs gridTheta");
-        if (p->n_pairs < 0 || p->n_pairs > NXS_MEANS_MAX_PAIRS) return fail(h, NXS_ERR_INVALID, "means_points_set: n_pairs = %d (0..%d)", p->n_pairs, NXS_MEANS_MAX_PAIRS);
-        const int n_nod = (int)h->means_ids[1].size();
-        for (int k = 0; k < p->n_pairs; ++k)
-            if (p->pair_first[k] < 0 || p->pair_first[k] >= n_nod || p->pair_second[k] < 0 || p->pair_second[k] >= n_nod)
-                return fail(h, NXS_ERR_INVALID, "means_points_set: pair %d names the columns %d and %d, the configured nodal list has %d", k, p->pair_first[k], p->pair_second[k], n_nod);
-        for (int i = 0; i < p->G; ++i)
-            if (!std::isfinite(p->gridX[i]) || !std::isfinite(p->gridY[i])) return fail(h, NXS_ERR_INVALID, "means_points_set: the coordinate of grid point %d is not finite", i);
-    }
+    if (p && p->G > 0)
+        if (int rc = mp_check_points(h, "means_points_set", p, (int)h->means_ids[1].size())) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));   // (a launch may still use the previous grid)
     if (!p || p->G == 0) { release_means_points(h); return NXS_OK; }
     const size_t G = (size_t)p->G;
-    // cosang / sinang: gridoutput.cpp:602-614, evaluated here, once, with the reference's own expressions
     std::vector<double> cs, sn;
-    if (p->rotation != NXS_MEANS_ROTATE_NONE) {
-        const double PI = NXS_MAPX_PI;   // contrib/mapx/include/mapx.h:47, the PI gridoutput.cpp sees
-        const double rotation_angle = p->rotation_angle;
-        cs.resize(G); sn.resize(G);
-        for (size_t i = 0; i < G; ++i) {
-            if (p->rotation == NXS_MEANS_ROTATE_NORTH_EAST) {
-                cs[i] = std::cos(rotation_angle - p->gridLON[i]*PI/180);
-                sn[i] = std::sin(rotation_angle - p->gridLON[i]*PI/180);
-            } else {
-                cs[i] = std::cos(rotation_angle - p->gridTheta[i]);
-                sn[i] = std::sin(rotation_angle - p->gridTheta[i]);
-            }
-            if (!std::isfinite(cs[i]) || !std::isfinite(sn[i])) return fail(h, NXS_ERR_INVALID, "means_points_set: the angle of grid point %d is not finite", (int)i);
-        }
-    }
+    if (int rc = mp_angles(h, "means_points_set", p, cs, sn)) return rc;
     release_means_points(h);
     int rc;
     if ((rc = dev_alloc(h, h->mp_allocs, &h->mp_gx, G)) || (rc = dev_alloc(h, h->mp_allocs, &h->mp_gy, G))) { release_means_points(h); return rc; }

@@ -286,6 +286,33 @@ NXS_HD inline double grid_value(const double *in, int nb_var, int var, const int
     v *= r_cell_area;
     return v;
 }
+// mesh -> grid for the coupler's put (nxs_gridmap_send_rows): the nv <= NV variables col0 .. col0 + nv - 1 of one wet cell over ONE walk of its row --
+// per variable the statements of grid_value (ConservativeRemapping.cpp:128-132: v = 0; v += in[tri*nb_var+var]*w in list order; v *= r_cell_area), so the same
+// bits.  The loops over NV are unrolled with constant indices: v[] stays in registers on the device (nv only predicates the loads).
+template <int NV>
+NXS_HD inline void grid_values(const double *in, int nb_var, int col0, int nv, const int *tris, const double *w, int n, double r_cell_area, double *v) {
+    for (int i = 0; i < NV; ++i) v[i] = 0.;
+    int k = 0;
+    // four entries at a time: their (triangle, weight) pairs and then their rows are requested together, the sums are still taken entry by entry in list order --
+    // the walk is a chain of dependent loads (tris[k], then the row), and one entry at a time left a lane waiting for two memory latencies per entry
+    for (; k + 4 <= n; k += 4) {
+        const double *r0 = in + (long long)tris[k] * nb_var + col0, *r1 = in + (long long)tris[k + 1] * nb_var + col0;
+        const double *r2 = in + (long long)tris[k + 2] * nb_var + col0, *r3 = in + (long long)tris[k + 3] * nb_var + col0;
+        const double w0 = w[k], w1 = w[k + 1], w2 = w[k + 2], w3 = w[k + 3];
+        double x0[NV], x1[NV], x2[NV], x3[NV];
+        for (int i = 0; i < NV; ++i)
+            if (i < nv) { x0[i] = r0[i]; x1[i] = r1[i]; x2[i] = r2[i]; x3[i] = r3[i]; }
+        for (int i = 0; i < NV; ++i)
+            if (i < nv) { v[i] += x0[i] * w0; v[i] += x1[i] * w1; v[i] += x2[i] * w2; v[i] += x3[i] * w3; }
+    }
+    for (; k < n; ++k) {
+        const double *row = in + (long long)tris[k] * nb_var + col0;
+        const double wk = w[k];
+        for (int i = 0; i < NV; ++i)
+            if (i < nv) v[i] += row[i] * wk;
+    }
+    for (int i = 0; i < NV; ++i) v[i] *= r_cell_area;
+}
 // grid -> mesh (ConservativeRemapping.cpp:145-170) as a gather: variable `var` of one triangle; pos[0..n) = its entries' indices in the forward
 // lists, ascending -- the order in which the reference's scatter over (cell, position) reaches this triangle; cell[p] = gridP of entry p's row.
 // A triangle without an entry gets 0 * (1 / 0.), a NaN, as in the reference.

@@ -157,6 +157,14 @@ def load_library():
     L.nxs_dyn_means_points_update.argtypes = [H]
     L.nxs_dyn_means_points_get.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
     L.nxs_dyn_means_points_reset.argtypes = [H]
+    L.nxs_dyn_cpl_out_configure.argtypes = [H, P(_abi.MeansConfig)]
+    L.nxs_dyn_cpl_out_update.argtypes = [H, C.c_double]
+    L.nxs_dyn_cpl_out_get.argtypes = [H, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
+    L.nxs_dyn_cpl_out_reset.argtypes = [H]
+    L.nxs_dyn_cpl_out_attach_grid.argtypes = [H, C.c_void_p, P(_abi.MeansPoints)]
+    L.nxs_dyn_cpl_out_put.argtypes = [H, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p), C.c_int32]
+    L.nxs_dyn_cpl_out_reset_grid.argtypes = [H]
+    L.nxs_dyn_fsd_diag_configure.argtypes = [H, C.c_double, C.c_double, C.c_double]
     L.nxs_dyn_drifters_set.argtypes = [H, C.c_int32, C.c_int32, _abi.c_double_p, _abi.c_double_p, _abi.c_int32_p]
     L.nxs_dyn_drifters_clear.argtypes = [H, C.c_int32]
     L.nxs_dyn_drifters_mesh_bbox.argtypes = [H, C.c_int32, _abi.c_double_p]
@@ -282,6 +290,8 @@ EXPORTS = (
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_to_grid_conservative", "nxs_dyn_means_reset",
     "nxs_dyn_means_points_set", "nxs_dyn_means_points_lsm", "nxs_dyn_means_points_update", "nxs_dyn_means_points_get", "nxs_dyn_means_points_reset",
+    "nxs_dyn_cpl_out_configure", "nxs_dyn_cpl_out_update", "nxs_dyn_cpl_out_get", "nxs_dyn_cpl_out_reset", "nxs_dyn_cpl_out_attach_grid", "nxs_dyn_cpl_out_put",
+    "nxs_dyn_cpl_out_reset_grid", "nxs_dyn_fsd_diag_configure",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
     "nxs_dyn_drifters_get", "nxs_dyn_regrid", "nxs_dyn_regrid_carry_thermo", "nxs_dyn_regrid_thermo_info_get",
     "nxs_dyn_explicit_solve", "nxs_dyn_update", "nxs_dyn_synchronize", "nxs_dyn_step_host",
@@ -292,7 +302,7 @@ INTERP_EXPORTS = ("nxs_interp_mesh_to_mesh_2d", "nxs_interp_mesh_to_grid", "nxs_
                   "nxs_interp_last_error", "nxs_interp_last_info", "nxs_mesh_convex_completion", "nxs_mesh_convex_completion_mode", "nxs_regrid_create", "nxs_regrid_destroy",
                   "nxs_regrid_interp_nodes", "nxs_regrid_remap_elements", "nxs_interp_last_timing", "nxs_regrid_debug_tables", "nxs_gridmap_create", "nxs_gridmap_destroy",
                   "nxs_gridmap_info", "nxs_gridmap_mesh_to_grid", "nxs_gridmap_grid_to_mesh", "nxs_gridmap_export", "nxs_gridmap_import", "nxs_gridmap_restrict",
-                  "nxs_gridmap_debug_chunk", "nxs_gridmap_receive_rows", "nxs_gridmap_debug_receive_lists")
+                  "nxs_gridmap_debug_chunk", "nxs_gridmap_receive_rows", "nxs_gridmap_debug_receive_lists", "nxs_gridmap_send_rows")
 
 
 def selftest_quotients(n: int, seed: int = 1, mode: int = 0, device: int = 0) -> int:
@@ -1516,7 +1526,7 @@ class FiniteElementDynamics:
         ids, masks = [], []
         for v in variables or ():
             name, mask = v if isinstance(v, (tuple, list)) else (v, False)
-            ids.append(_abi.MEANS_ID[name] if isinstance(name, str) else int(name))
+            ids.append((_abi.MEANS_FSD_ID[name] if name in _abi.MEANS_FSD_ID else _abi.MEANS_ID[name]) if isinstance(name, str) else int(name))
             masks.append(1 if mask else 0)
         return np.asarray(ids, np.int32), np.asarray(masks, np.uint8)
 
@@ -1525,6 +1535,11 @@ class FiniteElementDynamics:
         elemental list takes both, mixed) / MEANS_NODAL (or NXS_MEANS_* numbers), each optionally as (name, mask) for Variable::mask.  Two empty lists switch the
         feature off.  Survives set_mesh.  A thermodynamic variable reads the row fluxes() / column() / slab() left on the handle: means_update refuses while it is
         missing."""
+        c, keep = self._means_config(elemental, nodal)
+        self._chk(self.L.nxs_dyn_means_configure(self.h, C.byref(c)))
+        self._means_n = (int(keep[0].size), int(keep[2].size))
+
+    def _means_config(self, elemental, nodal):
         ei, em = self._means_list(elemental, 0, len(_abi.MEANS_ELEMENTAL))
         ni, nm = self._means_list(nodal, _abi.NXS_MEANS_NODAL_BEGIN, _abi.NXS_MEANS_NODAL_BEGIN + len(_abi.MEANS_NODAL))
         c = _abi.MeansConfig()
@@ -1533,8 +1548,7 @@ class FiniteElementDynamics:
             c.elemental_ids, c.elemental_mask = _abi.iptr(ei), _abi.bptr(em)
         if ni.size:
             c.nodal_ids, c.nodal_mask = _abi.iptr(ni), _abi.bptr(nm)
-        self._chk(self.L.nxs_dyn_means_configure(self.h, C.byref(c)))
-        self._means_n = (int(ei.size), int(ni.size))
+        return c, (ei, em, ni, nm)
 
     def means_set_tau_ow(self, tau_ow):
         """D_tau_ow ([Ne], written by the thermodynamics): the input of taux / tauy / taumod that is not the handle's.  None detaches it."""
@@ -1651,6 +1665,82 @@ class FiniteElementDynamics:
     def means_points_reset(self):
         """resetGridMean(): the grid accumulators to zero, on the stream."""
         self._chk(self.L.nxs_dyn_means_points_reset(self.h))
+
+    # ---- the coupler's outgoing fields: M_cpl_out, the "coupler put" of step() (FE.cpp:8226-8266) and the put in front of a regrid (FE.cpp:8012-8052) ----
+    def cpl_out_configure(self, elemental=(), nodal=()):
+        """The variables of M_cpl_out, a second accumulator set beside the Moorings': the names (or numbers) means_configure takes, `dmax` / `dmean` among them;
+        a mask flag is refused.  Two empty lists switch the set off and free it, the attached grid included.  Survives set_mesh / regrid."""
+        c, keep = self._means_config(elemental, nodal)
+        self._chk(self.L.nxs_dyn_cpl_out_configure(self.h, C.byref(c)))
+        self._cpl_n = (int(keep[0].size), int(keep[2].size))
+        if self._cpl_n == (0, 0):
+            self._cpl_map, self._cpl_G = None, 0
+
+    def cpl_out_update(self, time_factor: float):
+        """updateMeans(M_cpl_out, cpl_time_factor): the kernels of means_update on this set; asynchronous on the handle's stream."""
+        self._chk(self.L.nxs_dyn_cpl_out_update(self.h, float(time_factor)))
+
+    def cpl_out_get(self, want_host: bool = True):
+        """(elemental [Ne, n_el] or None, nodal [Nn, n_nod] or None, device pointer of the elemental rows, of the nodal rows) of the mesh accumulators."""
+        n_el, n_nod = getattr(self, "_cpl_n", (0, 0))
+        el = np.empty((self.lm.num_elements, n_el)) if want_host and n_el else None
+        nod = np.empty((self.lm.num_nodes, n_nod)) if want_host and n_nod else None
+        de, dn = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.nxs_dyn_cpl_out_get(self.h, _abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None, C.byref(de), C.byref(dn)))
+        return el, nod, de.value, dn.value
+
+    def cpl_out_reset(self):
+        """resetMeshMean(bamgmesh) of M_cpl_out: both mesh accumulators to zero, on the stream."""
+        self._chk(self.L.nxs_dyn_cpl_out_reset(self.h))
+
+    def cpl_out_attach_grid(self, gridmap, gridX=None, gridY=None, miss_val=-1e14, rotation="none", gridLON=None, gridTheta=None, rotation_angle=0., pairs=()):
+        """The exchange grid of M_cpl_out: `gridmap` is the interp.GridMap of THIS mesh (borrowed: keep it alive; dropped by set_mesh / regrid, attach the new one
+        again), the P-points with their rotation and pairs as means_points_set takes them (needed only with nodal variables).  The grid accumulators survive
+        set_mesh / regrid and a new attach on a grid of the same size."""
+        p, keep = None, []
+        if gridX is not None and np.size(gridX):
+            x, y = np.ascontiguousarray(gridX, np.float64).ravel(), np.ascontiguousarray(gridY, np.float64).ravel()
+            if x.shape != y.shape:
+                raise ValueError("gridX and gridY differ in length")
+            p = _abi.MeansPoints()
+            p.G, p.rotation = x.size, _abi.MEANS_ROTATION[rotation] if isinstance(rotation, str) else int(rotation)
+            p.gridX, p.gridY = _abi.dptr(x), _abi.dptr(y)
+            keep += [x, y]
+            for name, a in (("gridLON", gridLON), ("gridTheta", gridTheta)):
+                if a is not None:
+                    a = np.ascontiguousarray(a, np.float64).ravel()
+                    if a.shape != x.shape:
+                        raise ValueError(f"{name} has {a.size} entries, the grid {x.size}")
+                    keep.append(a)
+                    setattr(p, name, _abi.dptr(a))
+            p.rotation_angle, p.miss_val = float(rotation_angle), float(miss_val)
+            pairs = list(pairs)
+            p.n_pairs = len(pairs)
+            for k, (first, second) in enumerate(pairs[:_abi.NXS_MEANS_MAX_PAIRS]):
+                p.pair_first[k], p.pair_second[k] = int(first), int(second)
+        self._chk(self.L.nxs_dyn_cpl_out_attach_grid(self.h, gridmap.h if gridmap is not None else None, C.byref(p) if p is not None else None))
+        self._cpl_map, self._cpl_G = gridmap, gridmap.info()["grid_size"]
+
+    def cpl_out_put(self, want_host: bool = True, reset: bool = False):
+        """M_cpl_out.updateGridMean() on the handle's stream: (grid_elemental [n_el, G] or None, grid_nodal [n_nod, G] or None, device pointer of the elemental
+        grid rows, of the nodal ones).  want_host False: asynchronous, nothing is copied.  reset: resetMeshMean + resetGridMean behind the copies."""
+        n_el, n_nod = getattr(self, "_cpl_n", (0, 0))
+        G = getattr(self, "_cpl_G", 0)
+        el = np.empty((n_el, G)) if want_host and n_el else None
+        nod = np.empty((n_nod, G)) if want_host and n_nod else None
+        de, dn = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.nxs_dyn_cpl_out_put(self.h, _abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None, C.byref(de), C.byref(dn),
+                                             _abi.NXS_CPL_OUT_RESET if reset else 0))
+        return el, nod, de.value, dn.value
+
+    def cpl_out_reset_grid(self):
+        """resetGridMean() of M_cpl_out: the grid accumulators to zero, on the stream."""
+        self._chk(self.L.nxs_dyn_cpl_out_reset_grid(self.h))
+
+    def fsd_diag_configure(self, dmax_c_threshold=0.1, fsd_unbroken_floe_size=1000., fsd_min_floe_size=10.):
+        """The three options of D_dmax / D_dmean (wave_coupling.dmax_c_threshold, fsd_unbroken_floe_size, fsd_min_floe_size; the defaults of options.cpp:510-518):
+        what the means `dmax` / `dmean` of either set read beside fsd_configure's bin limits and centres."""
+        self._chk(self.L.nxs_dyn_fsd_diag_configure(self.h, float(dmax_c_threshold), float(fsd_unbroken_floe_size), float(fsd_min_floe_size)))
 
     # ---- the drifters: checkMoveDrifters / checkUpdateDrifters (FE.cpp:8375-8437), Drifters::move / updateConc / maskXY (drifters.cpp:468-579) ----
     @staticmethod

@@ -453,6 +453,37 @@ class GridMap:
         return out
 
 
+    def send_rows(self, data=None, data_grid=None, in_device=None, out_device=None, stream=None):
+        """nxs_gridmap_send_rows: the coupler's put of element variables, ADDED to data_grid [n_var, G] (made of zeros when None) in one launch per twelve
+        variables.  data [nels, n_var], or in_device = (device pointer, n_var); out_device = the device address of the [n_var, G] rows (then None is returned).
+        stream: a hipStream_t as an int (asynchronous when both sides are on the device), None for the library's own."""
+        i = self.info()
+        flags, keep = 0, None
+        if in_device is not None:
+            dptr, nv = in_device
+            src = C.c_void_p(int(dptr)); flags |= self.IN_DEVICE
+        else:
+            keep = np.ascontiguousarray(data, np.float64)
+            if keep.ndim == 1:
+                keep = keep[:, None]
+            if keep.shape[0] != i["nels"]:
+                raise ValueError(f"data has {keep.shape[0]} rows, expected {i['nels']}")
+            nv = keep.shape[1]
+            src = C.c_void_p(keep.ctypes.data)
+        if out_device is not None:
+            data_grid = None
+            dst = C.c_void_p(int(out_device)); flags |= self.OUT_DEVICE
+        else:
+            if data_grid is None:
+                data_grid = np.zeros((nv, i["grid_size"]))
+            if data_grid.shape != (nv, i["grid_size"]) or data_grid.dtype != np.float64 or not data_grid.flags.c_contiguous:
+                raise ValueError(f"data_grid has shape {data_grid.shape}, expected a C-contiguous float64 ({nv}, {i['grid_size']})")
+            dst = C.c_void_p(data_grid.ctypes.data)
+        self._chk(self.L.nxs_gridmap_send_rows(self.h, int(nv), src, dst, flags, C.c_void_p(int(stream)) if stream else None))
+        del keep
+        return data_grid
+
+
 def gridmap_debug_receive_lists(mode: int) -> int:
     """Test door: 0 = receive_rows reads cell and weight through the index list, 1 = through copies in transposed order.  Returns the mode before."""
     L = _declare_gridmap()
@@ -479,7 +510,8 @@ def _declare_gridmap():
         L.nxs_gridmap_debug_chunk.argtypes = [C.c_int32, P32]
         L.nxs_gridmap_receive_rows.argtypes = [V, C.c_int32, C.POINTER(V), D, D, D, D, C.POINTER(V), C.c_int32, V]
         L.nxs_gridmap_debug_receive_lists.argtypes = [C.c_int32, P32]
-        for n in ("create", "destroy", "info", "mesh_to_grid", "grid_to_mesh", "export", "import", "restrict", "debug_chunk", "receive_rows", "debug_receive_lists"):
+        L.nxs_gridmap_send_rows.argtypes = [V, C.c_int32, V, V, C.c_int32, V]
+        for n in ("create", "destroy", "info", "mesh_to_grid", "grid_to_mesh", "export", "import", "restrict", "debug_chunk", "receive_rows", "debug_receive_lists", "send_rows"):
             getattr(L, "nxs_gridmap_" + n).restype = C.c_int
         L._gridmap_declared = True
     return L
