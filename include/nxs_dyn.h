@@ -32,6 +32,7 @@
  *   thermo(): thermoWinton / thermoIce0 columns nxs_dyn_column, nxs_dyn_column_* (FE.cpp:5306-5411, 6396-6448, 6633-6962)
  *   thermo(): the slab loop from new ice to tracers nxs_dyn_slab, nxs_dyn_slab_*, nxs_slab_* (FE.cpp:5413-6133, 6538-6627)
  *   thermo() under OceanType::COUPLED + the receive nxs_dyn_ocean_coupled_*, nxs_gridmap_receive_rows (FE.cpp:5150-5157, 5348-5358, 5826-5841; externaldata.cpp:163-236)
+ *   ... and its nodal half: I_Uocn, I_Vocn, I_SSH, I_tauwix / y   nxs_dyn_nodes_coupled_*, nxs_nodemap_* (dataset.cpp:11157-11175; externaldata.cpp:498-509, 1246-1281, 1457-1463)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -1323,8 +1324,8 @@ NXS_API int nxs_dyn_flux_device_rows(nxs_dyn_handle *h, const double **device_ro
  *   nxs_dyn_ocean_coupled_get      synchronised; [Ne] host rows, a NULL row is skipped, a row asked for that was never given on this mesh is NXS_ERR_STATE.
  *                  device_rows (may be NULL) [NXS_OC_ROWS]: the device addresses, NULL for a missing row -- device_rows[NXS_OC_WLBK] is what a host hands
  *                  nxs_dyn_fsd_breakup(..., NXS_FSD_WLBK_ON_DEVICE, ...)
- * OUT OF SCOPE: the nodal half of the receive (I_Uocn, I_Vocn, I_SSH, I_tauwix / y go through FromMeshToMeshQuick on a triangulated source, the gridTheta
- * rotation of transformData; those rows keep nxs_dyn_set_forcing_pair / nxs_dyn_set_wave_stress), ocean_turning_angle = 0 (a parameter the host sets), the
+ * The nodal half of the receive (I_Uocn, I_Vocn, I_SSH, I_tauwix / y: FromMeshToMeshQuick on a triangulated source, the gridTheta rotation of transformData) is
+ * nxs_dyn_nodes_coupled_*, below.  OUT OF SCOPE: ocean_turning_angle = 0 (a parameter the host sets), the
  * reduction over ranks and the OASIS put of the outgoing side (its accumulators and grid: nxs_dyn_cpl_out_*), OASIS itself, reading and projecting the exchange
  * grid file, AEROBULK. */
 enum { NXS_OC_OCEAN_TEMP = 0, NXS_OC_OCEAN_SALT = 1, NXS_OC_QSRML = 2, NXS_OC_MLD = 3, NXS_OC_WLBK = 4, NXS_OC_ROWS = 5 };
@@ -1342,6 +1343,38 @@ NXS_API int nxs_dyn_ocean_coupled_attach(nxs_dyn_handle *h, struct nxs_gridmap *
 NXS_API int nxs_dyn_ocean_coupled_receive(nxs_dyn_handle *h, const double *const *fields, int32_t flags);
 NXS_API int nxs_dyn_ocean_coupled_put_rows(nxs_dyn_handle *h, const nxs_dyn_ocean_coupled_rows *rows);
 NXS_API int nxs_dyn_ocean_coupled_get(nxs_dyn_handle *h, const nxs_dyn_ocean_coupled_rows *out /* may be NULL */, const double **device_rows /* [NXS_OC_ROWS], may be NULL */);
+
+/* ---- The NODAL half of a coupled run's receive on the device: I_Uocn, I_Vocn, I_SSH of ocean_cpl_nodes and I_tauwix, I_tauwiy of wave_cpl_nodes through a node map
+ * (nxs_nodemap_*, include/nxs_interp.h: InterpFromMeshToMesh2dx_weights once per mesh, _apply per coupling step; FE.cpp:7690-7697, 8041-8048, dataset.cpp:11157-11175,
+ * externaldata.cpp:498-509, 944-1288, 1457-1463).  Everything here is additive: a handle that never attaches allocates nothing, launches nothing and keeps its bits.
+ *   nxs_dyn_nodes_coupled_attach   which = NXS_NC_OCEAN or NXS_NC_WAVE: two datasets, two maps (their exchange grids may differ).  The map is BORROWED (the caller
+ *                  keeps it alive and destroys it) and must have the handle's Nn targets, ghosts included, and a source (nxs_nodemap_set_source: reduced, the
+ *                  rotation, lat / lon of an east/north pair).  c: a, b of receiveCouplingData and factor, bias of ExternalData::get per FIELD, in the order the
+ *                  fields arrive; c == NULL detaches.  The attachment goes with the mesh: nxs_dyn_set_mesh and nxs_dyn_regrid drop it (the weights were the old
+ *                  mesh's), attach the new map afterwards.
+ *   nxs_dyn_nodes_coupled_receive  fields[k], k < n_fields: the [G] fields as OASIS delivers them, host pointers or, with NXS_REGRID_IN_DEVICE, device pointers.
+ *                  Two launches on the handle's stream (k_nodemap_source, k_nodemap_gather), asynchronous; with device fields there is no host synchronisation.
+ *                  NXS_NC_OCEAN: three fields, the vector (0, 1).  The interpolated values are stored RAW into snapshot 0 of the half-rows NXS_NF_OCEAN_U,
+ *                  NXS_NF_OCEAN_V, NXS_NF_SSH -- the rows nxs_dyn_set_forcing_pair owns, marked as nxs_dyn_forcing_ingest marks them -- so that
+ *                  nxs_dyn_set_forcing_time_rows with NXS_TF_STEP for the ocean and ssh groups IS ExternalData::get (factor and bias are that call's; the
+ *                  attachment's are not read).  NXS_NC_WAVE: two fields, the vector (0, 1); factor*x + bias goes straight into the handle's M_tau_wi [u | v], which
+ *                  is attached exactly as nxs_dyn_set_wave_stress(h, non-NULL) attaches it: the launch plan picks the wave-stress kernel builds as it does today.
+ *                  (The receive that attaches it for the first time waits for the stream once, as that call does; every later one is asynchronous.)
+ *   nxs_dyn_nodes_coupled_get      synchronised; out[k] (may be NULL, as may out) receives the [Nn] row of field k, device_rows[k] its device address.
+ * NXS_ERR_STATE: before nxs_dyn_set_mesh, without an attachment of `which` on this mesh, a map without a source, a row asked for that was never received.
+ * NXS_ERR_INVALID: h NULL, an unknown `which`, a map whose N is not Nn or that lives on another device than the handle, n_fields that is not the dataset's, a NULL field, a coefficient that is not finite. */
+struct nxs_nodemap;   /* include/nxs_interp.h */
+enum { NXS_NC_OCEAN = 0, NXS_NC_WAVE = 1 };
+#define NXS_NC_DATASETS 2
+#define NXS_NC_MAX_FIELDS 3
+typedef struct nxs_dyn_nodes_coupled_config {
+    double a[NXS_NC_MAX_FIELDS], b[NXS_NC_MAX_FIELDS];            /* receiveCouplingData: t *= a; t += b */
+    double factor[NXS_NC_MAX_FIELDS], bias[NXS_NC_MAX_FIELDS];    /* ExternalData::get (NXS_NC_WAVE) */
+} nxs_dyn_nodes_coupled_config;
+NXS_API int nxs_nodes_coupled_default_config(nxs_dyn_nodes_coupled_config *c);   /* a = 1, b = 0, factor = 1, bias = 0 */
+NXS_API int nxs_dyn_nodes_coupled_attach(nxs_dyn_handle *h, int32_t which, struct nxs_nodemap *map, const nxs_dyn_nodes_coupled_config *c /* NULL: detach */);
+NXS_API int nxs_dyn_nodes_coupled_receive(nxs_dyn_handle *h, int32_t which, const double *const *fields, int32_t n_fields, int32_t flags);
+NXS_API int nxs_dyn_nodes_coupled_get(nxs_dyn_handle *h, int32_t which, double *const *out /* may be NULL */, const double **device_rows /* may be NULL */);
 
 /* ---- The rest of thermo()'s slab loop on the device: FE.cpp:5413-6133 as a default (non-OASIS) build compiles it -- the assimilation flux (FE.cpp:5415-5425),
  * section 6: new ice over open water and lateral melt (FE.cpp:5434-5646; newice_type 1 .. 4, type 3 with windSpeedElement, FE.cpp:6359-6370; melt_type 1, 2), the

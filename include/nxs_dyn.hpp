@@ -136,6 +136,9 @@ public:
     void oceanCoupledReceive(const double *const *fields, int32_t flags = 0) { check(nxs_dyn_ocean_coupled_receive(h_, fields, flags), "ocean_coupled_receive"); }
     void oceanCoupledPutRows(const nxs_dyn_ocean_coupled_rows &rows) { check(nxs_dyn_ocean_coupled_put_rows(h_, &rows), "ocean_coupled_put_rows"); }
     void oceanCoupledGet(const nxs_dyn_ocean_coupled_rows *out, const double **device_rows = nullptr) { check(nxs_dyn_ocean_coupled_get(h_, out, device_rows), "ocean_coupled_get"); }
+    void nodesCoupledAttach(int32_t which, struct nxs_nodemap *map, const nxs_dyn_nodes_coupled_config *cfg) { check(nxs_dyn_nodes_coupled_attach(h_, which, map, cfg), "nodes_coupled_attach"); }
+    void nodesCoupledReceive(int32_t which, const double *const *fields, int32_t n_fields, int32_t flags = 0) { check(nxs_dyn_nodes_coupled_receive(h_, which, fields, n_fields, flags), "nodes_coupled_receive"); }
+    void nodesCoupledGet(int32_t which, double *const *out, const double **device_rows = nullptr) { check(nxs_dyn_nodes_coupled_get(h_, which, out, device_rows), "nodes_coupled_get"); }
     nxs_dyn_handle *handle() { return h_; }
 
 private:

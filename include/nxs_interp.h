@@ -243,6 +243,78 @@ NXS_INTERP_API int nxs_gridmap_restrict(nxs_gridmap *map, const int32_t *local_o
 /* test door: build the weights in chunks of `cells` cells (0 = as many as the arena allows); *last_chunks (may be NULL) = the chunks the last build took */
 NXS_INTERP_API int nxs_gridmap_debug_chunk(int32_t cells, int32_t *last_chunks);
 
+/* ---- the coupler's receive of NODAL fields (I_Uocn, I_Vocn, I_SSH of ocean_cpl_nodes; I_tauwix, I_tauwiy of wave_cpl_nodes): the location of every node in the
+ * triangulated exchange grid computed ONCE per mesh, three weights applied per coupling step.  Replaces, under #ifdef OASIS,
+ *
+ *   InterpFromMeshToMesh2dx_weights(M_areacoord, M_vertex, M_it, pfindex, gridX, gridY, ...)    DataSet::setNodalWeights, dataset.cpp:11157-11175
+ *   receiveCouplingData -> transformData -> InterpFromMeshToMesh2dx_apply -> ExternalData::get   externaldata.cpp:498-509, 944-1288, 1457-1463, 434-438
+ *
+ * nxs_nodemap_create runs contrib/bamg/src/InterpFromMeshToMesh2dx_weights.cpp:59-120 for nodal data on a regrid context made of the SOURCE triangulation
+ * (grid.pfindex, grid.gridX, grid.gridY of the reduced exchange-grid nodes; triangulating them stays the host's, as in DataSet::loadGrid).  x, y [N] are the targets
+ * in the dataset's coordinates (convertTargetXY's output, the host's job).  The integers, the division (double)dete[k]/tb.det and the hull projection
+ * (CloseBoundaryEdge, both outcomes) are those of nxs_regrid_interp_nodes with isdefault == 0; the map keeps the three 0-based source vertices and the three area
+ * coordinates of every target as six rows.  At the VERTEX outcome of CloseBoundaryEdge the weights are 1, 0, 0 in the triangle behind one of the two hull edges
+ * that end at the vertex; which of the two the reference takes depends on its walk, and the value differs only where a zero-weight vertex holds NaN or Inf.
+ *   NXS_ERR_INVALID: a NULL argument, N < 1, flags other than 0 (none is defined yet); a target inside the convex hull but in a triangle of the completion (the reference throws,
+ *   _weights.cpp:72-73): the message names their count and the first one, no map is made; a source the convex completion does not cover (the message carries the
+ *   context's own reason): a map never holds stand-in weights.
+ * nxs_nodemap_info: targets, source nodes, targets beyond the hull (-1 for an imported map; any pointer may be NULL).  nxs_nodemap_device: the device the map's rows live on (the context's, or nxs_nodemap_import's argument).  nxs_nodemap_export hands out the six rows (M_vertex / M_areacoord
+ * transposed; any pointer may be NULL), nxs_nodemap_import makes a map of such rows (vertices in 0 .. nods_src - 1, else NXS_ERR_INVALID).
+ *
+ * nxs_nodemap_set_source gives the source side of the dataset; everything is copied.
+ *   G        MN_full, the length of a field as OASIS3::get_2d delivers it
+ *   R        the reduced nodes: the map's source nodes (else NXS_ERR_INVALID); reduced [R] = grid.reduced_nodes_ind (0 .. G - 1), NULL = the identity and R == G
+ *   rotation_mode  what transformData does to a vector pair after the east/north branch: NXS_NODEMAP_ROTATE_NONE; _UNIFORM (dataset->rotation_angle != 0.,
+ *            externaldata.cpp:1246-1261) with cos_m_diff_angle, sin_m_diff_angle as the host computed them; _GRID_THETA (grid.gridded_rotation_angle, :1263-1281)
+ *            with rotation = mapNextsim->rotation*PI/180. and theta [R] = grid.gridTheta: std::cos(rotation - theta[i]) and std::sin(rotation - theta[i]) are
+ *            evaluated here, once, ON THE HOST (the function nxs_dyn_means_points_set uses), and both rows stay resident: the device only multiplies and adds
+ *   east_west_oriented  the pairs are east / north components (wave_cpl_nodes, dataset.cpp:3202-3207): lat, lon [R] in degrees, map = the model's projection
+ *            (nxs_mapx_polar of nxs_dyn.h), delta_t = 1., the reference's constant (externaldata.cpp:956; anything else is NXS_ERR_INVALID)
+ * The wave-direction branch of transformData is not built.
+ *
+ * nxs_nodemap_receive_rows, per coupling step, 1 <= n_var <= NXS_NODEMAP_MAX_RECEIVE: two launches on `stream`.
+ *   k_nodemap_source    per reduced point and variable  t = fields[v][reduced[i]]; t *= a[v]; t += b[v]  (receiveCouplingData), then per pair the east/north
+ *                       branch and the rotation, new0 = c*t0 + s*t1, new1 = -s*t0 + c*t1: loaded_data, [n_var][R] rows of the map
+ *   k_nodemap_gather    per target and variable  a0*d[v0] + a1*d[v1] + a2*d[v2], left to right (_apply.cpp:57-59); with NXS_NODEMAP_GET the value stored is
+ *                       factor[v]*x + bias[v] (ExternalData::get, always evaluated), else x
+ *   pairs    [n_var] or NULL: pairs[v] = w >= 0 names the vector (v, w), component 0 first; -1 elsewhere.  At most two pairs, no variable in two of them.
+ *   flags    NXS_REGRID_IN_DEVICE = fields[] are device pointers, NXS_REGRID_OUT_DEVICE = out_rows[] are ([N] each), NXS_NODEMAP_GET.  stream as for
+ *            nxs_gridmap_receive_rows: with a stream and device rows out the call is ASYNCHRONOUS on it (host fields are uploaded on it first, and the call waits
+ *            for the uploads only); with device fields too there is no host synchronisation at all.
+ *   NXS_ERR_STATE before nxs_nodemap_set_source.  NXS_ERR_INVALID: a NULL argument or field, n_var out of range, a pair that is out of range or names a variable twice.
+ *   ONE STREAM AT A TIME: the rows of loaded_data and the buffer host fields are uploaded to are the MAP's, one of each.  Two receives on one map are ordered only
+ *            when they are enqueued on the same stream (as a handle's are); on two streams the caller orders them.
+ * nxs_nodemap_debug_source (test door): the first n_var rows of the last receive's loaded_data, [n_var][R].
+ * There is no CPU path: NXS_ERR_NO_DEVICE without a device. */
+typedef struct nxs_nodemap nxs_nodemap;
+struct nxs_mapx_polar;
+#define NXS_NODEMAP_MAX_RECEIVE 4
+#define NXS_NODEMAP_GET 4   /* flags of nxs_nodemap_receive_rows, beside NXS_REGRID_IN_DEVICE / NXS_REGRID_OUT_DEVICE */
+enum { NXS_NODEMAP_ROTATE_NONE = 0, NXS_NODEMAP_ROTATE_UNIFORM = 1, NXS_NODEMAP_ROTATE_GRID_THETA = 2 };
+typedef struct nxs_nodemap_source {
+    int32_t G, R;
+    const int32_t *reduced;
+    int32_t rotation_mode;
+    int32_t east_west_oriented;
+    double cos_m_diff_angle, sin_m_diff_angle;
+    double rotation;
+    const double *theta;
+    const double *lat, *lon;
+    const struct nxs_mapx_polar *map;
+    double delta_t;
+} nxs_nodemap_source;
+NXS_INTERP_API int nxs_nodemap_create(nxs_regrid *src, const double *x, const double *y, int32_t N, int32_t flags, nxs_nodemap **out);
+NXS_INTERP_API int nxs_nodemap_destroy(nxs_nodemap *map);
+NXS_INTERP_API int nxs_nodemap_info(const nxs_nodemap *map, int32_t *N, int32_t *nods_src, int32_t *beyond_hull);
+NXS_INTERP_API int nxs_nodemap_device(const nxs_nodemap *map, int32_t *device);
+NXS_INTERP_API int nxs_nodemap_export(nxs_nodemap *map, int32_t *v0, int32_t *v1, int32_t *v2, double *a0, double *a1, double *a2);
+NXS_INTERP_API int nxs_nodemap_import(int32_t device, int32_t N, int32_t nods_src, const int32_t *v0, const int32_t *v1, const int32_t *v2, const double *a0,
+                                      const double *a1, const double *a2, nxs_nodemap **out);
+NXS_INTERP_API int nxs_nodemap_set_source(nxs_nodemap *map, const nxs_nodemap_source *s);
+NXS_INTERP_API int nxs_nodemap_receive_rows(nxs_nodemap *map, int32_t n_var, const double *const *fields, const double *a, const double *b, const int32_t *pairs,
+                                            const double *factor, const double *bias, double *const *out_rows, int32_t flags, void *stream);
+NXS_INTERP_API int nxs_nodemap_debug_source(nxs_nodemap *map, double *out, int32_t n_var);
+
 
 #ifdef __cplusplus
 }

@@ -359,6 +359,25 @@ class ForcingVectors(C.Structure):   # nxs_dyn_forcing_vectors
                                                                                                         ("cos_m_diff_angle", C.c_double), ("sin_m_diff_angle", C.c_double)])
 
 
+# ---- the coupler's receive of nodal fields (include/nxs_interp.h, nxs_nodemap_*; include/nxs_dyn.h, nxs_dyn_nodes_coupled_*)
+NXS_NODEMAP_MAX_RECEIVE = 4
+NXS_NODEMAP_GET = 4
+NODEMAP_ROTATE = {"none": 0, "uniform": 1, "grid_theta": 2}      # NXS_NODEMAP_ROTATE_*
+NC_DATASETS = ("ocean", "wave")                                   # NXS_NC_OCEAN, NXS_NC_WAVE
+NC_FIELDS = {"ocean": ("I_Uocn", "I_Vocn", "I_SSH"), "wave": ("I_tauwix", "I_tauwiy")}
+NXS_NC_MAX_FIELDS = 3
+
+
+class NodemapSource(C.Structure):   # nxs_nodemap_source
+    _fields_ = [("G", C.c_int32), ("R", C.c_int32), ("reduced", c_int32_p), ("rotation_mode", C.c_int32), ("east_west_oriented", C.c_int32),
+                ("cos_m_diff_angle", C.c_double), ("sin_m_diff_angle", C.c_double), ("rotation", C.c_double), ("theta", c_double_p), ("lat", c_double_p),
+                ("lon", c_double_p), ("map", C.POINTER(MapxPolar)), ("delta_t", C.c_double)]
+
+
+class NodesCoupledConfig(C.Structure):   # nxs_dyn_nodes_coupled_config
+    _fields_ = [(k, C.c_double * NXS_NC_MAX_FIELDS) for k in ("a", "b", "factor", "bias")]
+
+
 class ForcingRows(C.Structure):   # nxs_dyn_forcing_rows
     _fields_ = [("row", c_double_p * NXS_NF_ROWS)]
 

@@ -52,6 +52,7 @@
 #include "nxs_drifters.hpp"
 #include "nxs_patchcut.hpp"
 #include "nxs_resident_registry.hpp"
+#include "nxs_angles.hpp"
 
 #include "nxs_dyn_kernels.inl"
 #include "nxs_fsd_kernels.inl"
@@ -253,6 +254,12 @@ struct OceanCoupled {      // nxs_dyn_ocean_coupled_*: the attachment of a coupl
     double *d_oc_qsrml = nullptr, *d_oc_wlbk = nullptr;   // [Ne] M_qsrml, M_wlbk, made when first given
     unsigned oc_have = 0;                  // bit NXS_OC_QSRML / NXS_OC_WLBK: that row was given on this mesh
 };
+struct NodesCoupled {      // nxs_dyn_nodes_coupled_*: the attachments of ocean_cpl_nodes and wave_cpl_nodes.  No array of its own: the rows are the forcing pair's and M_tau_wi
+    std::vector<void *> nc_allocs;
+    bool nc_attached[NXS_NC_DATASETS] = {false, false};
+    struct nxs_nodemap *nc_map[NXS_NC_DATASETS] = {nullptr, nullptr};   // borrowed
+    nxs_dyn_nodes_coupled_config nc_cfg[NXS_NC_DATASETS] = {};
+};
 struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stress / nxs_dyn_put_coupled) and the floe-size distribution's (nxs_dyn_fsd_*)
     std::vector<void *> coupled_allocs;
     // ATTACHED is what h->dw says (tau_wi, cum_damage, conc_fsd non-NULL) and fsd_mech / fsd_cumw non-NULL; a detached buffer is kept for the next attach (no hipFree
@@ -294,7 +301,7 @@ struct CplOutGrid {        // ... and the exchange grid's side: the P-points, co
     int cpl_grid_n[2] = {0, 0};                // the list sizes the accumulators were made for
 };
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, CoupledBuffers, MeansPoints, CplOut, CplOutGrid {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, NodesCoupled, CoupledBuffers, MeansPoints, CplOut, CplOutGrid {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -713,6 +720,8 @@ void release_nesting(nxs_dyn_handle *h) { release_group<Nesting>(h, h->nest_allo
 void release_diffusion(nxs_dyn_handle *h) { release_group<Diffusion>(h, h->diff_allocs); }
 // the coupled ocean: its two rows and the attachment itself -- the map was the old mesh's (FE.cpp:8037-8049: new weights after a regrid)
 void release_ocean_coupled(nxs_dyn_handle *h) { release_group<OceanCoupled>(h, h->oc_allocs); }
+// the nodal receive's two attachments: their maps held the old mesh's weights (FE.cpp:8041-8048)
+void release_nodes_coupled(nxs_dyn_handle *h) { release_group<NodesCoupled>(h, h->nc_allocs); }
 // thermo() runs its OceanType::COUPLED branches (FE.cpp:5150-5157, 5348-5358, 5826-5841): a coupled ocean is attached with ocean_temp, ocean_salt and qsrml configured
 inline bool ocean_coupled_on(const nxs_dyn_handle *h) {
     const unsigned need = (1u << NXS_OC_OCEAN_TEMP) | (1u << NXS_OC_OCEAN_SALT) | (1u << NXS_OC_QSRML);
@@ -757,6 +766,7 @@ void release_mesh(nxs_dyn_handle *h) {
     release_nesting(h);
     release_diffusion(h);
     release_ocean_coupled(h);
+    release_nodes_coupled(h);
     release_cpl_out(h);
     release_coupled(h);
     h->no_big_cut = false;
@@ -3086,6 +3096,15 @@ int nxs_dyn_set_forcing_time(nxs_dyn_handle *h, double fcoeff0, double fcoeff1, 
 } catch (...) { return dyn_caught(h, "nxs_dyn_set_forcing_time"); }
 
 // ---- the coupled build's terms (#ifdef OASIS in the reference): see include/nxs_dyn.h
+// M_tau_wi's buffer and its attachment: the one path of nxs_dyn_set_wave_stress (values from the host) and nxs_dyn_nodes_coupled_receive (values from a launch)
+static int wave_stress_buffer(nxs_dyn_handle *h) {
+    if (h->d_tau_wi) return NXS_OK;
+    return dev_alloc(h, h->coupled_allocs, &h->d_tau_wi, 2 * (size_t)h->dm.Nn);   // (tau_sum: by the first step that runs the full prep, explicit_solve)
+}
+static void wave_stress_attach(nxs_dyn_handle *h, bool was) {
+    h->dw.tau_wi = h->d_tau_wi; h->dw.tau_sum = h->d_tau_sum;
+    if (!was) release_graph(h);   // (kernel arguments are baked into the graphs)
+}
 int nxs_dyn_set_wave_stress(nxs_dyn_handle *h, const double *tau_wi) try {   // M_tau_wi, FE.cpp:10353-10354, 10408-10414, 10509-10518
     if (!h) return NXS_ERR_INVALID;
     if (!h->have_mesh) return fail(h, NXS_ERR_STATE, "set_wave_stress before set_mesh");
@@ -3097,13 +3116,11 @@ int nxs_dyn_set_wave_stress(nxs_dyn_handle *h, const double *tau_wi) try {   // 
         if (was) release_graph(h);   // (kernel arguments are baked into the graphs)
         return NXS_OK;
     }
-    int rc;
-    if (!h->d_tau_wi && (rc = dev_alloc(h, h->coupled_allocs, &h->d_tau_wi, n2))) return rc;   // (tau_sum: by the first step that runs the full prep, explicit_solve)
+    if (int rc = wave_stress_buffer(h)) return rc;
     pin_host_buffer(h, tau_wi, n2 * sizeof(double));
     HIPCHK(h, hipMemcpyAsync(h->d_tau_wi, tau_wi, n2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->dw.tau_wi = h->d_tau_wi; h->dw.tau_sum = h->d_tau_sum;
-    if (!was) release_graph(h);
+    wave_stress_attach(h, was);
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_set_wave_stress"); }
 
@@ -4178,6 +4195,7 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_nesting.inl"
 #include "nxs_nodal_forcing.inl"
 #include "nxs_ocean_coupled.inl"
+#include "nxs_nodes_coupled.inl"
 #include "nxs_means_points.inl"
 #include "nxs_cpl_out.inl"
 

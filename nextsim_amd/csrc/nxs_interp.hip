@@ -30,6 +30,7 @@
 #include "nxs_interp.h"
 #include "nxs_hull.inl"
 #include "nxs_drifters.hpp"
+#include "nxs_angles.hpp"
 
 namespace {
 
@@ -1454,6 +1455,251 @@ extern "C" int nxs_gridmap_debug_chunk(int32_t cells, int32_t *last_chunks) try 
     if (last_chunks) *last_chunks = g_gridmap_last_chunks;
     return NXS_OK;
 } catch (...) { return entry_caught("nxs_gridmap_debug_chunk"); }
+
+// ---------------------------------------------------------------------------------------------------------
+// The coupler's receive of nodal fields: InterpFromMeshToMesh2dx_weights once per mesh, _apply per coupling step (nxs_nodemap_*, include/nxs_interp.h)
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+#include "nxs_nodemap_kernels.inl"
+}  // namespace
+
+struct nxs_nodemap {
+    int device = 0, N = 0, nods = 0, beyond_hull = 0;
+    DevBuf<int> v0, v1, v2;            // [N] the 0-based source vertices of every target
+    DevBuf<double> a0, a1, a2;         // [N] their area coordinates
+    // the source side (nxs_nodemap_set_source)
+    bool have_source = false;
+    int G = 0, R = 0, rotate = 0, east_west = 0;
+    bool identity = true;
+    double c = 1., s = 0.;
+    nxs_mapx_polar map{};
+    DevBuf<int> dreduced;
+    DevBuf<double> dcs, dsn, dlat, dlon;
+    DevBuf<double> dstage;             // [NXS_NODEMAP_MAX_RECEIVE][R] loaded_data, made by set_source
+    DevBuf<double> dfields;            // with host fields: where they are uploaded, [n_var][G]; it only grows
+    size_t fields_cap = 0;
+    int last_n_var = 0;
+};
+
+namespace {
+
+int nodemap_alloc(nxs_nodemap *m) {
+    const size_t N = (size_t)m->N;
+    if (m->v0.alloc(N) || m->v1.alloc(N) || m->v2.alloc(N) || m->a0.alloc(N) || m->a1.alloc(N) || m->a2.alloc(N))
+        return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int nxs_nodemap_create(nxs_regrid *src, const double *x, const double *y, int32_t N, int32_t flags, nxs_nodemap **out) try {
+    if (!out) return fail(NXS_ERR_INVALID, "nodemap_create: out is NULL");
+    *out = nullptr;
+    if (!src || !x || !y) return fail(NXS_ERR_INVALID, "nodemap_create: NULL argument");
+    if (N < 1) return fail(NXS_ERR_INVALID, "nodemap_create: N = %d must be positive", N);
+    if (flags != 0) return fail(NXS_ERR_INVALID, "nodemap_create: flags = %d (0 expected)", flags);
+    if (hipSetDevice(src->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    Locator *locp = nullptr;
+    if (int rc = regrid_locator(src, true, &locp)) return rc;
+    if (!locp->comp.ok || locp->d.nhull < 1)
+        return fail(NXS_ERR_INVALID, "nodemap_create: the source triangulation has no convex completion (%s): a map never holds stand-in weights",
+                    locp->comp.why.empty() ? "no hull edge" : locp->comp.why.c_str());
+    std::unique_ptr<nxs_nodemap> m(new nxs_nodemap());
+    m->device = src->device; m->N = N; m->nods = src->nods;
+    if (int rc = nodemap_alloc(m.get())) return rc;
+    DevBuf<double> dx, dy;
+    DevBuf<int> dcounts;
+    const int counts0[4] = {0, 0x7fffffff, 0, 0};
+    if (dx.upload(x, N) || dy.upload(y, N) || dcounts.upload(counts0, 4)) return fail(NXS_ERR_HIP, "device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));
+    InterpDev d = locp->d;
+    d.N_data = 0; d.N_interp = N; d.nodal = 1; d.isdefault = 0; d.defaultvalue = 0.;
+    hipLaunchKernelGGL(nodemap::k_nodemap_weights, dim3((N + 255) / 256), dim3(256), 0, S(), d, (const double *)dx.p, (const double *)dy.p,
+                       nodemap::Weights{m->v0.p, m->v1.p, m->v2.p, m->a0.p, m->a1.p, m->a2.p}, dcounts.p);
+    int counts[4] = {0, 0, 0, 0};
+    if (copy_sync(counts, dcounts.p, sizeof counts, hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "weights kernel failed: %s", hipGetErrorString(hipGetLastError()));
+    if (counts[0] > 0)   // _weights.cpp:72-73
+        return fail(NXS_ERR_INVALID, "nodemap_create: %d target%s outside of the source mesh but inside its convex hull (the first: target %d at %.17g, %.17g): "
+                    "InterpFromMeshToMesh2dx_weights throws there", counts[0], counts[0] == 1 ? " is" : "s are", counts[1], x[counts[1]], y[counts[1]]);
+    if (counts[3] > 0) return fail(NXS_ERR_INVALID, "nodemap_create: %d targets beyond the hull that no hull edge faces", counts[3]);
+    m->beyond_hull = counts[2];
+    *out = m.release();
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_create"); }
+
+extern "C" int nxs_nodemap_destroy(nxs_nodemap *m) try {
+    if (!m) return NXS_OK;
+    (void)hipSetDevice(m->device);
+    delete m;
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_destroy"); }
+
+extern "C" int nxs_nodemap_info(const nxs_nodemap *m, int32_t *N, int32_t *nods_src, int32_t *beyond_hull) try {
+    if (!m) return fail(NXS_ERR_INVALID, "nodemap_info: NULL argument");
+    if (N) *N = m->N;
+    if (nods_src) *nods_src = m->nods;
+    if (beyond_hull) *beyond_hull = m->beyond_hull;
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_info"); }
+
+extern "C" int nxs_nodemap_device(const nxs_nodemap *m, int32_t *device) try {
+    if (!m || !device) return fail(NXS_ERR_INVALID, "nodemap_device: NULL argument");
+    *device = m->device;
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_device"); }
+
+extern "C" int nxs_nodemap_export(nxs_nodemap *m, int32_t *v0, int32_t *v1, int32_t *v2, double *a0, double *a1, double *a2) try {
+    if (!m) return fail(NXS_ERR_INVALID, "nodemap_export: NULL argument");
+    if (hipSetDevice(m->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    const size_t N = (size_t)m->N;
+    int32_t *vi[3] = {v0, v1, v2};
+    const int *vd[3] = {m->v0.p, m->v1.p, m->v2.p};
+    double *ai[3] = {a0, a1, a2};
+    const double *ad[3] = {m->a0.p, m->a1.p, m->a2.p};
+    for (int k = 0; k < 3; ++k) {
+        if (vi[k] && copy_sync(vi[k], vd[k], N * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+        if (ai[k] && copy_sync(ai[k], ad[k], N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    }
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_export"); }
+
+extern "C" int nxs_nodemap_import(int32_t device, int32_t N, int32_t nods_src, const int32_t *v0, const int32_t *v1, const int32_t *v2, const double *a0,
+                                  const double *a1, const double *a2, nxs_nodemap **out) try {
+    if (!out) return fail(NXS_ERR_INVALID, "nodemap_import: out is NULL");
+    *out = nullptr;
+    if (!v0 || !v1 || !v2 || !a0 || !a1 || !a2) return fail(NXS_ERR_INVALID, "nodemap_import: NULL argument");
+    if (N < 1 || nods_src < 1) return fail(NXS_ERR_INVALID, "nodemap_import: N = %d, nods_src = %d must be positive", N, nods_src);
+    const int32_t *vi[3] = {v0, v1, v2};
+    for (int k = 0; k < 3; ++k)
+        for (int i = 0; i < N; ++i)
+            if (vi[k][i] < 0 || vi[k][i] >= nods_src) return fail(NXS_ERR_INVALID, "nodemap_import: v%d[%d] = %d is not a source node (0 .. %d)", k, i, vi[k][i], nods_src - 1);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NXS_ERR_NO_DEVICE, "no HIP device visible: the node map has no CPU path");
+    if (device < 0 || device >= ndev) return fail(NXS_ERR_INVALID, "device %d out of range", device);
+    if (hipSetDevice(device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    std::unique_ptr<nxs_nodemap> m(new nxs_nodemap());
+    m->device = device; m->N = N; m->nods = nods_src;
+    if (m->v0.upload(v0, N) || m->v1.upload(v1, N) || m->v2.upload(v2, N) || m->a0.upload(a0, N) || m->a1.upload(a1, N) || m->a2.upload(a2, N))
+        return fail(NXS_ERR_HIP, "device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));
+    m->beyond_hull = -1;   // (not known to an imported map: weights inside a triangle and on a hull edge look alike)
+    *out = m.release();
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_import"); }
+
+extern "C" int nxs_nodemap_set_source(nxs_nodemap *m, const nxs_nodemap_source *s) try {
+    if (!m || !s) return fail(NXS_ERR_INVALID, "nodemap_set_source: NULL argument");
+    if (s->R != m->nods) return fail(NXS_ERR_INVALID, "nodemap_set_source: R = %d, the map's source has %d nodes", s->R, m->nods);
+    if (s->G < s->R) return fail(NXS_ERR_INVALID, "nodemap_set_source: G = %d is smaller than R = %d", s->G, s->R);
+    if (!s->reduced && s->G != s->R) return fail(NXS_ERR_INVALID, "nodemap_set_source: reduced is NULL (the identity) but G = %d and R = %d differ", s->G, s->R);
+    const size_t R = (size_t)s->R;
+    if (s->reduced)
+        for (size_t i = 0; i < R; ++i)
+            if (s->reduced[i] < 0 || s->reduced[i] >= s->G) return fail(NXS_ERR_INVALID, "nodemap_set_source: reduced[%d] = %d is not in 0 .. %d", (int)i, s->reduced[i], s->G - 1);
+    if (s->rotation_mode != NXS_NODEMAP_ROTATE_NONE && s->rotation_mode != NXS_NODEMAP_ROTATE_UNIFORM && s->rotation_mode != NXS_NODEMAP_ROTATE_GRID_THETA)
+        return fail(NXS_ERR_INVALID, "nodemap_set_source: rotation_mode = %d is not an NXS_NODEMAP_ROTATE_* mode", s->rotation_mode);
+    if (s->rotation_mode == NXS_NODEMAP_ROTATE_UNIFORM && (!std::isfinite(s->cos_m_diff_angle) || !std::isfinite(s->sin_m_diff_angle)))
+        return fail(NXS_ERR_INVALID, "nodemap_set_source: cos_m_diff_angle / sin_m_diff_angle is not finite");
+    if (s->rotation_mode == NXS_NODEMAP_ROTATE_GRID_THETA && !s->theta) return fail(NXS_ERR_INVALID, "nodemap_set_source: NXS_NODEMAP_ROTATE_GRID_THETA needs theta");
+    if (s->east_west_oriented) {
+        if (!s->lat || !s->lon || !s->map) return fail(NXS_ERR_INVALID, "nodemap_set_source: east_west_oriented needs lat, lon and map");
+        if (s->delta_t != 1.) return fail(NXS_ERR_INVALID, "nodemap_set_source: delta_t = %g (the reference's constant is 1.)", s->delta_t);
+    }
+    std::vector<double> cs, sn;
+    if (s->rotation_mode == NXS_NODEMAP_ROTATE_GRID_THETA) {   // externaldata.cpp:1272-1273, on the host
+        cs.resize(R); sn.resize(R);
+        for (size_t i = 0; i < R; ++i) {
+            nxs_cos_sin_of_difference(s->rotation, s->theta[i], &cs[i], &sn[i]);
+            if (!std::isfinite(cs[i]) || !std::isfinite(sn[i])) return fail(NXS_ERR_INVALID, "nodemap_set_source: the angle of source point %d is not finite", (int)i);
+        }
+    }
+    if (hipSetDevice(m->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(NXS_ERR_HIP, "hipDeviceSynchronize failed");   // (a receive on any stream may still read the previous source)
+    m->have_source = false;
+    if ((s->reduced && m->dreduced.upload(s->reduced, R)) || (!cs.empty() && (m->dcs.upload(cs.data(), R) || m->dsn.upload(sn.data(), R))) ||
+        (s->east_west_oriented && (m->dlat.upload(s->lat, R) || m->dlon.upload(s->lon, R))) || m->dstage.alloc((size_t)NXS_NODEMAP_MAX_RECEIVE * R))
+        return fail(NXS_ERR_HIP, "device allocation / upload failed: %s", hipGetErrorString(hipGetLastError()));
+    m->G = s->G; m->R = s->R; m->identity = s->reduced == nullptr;
+    m->rotate = s->rotation_mode; m->east_west = s->east_west_oriented != 0;
+    m->c = s->cos_m_diff_angle; m->s = s->sin_m_diff_angle;
+    if (s->east_west_oriented) m->map = *s->map;
+    m->last_n_var = 0;
+    m->have_source = true;
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_set_source"); }
+
+extern "C" int nxs_nodemap_receive_rows(nxs_nodemap *m, int32_t n_var, const double *const *fields, const double *a, const double *b, const int32_t *pairs,
+                                        const double *factor, const double *bias, double *const *out_rows, int32_t flags, void *stream) try {
+    if (!m || !fields || !a || !b || !factor || !bias || !out_rows) return fail(NXS_ERR_INVALID, "nodemap_receive_rows: NULL argument");
+    if (n_var < 1 || n_var > nodemap::kMaxVar) return fail(NXS_ERR_INVALID, "nodemap_receive_rows: n_var = %d (1 .. %d)", n_var, nodemap::kMaxVar);
+    for (int v = 0; v < n_var; ++v)
+        if (!fields[v] || !out_rows[v]) return fail(NXS_ERR_INVALID, "nodemap_receive_rows: %s %d is NULL", fields[v] ? "output row" : "field", v);
+    if (!m->have_source) return fail(NXS_ERR_STATE, "nodemap_receive_rows: before nxs_nodemap_set_source");
+    nodemap::SourceArgs sa{};
+    if (pairs) {
+        int used[nodemap::kMaxVar] = {0, 0, 0, 0};
+        for (int v = 0; v < n_var; ++v) {
+            const int w = pairs[v];
+            if (w < 0) continue;
+            if (w >= n_var || w == v) return fail(NXS_ERR_INVALID, "nodemap_receive_rows: pairs[%d] = %d is not another variable (0 .. %d)", v, w, n_var - 1);
+            if (used[v] || used[w]) return fail(NXS_ERR_INVALID, "nodemap_receive_rows: variable %d is named by two pairs", used[v] ? v : w);
+            used[v] = used[w] = 1;
+            sa.j0[sa.npairs] = v; sa.j1[sa.npairs] = w; ++sa.npairs;   // (four variables hold at most two pairs)
+        }
+    }
+    if (hipSetDevice(m->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    const bool in_dev = flags & NXS_REGRID_IN_DEVICE, out_dev = flags & NXS_REGRID_OUT_DEVICE;
+    const hipStream_t st = stream ? (hipStream_t)stream : S();
+    const size_t G = (size_t)m->G, N = (size_t)m->N;
+    if (!in_dev) {   // the fields go up on the same stream; the host arrays are the caller's again on return
+        if (m->fields_cap < (size_t)n_var * G) {
+            if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "hipStreamSynchronize failed");   // (an earlier receive may still read the buffer)
+            if (m->dfields.alloc((size_t)n_var * G)) { m->fields_cap = 0; return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError())); }
+            m->fields_cap = (size_t)n_var * G;
+        }
+        for (int v = 0; v < n_var; ++v)
+            if (hipMemcpyAsync(m->dfields.p + (size_t)v * G, fields[v], G * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return fail(NXS_ERR_HIP, "upload failed");
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "upload failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    DevBuf<double> dout;
+    if (!out_dev && dout.alloc((size_t)n_var * N)) return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+    nodemap::GatherArgs ga{};
+    for (int v = 0; v < n_var; ++v) {
+        sa.field[v] = in_dev ? fields[v] : m->dfields.p + (size_t)v * G;
+        sa.a[v] = a[v]; sa.b[v] = b[v];
+        ga.out[v] = out_dev ? out_rows[v] : dout.p + (size_t)v * N;
+        ga.factor[v] = factor[v]; ga.bias[v] = bias[v];
+    }
+    sa.n_var = n_var; sa.R = m->R; sa.reduced = m->identity ? nullptr : m->dreduced.p;
+    sa.east_west = m->east_west; sa.lat = m->dlat.p; sa.lon = m->dlon.p; sa.map = m->map; sa.Re = NXS_MAPX_RE_KM * 1000.;
+    sa.rotate = m->rotate; sa.c = m->c; sa.s = m->s; sa.cs = m->dcs.p; sa.sn = m->dsn.p;
+    sa.stage = m->dstage.p;
+    ga.stage = m->dstage.p; ga.R = m->R; ga.N = m->N; ga.get = (flags & NXS_NODEMAP_GET) ? 1 : 0;
+    hipLaunchKernelGGL(nodemap::k_nodemap_source, dim3((unsigned)((m->R + 255) / 256)), dim3(256), 0, st, sa);
+    const dim3 grid((unsigned)((N + 255) / 256)), block(256);
+    const int *v0 = m->v0.p, *v1 = m->v1.p, *v2 = m->v2.p;
+    const double *a0 = m->a0.p, *a1 = m->a1.p, *a2 = m->a2.p;
+#define NXS_GATHER(NV) case NV: hipLaunchKernelGGL((nodemap::k_nodemap_gather<NV>), grid, block, 0, st, ga, v0, v1, v2, a0, a1, a2); break;
+    switch (n_var) { NXS_GATHER(1) NXS_GATHER(2) NXS_GATHER(3) NXS_GATHER(4) }
+#undef NXS_GATHER
+    m->last_n_var = n_var;
+    if (hipGetLastError() != hipSuccess) return fail(NXS_ERR_HIP, "nodemap_receive_rows: kernel launch failed");
+    if (stream && out_dev) return NXS_OK;   // asynchronous on the caller's stream
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "nodemap_receive_rows: kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!out_dev)
+        for (int v = 0; v < n_var; ++v)
+            if (copy_sync(out_rows[v], dout.p + (size_t)v * N, N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_receive_rows"); }
+
+// test door: loaded_data of the last receive, [n_var][R]
+extern "C" int nxs_nodemap_debug_source(nxs_nodemap *m, double *out, int32_t n_var) try {
+    if (!m || !out) return fail(NXS_ERR_INVALID, "nodemap_debug_source: NULL argument");
+    if (!m->have_source || m->last_n_var < 1) return fail(NXS_ERR_STATE, "nodemap_debug_source: no nxs_nodemap_receive_rows on this source yet");
+    if (n_var < 1 || n_var > m->last_n_var) return fail(NXS_ERR_INVALID, "nodemap_debug_source: n_var = %d, the last receive had %d", n_var, m->last_n_var);
+    if (hipSetDevice(m->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(NXS_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(hipGetLastError()));
+    if (copy_sync(out, m->dstage.p, (size_t)n_var * m->R * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_debug_source"); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Structured grid -> mesh nodes: the forcing ingest (InterpFromGridToMeshx, called at externaldata.cpp:1436)

@@ -44,13 +44,7 @@ static int mp_angles(nxs_dyn_handle *h, const char *who, const nxs_dyn_means_poi
     const double rotation_angle = p->rotation_angle;
     cs.resize(G); sn.resize(G);
     for (size_t i = 0; i < G; ++i) {
-        if (p->rotation == NXS_MEANS_ROTATE_NORTH_EAST) {
-            cs[i] = std::cos(rotation_angle - p->gridLON[i]*PI/180);
-            sn[i] = std::sin(rotation_angle - p->gridLON[i]*PI/180);
-        } else {
-            cs[i] = std::cos(rotation_angle - p->gridTheta[i]);
-            sn[i] = std::sin(rotation_angle - p->gridTheta[i]);
-        }
+        nxs_cos_sin_of_difference(rotation_angle, p->rotation == NXS_MEANS_ROTATE_NORTH_EAST ? p->gridLON[i]*PI/180 : p->gridTheta[i], &cs[i], &sn[i]);
         if (!std::isfinite(cs[i]) || !std::isfinite(sn[i])) return fail(h, NXS_ERR_INVALID, "%s: the angle of grid point %d is not finite", who, (int)i);
     }
     return NXS_OK;

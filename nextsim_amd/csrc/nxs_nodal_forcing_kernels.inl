@@ -17,7 +17,7 @@
 // Plain loads and stores, no LDS, no atomics.  The bodies compile for the host (tests/nodal_forcing_host_kernel.cpp defines the HIP qualifiers away).  The build is
 // uncontracted (-ffp-contract=off).
 
-#include "nxs_mapx_body.inl"
+#include "nxs_east_north_body.inl"   // nxs_mapx_body.inl and nf_east_north_point, shared with k_nodemap_source (nxs_nodemap_kernels.inl)
 
 enum { NF_ROWS = 5, NF_SETS = 4, NF_MAX_COLUMNS = 32, NF_MAX_VECTORS = 4, NF_GROUPS = 3 };
 static_assert(NF_ROWS == NXS_NF_ROWS && NF_SETS == NXS_NF_SETS && NF_MAX_COLUMNS == NXS_NF_MAX_COLUMNS && NF_MAX_VECTORS == NXS_NF_MAX_VECTORS && NF_GROUPS == NXS_NF_GROUPS,
@@ -48,36 +48,6 @@ struct NfVectors {
     double c, s;                   // cos(-rotation_angle), sin(-rotation_angle)
 };
 
-// externaldata.cpp:1157-1203 for one point
-__device__ __forceinline__ void nf_east_north_point(const NfVectors &a, double lat0, double lon0, double *p0, double *p1) {
-    const double PI = NXS_MAPX_PI, dt = 1.;
-    const double east = *p0, north = *p1;
-    double east_deg, north_deg;
-    if (lat0 < 90.) {
-        east_deg = east / (a.R * cos(lat0 * PI / 180.)) * 180. / PI;
-        north_deg = north / a.R * 180. / PI;
-    } else {
-        east_deg = 0.;
-        north_deg = 0.;
-    }
-    const double lat1 = lat0 + north_deg * dt;
-    double lon1 = lon0 + east_deg * dt;
-    lon1 = lon1 - 360. * floor(lon1 / (360.));
-    double x0, y0, x1, y1;
-    nxs_mapx_forward_point(a.map, lat0, lon0, &x0, &y0);
-    nxs_mapx_forward_point(a.map, lat1, lon1, &x1, &y1);
-    double vx = (x1 - x0) / dt;
-    double vy = (y1 - y0) / dt;
-    const double speed = hypot(east, north);
-    const double moved = hypot(vx, vy);
-    if (moved > 0.) {
-        vx = vx / moved * speed;
-        vy = vy / moved * speed;
-    }
-    *p0 = vx;
-    *p1 = vy;
-}
-
 __global__ void __launch_bounds__(BLOCK) k_nf_east_north(NfVectors a) {
     const int k = blockIdx.y;
     if (!a.east_west[k]) return;
@@ -86,7 +56,7 @@ __global__ void __launch_bounds__(BLOCK) k_nf_east_north(NfVectors a) {
     const int y_ind = i / a.g.N, x_ind = i % a.g.N;
     double *cell = a.g.data + ((size_t)y_ind * a.g.cN + x_ind) * a.g.N_data;
     const double lat = a.per_point ? a.lat[i] : a.lat[y_ind], lon = a.per_point ? a.lon[i] : a.lon[x_ind];
-    nf_east_north_point(a, lat, lon, cell + a.j0[k], cell + a.j1[k]);
+    nf_east_north_point(a.map, a.R, lat, lon, cell + a.j0[k], cell + a.j1[k]);
 }
 
 __global__ void __launch_bounds__(BLOCK) k_nf_pole(NfVectors a) {

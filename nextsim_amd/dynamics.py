@@ -132,6 +132,10 @@ def load_library():
     L.nxs_dyn_ocean_coupled_receive.argtypes = [H, P(C.c_void_p), C.c_int32]
     L.nxs_dyn_ocean_coupled_put_rows.argtypes = [H, P(_abi.OceanCoupledRows)]
     L.nxs_dyn_ocean_coupled_get.argtypes = [H, P(_abi.OceanCoupledRows), P(C.c_void_p)]
+    L.nxs_nodes_coupled_default_config.argtypes = [P(_abi.NodesCoupledConfig)]
+    L.nxs_dyn_nodes_coupled_attach.argtypes = [H, C.c_int32, C.c_void_p, P(_abi.NodesCoupledConfig)]
+    L.nxs_dyn_nodes_coupled_receive.argtypes = [H, C.c_int32, P(C.c_void_p), C.c_int32, C.c_int32]
+    L.nxs_dyn_nodes_coupled_get.argtypes = [H, C.c_int32, P(C.c_void_p), P(C.c_void_p)]
     L.nxs_slab_default_config.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_config_check.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_constants.argtypes = [P(C.c_double), C.c_int32]
@@ -285,7 +289,7 @@ EXPORTS = (
     "nxs_nesting_config_check", "nxs_dyn_nesting_configure", "nxs_dyn_nesting_pair", "nxs_dyn_nesting_time", "nxs_dyn_nesting_ice", "nxs_dyn_nesting_dynamics",
     "nxs_dyn_nesting_get", "nxs_dyn_diffusion_configure", "nxs_dyn_diffuse", "nxs_dyn_flux_device_rows",
     "nxs_ocean_coupled_default_config", "nxs_ocean_coupled_config_check", "nxs_dyn_ocean_coupled_attach", "nxs_dyn_ocean_coupled_receive", "nxs_dyn_ocean_coupled_put_rows",
-    "nxs_dyn_ocean_coupled_get",
+    "nxs_dyn_ocean_coupled_get", "nxs_nodes_coupled_default_config", "nxs_dyn_nodes_coupled_attach", "nxs_dyn_nodes_coupled_receive", "nxs_dyn_nodes_coupled_get",
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_to_grid_conservative", "nxs_dyn_means_reset",
@@ -302,7 +306,8 @@ INTERP_EXPORTS = ("nxs_interp_mesh_to_mesh_2d", "nxs_interp_mesh_to_grid", "nxs_
                   "nxs_interp_last_error", "nxs_interp_last_info", "nxs_mesh_convex_completion", "nxs_mesh_convex_completion_mode", "nxs_regrid_create", "nxs_regrid_destroy",
                   "nxs_regrid_interp_nodes", "nxs_regrid_remap_elements", "nxs_interp_last_timing", "nxs_regrid_debug_tables", "nxs_gridmap_create", "nxs_gridmap_destroy",
                   "nxs_gridmap_info", "nxs_gridmap_mesh_to_grid", "nxs_gridmap_grid_to_mesh", "nxs_gridmap_export", "nxs_gridmap_import", "nxs_gridmap_restrict",
-                  "nxs_gridmap_debug_chunk", "nxs_gridmap_receive_rows", "nxs_gridmap_debug_receive_lists", "nxs_gridmap_send_rows")
+                  "nxs_gridmap_debug_chunk", "nxs_gridmap_receive_rows", "nxs_gridmap_debug_receive_lists", "nxs_gridmap_send_rows", "nxs_nodemap_create", "nxs_nodemap_destroy",
+                  "nxs_nodemap_info", "nxs_nodemap_device", "nxs_nodemap_export", "nxs_nodemap_import", "nxs_nodemap_set_source", "nxs_nodemap_receive_rows", "nxs_nodemap_debug_source")
 
 
 def selftest_quotients(n: int, seed: int = 1, mode: int = 0, device: int = 0) -> int:
@@ -1377,6 +1382,55 @@ class FiniteElementDynamics:
         self._chk(self.L.nxs_dyn_ocean_coupled_get(self.h, C.byref(r), dev if want_device else None))
         if want_device:
             return out, dict(zip(_abi.OC_ROWS, (int(p or 0) for p in dev)))
+        return out
+
+    # ---- the nodal half of a coupled run's receive (include/nxs_dyn.h, nxs_dyn_nodes_coupled_*) ----
+    def nodes_coupled_attach(self, which, nodemap, a=1., b=0., factor=1., bias=0.):
+        """nxs_dyn_nodes_coupled_attach.  which: "ocean" (I_Uocn, I_Vocn, I_SSH) or "wave" (I_tauwix, I_tauwiy); nodemap: an interp.NodeMap with this mesh's nodes as
+        targets and a source set (borrowed: keep it alive); a, b, factor, bias per field (scalars are broadcast)."""
+        w = _abi.NC_DATASETS.index(which)
+        c = _abi.NodesCoupledConfig()
+        n = len(_abi.NC_FIELDS[which])
+        for name, v, dflt in (("a", a, 1.), ("b", b, 0.), ("factor", factor, 1.), ("bias", bias, 0.)):
+            vals = np.broadcast_to(np.asarray(v, np.float64), (n,))
+            for k in range(_abi.NXS_NC_MAX_FIELDS):
+                getattr(c, name)[k] = float(vals[k]) if k < n else dflt
+        self._chk(self.L.nxs_dyn_nodes_coupled_attach(self.h, w, nodemap.h if nodemap is not None else None, C.byref(c)))
+        if not hasattr(self, "_nc_maps"):
+            self._nc_maps = {}
+        self._nc_maps[which] = nodemap
+
+    def nodes_coupled_detach(self, which):
+        """nxs_dyn_nodes_coupled_attach(h, which, NULL, NULL)"""
+        self._chk(self.L.nxs_dyn_nodes_coupled_attach(self.h, _abi.NC_DATASETS.index(which), None, None))
+        getattr(self, "_nc_maps", {}).pop(which, None)
+
+    def nodes_coupled_receive(self, which, fields, device: bool = False):
+        """nxs_dyn_nodes_coupled_receive: fields = one [G] array per field of the dataset, in order -- or, with device=True, one device address each.  Two launches on
+        the handle's stream."""
+        n = len(fields)
+        ptrs = (C.c_void_p * max(n, 1))()
+        keep = []
+        for k, f in enumerate(fields):
+            if device:
+                ptrs[k] = int(f) if f is not None else None
+            elif f is not None:
+                arr = np.ascontiguousarray(f, np.float64).ravel()
+                keep.append(arr)
+                ptrs[k] = arr.ctypes.data
+        self._chk(self.L.nxs_dyn_nodes_coupled_receive(self.h, _abi.NC_DATASETS.index(which), ptrs, n, 1 if device else 0))   # NXS_REGRID_IN_DEVICE
+        del keep
+
+    def nodes_coupled_get(self, which, want_device: bool = False):
+        """The received rows [n_fields, Nn] (synchronised); with want_device also their device addresses."""
+        n = len(_abi.NC_FIELDS[which])
+        out = np.empty((n, self.lm.num_nodes))
+        ptrs, dev = (C.c_void_p * _abi.NXS_NC_MAX_FIELDS)(), (C.c_void_p * _abi.NXS_NC_MAX_FIELDS)()
+        for k in range(n):
+            ptrs[k] = out[k].ctypes.data
+        self._chk(self.L.nxs_dyn_nodes_coupled_get(self.h, _abi.NC_DATASETS.index(which), ptrs, dev if want_device else None))
+        if want_device:
+            return out, [int(p or 0) for p in dev[:n]]
         return out
 
     def flux_device_rows(self) -> dict:

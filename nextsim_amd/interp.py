@@ -484,6 +484,171 @@ class GridMap:
         return data_grid
 
 
+class NodeMap:
+    """The coupler's receive of nodal fields with the weights resident on the device (include/nxs_interp.h, nxs_nodemap_*): InterpFromMeshToMesh2dx_weights once per
+    mesh, receiveCouplingData -> transformData -> InterpFromMeshToMesh2dx_apply -> ExternalData::get per coupling step.  Made by weights() from a Regrid context of
+    the SOURCE triangulation and the targets, or by import_() from exported rows."""
+
+    IN_DEVICE, OUT_DEVICE, GET = 1, 2, _abi.NXS_NODEMAP_GET
+
+    def __init__(self, handle):
+        self.L = _declare_nodemap()
+        self.h = handle
+        self._keep = None
+
+    @classmethod
+    def weights(cls, regrid, x, y):
+        """nxs_nodemap_create: x, y [N] the targets in the dataset's coordinates."""
+        L = _declare_nodemap()
+        x, y = np.ascontiguousarray(x, np.float64).ravel(), np.ascontiguousarray(y, np.float64).ravel()
+        if x.size != y.size:
+            raise ValueError("x and y [N] expected")
+        h = C.c_void_p()
+        rc = L.nxs_nodemap_create(regrid.h, _abi.dptr(x), _abi.dptr(y), x.size, 0, C.byref(h))
+        if rc:
+            raise NxsError(rc, (L.nxs_interp_last_error() or b"").decode())
+        return cls(h)
+
+    @classmethod
+    def import_(cls, rows, device=0):
+        """A map out of what export() returned: v [N, 3] the 0-based source vertices, a [N, 3] their area coordinates, nods_src."""
+        L = _declare_nodemap()
+        v, a = np.asarray(rows["v"], np.int32), np.asarray(rows["a"], np.float64)
+        if v.ndim != 2 or v.shape[1] != 3 or a.shape != v.shape:
+            raise ValueError("v and a [N, 3] expected")
+        vc = [np.ascontiguousarray(v[:, k]) for k in range(3)]
+        ac = [np.ascontiguousarray(a[:, k]) for k in range(3)]
+        h = C.c_void_p()
+        rc = L.nxs_nodemap_import(device, v.shape[0], int(rows["nods_src"]), *(_abi.iptr(q) for q in vc), *(_abi.dptr(q) for q in ac), C.byref(h))
+        if rc:
+            raise NxsError(rc, (L.nxs_interp_last_error() or b"").decode())
+        return cls(h)
+
+    def _chk(self, rc):
+        if rc:
+            raise NxsError(rc, (self.L.nxs_interp_last_error() or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.nxs_nodemap_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        N, nods, beyond = C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(self.L.nxs_nodemap_info(self.h, C.byref(N), C.byref(nods), C.byref(beyond)))
+        dev = C.c_int32(-1)
+        self._chk(self.L.nxs_nodemap_device(self.h, C.byref(dev)))
+        return {"N": N.value, "nods_src": nods.value, "beyond_hull": beyond.value, "device": dev.value}
+
+    def export(self):
+        """v [N, 3] int32, a [N, 3] (M_vertex, M_areacoord) and nods_src."""
+        i = self.info()
+        vc, ac = [np.empty(i["N"], np.int32) for _ in range(3)], [np.empty(i["N"]) for _ in range(3)]
+        self._chk(self.L.nxs_nodemap_export(self.h, *(_abi.iptr(q) for q in vc), *(_abi.dptr(q) for q in ac)))
+        return {"v": np.stack(vc, axis=1), "a": np.stack(ac, axis=1), "nods_src": i["nods_src"]}
+
+    def set_source(self, G, reduced=None, rotation="none", cos_m_diff_angle=1., sin_m_diff_angle=0., map_rotation=0., theta=None, east_west=False, lat=None, lon=None,
+                   mapx=None, delta_t=1.):
+        """nxs_nodemap_set_source.  G: the length of a delivered field; reduced [R]: grid.reduced_nodes_ind (None: the identity); rotation: "none", "uniform"
+        (cos_m_diff_angle, sin_m_diff_angle) or "grid_theta" (map_rotation = mapNextsim->rotation*PI/180., theta [R]); east_west: the pairs are east / north components
+        (lat, lon [R] degrees, mapx = dynamics.mapx_polar_north(...))."""
+        s = _abi.NodemapSource()
+        keep = []
+
+        def arr(a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt).ravel()
+            keep.append(a)
+            return _abi.iptr(a) if dt == np.int32 else _abi.dptr(a)
+        R = self.info()["nods_src"] if reduced is None else np.asarray(reduced).size
+        s.G, s.R, s.reduced = int(G), int(R), arr(reduced, np.int32)
+        s.rotation_mode = _abi.NODEMAP_ROTATE[rotation] if isinstance(rotation, str) else int(rotation)
+        s.east_west_oriented = int(bool(east_west))
+        s.cos_m_diff_angle, s.sin_m_diff_angle, s.rotation = float(cos_m_diff_angle), float(sin_m_diff_angle), float(map_rotation)
+        s.theta, s.lat, s.lon = arr(theta, np.float64), arr(lat, np.float64), arr(lon, np.float64)
+        for name, a in (("theta", theta), ("lat", lat), ("lon", lon)):
+            if a is not None and np.asarray(a).size != R:
+                raise ValueError(f"{name} has {np.asarray(a).size} entries, expected R = {R}")
+        if mapx is not None:
+            keep.append(mapx)
+            s.map = C.pointer(mapx)
+        s.delta_t = float(delta_t)
+        self._chk(self.L.nxs_nodemap_set_source(self.h, C.byref(s)))
+        self._G = int(G)
+        del keep
+
+    def receive_rows(self, fields, a=1., b=0., pairs=(), factor=1., bias=0., get=False, in_device=False, out_device=None, stream=None):
+        """nxs_nodemap_receive_rows: up to four nodal variables in two launches.  fields: one [G] array per variable (in_device: one device address each); pairs:
+        [(j0, j1)] the vector pairs, component 0 first; a, b, factor, bias per variable (scalars are broadcast); get: store factor*x + bias, else x.  Returns
+        [n_var, N] rows -- or, with out_device (one device address of an [N] row per variable), None.  stream: a hipStream_t as an int, None for the library's own."""
+        i = self.info()
+        n = len(fields)
+        co = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (max(n, 1),))) for v in (a, b, factor, bias)]
+        pr = np.full(max(n, 1), -1, np.int32)
+        for j0, j1 in pairs:
+            pr[j0] = j1
+        src, dst, keep, flags = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))(), [], 0
+        for k, f in enumerate(fields):
+            if in_device:
+                src[k] = int(f)
+            else:
+                arr = np.ascontiguousarray(f, np.float64).ravel()
+                if arr.size != getattr(self, "_G", arr.size):
+                    raise ValueError(f"field {k} has {arr.size} points, expected {self._G}")
+                keep.append(arr)
+                src[k] = arr.ctypes.data
+        flags |= self.IN_DEVICE if in_device else 0
+        flags |= self.GET if get else 0
+        out = None
+        if out_device is not None:
+            if len(out_device) != n:
+                raise ValueError("one output row per field expected")
+            for k, p in enumerate(out_device):
+                dst[k] = int(p)
+            flags |= self.OUT_DEVICE
+        else:
+            out = np.empty((n, i["N"]))
+            for k in range(n):
+                dst[k] = out[k].ctypes.data
+        self._chk(self.L.nxs_nodemap_receive_rows(self.h, n, src, _abi.dptr(co[0]), _abi.dptr(co[1]), _abi.iptr(pr) if len(pairs) else None, _abi.dptr(co[2]),
+                                                  _abi.dptr(co[3]), dst, flags, C.c_void_p(int(stream)) if stream else None))
+        del keep
+        return out
+
+    def debug_source(self, n_var):
+        """Test door: loaded_data of the last receive, [n_var, R]."""
+        out = np.empty((int(n_var), self.info()["nods_src"]))
+        self._chk(self.L.nxs_nodemap_debug_source(self.h, _abi.dptr(out), int(n_var)))
+        return out
+
+
+def _declare_nodemap():
+    L = _lib()
+    if not hasattr(L, "_nodemap_declared"):
+        D, I, V = _abi.c_double_p, _abi.c_int32_p, C.c_void_p
+        P32 = C.POINTER(C.c_int32)
+        L.nxs_nodemap_create.argtypes = [V, D, D, C.c_int32, C.c_int32, C.POINTER(V)]
+        L.nxs_nodemap_destroy.argtypes = [V]
+        L.nxs_nodemap_info.argtypes = [V, P32, P32, P32]
+        L.nxs_nodemap_device.argtypes = [V, P32]
+        L.nxs_nodemap_export.argtypes = [V, I, I, I, D, D, D]
+        L.nxs_nodemap_import.argtypes = [C.c_int32, C.c_int32, C.c_int32, I, I, I, D, D, D, C.POINTER(V)]
+        L.nxs_nodemap_set_source.argtypes = [V, C.POINTER(_abi.NodemapSource)]
+        L.nxs_nodemap_receive_rows.argtypes = [V, C.c_int32, C.POINTER(V), D, D, I, D, D, C.POINTER(V), C.c_int32, V]
+        L.nxs_nodemap_debug_source.argtypes = [V, D, C.c_int32]
+        for n in ("create", "destroy", "info", "device", "export", "import", "set_source", "receive_rows", "debug_source"):
+            getattr(L, "nxs_nodemap_" + n).restype = C.c_int
+        L._nodemap_declared = True
+    return L
+
+
 def gridmap_debug_receive_lists(mode: int) -> int:
     """Test door: 0 = receive_rows reads cell and weight through the index list, 1 = through copies in transposed order.  Returns the mode before."""
     L = _declare_gridmap()
