@@ -33,6 +33,7 @@
  *   thermo(): the slab loop from new ice to tracers nxs_dyn_slab, nxs_dyn_slab_*, nxs_slab_* (FE.cpp:5413-6133, 6538-6627)
  *   thermo() under OceanType::COUPLED + the receive nxs_dyn_ocean_coupled_*, nxs_gridmap_receive_rows (FE.cpp:5150-5157, 5348-5358, 5826-5841; externaldata.cpp:163-236)
  *   ... and its nodal half: I_Uocn, I_Vocn, I_SSH, I_tauwix / y   nxs_dyn_nodes_coupled_*, nxs_nodemap_* (dataset.cpp:11157-11175; externaldata.cpp:498-509, 1246-1281, 1457-1463)
+ *   loadDataset of a dataset on a triangulated source (topaz4r_*)   nxs_dyn_forcing_*_mesh, nxs_dyn_thermo_forcing_*_mesh, nxs_nodemap_load_rows (externaldata.cpp:886-931, 944-1288, 1334-1383, 1442-1448)
  *   BamgConvertMeshx connectivity tables        nxs_mesh_connectivity   (contrib/bamg/src/Mesh.cpp:495-865)
  *
  * Conventions
@@ -1375,6 +1376,32 @@ NXS_API int nxs_nodes_coupled_default_config(nxs_dyn_nodes_coupled_config *c);  
 NXS_API int nxs_dyn_nodes_coupled_attach(nxs_dyn_handle *h, int32_t which, struct nxs_nodemap *map, const nxs_dyn_nodes_coupled_config *c /* NULL: detach */);
 NXS_API int nxs_dyn_nodes_coupled_receive(nxs_dyn_handle *h, int32_t which, const double *const *fields, int32_t n_fields, int32_t flags);
 NXS_API int nxs_dyn_nodes_coupled_get(nxs_dyn_handle *h, int32_t which, double *const *out /* may be NULL */, const double **device_rows /* may be NULL */);
+
+/* ---- Forcing given on a TRIANGULATED source on the device: topaz4r_nodes (u, v, ssh at the nodes), topaz4r_elements (sst, sss, mld at the elements),
+ * ocean_currents_nodes and their kin (grid.interpolation_method == FromMeshToMesh2dx, dataset.cpp:1777-2150, 10321-10690) through a node map
+ * (nxs_nodemap_load_rows, include/nxs_interp.h: the tail of loadDataset, transformData and InterpFromMeshToMesh2dx, externaldata.cpp:886-931, 944-1288, 1334-1383,
+ * 1442-1448).  The counterparts of nxs_dyn_forcing_ingest / nxs_dyn_thermo_forcing_ingest for a source that is a mesh.  Everything here is additive: a handle that
+ * never attaches allocates nothing, launches nothing and keeps its bits; nxs_dyn_step's launch plan is untouched.
+ *   nxs_dyn_forcing_attach_mesh         set 0 .. NXS_NF_SETS - 1: the map of that dataset, BORROWED (the caller keeps it alive and destroys it), with the handle's Nn
+ *                  targets, ghosts included, on the handle's device, and a source (nxs_nodemap_set_source).  map == NULL detaches.  The attachment goes with the
+ *                  mesh: nxs_dyn_set_mesh and nxs_dyn_regrid drop it (the weights were the old mesh's); attach the new map afterwards.
+ *   nxs_dyn_forcing_ingest_mesh         one loadDataset: l as nxs_nodemap_load_rows takes it (fields host pointers or, with NXS_REGRID_IN_DEVICE, device pointers);
+ *                  row [n_var]: variable j goes to the half-row row[j] (NXS_NF_*), -1 skips it.  Column (fstep, j) is stored to snapshot fstep of that half-row --
+ *                  the rows nxs_dyn_set_forcing_pair owns, made here when never given, marked as nxs_dyn_forcing_ingest marks them (the routes mix per half-row;
+ *                  the pair is complete once all ten are there).  n_step == 1 fills snapshot 0 only (a `constant` or `nearest_daily` dataset: NXS_TF_STEP).
+ *                  Two launches on the handle's stream, asynchronous; with device fields there is no host synchronisation.  The time blend is
+ *                  nxs_dyn_set_forcing_time_rows.
+ *   nxs_dyn_thermo_forcing_attach_mesh  set 0 .. NXS_TF_SETS - 1: a map whose targets are the handle's Ne element barycentres.
+ *   nxs_dyn_thermo_forcing_ingest_mesh  row [n_var]: NXS_TF_*, -1 skips.  Column (fstep, j) goes to snapshot fstep of row row[j] -- the rows
+ *                  nxs_dyn_thermo_forcing_pair owns, made here when never given.  The time blend is nxs_dyn_thermo_forcing_time.
+ * NXS_ERR_STATE: before nxs_dyn_set_mesh, without an attachment of `set` on this mesh, a map without a source.
+ * NXS_ERR_INVALID: h, l or row NULL, a set out of range, a map on another device or with another target count, n_var or n_step out of range, a row out of range or
+ * named twice, every variable skipped, flags other than NXS_REGRID_IN_DEVICE, and whatever nxs_nodemap_load_rows refuses (its message is passed on). */
+struct nxs_nodemap_load;   /* include/nxs_interp.h */
+NXS_API int nxs_dyn_forcing_attach_mesh(nxs_dyn_handle *h, int32_t set, struct nxs_nodemap *map /* NULL detaches */);
+NXS_API int nxs_dyn_forcing_ingest_mesh(nxs_dyn_handle *h, int32_t set, const struct nxs_nodemap_load *l, const int32_t *row /* [n_var] NXS_NF_*, -1 skips */, int32_t flags);
+NXS_API int nxs_dyn_thermo_forcing_attach_mesh(nxs_dyn_handle *h, int32_t set, struct nxs_nodemap *map /* NULL detaches */);
+NXS_API int nxs_dyn_thermo_forcing_ingest_mesh(nxs_dyn_handle *h, int32_t set, const struct nxs_nodemap_load *l, const int32_t *row /* [n_var] NXS_TF_*, -1 skips */, int32_t flags);
 
 /* ---- The rest of thermo()'s slab loop on the device: FE.cpp:5413-6133 as a default (non-OASIS) build compiles it -- the assimilation flux (FE.cpp:5415-5425),
  * section 6: new ice over open water and lateral melt (FE.cpp:5434-5646; newice_type 1 .. 4, type 3 with windSpeedElement, FE.cpp:6359-6370; melt_type 1, 2), the

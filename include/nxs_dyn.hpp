@@ -139,6 +139,11 @@ public:
     void nodesCoupledAttach(int32_t which, struct nxs_nodemap *map, const nxs_dyn_nodes_coupled_config *cfg) { check(nxs_dyn_nodes_coupled_attach(h_, which, map, cfg), "nodes_coupled_attach"); }
     void nodesCoupledReceive(int32_t which, const double *const *fields, int32_t n_fields, int32_t flags = 0) { check(nxs_dyn_nodes_coupled_receive(h_, which, fields, n_fields, flags), "nodes_coupled_receive"); }
     void nodesCoupledGet(int32_t which, double *const *out, const double **device_rows = nullptr) { check(nxs_dyn_nodes_coupled_get(h_, which, out, device_rows), "nodes_coupled_get"); }
+    // Forcing given on a triangulated source (topaz4r_nodes, topaz4r_elements): one loadDataset through a node map (nxs_nodemap_load of include/nxs_interp.h); map == nullptr detaches
+    void forcingAttachMesh(int32_t set, struct nxs_nodemap *map) { check(nxs_dyn_forcing_attach_mesh(h_, set, map), "forcing_attach_mesh"); }
+    void forcingIngestMesh(int32_t set, const struct nxs_nodemap_load *l, const int32_t *row, int32_t flags = 0) { check(nxs_dyn_forcing_ingest_mesh(h_, set, l, row, flags), "forcing_ingest_mesh"); }
+    void thermoForcingAttachMesh(int32_t set, struct nxs_nodemap *map) { check(nxs_dyn_thermo_forcing_attach_mesh(h_, set, map), "thermo_forcing_attach_mesh"); }
+    void thermoForcingIngestMesh(int32_t set, const struct nxs_nodemap_load *l, const int32_t *row, int32_t flags = 0) { check(nxs_dyn_thermo_forcing_ingest_mesh(h_, set, l, row, flags), "thermo_forcing_ingest_mesh"); }
     nxs_dyn_handle *handle() { return h_; }
 
 private:

@@ -315,6 +315,50 @@ NXS_INTERP_API int nxs_nodemap_receive_rows(nxs_nodemap *map, int32_t n_var, con
                                             const double *factor, const double *bias, double *const *out_rows, int32_t flags, void *stream);
 NXS_INTERP_API int nxs_nodemap_debug_source(nxs_nodemap *map, double *out, int32_t n_var);
 
+/* ---- forcing given on a TRIANGULATED source (topaz4r_nodes, topaz4r_elements, ocean_currents_nodes, the nesting_* datasets: grid.interpolation_method ==
+ * FromMeshToMesh2dx, dataset.cpp:1777-2150, 10321-10690) through the weights of a node map.  nxs_nodemap_load_rows is ONE loadDataset on a map that has its source
+ * (nxs_nodemap_set_source: reduced, the rotation, lat / lon of an east/north pair); it replaces
+ *
+ *   the tail of loadDataset        externaldata.cpp:886-931     d = (d*scale_factor + add_offset)*a + b on data_in_tmp, NaN -> 0., loaded_data[fstep][i] = d[reduced[i]]
+ *   transformData                  externaldata.cpp:944-1288    per forcing step and vector pair: the east/north branch, then the uniform or the gridTheta rotation
+ *   interpolateDataset             externaldata.cpp:1334-1383, 1442-1448   data_in in the order fstep*n_var + j, InterpFromMeshToMesh2dx(..., isdefault = false)
+ *
+ * The map's targets are any points: the nodes for a nodal dataset, the element barycentres for an elemental one (nxs_nodemap_create takes both).  The source has
+ * not moved since the map was made, so nothing is located again: InterpFromMeshToMesh2dx with isdefault == false is statement for statement _weights followed by
+ * _apply, and the weights are the map's.  Two launches on `stream`:
+ *   k_nodemap_load          one thread per reduced point.  Per column c = fstep*n_var + j: d = fields[c][reduced[i]]; d = (d*scale_factor[c] + add_offset[c])*a[c] + b[c]
+ *                           as FOUR separately rounded operations in that order; NaN becomes 0. (the wave-direction exception is not built).  Then per forcing step and
+ *                           pair the east/north branch and the rotation of nxs_nodemap_receive_rows, on the point's own two entries.  loaded_data, [n_step*n_var][R]
+ *                           rows of a staging buffer the map makes at its first load (a map that never loads allocates nothing for it).
+ *   k_nodemap_cols_gather   one thread per target: three vertices and three weights loaded once, per KEPT column a0*d[v0] + a1*d[v1] + a2*d[v2], left to right
+ *                           (InterpFromMeshToMesh2dx.cpp:157-159), stored to out_rows[c].  No factor / bias: ExternalData::get is the time blend's
+ *                           (nxs_dyn_set_forcing_time_rows, nxs_dyn_thermo_forcing_time).
+ *   n_var    dataset->variables.size(), 1 .. 4;  n_step  dataset->nb_forcing_step, 1 or 2
+ *   fields   [n_step*n_var] host array of pointers; entry fstep*n_var + j is data_in_tmp of variable j of forcing step fstep, [G], as read from the file
+ *   scale_factor, add_offset   the file's attributes per COLUMN (the two forcing steps may come from two files); a, b  Variable::a, ::b per column
+ *   pairs    as nxs_nodemap_receive_rows: pairs[j] = w >= 0 names the vector (j, w) of VARIABLES, -1 elsewhere; the pair is transformed in EVERY forcing step
+ *   out_rows [n_step*n_var] host array of pointers to [N] rows; a NULL entry skips that column (it is still loaded: a pair may need it)
+ *   flags    NXS_REGRID_IN_DEVICE = fields[] are device pointers, NXS_REGRID_OUT_DEVICE = out_rows[] are.  stream as for nxs_nodemap_receive_rows: with a stream and
+ *            device rows out the call is ASYNCHRONOUS on it (host fields are uploaded on it first, and the call waits for the uploads only); with device fields too
+ *            there is no host synchronisation at all (the first load on a map, and the first with more columns, allocates the staging buffer behind one).
+ *   NXS_ERR_STATE before nxs_nodemap_set_source.  NXS_ERR_INVALID: a NULL argument or field, n_var or n_step out of range, a pair that is out of range or names a
+ *   variable twice, a scale_factor, add_offset, a or b that is not finite, every column skipped, an unknown flag.  NXS_ERR_NO_DEVICE without a device: no CPU path.
+ *   ONE STREAM AT A TIME, as for nxs_nodemap_receive_rows: the staging rows and the upload buffer are the MAP's; a load and a receive on one map are ordered when
+ *   they are enqueued on the same stream.
+ * nxs_nodemap_debug_load (test door): the first n_cols rows of the last load's loaded_data, [n_cols][R].
+ * NOT BUILT: reading the files, the two time indices, the mask and reduced_nodes_ind, BamgTriangulatex of the source, convertTargetXY, the wave-direction branch and
+ * the North-Pole mean of transformData (:1206-1243 compares gridY with 90., which a projected source never holds). */
+#define NXS_NODEMAP_MAX_LOAD 8          /* columns: up to 4 variables x nb_forcing_step (1 or 2) */
+typedef struct nxs_nodemap_load {
+    int32_t n_var, n_step;
+    const double *const *fields;
+    double scale_factor[NXS_NODEMAP_MAX_LOAD], add_offset[NXS_NODEMAP_MAX_LOAD];
+    double a[NXS_NODEMAP_MAX_LOAD], b[NXS_NODEMAP_MAX_LOAD];
+    int32_t pairs[4];
+} nxs_nodemap_load;
+NXS_INTERP_API int nxs_nodemap_load_rows(nxs_nodemap *map, const nxs_nodemap_load *l, double *const *out_rows, int32_t flags, void *stream);
+NXS_INTERP_API int nxs_nodemap_debug_load(nxs_nodemap *map, double *out, int32_t n_cols);
+
 
 #ifdef __cplusplus
 }

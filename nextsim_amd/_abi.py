@@ -374,6 +374,14 @@ class NodemapSource(C.Structure):   # nxs_nodemap_source
                 ("lon", c_double_p), ("map", C.POINTER(MapxPolar)), ("delta_t", C.c_double)]
 
 
+NXS_NODEMAP_MAX_LOAD = 8      # columns of nxs_nodemap_load_rows: up to 4 variables x nb_forcing_step (1 or 2)
+
+
+class NodemapLoad(C.Structure):   # nxs_nodemap_load
+    _fields_ = ([("n_var", C.c_int32), ("n_step", C.c_int32), ("fields", C.POINTER(C.c_void_p))]
+                + [(k, C.c_double * NXS_NODEMAP_MAX_LOAD) for k in ("scale_factor", "add_offset", "a", "b")] + [("pairs", C.c_int32 * 4)])
+
+
 class NodesCoupledConfig(C.Structure):   # nxs_dyn_nodes_coupled_config
     _fields_ = [(k, C.c_double * NXS_NC_MAX_FIELDS) for k in ("a", "b", "factor", "bias")]
 

@@ -260,6 +260,11 @@ struct NodesCoupled {      // nxs_dyn_nodes_coupled_*: the attachments of ocean_
     struct nxs_nodemap *nc_map[NXS_NC_DATASETS] = {nullptr, nullptr};   // borrowed
     nxs_dyn_nodes_coupled_config nc_cfg[NXS_NC_DATASETS] = {};
 };
+struct MeshForcing {       // nxs_dyn_forcing_attach_mesh / nxs_dyn_thermo_forcing_attach_mesh: the node maps of datasets on a triangulated source.  No array of its own: the rows are the forcing pair's and ThermoForcing's
+    std::vector<void *> mf_allocs;
+    struct nxs_nodemap *mf_node_map[NF_SETS] = {};   // borrowed; N == Nn
+    struct nxs_nodemap *mf_elem_map[TF_SETS] = {};   // borrowed; N == Ne
+};
 struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stress / nxs_dyn_put_coupled) and the floe-size distribution's (nxs_dyn_fsd_*)
     std::vector<void *> coupled_allocs;
     // ATTACHED is what h->dw says (tau_wi, cum_damage, conc_fsd non-NULL) and fsd_mech / fsd_cumw non-NULL; a detached buffer is kept for the next attach (no hipFree
@@ -301,7 +306,7 @@ struct CplOutGrid {        // ... and the exchange grid's side: the P-points, co
     int cpl_grid_n[2] = {0, 0};                // the list sizes the accumulators were made for
 };
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, NodesCoupled, CoupledBuffers, MeansPoints, CplOut, CplOutGrid {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, NodesCoupled, MeshForcing, CoupledBuffers, MeansPoints, CplOut, CplOutGrid {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -722,6 +727,8 @@ void release_diffusion(nxs_dyn_handle *h) { release_group<Diffusion>(h, h->diff_
 void release_ocean_coupled(nxs_dyn_handle *h) { release_group<OceanCoupled>(h, h->oc_allocs); }
 // the nodal receive's two attachments: their maps held the old mesh's weights (FE.cpp:8041-8048)
 void release_nodes_coupled(nxs_dyn_handle *h) { release_group<NodesCoupled>(h, h->nc_allocs); }
+// the node maps of forcing on a triangulated source: their weights were the old mesh's nodes' and barycentres'
+void release_mesh_forcing(nxs_dyn_handle *h) { release_group<MeshForcing>(h, h->mf_allocs); }
 // thermo() runs its OceanType::COUPLED branches (FE.cpp:5150-5157, 5348-5358, 5826-5841): a coupled ocean is attached with ocean_temp, ocean_salt and qsrml configured
 inline bool ocean_coupled_on(const nxs_dyn_handle *h) {
     const unsigned need = (1u << NXS_OC_OCEAN_TEMP) | (1u << NXS_OC_OCEAN_SALT) | (1u << NXS_OC_QSRML);
@@ -767,6 +774,7 @@ void release_mesh(nxs_dyn_handle *h) {
     release_diffusion(h);
     release_ocean_coupled(h);
     release_nodes_coupled(h);
+    release_mesh_forcing(h);
     release_cpl_out(h);
     release_coupled(h);
     h->no_big_cut = false;
@@ -4196,6 +4204,7 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_nodal_forcing.inl"
 #include "nxs_ocean_coupled.inl"
 #include "nxs_nodes_coupled.inl"
+#include "nxs_mesh_forcing.inl"
 #include "nxs_means_points.inl"
 #include "nxs_cpl_out.inl"
 

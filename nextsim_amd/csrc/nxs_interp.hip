@@ -1461,6 +1461,7 @@ extern "C" int nxs_gridmap_debug_chunk(int32_t cells, int32_t *last_chunks) try 
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 #include "nxs_nodemap_kernels.inl"
+#include "nxs_nodemap_load_kernels.inl"
 }  // namespace
 
 struct nxs_nodemap {
@@ -1479,6 +1480,9 @@ struct nxs_nodemap {
     DevBuf<double> dfields;            // with host fields: where they are uploaded, [n_var][G]; it only grows
     size_t fields_cap = 0;
     int last_n_var = 0;
+    DevBuf<double> dload;              // [n_step*n_var][R] loaded_data of nxs_nodemap_load_rows, made by the first load (a map that never loads has none); it only grows
+    size_t load_cap = 0;
+    int last_load_cols = 0;
 };
 
 namespace {
@@ -1621,7 +1625,7 @@ extern "C" int nxs_nodemap_set_source(nxs_nodemap *m, const nxs_nodemap_source *
     m->rotate = s->rotation_mode; m->east_west = s->east_west_oriented != 0;
     m->c = s->cos_m_diff_angle; m->s = s->sin_m_diff_angle;
     if (s->east_west_oriented) m->map = *s->map;
-    m->last_n_var = 0;
+    m->last_n_var = 0; m->last_load_cols = 0;
     m->have_source = true;
     return NXS_OK;
 } catch (...) { return entry_caught("nxs_nodemap_set_source"); }
@@ -1700,6 +1704,99 @@ extern "C" int nxs_nodemap_debug_source(nxs_nodemap *m, double *out, int32_t n_v
     if (copy_sync(out, m->dstage.p, (size_t)n_var * m->R * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
     return NXS_OK;
 } catch (...) { return entry_caught("nxs_nodemap_debug_source"); }
+
+// One loadDataset of a FromMeshToMesh2dx dataset (externaldata.cpp:886-931, 944-1288, 1334-1383, 1442-1448): k_nodemap_load, k_nodemap_cols_gather on `stream`
+extern "C" int nxs_nodemap_load_rows(nxs_nodemap *m, const nxs_nodemap_load *l, double *const *out_rows, int32_t flags, void *stream) try {
+    if (!m || !l || !out_rows) return fail(NXS_ERR_INVALID, "nodemap_load_rows: NULL argument");
+    if (!l->fields) return fail(NXS_ERR_INVALID, "nodemap_load_rows: NULL argument (fields)");
+    if (l->n_var < 1 || l->n_var > nodemap::kMaxVar) return fail(NXS_ERR_INVALID, "nodemap_load_rows: n_var = %d (1 .. %d)", l->n_var, nodemap::kMaxVar);
+    if (l->n_step < 1 || l->n_step > 2) return fail(NXS_ERR_INVALID, "nodemap_load_rows: n_step = %d (1 or 2)", l->n_step);
+    const int n_var = l->n_var, ncols = l->n_step * l->n_var;
+    static_assert(NXS_NODEMAP_MAX_LOAD == nodemap::kMaxLoad && nodemap::kMaxLoad == 2 * nodemap::kMaxVar, "columns: variables x forcing steps");
+    nodemap::ColsArgs ga{};
+    int kept = 0;
+    for (int c = 0; c < ncols; ++c) {
+        if (!l->fields[c]) return fail(NXS_ERR_INVALID, "nodemap_load_rows: field %d (forcing step %d, variable %d) is NULL", c, c / n_var, c % n_var);
+        if (!std::isfinite(l->scale_factor[c]) || !std::isfinite(l->add_offset[c]) || !std::isfinite(l->a[c]) || !std::isfinite(l->b[c]))
+            return fail(NXS_ERR_INVALID, "nodemap_load_rows: scale_factor, add_offset, a or b of column %d is not finite", c);
+        if (out_rows[c]) ga.col[kept++] = c;   // skipped columns are compacted away
+    }
+    if (kept == 0) return fail(NXS_ERR_INVALID, "nodemap_load_rows: every column is skipped");
+    nodemap::LoadArgs sa{};
+    {
+        int used[nodemap::kMaxVar] = {0, 0, 0, 0};
+        for (int v = 0; v < n_var; ++v) {
+            const int w = l->pairs[v];
+            if (w < 0) continue;
+            if (w >= n_var || w == v) return fail(NXS_ERR_INVALID, "nodemap_load_rows: pairs[%d] = %d is not another variable (0 .. %d)", v, w, n_var - 1);
+            if (used[v] || used[w]) return fail(NXS_ERR_INVALID, "nodemap_load_rows: variable %d is named by two pairs", used[v] ? v : w);
+            used[v] = used[w] = 1;
+            sa.j0[sa.npairs] = v; sa.j1[sa.npairs] = w; ++sa.npairs;   // (four variables hold at most two pairs)
+        }
+    }
+    if (!m->have_source) return fail(NXS_ERR_STATE, "nodemap_load_rows: before nxs_nodemap_set_source");
+    if (flags & ~(NXS_REGRID_IN_DEVICE | NXS_REGRID_OUT_DEVICE)) return fail(NXS_ERR_INVALID, "nodemap_load_rows: flags = 0x%x (NXS_REGRID_IN_DEVICE, NXS_REGRID_OUT_DEVICE)", flags);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(NXS_ERR_NO_DEVICE, "no HIP device visible: the node map has no CPU path");
+    if (hipSetDevice(m->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    const bool in_dev = flags & NXS_REGRID_IN_DEVICE, out_dev = flags & NXS_REGRID_OUT_DEVICE;
+    const hipStream_t st = stream ? (hipStream_t)stream : S();
+    const size_t G = (size_t)m->G, N = (size_t)m->N, R = (size_t)m->R;
+    if (m->load_cap < (size_t)ncols * R) {   // the first load, or the first with this many columns
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "hipStreamSynchronize failed");   // (an earlier load may still read the buffer)
+        m->last_load_cols = 0;
+        if (m->dload.alloc((size_t)ncols * R)) { m->load_cap = 0; return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError())); }
+        m->load_cap = (size_t)ncols * R;
+    }
+    if (!in_dev) {   // the fields go up on the same stream; the host arrays are the caller's again on return
+        if (m->fields_cap < (size_t)ncols * G) {
+            if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "hipStreamSynchronize failed");   // (an earlier load or receive may still read the buffer)
+            if (m->dfields.alloc((size_t)ncols * G)) { m->fields_cap = 0; return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError())); }
+            m->fields_cap = (size_t)ncols * G;
+        }
+        for (int c = 0; c < ncols; ++c)
+            if (hipMemcpyAsync(m->dfields.p + (size_t)c * G, l->fields[c], G * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) return fail(NXS_ERR_HIP, "upload failed");
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "upload failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    DevBuf<double> dout;
+    if (!out_dev && dout.alloc((size_t)kept * N)) return fail(NXS_ERR_HIP, "device allocation failed: %s", hipGetErrorString(hipGetLastError()));
+    for (int c = 0; c < ncols; ++c) {
+        sa.field[c] = in_dev ? l->fields[c] : m->dfields.p + (size_t)c * G;
+        sa.scale_factor[c] = l->scale_factor[c]; sa.add_offset[c] = l->add_offset[c]; sa.a[c] = l->a[c]; sa.b[c] = l->b[c];
+    }
+    for (int k = 0; k < kept; ++k) ga.out[k] = out_dev ? out_rows[ga.col[k]] : dout.p + (size_t)k * N;
+    sa.n_var = n_var; sa.n_step = l->n_step; sa.R = m->R; sa.reduced = m->identity ? nullptr : m->dreduced.p;
+    sa.east_west = m->east_west; sa.lat = m->dlat.p; sa.lon = m->dlon.p; sa.map = m->map; sa.Re = NXS_MAPX_RE_KM * 1000.;
+    sa.rotate = m->rotate; sa.c = m->c; sa.s = m->s; sa.cs = m->dcs.p; sa.sn = m->dsn.p;
+    sa.stage = m->dload.p;
+    ga.stage = m->dload.p; ga.R = m->R; ga.N = m->N;
+    hipLaunchKernelGGL(nodemap::k_nodemap_load, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, sa);
+    const dim3 grid((unsigned)((N + 255) / 256)), block(256);
+    const int *v0 = m->v0.p, *v1 = m->v1.p, *v2 = m->v2.p;
+    const double *a0 = m->a0.p, *a1 = m->a1.p, *a2 = m->a2.p;
+#define NXS_GATHER(NC) case NC: hipLaunchKernelGGL((nodemap::k_nodemap_cols_gather<NC>), grid, block, 0, st, ga, v0, v1, v2, a0, a1, a2); break;
+    switch (kept) { NXS_GATHER(1) NXS_GATHER(2) NXS_GATHER(3) NXS_GATHER(4) NXS_GATHER(5) NXS_GATHER(6) NXS_GATHER(7) NXS_GATHER(8) }
+#undef NXS_GATHER
+    m->last_load_cols = ncols;
+    if (hipGetLastError() != hipSuccess) return fail(NXS_ERR_HIP, "nodemap_load_rows: kernel launch failed");
+    if (stream && out_dev) return NXS_OK;   // asynchronous on the caller's stream
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(NXS_ERR_HIP, "nodemap_load_rows: kernels failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!out_dev)
+        for (int k = 0; k < kept; ++k)
+            if (copy_sync(out_rows[ga.col[k]], dout.p + (size_t)k * N, N * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_load_rows"); }
+
+// test door: loaded_data of the last load, [n_cols][R]
+extern "C" int nxs_nodemap_debug_load(nxs_nodemap *m, double *out, int32_t n_cols) try {
+    if (!m || !out) return fail(NXS_ERR_INVALID, "nodemap_debug_load: NULL argument");
+    if (!m->have_source || m->last_load_cols < 1) return fail(NXS_ERR_STATE, "nodemap_debug_load: no nxs_nodemap_load_rows on this source yet");
+    if (n_cols < 1 || n_cols > m->last_load_cols) return fail(NXS_ERR_INVALID, "nodemap_debug_load: n_cols = %d, the last load had %d", n_cols, m->last_load_cols);
+    if (hipSetDevice(m->device) != hipSuccess) return fail(NXS_ERR_HIP, "hipSetDevice failed");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(NXS_ERR_HIP, "hipDeviceSynchronize failed: %s", hipGetErrorString(hipGetLastError()));
+    if (copy_sync(out, m->dload.p, (size_t)n_cols * m->R * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(NXS_ERR_HIP, "copy back failed");
+    return NXS_OK;
+} catch (...) { return entry_caught("nxs_nodemap_debug_load"); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Structured grid -> mesh nodes: the forcing ingest (InterpFromGridToMeshx, called at externaldata.cpp:1436)

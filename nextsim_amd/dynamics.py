@@ -136,6 +136,10 @@ def load_library():
     L.nxs_dyn_nodes_coupled_attach.argtypes = [H, C.c_int32, C.c_void_p, P(_abi.NodesCoupledConfig)]
     L.nxs_dyn_nodes_coupled_receive.argtypes = [H, C.c_int32, P(C.c_void_p), C.c_int32, C.c_int32]
     L.nxs_dyn_nodes_coupled_get.argtypes = [H, C.c_int32, P(C.c_void_p), P(C.c_void_p)]
+    for _n in ("nxs_dyn_forcing_attach_mesh", "nxs_dyn_thermo_forcing_attach_mesh"):
+        getattr(L, _n).argtypes = [H, C.c_int32, C.c_void_p]
+    for _n in ("nxs_dyn_forcing_ingest_mesh", "nxs_dyn_thermo_forcing_ingest_mesh"):
+        getattr(L, _n).argtypes = [H, C.c_int32, P(_abi.NodemapLoad), P(C.c_int32), C.c_int32]
     L.nxs_slab_default_config.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_config_check.argtypes = [P(_abi.SlabConfig)]
     L.nxs_slab_constants.argtypes = [P(C.c_double), C.c_int32]
@@ -290,6 +294,7 @@ EXPORTS = (
     "nxs_dyn_nesting_get", "nxs_dyn_diffusion_configure", "nxs_dyn_diffuse", "nxs_dyn_flux_device_rows",
     "nxs_ocean_coupled_default_config", "nxs_ocean_coupled_config_check", "nxs_dyn_ocean_coupled_attach", "nxs_dyn_ocean_coupled_receive", "nxs_dyn_ocean_coupled_put_rows",
     "nxs_dyn_ocean_coupled_get", "nxs_nodes_coupled_default_config", "nxs_dyn_nodes_coupled_attach", "nxs_dyn_nodes_coupled_receive", "nxs_dyn_nodes_coupled_get",
+    "nxs_dyn_forcing_attach_mesh", "nxs_dyn_forcing_ingest_mesh", "nxs_dyn_thermo_forcing_attach_mesh", "nxs_dyn_thermo_forcing_ingest_mesh",
     "nxs_slab_default_config", "nxs_slab_config_check", "nxs_slab_constants", "nxs_dyn_slab_configure", "nxs_dyn_slab_put", "nxs_dyn_slab_get_state", "nxs_dyn_slab",
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_to_grid_conservative", "nxs_dyn_means_reset",
@@ -307,7 +312,8 @@ INTERP_EXPORTS = ("nxs_interp_mesh_to_mesh_2d", "nxs_interp_mesh_to_grid", "nxs_
                   "nxs_regrid_interp_nodes", "nxs_regrid_remap_elements", "nxs_interp_last_timing", "nxs_regrid_debug_tables", "nxs_gridmap_create", "nxs_gridmap_destroy",
                   "nxs_gridmap_info", "nxs_gridmap_mesh_to_grid", "nxs_gridmap_grid_to_mesh", "nxs_gridmap_export", "nxs_gridmap_import", "nxs_gridmap_restrict",
                   "nxs_gridmap_debug_chunk", "nxs_gridmap_receive_rows", "nxs_gridmap_debug_receive_lists", "nxs_gridmap_send_rows", "nxs_nodemap_create", "nxs_nodemap_destroy",
-                  "nxs_nodemap_info", "nxs_nodemap_device", "nxs_nodemap_export", "nxs_nodemap_import", "nxs_nodemap_set_source", "nxs_nodemap_receive_rows", "nxs_nodemap_debug_source")
+                  "nxs_nodemap_info", "nxs_nodemap_device", "nxs_nodemap_export", "nxs_nodemap_import", "nxs_nodemap_set_source", "nxs_nodemap_receive_rows", "nxs_nodemap_debug_source",
+                  "nxs_nodemap_load_rows", "nxs_nodemap_debug_load")
 
 
 def selftest_quotients(n: int, seed: int = 1, mode: int = 0, device: int = 0) -> int:
@@ -1167,6 +1173,19 @@ class FiniteElementDynamics:
         g = _abi.ForcingGrid(_abi.dptr(x_in), _abi.dptr(y_in), x_in.size, y_in.size, M, N, int(interp), int(bool(row_major)), float(default_value))
         self._chk(self.L.nxs_dyn_thermo_forcing_ingest(self.h, int(set), C.byref(g), _abi.dptr(data), data.shape[2], _abi.iptr(rows), _abi.iptr(snaps)))
 
+    def thermo_forcing_attach_mesh(self, set: int, nodemap):
+        """nxs_dyn_thermo_forcing_attach_mesh: an interp.NodeMap whose targets are this mesh's element barycentres (borrowed: keep it alive); None detaches."""
+        self._chk(self.L.nxs_dyn_thermo_forcing_attach_mesh(self.h, int(set), nodemap.h if nodemap is not None else None))
+        self._mf_elem_maps = getattr(self, "_mf_elem_maps", {})
+        self._mf_elem_maps[int(set)] = nodemap
+
+    def thermo_forcing_ingest_mesh(self, set: int, fields, row, n_step=2, scale_factor=1., add_offset=0., a=1., b=0., pairs=(), device: bool = False):
+        """nxs_dyn_thermo_forcing_ingest_mesh: one loadDataset of a dataset on a triangulated source (interp.NodeMap.load_rows' arguments: n_step*n_var fields in
+        the order fstep*n_var + j).  Variable j goes to row[j] (a name of _abi.TF_ROWS, NXS_TF_*, or -1 / None: skipped), forcing step fstep to snapshot fstep.
+        The launches are asynchronous."""
+        self._ingest_mesh(self.L.nxs_dyn_thermo_forcing_ingest_mesh, getattr(self, "_mf_elem_maps", {}).get(int(set)), _abi.TF_ROWS, set, fields, row, n_step,
+                          scale_factor, add_offset, a, b, pairs, device)
+
     def thermo_forcing_get(self, which: int, names=_abi.TF_ROWS) -> dict:
         """nxs_dyn_thermo_forcing_get: the named rows of snapshot 0 / 1 (which = 0 / 1) or as the launches will read them (which = 2)."""
         out = {k: np.empty(self.lm.num_elements) for k in names}
@@ -1200,6 +1219,28 @@ class FiniteElementDynamics:
         self._chk(self.L.nxs_dyn_forcing_ingest(self.h, int(set), C.byref(g), int(bool(cyclic_x)), int(bool(cyclic_y)), _abi.dptr(data), data.shape[2], _abi.iptr(rows),
                                                 _abi.iptr(snaps), C.byref(v) if v is not None else None))
         self._nf_grid_shape = (M + int(bool(cyclic_y)), N + int(bool(cyclic_x)), data.shape[2])
+        del keep
+
+    def forcing_attach_mesh(self, set: int, nodemap):
+        """nxs_dyn_forcing_attach_mesh: an interp.NodeMap with this mesh's nodes as targets (borrowed: keep it alive); None detaches."""
+        self._chk(self.L.nxs_dyn_forcing_attach_mesh(self.h, int(set), nodemap.h if nodemap is not None else None))
+        self._mf_node_maps = getattr(self, "_mf_node_maps", {})
+        self._mf_node_maps[int(set)] = nodemap
+
+    def forcing_ingest_mesh(self, set: int, fields, row, n_step=2, scale_factor=1., add_offset=0., a=1., b=0., pairs=(), device: bool = False):
+        """nxs_dyn_forcing_ingest_mesh: one loadDataset of a dataset on a triangulated source (interp.NodeMap.load_rows' arguments: n_step*n_var fields in the order
+        fstep*n_var + j).  Variable j goes to the half-row row[j] (a name of _abi.NF_ROWS, NXS_NF_*, or -1 / None: skipped), forcing step fstep to snapshot fstep.
+        The launches are asynchronous."""
+        self._ingest_mesh(self.L.nxs_dyn_forcing_ingest_mesh, getattr(self, "_mf_node_maps", {}).get(int(set)), _abi.NF_ROWS, set, fields, row, n_step,
+                          scale_factor, add_offset, a, b, pairs, device)
+
+    def _ingest_mesh(self, entry, nodemap, names, set, fields, row, n_step, scale_factor, add_offset, a, b, pairs, device):
+        from . import interp
+        l, keep = interp.NodeMap._load_struct(nodemap, fields, n_step, scale_factor, add_offset, a, b, pairs, device)   # (without a map: the library refuses the call)
+        rows = np.array([-1 if r is None else names.index(r) if isinstance(r, str) else int(r) for r in row], np.int32)
+        if rows.shape != (l.n_var,):
+            raise ValueError(f"row must name the {l.n_var} variables")
+        self._chk(entry(self.h, int(set), C.byref(l), _abi.iptr(rows), 1 if device else 0))   # NXS_REGRID_IN_DEVICE
         del keep
 
     def set_forcing_time_rows(self, groups: dict):

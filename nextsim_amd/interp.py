@@ -628,6 +628,64 @@ class NodeMap:
         self._chk(self.L.nxs_nodemap_debug_source(self.h, _abi.dptr(out), int(n_var)))
         return out
 
+    def _load_struct(self, fields, n_step, scale_factor=1., add_offset=0., a=1., b=0., pairs=(), in_device=False):
+        """(nxs_nodemap_load, what it points to) of n_step*n_var fields in loadDataset's order fstep*n_var + j; the coefficients per column (scalars are broadcast)."""
+        n_cols, n_step = len(fields), int(n_step)
+        if not 1 <= n_cols <= _abi.NXS_NODEMAP_MAX_LOAD or n_step not in (1, 2) or n_cols % n_step:
+            raise ValueError(f"{n_cols} fields for n_step = {n_step}: n_step*n_var fields (n_var 1 .. 4, n_step 1 or 2) expected")
+        l, keep = _abi.NodemapLoad(), []
+        l.n_step, l.n_var = n_step, n_cols // n_step
+        src = (C.c_void_p * _abi.NXS_NODEMAP_MAX_LOAD)()
+        for k, f in enumerate(fields):
+            if in_device:
+                src[k] = int(f) if f is not None else None
+            elif f is not None:
+                arr = np.ascontiguousarray(f, np.float64).ravel()
+                if arr.size != getattr(self, "_G", arr.size):
+                    raise ValueError(f"field {k} has {arr.size} points, expected {self._G}")
+                keep.append(arr)
+                src[k] = arr.ctypes.data
+        keep.append(src)
+        l.fields = C.cast(src, C.POINTER(C.c_void_p))
+        for name, v in (("scale_factor", scale_factor), ("add_offset", add_offset), ("a", a), ("b", b)):
+            co = np.broadcast_to(np.asarray(v, np.float64), (n_cols,))
+            for k in range(n_cols):
+                getattr(l, name)[k] = co[k]
+        for j in range(4):
+            l.pairs[j] = -1
+        for j0, j1 in pairs:
+            l.pairs[j0] = j1
+        return l, keep
+
+    def load_rows(self, fields, n_step=2, scale_factor=1., add_offset=0., a=1., b=0., pairs=(), skip=(), in_device=False, out_device=None, stream=None):
+        """nxs_nodemap_load_rows: one loadDataset of a dataset on a triangulated source in two launches.  fields: n_step*n_var [G] arrays in the order fstep*n_var + j
+        (in_device: one device address each); scale_factor, add_offset, a, b per COLUMN (scalars are broadcast); pairs: [(j0, j1)] the vector pairs of VARIABLES,
+        transformed in every forcing step; skip: columns that are loaded but not gathered.  Returns [n_cols, N] rows (a skipped column's row is NaN) -- or, with
+        out_device (one device address of an [N] row per column, None / 0 skips), None.  stream: a hipStream_t as an int, None for the library's own."""
+        i = self.info()
+        l, keep = self._load_struct(fields, n_step, scale_factor, add_offset, a, b, pairs, in_device)
+        n_cols = len(fields)
+        dst, flags, out = (C.c_void_p * _abi.NXS_NODEMAP_MAX_LOAD)(), (self.IN_DEVICE if in_device else 0), None
+        if out_device is not None:
+            if len(out_device) != n_cols:
+                raise ValueError("one output row per column expected")
+            for k, p in enumerate(out_device):
+                dst[k] = int(p) if p else None
+            flags |= self.OUT_DEVICE
+        else:
+            out = np.full((n_cols, i["N"]), np.nan)
+            for k in range(n_cols):
+                dst[k] = None if k in skip else out[k].ctypes.data
+        self._chk(self.L.nxs_nodemap_load_rows(self.h, C.byref(l), dst, flags, C.c_void_p(int(stream)) if stream else None))
+        del keep
+        return out
+
+    def debug_load(self, n_cols):
+        """Test door: loaded_data of the last load, [n_cols, R]."""
+        out = np.empty((int(n_cols), self.info()["nods_src"]))
+        self._chk(self.L.nxs_nodemap_debug_load(self.h, _abi.dptr(out), int(n_cols)))
+        return out
+
 
 def _declare_nodemap():
     L = _lib()
@@ -643,7 +701,9 @@ def _declare_nodemap():
         L.nxs_nodemap_set_source.argtypes = [V, C.POINTER(_abi.NodemapSource)]
         L.nxs_nodemap_receive_rows.argtypes = [V, C.c_int32, C.POINTER(V), D, D, I, D, D, C.POINTER(V), C.c_int32, V]
         L.nxs_nodemap_debug_source.argtypes = [V, D, C.c_int32]
-        for n in ("create", "destroy", "info", "device", "export", "import", "set_source", "receive_rows", "debug_source"):
+        L.nxs_nodemap_load_rows.argtypes = [V, C.POINTER(_abi.NodemapLoad), C.POINTER(V), C.c_int32, V]
+        L.nxs_nodemap_debug_load.argtypes = [V, D, C.c_int32]
+        for n in ("create", "destroy", "info", "device", "export", "import", "set_source", "receive_rows", "debug_source", "load_rows", "debug_load"):
             getattr(L, "nxs_nodemap_" + n).restype = C.c_int
         L._nodemap_declared = True
     return L
