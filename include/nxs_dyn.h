@@ -26,6 +26,7 @@
  *   #ifdef OASIS: M_cum_damage, M_conc_fsd      nxs_dyn_put_coupled / nxs_dyn_get_coupled (FE.cpp:4233-4238, 3991-3994)
  *   updateMeans(M_moorings, time_factor)        nxs_dyn_means_update    (FE.cpp:8518-9024; configure / get / to_grid / reset beside it)
  *   M_moorings.updateGridMean() on a loaded grid nxs_dyn_means_points_update (gridoutput.cpp:387-415, 470-485; set / lsm / get / reset beside it)
+ *   M_moorings.updateGridMean() on the regular grid nxs_dyn_means_regular_update (gridoutput.cpp:387-415, 486-538; set / lsm / get / reset beside it)
  *   interpFields() + assignVariables()          nxs_dyn_regrid          (FE.cpp:3071-3154, 2120-2151, 2196-2258, 3161-3297, 553-572)
  *   #ifdef OASIS: initFsd / updateFSD / redistributeFSD / weldingRoach   nxs_fsd_bins, nxs_dyn_fsd_* (FE.cpp:7408-7576, 4674-4732, 4268-4483, 4737-4870, 5888-5896)
  *   thermo(): OWBulkFluxes + IABulkFluxes       nxs_dyn_fluxes, nxs_dyn_flux_* (FE.cpp:5214-5277, 5032-5159, 6148-6353, 4966-5019, 6359-6389, 6454-6535)
@@ -397,7 +398,8 @@ NXS_API int nxs_dyn_ice_diagnostics(nxs_dyn_handle *h, nxs_dyn_ice_diag *d, cons
  * land-sea mask are nxs_dyn_means_points_* below.
  * dmax / dmean (NXS_MEANS_FSD_BEGIN ..), the floe-size diagnostics of the coupled build, need nxs_dyn_fsd_diag_configure below.  The coupler's means (M_cpl_out)
  * are a second set of accumulators beside these: nxs_dyn_cpl_out_* below.
- * OUT OF SCOPE (the host keeps doing those itself): rotateVectors and the land-sea mask on the REGULAR grid of nxs_dyn_means_to_grid. */
+ * On the REGULAR grid (moorings.grid_type=regular, the default) nxs_dyn_means_to_grid samples through the host at every call; nxs_dyn_means_regular_* below keep
+ * the grid, rotateVectors, the land-sea mask and the grid accumulators on the device. */
 enum nxs_means_var {
     /* elemental: accumulated over the owned elements i < M_local_nelements, the rows of ghost elements stay 0 (FE.cpp:8527) */
     NXS_MEANS_CONC = 0,           /* FE.cpp:8526  D_conc */
@@ -624,6 +626,66 @@ NXS_API int nxs_dyn_means_points_update(nxs_dyn_handle *h);
 NXS_API int nxs_dyn_means_points_get(nxs_dyn_handle *h, int32_t apply_lsm, double *grid_elemental /* [n_el][G] */, double *grid_nodal /* [n_nod][G] */,
                                      const double **elemental_dev, const double **nodal_dev);
 NXS_API int nxs_dyn_means_points_reset(nxs_dyn_handle *h);
+
+/* ---- The Moorings means on the REGULAR grid (moorings.grid_type=regular, the reference's default): GridOutput::updateGridMean() through the M_is_regular_grid
+ * branch of updateGridMeanWorker (model/gridoutput.cpp:387-415, 486-505, 511-538), setProcMask (:360-378), setLSM / applyLSM (:558-574, :639-651), rotateVectors
+ * (:578-623), resetGridMean (:627-635) and the arithmetic of contrib/bamg/src/InterpFromMeshToGridx.cpp, bit for bit.  The grid, its rotation, the land-sea mask
+ * and the grid accumulators (data_grid) live on the handle.  nxs_dyn_means_regular_update is two launches on the handle's stream and nothing else: the mesh is
+ * x0 + M_UM formed on the device; the reference's three InterpFromMeshToGridx calls (proc mask, elemental variables, nodal variables) see the same mesh and the same
+ * points, so the winner of every point -- the HIGHEST element number that holds it, the reference's element loop overwrites -- is found once (one thread per
+ * element, an integer atomic maximum per held point), and one thread per grid point then gathers, rotates, accumulates in grid order and applies the ice-mask rule.
+ * No copy in either direction, no host loop, no synchronisation.  The object, its mask and its accumulators SURVIVE nxs_dyn_set_mesh and nxs_dyn_regrid: the
+ * reference calls updateGridMean just before a regrid (FE.cpp:8005-8010) and goes on adding after it.  A handle that never calls these functions allocates and
+ * launches nothing for them.  nxs_dyn_means_to_grid stays what it was.
+ * rotateVectors indexes interp_out in BAMG order (b = i * M_nrows + j for column i, row j) and M_grid.gridLON by the SAME number, although initRegularGrid fills
+ * gridLON in grid order (i + M_ncols * j): a point is rotated by the longitude of whichever point has the grid index b.  That is restated as it stands; a
+ * square grid hides it.
+ * OUT OF SCOPE: inverse_mapx for gridLAT / gridLON (the caller passes gridLON), the NetCDF writer, the reduction over ranks (FE.cpp:9476-9487: ranks fetch with
+ * apply_lsm = 0, sum, and mask with the root's LSM). */
+typedef struct nxs_dyn_means_regular {
+    int32_t ncols, nrows;      /* M_ncols (along x), M_nrows (along y); 0 in either removes the object */
+    double xmin, ymax;         /* M_xmin, M_ymax */
+    double mooring_spacing;    /* M_mooring_spacing > 0 */
+    double miss_val;           /* M_miss_val */
+    int32_t rotation;          /* NXS_MEANS_ROTATE_NONE or NXS_MEANS_ROTATE_NORTH_EAST; NXS_MEANS_ROTATE_GRID_THETA is refused: M_grid = Grid() has no theta */
+    const double *gridLON;     /* [ncols * nrows] degrees, as initRegularGrid fills it (gridoutput.cpp:199-213: entry i + ncols * j); NORTH_EAST only */
+    double rotation_angle;     /* radians: mapNextsim->rotation * PI / 180 */
+    int32_t n_pairs;           /* M_vectorial_variables.size(), <= NXS_MEANS_MAX_PAIRS */
+    int32_t pair_first[NXS_MEANS_MAX_PAIRS];    /* components_Id.first: a column of the configured nodal list */
+    int32_t pair_second[NXS_MEANS_MAX_PAIRS];   /* components_Id.second */
+} nxs_dyn_means_regular;
+
+/*   nxs_dyn_means_regular_set     everything is copied.  x_grid[i] = xmin + spacing * i and y_grid[nrows - 1 - i] = ymax - spacing * i are built as
+ *                  InterpFromMeshToGridx.cpp:78, 88 builds them (the second is not ymin + spacing * j in its last bit); cosang / sinang (gridoutput.cpp:608-609)
+ *                  are evaluated here, once, on the host with std::cos / std::sin of the reference's own expression, entry k from gridLON[k].  A new set replaces
+ *                  the previous one (mask and accumulators included).  ncols == 0, nrows == 0 or p == NULL removes the object and frees its memory.
+ *                  nxs_dyn_means_configure with other list sizes drops the accumulators; they are made again, zeroed, at the new sizes by the next
+ *                  nxs_dyn_means_regular_update / _get / _reset.  NXS_ERR_INVALID: a negative ncols or nrows, more than 2^31 - 1 grid points, a spacing that is
+ *                  not positive and finite, a non-finite xmin / ymax, an unknown rotation mode, NXS_MEANS_ROTATE_GRID_THETA, NORTH_EAST without gridLON or with
+ *                  a non-finite angle, n_pairs outside 0 .. NXS_MEANS_MAX_PAIRS, a pair index outside the configured nodal list.
+ *   nxs_dyn_means_regular_lsm     setLSM.  lsm_in == NULL: computed on the handle's own mesh AT REST (M_UM = 0) with the arithmetic of the update's search: 1
+ *                  where any triangle, ghosts included, holds the point, else 0 (needs nxs_dyn_set_mesh).  lsm_in != NULL: [ncols * nrows] in grid order, taken
+ *                  as given (a partitioned run's root computes it on the root mesh, which no handle holds).  lsm_out (may be NULL) receives it.  Without
+ *                  this call there is no mask (M_use_lsm = false).
+ *   nxs_dyn_means_regular_update  updateGridMean(): asynchronous on the handle's stream.  Per grid point: the winner is the highest-numbered element whose box holds
+ *                  the point (:143, :148) and whose area_1, area_2, area_3 of :152-158 are all > -10e-12; data_grid[nv][i + ncols * j] += the accumulator row of
+ *                  the winner, 0. when none holds the point; the nodal variables area_1 * d0, += area_2 * d1, += area_3 * d2 without contraction; a NaN value
+ *                  becomes the default 0. (:175) BEFORE the proc mask -- unlike the loaded grid, where NaN * 0. stays a NaN; rotateVectors per pair in list
+ *                  order with the skip interp_out[first] == miss_val; the nodal value times the proc mask (1. for a winner below M_local_nelements, else 0.);
+ *                  the ice-mask rule of :404-414, nodal variables first.  NXS_ERR_STATE: before nxs_dyn_set_mesh / nxs_dyn_put_state, without a grid, nothing
+ *                  configured, a pair index outside the nodal list as configured NOW.
+ *   nxs_dyn_means_regular_get     synchronised on return.  grid_elemental [num_elemental][ncols * nrows], grid_nodal [num_nodal][ncols * nrows] host arrays in
+ *                  grid order (either may be NULL).  apply_lsm != 0 with a mask present: applyLSM on the copy handed out (miss_val where the mask is 0); the
+ *                  resident rows stay as they are.  *elemental_dev / *nodal_dev (either may be NULL) receive the DEVICE pointers of the resident rows
+ *                  (library-owned, valid until nxs_dyn_means_regular_set / nxs_dyn_means_configure; NULL for an empty list).
+ *   nxs_dyn_means_regular_reset   resetGridMean(): the grid accumulators to zero, on the stream.
+ * Option "means_timing" 1 puts events around the two launches: nxs_dyn_debug_array "means_regular_ms" returns [the search, the gather] of the last update in ms. */
+NXS_API int nxs_dyn_means_regular_set(nxs_dyn_handle *h, const nxs_dyn_means_regular *p);
+NXS_API int nxs_dyn_means_regular_lsm(nxs_dyn_handle *h, const int32_t *lsm_in /* [ncols * nrows] or NULL */, int32_t *lsm_out /* [ncols * nrows] or NULL */);
+NXS_API int nxs_dyn_means_regular_update(nxs_dyn_handle *h);
+NXS_API int nxs_dyn_means_regular_get(nxs_dyn_handle *h, int32_t apply_lsm, double *grid_elemental /* [n_el][ncols * nrows] */, double *grid_nodal /* [n_nod][ncols * nrows] */,
+                                      const double **elemental_dev, const double **nodal_dev);
+NXS_API int nxs_dyn_means_regular_reset(nxs_dyn_handle *h);
 
 /* ---- The coupler's outgoing fields: M_cpl_out, the second GridOutput of a coupled build.  FiniteElement::step() runs, every time step ("coupler put",
  * FE.cpp:8226-8266): updateIceDiagnostics(); updateMeans(M_cpl_out, cpl_time_factor); and, when a coupling step ends, M_cpl_out.updateGridMean(bamgmesh,

@@ -98,6 +98,15 @@ public:
         check(nxs_dyn_means_points_get(h_, apply_lsm ? 1 : 0, grid_elemental, grid_nodal, elemental_dev, nodal_dev), "means_points_get");
     }
     void meansPointsResetGridMean() { check(nxs_dyn_means_points_reset(h_), "means_points_reset"); }
+    // The Moorings means on the REGULAR grid (moorings.grid_type=regular): the same five on the M_is_regular_grid branch (gridoutput.cpp:486-538), InterpFromMeshToGridx
+    // restated on the device.  The grid, its mask and its accumulators survive setMesh and regrid.
+    void meansRegularSet(const nxs_dyn_means_regular *p) { check(nxs_dyn_means_regular_set(h_, p), "means_regular_set"); }   // NULL, ncols == 0 or nrows == 0: removed
+    void meansRegularSetLSM(const int32_t *lsm_in = nullptr, int32_t *lsm_out = nullptr) { check(nxs_dyn_means_regular_lsm(h_, lsm_in, lsm_out), "means_regular_lsm"); }
+    void meansRegularUpdateGridMean() { check(nxs_dyn_means_regular_update(h_), "means_regular_update"); }
+    void meansRegularGet(bool apply_lsm, double *grid_elemental, double *grid_nodal, const double **elemental_dev = nullptr, const double **nodal_dev = nullptr) {
+        check(nxs_dyn_means_regular_get(h_, apply_lsm ? 1 : 0, grid_elemental, grid_nodal, elemental_dev, nodal_dev), "means_regular_get");
+    }
+    void meansRegularResetGridMean() { check(nxs_dyn_means_regular_reset(h_), "means_regular_reset"); }
     // The coupler's outgoing fields, M_cpl_out: updateMeans(M_cpl_out, cpl_time_factor), M_cpl_out.updateGridMean, resetMeshMean, resetGridMean (FE.cpp:8012-8052,
     // 8226-8266) on a second accumulator set; the exchange grid's accumulators survive setMesh and regrid, the map is attached again after either.
     void cplOutConfigure(const nxs_dyn_means_config &c) { check(nxs_dyn_cpl_out_configure(h_, &c), "cpl_out_configure"); }

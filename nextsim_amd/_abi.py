@@ -564,6 +564,12 @@ class MeansPoints(C.Structure):   # nxs_dyn_means_points
                 ("pair_second", C.c_int32 * NXS_MEANS_MAX_PAIRS)]
 
 
+class MeansRegular(C.Structure):   # nxs_dyn_means_regular
+    _fields_ = [("ncols", C.c_int32), ("nrows", C.c_int32), ("xmin", C.c_double), ("ymax", C.c_double), ("mooring_spacing", C.c_double), ("miss_val", C.c_double),
+                ("rotation", C.c_int32), ("gridLON", c_double_p), ("rotation_angle", C.c_double), ("n_pairs", C.c_int32),
+                ("pair_first", C.c_int32 * NXS_MEANS_MAX_PAIRS), ("pair_second", C.c_int32 * NXS_MEANS_MAX_PAIRS)]
+
+
 NXS_DRIFTER_SETS = 8   # include/nxs_dyn.h: drifter sets per handle (nxs_dyn_drifters_*)
 
 ICE_DIAG = ("D_conc", "D_thick", "D_snow_thick", "D_sigma0", "D_sigma1", "D_divergence")

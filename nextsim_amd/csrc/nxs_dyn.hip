@@ -63,6 +63,8 @@
 #include "nxs_thermo_forcing_kernels.inl"
 #include "nxs_nesting_kernels.inl"
 #include "nxs_nodal_forcing_kernels.inl"
+#include "nxs_means_regular_body.inl"
+#include "nxs_means_regular_kernels.inl"
 
 // ================================================================================================
 // host side
@@ -287,6 +289,20 @@ struct MeansPoints {       // nxs_dyn_means_points_*: a loaded grid, its rotatio
     bool mp_have_lsm = false;                  // M_use_lsm
     std::vector<int32_t> mp_lsm;               // [G] M_lsm (applyLSM works on the copy nxs_dyn_means_points_get hands out)
 };
+struct MeansRegular {      // nxs_dyn_means_regular_*: the REGULAR grid of the Moorings, its rotation, its land-sea mask and the grid accumulators (data_grid).  NOT the mesh's: release_mesh leaves them
+    std::vector<void *> mr_allocs;
+    bool mr_set = false;
+    int mr_ncols = 0, mr_nrows = 0, mr_G = 0, mr_n_pairs = 0;
+    int mr_first[NXS_MEANS_MAX_PAIRS] = {}, mr_second[NXS_MEANS_MAX_PAIRS] = {};
+    double mr_spacing = 0., mr_miss_val = 0.;
+    double *mr_xg = nullptr, *mr_yg = nullptr;     // [ncols], [nrows] x_grid, y_grid of InterpFromMeshToGridx.cpp:78, 88
+    double *mr_cos = nullptr, *mr_sin = nullptr;   // [G] by BAMG index; NULL: NXS_MEANS_ROTATE_NONE
+    int *mr_hit = nullptr;                         // [G] the winning element of every grid point, the hand-over between the two launches
+    double *mr_grid[2] = {nullptr, nullptr};       // [n_el][G], [n_nod][G] in grid order
+    int mr_grid_n[2] = {0, 0};                     // the list sizes the accumulators were made for
+    bool mr_have_lsm = false;                      // M_use_lsm
+    std::vector<int32_t> mr_lsm;                   // [G] M_lsm (applyLSM works on the copy nxs_dyn_means_regular_get hands out)
+};
 struct CplOut {            // nxs_dyn_cpl_out_*: the coupler's means (M_cpl_out), a second accumulator set beside the Moorings' -- the MESH side: gone with the mesh (release_mesh), the
                            // accumulators made again, zeroed, at the new sizes by set_mesh / regrid; the borrowed map was the old mesh's (FE.cpp:8033)
     std::vector<void *> cpl_allocs;
@@ -306,7 +322,7 @@ struct CplOutGrid {        // ... and the exchange grid's side: the P-points, co
     int cpl_grid_n[2] = {0, 0};                // the list sizes the accumulators were made for
 };
 
-struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, NodesCoupled, MeshForcing, CoupledBuffers, MeansPoints, CplOut, CplOutGrid {
+struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, NodesCoupled, MeshForcing, CoupledBuffers, MeansPoints, MeansRegular, CplOut, CplOutGrid {
     int device = 0;
     std::string reg_key;    // the device's name in the registry of resident grids (its PCI bus id): nxs_resident_registry.hpp
     hipStream_t stream = nullptr;
@@ -422,6 +438,8 @@ struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, Pa
     int means_timing = 0;                          // option "means_timing": events around the two launches of nxs_dyn_means_update (nxs_dyn_debug_array "means_update_ms")
     hipEvent_t means_ev[3] = {nullptr, nullptr, nullptr};
     bool means_timed = false;
+    hipEvent_t mr_ev[3] = {nullptr, nullptr, nullptr};   // the same option: around the two launches of nxs_dyn_means_regular_update (nxs_dyn_debug_array "means_regular_ms")
+    bool mr_timed = false;
     // the coupler's means (nxs_dyn_cpl_out_*): the configuration is the handle's and survives set_mesh; the buffers are CplOut's and CplOutGrid's
     std::vector<int> cpl_ids[2];
     MeansTable cpl_tab[2] = {};
@@ -736,6 +754,8 @@ inline bool ocean_coupled_on(const nxs_dyn_handle *h) {
 }
 // the loaded grid of the Moorings with its accumulators: nxs_dyn_means_points_set (a new grid, or none) and nxs_dyn_destroy -- not release_mesh
 void release_means_points(nxs_dyn_handle *h) { release_group<MeansPoints>(h, h->mp_allocs); }
+// the regular grid of the Moorings with its accumulators: nxs_dyn_means_regular_set (a new grid, or none) and nxs_dyn_destroy -- not release_mesh
+void release_means_regular(nxs_dyn_handle *h) { release_group<MeansRegular>(h, h->mr_allocs); }
 // the coupler's means: the mesh accumulators and the borrowed map go with the mesh; the exchange grid with its accumulators at nxs_dyn_cpl_out_configure with two
 // empty lists and nxs_dyn_destroy -- not at release_mesh
 void release_cpl_out(nxs_dyn_handle *h) { release_group<CplOut>(h, h->cpl_allocs); }
@@ -2176,6 +2196,7 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     ipc_release(h);
     release_mesh(h);
     release_means_points(h);
+    release_means_regular(h);
     release_cpl_out_grid(h);
     if (!h->reg_key.empty()) nxs_reg::table_for(h->reg_key).remove((uint64_t)(uintptr_t)h);
     unpin_all(h);
@@ -2191,6 +2212,7 @@ int nxs_dyn_destroy(nxs_dyn_handle *h) try {
     for (auto &set : h->ev) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
     for (auto &set : h->ev_flush) for (auto &ev : set) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : h->means_ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : h->mr_ev) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : h->slab_ev) if (ev) (void)hipEventDestroy(ev);
     nxs_drifters::destroy(h->drift); h->drift = nullptr;
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -2337,8 +2359,8 @@ int nxs_dyn_set_option(nxs_dyn_handle *h, const char *key, int64_t value) try {
         return NXS_OK;
     }
     if (!std::strcmp(key, "means_timing")) {
-        h->means_timing = value != 0; h->means_timed = false;
-        if (h->means_timing) { HIPCHK(h, hipSetDevice(h->device)); for (auto &ev : h->means_ev) if (!ev) HIPCHK(h, hipEventCreate(&ev)); }
+        h->means_timing = value != 0; h->means_timed = false; h->mr_timed = false;
+        if (h->means_timing) { HIPCHK(h, hipSetDevice(h->device)); for (auto &ev : h->means_ev) if (!ev) HIPCHK(h, hipEventCreate(&ev)); for (auto &ev : h->mr_ev) if (!ev) HIPCHK(h, hipEventCreate(&ev)); }
         return NXS_OK;
     }
     if (!std::strcmp(key, "slab_coupled_timing")) {
@@ -3494,6 +3516,8 @@ int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) tr
     means_drop_buffers(h);
     for (int k = 0; k < 2; ++k)   // the grid accumulators of a loaded grid (nxs_dyn_means_points_*) are made again by their next call when a list changes its size
         if (h->mp_grid_n[k] != (int)ids[k].size()) { pool_free_one(h->mp_allocs, h->mp_grid[k]); h->mp_grid[k] = nullptr; h->mp_grid_n[k] = 0; }
+    for (int k = 0; k < 2; ++k)   // ... and those of the regular grid (nxs_dyn_means_regular_*)
+        if (h->mr_grid_n[k] != (int)ids[k].size()) { pool_free_one(h->mr_allocs, h->mr_grid[k]); h->mr_grid[k] = nullptr; h->mr_grid_n[k] = 0; }
     for (int k = 0; k < 2; ++k) { h->means_ids[k] = ids[k]; h->means_mask[k] = mask[k]; }
     h->means_ice_mask_col = ice_col;
     if (h->have_mesh) { int rc = means_make_buffers(h); if (rc) return rc; }
@@ -3836,6 +3860,13 @@ int nxs_dyn_debug_array(nxs_dyn_handle *h, const char *name, double *out, int64_
     if (!std::strcmp(name, "means_points_ms")) {   // [2] device time of the last nxs_dyn_means_points_update with option "drifters_timing" 1: its locator build (0: none), its kernel
         if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array means_points_ms has 2 entries");
         if (!h->drift || !nxs_drifters::means_points_timing(h->drift, out)) return fail(h, NXS_ERR_STATE, "debug_array means_points_ms: no timed nxs_dyn_means_points_update (option drifters_timing)");
+        return NXS_OK;
+    }
+    if (!std::strcmp(name, "means_regular_ms")) {   // [2] device time of the last nxs_dyn_means_regular_update with option "means_timing" 1: the memset and k_means_regular_hits, k_means_regular_gather
+        if (n != 2) return fail(h, NXS_ERR_INVALID, "debug_array means_regular_ms has 2 entries");
+        if (!h->mr_timed) return fail(h, NXS_ERR_STATE, "debug_array means_regular_ms: no timed nxs_dyn_means_regular_update (option means_timing)");
+        HIPCHK(h, hipEventSynchronize(h->mr_ev[2]));
+        for (int k = 0; k < 2; ++k) { float ms = 0.f; HIPCHK(h, hipEventElapsedTime(&ms, h->mr_ev[k], h->mr_ev[k + 1])); out[k] = ms; }
         return NXS_OK;
     }
     if (!std::strcmp(name, "means_update_ms")) {   // [2] device time of the last nxs_dyn_means_update with option "means_timing" 1: the elemental launch, the nodal launch
@@ -4206,6 +4237,7 @@ int nxs_dyn_check_fields_fast(nxs_dyn_handle *h, int32_t *crash_local) try {
 #include "nxs_nodes_coupled.inl"
 #include "nxs_mesh_forcing.inl"
 #include "nxs_means_points.inl"
+#include "nxs_means_regular.inl"
 #include "nxs_cpl_out.inl"
 
 }  // extern "C"

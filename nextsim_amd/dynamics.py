@@ -165,6 +165,11 @@ def load_library():
     L.nxs_dyn_means_points_update.argtypes = [H]
     L.nxs_dyn_means_points_get.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
     L.nxs_dyn_means_points_reset.argtypes = [H]
+    L.nxs_dyn_means_regular_set.argtypes = [H, P(_abi.MeansRegular)]
+    L.nxs_dyn_means_regular_lsm.argtypes = [H, _abi.c_int32_p, _abi.c_int32_p]
+    L.nxs_dyn_means_regular_update.argtypes = [H]
+    L.nxs_dyn_means_regular_get.argtypes = [H, C.c_int32, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
+    L.nxs_dyn_means_regular_reset.argtypes = [H]
     L.nxs_dyn_cpl_out_configure.argtypes = [H, P(_abi.MeansConfig)]
     L.nxs_dyn_cpl_out_update.argtypes = [H, C.c_double]
     L.nxs_dyn_cpl_out_get.argtypes = [H, _abi.c_double_p, _abi.c_double_p, P(C.c_void_p), P(C.c_void_p)]
@@ -299,6 +304,7 @@ EXPORTS = (
     "nxs_dyn_slab_get", "nxs_slab_coupled_config_check", "nxs_dyn_slab_coupled_configure", "nxs_dyn_slab_coupled", "nxs_dyn_slab_coupled_info",
     "nxs_dyn_means_configure", "nxs_dyn_means_set_tau_ow", "nxs_dyn_means_update", "nxs_dyn_means_get", "nxs_dyn_means_to_grid", "nxs_dyn_means_to_grid_conservative", "nxs_dyn_means_reset",
     "nxs_dyn_means_points_set", "nxs_dyn_means_points_lsm", "nxs_dyn_means_points_update", "nxs_dyn_means_points_get", "nxs_dyn_means_points_reset",
+    "nxs_dyn_means_regular_set", "nxs_dyn_means_regular_lsm", "nxs_dyn_means_regular_update", "nxs_dyn_means_regular_get", "nxs_dyn_means_regular_reset",
     "nxs_dyn_cpl_out_configure", "nxs_dyn_cpl_out_update", "nxs_dyn_cpl_out_get", "nxs_dyn_cpl_out_reset", "nxs_dyn_cpl_out_attach_grid", "nxs_dyn_cpl_out_put",
     "nxs_dyn_cpl_out_reset_grid", "nxs_dyn_fsd_diag_configure",
     "nxs_dyn_drifters_set", "nxs_dyn_drifters_clear", "nxs_dyn_drifters_mesh_bbox", "nxs_dyn_drifters_move", "nxs_dyn_drifters_conc", "nxs_dyn_drifters_mask",
@@ -1761,6 +1767,62 @@ class FiniteElementDynamics:
         """resetGridMean(): the grid accumulators to zero, on the stream."""
         self._chk(self.L.nxs_dyn_means_points_reset(self.h))
 
+    # ---- the Moorings means on the regular grid: the same five on the M_is_regular_grid branch (gridoutput.cpp:486-538, InterpFromMeshToGridx) ----
+    def means_regular_set(self, xmin=0., ymax=0., mooring_spacing=0., ncols=0, nrows=0, miss_val=-1e14, rotation="none", gridLON=None, rotation_angle=0., pairs=()):
+        """The regular grid of the Moorings on the handle: M_xmin, M_ymax, M_mooring_spacing, M_ncols (along x), M_nrows (along y), the rotation mode ("none", or
+        "north_east" with gridLON [ncols * nrows] in degrees, in grid order) with rotation_angle in radians, and the vectorial variables as pairs of columns of the
+        configured nodal list.  Everything is copied; the grid, its mask and its accumulators survive set_mesh and regrid.  ncols or nrows 0 removes the object."""
+        if not ncols or not nrows:
+            self._chk(self.L.nxs_dyn_means_regular_set(self.h, None))
+            self._regular_G = 0
+            return
+        p = _abi.MeansRegular()
+        p.ncols, p.nrows = int(ncols), int(nrows)
+        p.xmin, p.ymax, p.mooring_spacing, p.miss_val = float(xmin), float(ymax), float(mooring_spacing), float(miss_val)
+        p.rotation = _abi.MEANS_ROTATION[rotation] if isinstance(rotation, str) else int(rotation)
+        if gridLON is not None:
+            lon = np.ascontiguousarray(gridLON, np.float64).ravel()
+            if lon.size != int(ncols) * int(nrows):
+                raise ValueError(f"gridLON has {lon.size} entries, the grid {int(ncols) * int(nrows)}")
+            p.gridLON = _abi.dptr(lon)
+        p.rotation_angle = float(rotation_angle)
+        pairs = list(pairs)
+        p.n_pairs = len(pairs)
+        for k, (first, second) in enumerate(pairs[:_abi.NXS_MEANS_MAX_PAIRS]):
+            p.pair_first[k], p.pair_second[k] = int(first), int(second)
+        self._chk(self.L.nxs_dyn_means_regular_set(self.h, C.byref(p)))
+        self._regular_G = int(ncols) * int(nrows)
+
+    def means_regular_lsm(self, lsm=None) -> np.ndarray:
+        """setLSM: computed on the handle's own mesh at rest (1 where any triangle, ghosts included, holds the grid point) or, given, taken over.  Returns it."""
+        G = getattr(self, "_regular_G", 0)
+        out = np.empty(G, np.int32)
+        given = None if lsm is None else np.ascontiguousarray(lsm, np.int32).ravel()
+        if given is not None and given.size != G:
+            raise ValueError(f"lsm has {given.size} entries, the grid {G}")
+        self._chk(self.L.nxs_dyn_means_regular_lsm(self.h, _abi.iptr(given) if given is not None else None, _abi.iptr(out)))
+        return out
+
+    def means_regular_update(self):
+        """updateGridMean() on the regular grid: two launches on the handle's stream, nothing crosses to the host."""
+        self._chk(self.L.nxs_dyn_means_regular_update(self.h))
+
+    def means_regular_get(self, apply_lsm: bool = False, want_host: bool = True):
+        """(elemental [n_el, ncols * nrows] or None, nodal [n_nod, ncols * nrows] or None, device pointer of the elemental rows, of the nodal rows), grid order;
+        apply_lsm: applyLSM on the copy."""
+        n_el, n_nod = getattr(self, "_means_n", (0, 0))
+        G = getattr(self, "_regular_G", 0)
+        el = np.empty((n_el, G)) if want_host and n_el else None
+        nod = np.empty((n_nod, G)) if want_host and n_nod else None
+        de, dn = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.nxs_dyn_means_regular_get(self.h, int(bool(apply_lsm)), _abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None,
+                                                   C.byref(de), C.byref(dn)))
+        return el, nod, de.value, dn.value
+
+    def means_regular_reset(self):
+        """resetGridMean(): the grid accumulators to zero, on the stream."""
+        self._chk(self.L.nxs_dyn_means_regular_reset(self.h))
+
     # ---- the coupler's outgoing fields: M_cpl_out, the "coupler put" of step() (FE.cpp:8226-8266) and the put in front of a regrid (FE.cpp:8012-8052) ----
     def cpl_out_configure(self, elemental=(), nodal=()):
         """The variables of M_cpl_out, a second accumulator set beside the Moorings': the names (or numbers) means_configure takes, `dmax` / `dmean` among them;
@@ -1915,7 +1977,7 @@ class FiniteElementDynamics:
         n = {"rlmass": Nn, "node_mass": Nn, "C_bu": Nn, "grad_ssh": 2 * Nn, "fcor": Nn, "VTM": 2 * Nn,
              "shape": 6 * Ne, "emass": Ne, "ecbu": Ne, "force": 6 * Ne, "volume": Ne, "expC": Ne,
              "erec": 6 * Ne, "nrec": 10 * Nn, "xy": 2 * Nn, "delta_x": Ne, "surface": Ne, "tau_a": 2 * Nn, "drag_ui": Ne, "drag_ui_young": Ne, "slab_branches": Ne, "slab_fsd_branches": Ne,
-             "means_update_ms": 2, "means_points_ms": 2, "slab_coupled_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3, "diffuse_table": 3 * Ne}[name]
+             "means_update_ms": 2, "means_points_ms": 2, "means_regular_ms": 2, "slab_coupled_ms": 2, "drifters_ms": 4, "phase_times": 8 * 8192, "phase_times_prep": 8 * 8192, "shape_range": 1, "guard_launch": 2, "update_launch": 3, "diffuse_table": 3 * Ne}[name]
         out = np.empty(n)
         self._chk(self.L.nxs_dyn_debug_array(self.h, name.encode(), _abi.dptr(out), n))
         return out

@@ -212,3 +212,18 @@ def moorings_append_means(path, timestamp, fe, xmin, ymax, mooring_spacing, ncol
     if reset:
         fe.means_reset()
     return ge, gn
+
+
+def moorings_append_means_regular(path, timestamp, fe, averaging_period=0.0, reset=True):
+    """mooringsAppendNetcdf (FE.cpp:9468-9497) from the regular grid resident on `fe` (means_regular_set; means_regular_lsm for a mask): updateGridMean on the
+    device, the record with applyLSM appended in the order elemental variables, nodal variables -- the order `variables` of moorings_create must have --, then
+    resetMeshMean and resetGridMean.  Single rank: with several, fetch with apply_lsm=False, sum the ranks' grids (boost::mpi::reduce, FE.cpp:9476-9487), mask
+    with the root's LSM, then moorings_append."""
+    fe.means_regular_update()
+    ge, gn, _, _ = fe.means_regular_get(apply_lsm=True)
+    fields = [g for grid in (ge, gn) if grid is not None for g in grid]
+    moorings_append(path, timestamp, fields, averaging_period)
+    if reset:
+        fe.means_reset()
+        fe.means_regular_reset()
+    return ge, gn
