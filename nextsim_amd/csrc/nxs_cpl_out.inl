@@ -2,27 +2,12 @@
 // of FiniteElement::step() (FE.cpp:8226-8266) and the put in front of a regrid (FE.cpp:8012-8052).  Textually included by nxs_dyn.hip inside its extern "C" block,
 // behind nxs_means_points.inl, whose checks of a set of points and whose cos / sin it shares.
 // A second accumulator set beside the Moorings': its own id lists and tables on the handle, its mesh accumulators in the CplOut group (gone with the mesh, made
-// again zeroed by set_mesh / regrid), the exchange grid's points and data_grid in the CplOutGrid group (NOT the mesh's).  The accumulation is means_update_set --
+// again zeroed by set_mesh / regrid), the exchange grid's points and data_grid in the CplOutGrid group (NOT the mesh's): one OutputGrid, h->cplg, served by
+// nxs_output_grid.inl like the two grids of the Moorings, and a flag.  The accumulation is means_update_set --
 // the kernels of nxs_dyn_means_update --, the elemental leg of the put nxs_gridmap_send_rows (k_gridmap_send, nxs_gridmap_kernels.inl), the nodal leg
 // nxs_drifters::means_points_update on this set's rows with n_el = 0 and no ice mask: no second locator, no copy of the per-point body.
 
 static bool cpl_out_configured(const nxs_dyn_handle *h) { return !h->cpl_ids[0].empty() || !h->cpl_ids[1].empty(); }
-
-// data_grid at the sizes of the lists configured now, zeroed when made (nxs_dyn_cpl_out_configure with other sizes dropped them)
-static int cpl_out_ensure_grids(nxs_dyn_handle *h) {
-    for (int k = 0; k < 2; ++k) {
-        const int n = (int)h->cpl_ids[k].size();
-        if (h->cpl_grid_n[k] == n && (n == 0 || h->cpl_grid[k])) continue;
-        pool_free_one(h->cplg_allocs, h->cpl_grid[k]);
-        h->cpl_grid[k] = nullptr; h->cpl_grid_n[k] = 0;
-        if (!n) continue;
-        const size_t count = (size_t)n * h->cpl_G;
-        if (int rc = dev_alloc(h, h->cplg_allocs, &h->cpl_grid[k], count)) return rc;
-        HIPCHK(h, hipMemsetAsync(h->cpl_grid[k], 0, count * sizeof(double), h->stream));
-        h->cpl_grid_n[k] = n;
-    }
-    return NXS_OK;
-}
 
 int nxs_dyn_cpl_out_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) try {
     if (!h || !c) return NXS_ERR_INVALID;
@@ -37,8 +22,7 @@ int nxs_dyn_cpl_out_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) 
     for (double *&q : h->d_cpl) { pool_free_one(h->cpl_allocs, q); q = nullptr; }
     for (int k = 0; k < 2; ++k) h->cpl_ids[k] = ids[k];
     if (!cpl_out_configured(h)) { release_cpl_out(h); release_cpl_out_grid(h); return NXS_OK; }
-    for (int k = 0; k < 2; ++k)   // data_grid is made again by the next put / reset_grid when a list changes its size
-        if (h->cpl_grid_n[k] != (int)ids[k].size()) { pool_free_one(h->cplg_allocs, h->cpl_grid[k]); h->cpl_grid[k] = nullptr; h->cpl_grid_n[k] = 0; }
+    og_drop_resized(h->cplg, ids);   // data_grid is made again by the next put / reset_grid when a list changes its size
     if (h->have_mesh) { int rc = cpl_out_make_buffers(h); if (rc) return rc; }
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_cpl_out_configure"); }
@@ -67,17 +51,17 @@ int nxs_dyn_cpl_out_get(nxs_dyn_handle *h, double *elemental, double *nodal, con
     return NXS_OK;
 } catch (...) { return dyn_caught(h, "nxs_dyn_cpl_out_get"); }
 
-// resetMeshMean(bamgmesh) / resetGridMean() of this set, queued on the stream
+// resetMeshMean(bamgmesh) of this set, queued on the stream
 static int cpl_out_zero_mesh(nxs_dyn_handle *h) {
     const size_t len[2] = {(size_t)h->dm.Ne, (size_t)h->dm.Nn};
     for (int k = 0; k < 2; ++k)
         if (h->d_cpl[k]) HIPCHK(h, hipMemsetAsync(h->d_cpl[k], 0, len[k] * h->cpl_ids[k].size() * sizeof(double), h->stream));
     return NXS_OK;
 }
-static int cpl_out_zero_grid(nxs_dyn_handle *h) {
-    for (int k = 0; k < 2; ++k)
-        if (h->cpl_grid[k]) HIPCHK(h, hipMemsetAsync(h->cpl_grid[k], 0, (size_t)h->cpl_grid_n[k] * h->cpl_G * sizeof(double), h->stream));
-    return NXS_OK;
+// ... and resetGridMean() behind it: NXS_CPL_OUT_RESET (FE.cpp:8262-8263)
+static int cpl_out_zero_both(nxs_dyn_handle *h) {
+    if (int rc = cpl_out_zero_mesh(h)) return rc;
+    return og_zero(h, h->cplg);
 }
 
 int nxs_dyn_cpl_out_reset(nxs_dyn_handle *h) try {
@@ -102,27 +86,16 @@ int nxs_dyn_cpl_out_attach_grid(nxs_dyn_handle *h, struct nxs_gridmap *map, cons
     if (n_nod > 0 && !p) return fail(h, NXS_ERR_STATE, "cpl_out_attach_grid: %d nodal variables are configured but no points were given (the nodal leg locates the P-points)", n_nod);
     std::vector<double> cs, sn;
     if (p)
-        if (int rc = mp_angles(h, "cpl_out_attach_grid", p, cs, sn)) return rc;
+        if (int rc = mp_angles(h, "cpl_out_attach_grid", (size_t)p->G, p->rotation, p->rotation_angle, p->gridLON, p->gridTheta, cs, sn)) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (a launch may still use the previous points)
-    if (h->cpl_G != G) release_cpl_out_grid(h);   // another grid: its accumulators go too
-    for (double **q : {&h->cpl_gx, &h->cpl_gy, &h->cpl_cos, &h->cpl_sin}) { pool_free_one(h->cplg_allocs, *q); *q = nullptr; }
-    h->cpl_points = false; h->cpl_n_pairs = 0;
-    h->cpl_G = G;
+    if (h->cplg.G != G) release_cpl_out_grid(h);   // another grid: its accumulators go too
+    OutputGrid &g = h->cplg;
+    for (double **q : {&g.gx, &g.gy, &g.cos, &g.sin}) { pool_free_one(g.allocs, *q); *q = nullptr; }
+    h->cpl_points = false; g.n_pairs = 0;
+    g.G = G;
     if (p) {
-        const size_t n = (size_t)G;
-        int rc;
-        if ((rc = dev_alloc(h, h->cplg_allocs, &h->cpl_gx, n)) || (rc = dev_alloc(h, h->cplg_allocs, &h->cpl_gy, n))) return rc;
-        if (!cs.empty() && ((rc = dev_alloc(h, h->cplg_allocs, &h->cpl_cos, n)) || (rc = dev_alloc(h, h->cplg_allocs, &h->cpl_sin, n)))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->cpl_gx, p->gridX, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->cpl_gy, p->gridY, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        if (!cs.empty()) {
-            HIPCHK(h, hipMemcpyAsync(h->cpl_cos, cs.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(h->cpl_sin, sn.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));   // the caller's arrays, and cs / sn, may go away
-        h->cpl_miss_val = p->miss_val; h->cpl_n_pairs = p->n_pairs;
-        for (int k = 0; k < p->n_pairs; ++k) { h->cpl_first[k] = p->pair_first[k]; h->cpl_second[k] = p->pair_second[k]; }
+        if (int rc = og_upload(h, g, p->gridX, p->gridY, cs, sn, p->miss_val, p->n_pairs, p->pair_first, p->pair_second)) return rc;
         h->cpl_points = true;
     }
     h->cpl_map = map;
@@ -136,57 +109,31 @@ int nxs_dyn_cpl_out_put(nxs_dyn_handle *h, double *grid_elemental, double *grid_
     if (!n_el && !n_nod) return fail(h, NXS_ERR_STATE, "cpl_out_put: no variable is configured (nxs_dyn_cpl_out_configure)");
     if (!h->cpl_map) return fail(h, NXS_ERR_STATE, "cpl_out_put: no exchange grid is attached on this mesh (nxs_dyn_cpl_out_attach_grid; again after nxs_dyn_set_mesh / nxs_dyn_regrid)");
     if (n_nod > 0 && !h->cpl_points) return fail(h, NXS_ERR_STATE, "cpl_out_put: %d nodal variables are configured but the attached grid has no points", n_nod);
-    for (int k = 0; k < h->cpl_n_pairs; ++k)
-        if (h->cpl_first[k] >= n_nod || h->cpl_second[k] >= n_nod)
-            return fail(h, NXS_ERR_STATE, "cpl_out_put: pair %d names the columns %d and %d, the nodal list configured now has %d", k, h->cpl_first[k], h->cpl_second[k], n_nod);
+    if (int rc = og_check_stored_pairs(h, "cpl_out_put", h->cplg, n_nod)) return rc;
     if (flags & ~NXS_CPL_OUT_RESET) return fail(h, NXS_ERR_INVALID, "cpl_out_put: unknown flags %d", flags);
     if ((flags & NXS_CPL_OUT_RESET) && ((n_el && !grid_elemental) || (n_nod && !grid_nodal)))
         return fail(h, NXS_ERR_INVALID, "cpl_out_put: NXS_CPL_OUT_RESET without a host array for every configured list: the values would be gone");
     HIPCHK(h, hipSetDevice(h->device));
     if (int rc = launch_gave_up(h)) return rc;   // (as nxs_dyn_means_update: never a mean of a half-made step without an error)
-    if (int rc = cpl_out_ensure_grids(h)) return rc;
+    if (int rc = og_ensure(h, h->cplg, h->cpl_ids)) return rc;
     if (n_el > 0)   // the elemental leg: interpMethod::conservative (gridoutput.cpp:473, 545)
-        if (int rc = nxs_gridmap_send_rows(h->cpl_map, n_el, h->d_cpl[0], h->cpl_grid[0], NXS_REGRID_IN_DEVICE | NXS_REGRID_OUT_DEVICE, (void *)h->stream))
+        if (int rc = nxs_gridmap_send_rows(h->cpl_map, n_el, h->d_cpl[0], h->cplg.grid[0], NXS_REGRID_IN_DEVICE | NXS_REGRID_OUT_DEVICE, (void *)h->stream))
             return fail(h, rc, "cpl_out_put: %s", nxs_interp_last_error());
     if (n_nod > 0) {   // the nodal leg: the exact locator in the mesh displaced by M_UM, the P1 gather, rotateVectors, the proc mask (gridoutput.cpp:478-485, 511-543)
         if (!h->drift) h->drift = nxs_drifters::create();
-        nxs_mp::Args a{};
-        a.G = h->cpl_G; a.n_el = 0; a.n_nod = n_nod; a.n_pairs = h->cpl_n_pairs;
-        a.ice_col = -1; a.Neo = h->dm.Neo;
-        for (int k = 0; k < h->cpl_n_pairs; ++k) { a.first[k] = (unsigned char)h->cpl_first[k]; a.second[k] = (unsigned char)h->cpl_second[k]; }
-        a.miss_val = h->cpl_miss_val;
-        a.gx = h->cpl_gx; a.gy = h->cpl_gy; a.cosang = h->cpl_cos; a.sinang = h->cpl_sin;
-        a.el = nullptr; a.nod = h->d_cpl[1];
-        a.grid_el = nullptr; a.grid_nod = h->cpl_grid[1];
+        const nxs_mp::Args a = og_args(h, h->cplg, 0, n_nod, nullptr, -1, nullptr, h->d_cpl[1]);   // this set's rows, n_el = 0 and no ice mask
         std::string err;
         if (int rc = drift_rc(h, nxs_drifters::means_points_update(h->drift, h->stream, drift_view(h), h->ds.UM, a, err), "cpl_out_put", err)) return rc;
     }
-    double *dst[2] = {grid_elemental, grid_nodal};
-    bool copied = false;
-    for (int k = 0; k < 2; ++k) {
-        const size_t bytes = (size_t)h->cpl_G * h->cpl_grid_n[k] * sizeof(double);
-        if (dst[k] && bytes) { pin_host_buffer(h, dst[k], bytes); HIPCHK(h, hipMemcpyAsync(dst[k], h->cpl_grid[k], bytes, hipMemcpyDeviceToHost, h->stream)); copied = true; }
-    }
-    if (flags & NXS_CPL_OUT_RESET) {   // FE.cpp:8262-8263, behind the copies on the same stream
-        if (int rc = cpl_out_zero_mesh(h)) return rc;
-        if (int rc = cpl_out_zero_grid(h)) return rc;
-    }
-    if (copied) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->res_ready || h->flow_ready) { int rc = resident_error(h); if (rc) return rc; }   // (synchronised above)
-    }
-    if (elemental_dev) *elemental_dev = h->cpl_grid[0];
-    if (nodal_dev) *nodal_dev = h->cpl_grid[1];
-    return NXS_OK;
+    double *const dst[2] = {grid_elemental, grid_nodal};   // synchronises only when something was copied; the reset is queued behind the copies on the same stream
+    return og_copy_out(h, h->cplg, false, dst, elemental_dev, nodal_dev, false, (flags & NXS_CPL_OUT_RESET) ? cpl_out_zero_both : nullptr);
 } catch (...) { return dyn_caught(h, "nxs_dyn_cpl_out_put"); }
 
 int nxs_dyn_cpl_out_reset_grid(nxs_dyn_handle *h) try {
     if (!h) return NXS_ERR_INVALID;
     if (!cpl_out_configured(h)) return fail(h, NXS_ERR_STATE, "cpl_out_reset_grid: no variable is configured (nxs_dyn_cpl_out_configure)");
-    if (h->cpl_G <= 0) return fail(h, NXS_ERR_STATE, "cpl_out_reset_grid: no exchange grid was attached (nxs_dyn_cpl_out_attach_grid)");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (int rc = cpl_out_ensure_grids(h)) return rc;
-    return cpl_out_zero_grid(h);
+    if (h->cplg.G <= 0) return fail(h, NXS_ERR_STATE, "cpl_out_reset_grid: no exchange grid was attached (nxs_dyn_cpl_out_attach_grid)");
+    return og_reset(h, h->cplg, h->cpl_ids);
 } catch (...) { return dyn_caught(h, "nxs_dyn_cpl_out_reset_grid"); }
 
 // wave_coupling.dmax_c_threshold, fsd_unbroken_floe_size, fsd_min_floe_size (FE.cpp:1387, 1410-1411): what D_dmax / D_dmean read beside nxs_dyn_fsd_configure's tables

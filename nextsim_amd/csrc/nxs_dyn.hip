@@ -277,31 +277,30 @@ struct CoupledBuffers {    // the coupled build's arrays (nxs_dyn_set_wave_stres
     unsigned char *d_freezing = nullptr;
     size_t mech_capacity = 0;
 };
-struct MeansPoints {       // nxs_dyn_means_points_*: a loaded grid, its rotation, its land-sea mask and the grid accumulators (data_grid).  NOT the mesh's: release_mesh leaves them
-    std::vector<void *> mp_allocs;
-    bool mp_set = false;
-    int mp_G = 0, mp_n_pairs = 0;
-    int mp_first[NXS_MEANS_MAX_PAIRS] = {}, mp_second[NXS_MEANS_MAX_PAIRS] = {};
-    double mp_miss_val = 0.;
-    double *mp_gx = nullptr, *mp_gy = nullptr, *mp_cos = nullptr, *mp_sin = nullptr;   // [G]; cos / sin NULL: NXS_MEANS_ROTATE_NONE
-    double *mp_grid[2] = {nullptr, nullptr};   // [n_el][G], [n_nod][G]
-    int mp_grid_n[2] = {0, 0};                 // the list sizes the accumulators were made for
-    bool mp_have_lsm = false;                  // M_use_lsm
-    std::vector<int32_t> mp_lsm;               // [G] M_lsm (applyLSM works on the copy nxs_dyn_means_points_get hands out)
+struct OutputGrid {        // ONE output grid of a GridOutput object with its accumulators (data_grid): what the loaded-grid Moorings, the regular-grid Moorings and the coupler's
+                           // exchange grid each hold one of; the routines that serve all three are nxs_output_grid.inl.  One pool, owned by the group that wraps the grid
+    std::vector<void *> allocs;
+    int G = 0, n_pairs = 0;                    // the grid's points (G == 0: none); the vectorial variables as pairs of columns of the nodal list
+    int first[NXS_MEANS_MAX_PAIRS] = {}, second[NXS_MEANS_MAX_PAIRS] = {};
+    double miss_val = 0.;
+    double *gx = nullptr, *gy = nullptr;       // [G] the points (NULL on the regular grid, which has axes)
+    double *cos = nullptr, *sin = nullptr;     // [G] (the regular grid's by BAMG index); NULL: NXS_MEANS_ROTATE_NONE
+    double *grid[2] = {nullptr, nullptr};      // data_grid [n_el][G], [n_nod][G]
+    int grid_n[2] = {0, 0};                    // the list sizes the accumulators were made for
+    bool have_lsm = false;                     // M_use_lsm
+    std::vector<int32_t> lsm;                  // [G] M_lsm (applyLSM works on the copy a _get hands out)
 };
-struct MeansRegular {      // nxs_dyn_means_regular_*: the REGULAR grid of the Moorings, its rotation, its land-sea mask and the grid accumulators (data_grid).  NOT the mesh's: release_mesh leaves them
-    std::vector<void *> mr_allocs;
+struct MeansPoints {       // nxs_dyn_means_points_*: a loaded grid, its rotation, its land-sea mask and the grid accumulators.  NOT the mesh's: release_mesh leaves them
+    OutputGrid mp;
+    bool mp_set = false;
+};
+struct MeansRegular {      // nxs_dyn_means_regular_*: the REGULAR grid of the Moorings, its rotation, its land-sea mask and the grid accumulators (in grid order).  NOT the mesh's: release_mesh leaves them
+    OutputGrid mr;
     bool mr_set = false;
-    int mr_ncols = 0, mr_nrows = 0, mr_G = 0, mr_n_pairs = 0;
-    int mr_first[NXS_MEANS_MAX_PAIRS] = {}, mr_second[NXS_MEANS_MAX_PAIRS] = {};
-    double mr_spacing = 0., mr_miss_val = 0.;
+    int mr_ncols = 0, mr_nrows = 0;
+    double mr_spacing = 0.;
     double *mr_xg = nullptr, *mr_yg = nullptr;     // [ncols], [nrows] x_grid, y_grid of InterpFromMeshToGridx.cpp:78, 88
-    double *mr_cos = nullptr, *mr_sin = nullptr;   // [G] by BAMG index; NULL: NXS_MEANS_ROTATE_NONE
     int *mr_hit = nullptr;                         // [G] the winning element of every grid point, the hand-over between the two launches
-    double *mr_grid[2] = {nullptr, nullptr};       // [n_el][G], [n_nod][G] in grid order
-    int mr_grid_n[2] = {0, 0};                     // the list sizes the accumulators were made for
-    bool mr_have_lsm = false;                      // M_use_lsm
-    std::vector<int32_t> mr_lsm;                   // [G] M_lsm (applyLSM works on the copy nxs_dyn_means_regular_get hands out)
 };
 struct CplOut {            // nxs_dyn_cpl_out_*: the coupler's means (M_cpl_out), a second accumulator set beside the Moorings' -- the MESH side: gone with the mesh (release_mesh), the
                            // accumulators made again, zeroed, at the new sizes by set_mesh / regrid; the borrowed map was the old mesh's (FE.cpp:8033)
@@ -309,17 +308,10 @@ struct CplOut {            // nxs_dyn_cpl_out_*: the coupler's means (M_cpl_out)
     double *d_cpl[2] = {nullptr, nullptr};     // [Ne][n_el], [Nn][n_nod] interleaved like d_means
     struct nxs_gridmap *cpl_map = nullptr;     // borrowed (nxs_dyn_cpl_out_attach_grid)
 };
-struct CplOutGrid {        // ... and the exchange grid's side: the P-points, cos / sin, the pairs and data_grid.  NOT the mesh's: release_mesh leaves it (the reference puts
-                           // before a regrid and goes on adding after it)
-    std::vector<void *> cplg_allocs;
-    int cpl_G = 0;                             // the grid the accumulators are for; 0: none attached yet
+struct CplOutGrid {        // ... and the exchange grid's side: the P-points, cos / sin, the pairs and data_grid (no land-sea mask).  NOT the mesh's: release_mesh leaves it (the
+                           // reference puts before a regrid and goes on adding after it).  cplg.G is the grid the accumulators are for; 0: none attached yet
+    OutputGrid cplg;
     bool cpl_points = false;                   // the P-points were given
-    int cpl_n_pairs = 0;
-    int cpl_first[NXS_MEANS_MAX_PAIRS] = {}, cpl_second[NXS_MEANS_MAX_PAIRS] = {};
-    double cpl_miss_val = 0.;
-    double *cpl_gx = nullptr, *cpl_gy = nullptr, *cpl_cos = nullptr, *cpl_sin = nullptr;   // [G]; cos / sin NULL: NXS_MEANS_ROTATE_NONE
-    double *cpl_grid[2] = {nullptr, nullptr};  // data_grid [n_el][G], [n_nod][G]
-    int cpl_grid_n[2] = {0, 0};                // the list sizes the accumulators were made for
 };
 
 struct nxs_dyn_handle : MeshArrays, StateArrays, PatchTables, ResidentTables, PairPatches, SmoothPatches, VelocityRing, HaloFusedTables, HaloLists, ForcingPair, ThermoForcing, NodalForcing, Nesting, Diffusion, OceanCoupled, NodesCoupled, MeshForcing, CoupledBuffers, MeansPoints, MeansRegular, CplOut, CplOutGrid {
@@ -753,13 +745,13 @@ inline bool ocean_coupled_on(const nxs_dyn_handle *h) {
     return h->oc_attached && (h->oc_rows & need) == need;
 }
 // the loaded grid of the Moorings with its accumulators: nxs_dyn_means_points_set (a new grid, or none) and nxs_dyn_destroy -- not release_mesh
-void release_means_points(nxs_dyn_handle *h) { release_group<MeansPoints>(h, h->mp_allocs); }
+void release_means_points(nxs_dyn_handle *h) { release_group<MeansPoints>(h, h->mp.allocs); }
 // the regular grid of the Moorings with its accumulators: nxs_dyn_means_regular_set (a new grid, or none) and nxs_dyn_destroy -- not release_mesh
-void release_means_regular(nxs_dyn_handle *h) { release_group<MeansRegular>(h, h->mr_allocs); }
+void release_means_regular(nxs_dyn_handle *h) { release_group<MeansRegular>(h, h->mr.allocs); }
 // the coupler's means: the mesh accumulators and the borrowed map go with the mesh; the exchange grid with its accumulators at nxs_dyn_cpl_out_configure with two
 // empty lists and nxs_dyn_destroy -- not at release_mesh
 void release_cpl_out(nxs_dyn_handle *h) { release_group<CplOut>(h, h->cpl_allocs); }
-void release_cpl_out_grid(nxs_dyn_handle *h) { release_group<CplOutGrid>(h, h->cplg_allocs); }
+void release_cpl_out_grid(nxs_dyn_handle *h) { release_group<CplOutGrid>(h, h->cplg.allocs); }
 // the coupled build's buffers; their attachments are members of h->dw
 void release_coupled(nxs_dyn_handle *h) {
     release_group<CoupledBuffers>(h, h->coupled_allocs);
@@ -1847,6 +1839,7 @@ static void pool_free_one(std::vector<void *> &pool, void *p) {
     if (it != pool.end()) pool.erase(it);
     (void)hipFree(p);
 }
+#include "nxs_output_grid.inl"   // what the three output grids (MeansPoints, MeansRegular, CplOutGrid) share: here, because both *_configure entries drop accumulators
 static void means_drop_buffers(nxs_dyn_handle *h) {
     for (double *&q : h->d_means) { pool_free_one(h->state_allocs, q); q = nullptr; }
     pool_free_one(h->state_allocs, h->d_means_pm); h->d_means_pm = nullptr;
@@ -3514,10 +3507,8 @@ int nxs_dyn_means_configure(nxs_dyn_handle *h, const nxs_dyn_means_config *c) tr
     HIPCHK(h, hipSetDevice(h->device));
     if (h->stream) HIPCHK(h, hipStreamSynchronize(h->stream));
     means_drop_buffers(h);
-    for (int k = 0; k < 2; ++k)   // the grid accumulators of a loaded grid (nxs_dyn_means_points_*) are made again by their next call when a list changes its size
-        if (h->mp_grid_n[k] != (int)ids[k].size()) { pool_free_one(h->mp_allocs, h->mp_grid[k]); h->mp_grid[k] = nullptr; h->mp_grid_n[k] = 0; }
-    for (int k = 0; k < 2; ++k)   // ... and those of the regular grid (nxs_dyn_means_regular_*)
-        if (h->mr_grid_n[k] != (int)ids[k].size()) { pool_free_one(h->mr_allocs, h->mr_grid[k]); h->mr_grid[k] = nullptr; h->mr_grid_n[k] = 0; }
+    og_drop_resized(h->mp, ids);   // the grid accumulators of a loaded grid (nxs_dyn_means_points_*) are made again by their next call when a list changes its size
+    og_drop_resized(h->mr, ids);   // ... and those of the regular grid (nxs_dyn_means_regular_*)
     for (int k = 0; k < 2; ++k) { h->means_ids[k] = ids[k]; h->means_mask[k] = mask[k]; }
     h->means_ice_mask_col = ice_col;
     if (h->have_mesh) { int rc = means_make_buffers(h); if (rc) return rc; }

@@ -1707,22 +1707,26 @@ class FiniteElementDynamics:
         """resetMeshMean(bamgmesh): both accumulators to zero, on the stream."""
         self._chk(self.L.nxs_dyn_means_reset(self.h))
 
-    # ---- the Moorings means on a loaded grid: updateGridMean / setLSM / applyLSM / rotateVectors / resetGridMean (gridoutput.cpp:387-415, 470-485, 558-651) ----
-    def means_points_set(self, gridX=None, gridY=None, miss_val=-1e14, rotation="none", gridLON=None, gridTheta=None, rotation_angle=0., pairs=()):
-        """The loaded grid of the Moorings on the handle: projected coordinates gridX / gridY [G], the rotation mode ("none", "north_east" with gridLON in
-        degrees, "grid_theta" with gridTheta in radians) with rotation_angle in radians, and the vectorial variables as pairs of columns of the configured nodal
-        list.  Everything is copied; the grid, its mask and its accumulators survive set_mesh and regrid.  No coordinates (or empty ones) remove the object."""
+    # ---- what the three output grids of the handle (means_points_*, means_regular_*, cpl_out_attach_grid / _put) share ----
+    @staticmethod
+    def _grid_pairs(p, pairs):
+        """the vectorial variables of a grid descriptor: pairs of columns of the configured nodal list"""
+        pairs = list(pairs)
+        p.n_pairs = len(pairs)
+        for k, (first, second) in enumerate(pairs[:_abi.NXS_MEANS_MAX_PAIRS]):
+            p.pair_first[k], p.pair_second[k] = int(first), int(second)
+
+    def _grid_points(self, gridX, gridY, miss_val, rotation, gridLON, gridTheta, rotation_angle, pairs):
+        """(the _abi.MeansPoints of a set of points, the arrays it points into), or (None, []) without coordinates"""
         if gridX is None or np.size(gridX) == 0:
-            self._chk(self.L.nxs_dyn_means_points_set(self.h, None))
-            self._points_G = 0
-            return
+            return None, []
         x, y = np.ascontiguousarray(gridX, np.float64).ravel(), np.ascontiguousarray(gridY, np.float64).ravel()
         if x.shape != y.shape:
             raise ValueError("gridX and gridY differ in length")
         p = _abi.MeansPoints()
         p.G, p.rotation = x.size, _abi.MEANS_ROTATION[rotation] if isinstance(rotation, str) else int(rotation)
         p.gridX, p.gridY = _abi.dptr(x), _abi.dptr(y)
-        keep = []
+        keep = [x, y]
         for name, a in (("gridLON", gridLON), ("gridTheta", gridTheta)):
             if a is not None:
                 a = np.ascontiguousarray(a, np.float64).ravel()
@@ -1731,22 +1735,39 @@ class FiniteElementDynamics:
                 keep.append(a)
                 setattr(p, name, _abi.dptr(a))
         p.rotation_angle, p.miss_val = float(rotation_angle), float(miss_val)
-        pairs = list(pairs)
-        p.n_pairs = len(pairs)
-        for k, (first, second) in enumerate(pairs[:_abi.NXS_MEANS_MAX_PAIRS]):
-            p.pair_first[k], p.pair_second[k] = int(first), int(second)
-        self._chk(self.L.nxs_dyn_means_points_set(self.h, C.byref(p)))
-        self._points_G = int(x.size)
+        self._grid_pairs(p, pairs)
+        return p, keep
 
-    def means_points_lsm(self, lsm=None) -> np.ndarray:
-        """setLSM: computed on the handle's own mesh at rest (1 where a grid point lies in any triangle, ghosts included) or, given, uploaded.  Returns it."""
-        G = getattr(self, "_points_G", 0)
+    def _grid_lsm(self, entry, G, lsm) -> np.ndarray:
+        """setLSM of a grid of G points through `entry`: computed (lsm None) or taken over; returns it"""
         out = np.empty(G, np.int32)
         given = None if lsm is None else np.ascontiguousarray(lsm, np.int32).ravel()
         if given is not None and given.size != G:
             raise ValueError(f"lsm has {given.size} entries, the grid {G}")
-        self._chk(self.L.nxs_dyn_means_points_lsm(self.h, _abi.iptr(given) if given is not None else None, _abi.iptr(out)))
+        self._chk(entry(self.h, _abi.iptr(given) if given is not None else None, _abi.iptr(out)))
         return out
+
+    def _grid_rows(self, n, G, want_host, call):
+        """([n_el, G] or None, [n_nod, G] or None, the two device pointers) of a grid's accumulators: call(elemental, nodal, elemental_dev, nodal_dev) is the entry"""
+        n_el, n_nod = n
+        el = np.empty((n_el, G)) if want_host and n_el else None
+        nod = np.empty((n_nod, G)) if want_host and n_nod else None
+        de, dn = C.c_void_p(), C.c_void_p()
+        self._chk(call(_abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None, C.byref(de), C.byref(dn)))
+        return el, nod, de.value, dn.value
+
+    # ---- the Moorings means on a loaded grid: updateGridMean / setLSM / applyLSM / rotateVectors / resetGridMean (gridoutput.cpp:387-415, 470-485, 558-651) ----
+    def means_points_set(self, gridX=None, gridY=None, miss_val=-1e14, rotation="none", gridLON=None, gridTheta=None, rotation_angle=0., pairs=()):
+        """The loaded grid of the Moorings on the handle: projected coordinates gridX / gridY [G], the rotation mode ("none", "north_east" with gridLON in
+        degrees, "grid_theta" with gridTheta in radians) with rotation_angle in radians, and the vectorial variables as pairs of columns of the configured nodal
+        list.  Everything is copied; the grid, its mask and its accumulators survive set_mesh and regrid.  No coordinates (or empty ones) remove the object."""
+        p, keep = self._grid_points(gridX, gridY, miss_val, rotation, gridLON, gridTheta, rotation_angle, pairs)
+        self._chk(self.L.nxs_dyn_means_points_set(self.h, C.byref(p) if p is not None else None))
+        self._points_G = int(p.G) if p is not None else 0
+
+    def means_points_lsm(self, lsm=None) -> np.ndarray:
+        """setLSM: computed on the handle's own mesh at rest (1 where a grid point lies in any triangle, ghosts included) or, given, uploaded.  Returns it."""
+        return self._grid_lsm(self.L.nxs_dyn_means_points_lsm, getattr(self, "_points_G", 0), lsm)
 
     def means_points_update(self):
         """updateGridMean() on the loaded grid: one launch on the handle's stream that locates every grid point once in the mesh displaced by M_UM."""
@@ -1754,14 +1775,8 @@ class FiniteElementDynamics:
 
     def means_points_get(self, apply_lsm: bool = False, want_host: bool = True):
         """(elemental [n_el, G] or None, nodal [n_nod, G] or None, device pointer of the elemental rows, of the nodal rows); apply_lsm: applyLSM on the copy."""
-        n_el, n_nod = getattr(self, "_means_n", (0, 0))
-        G = getattr(self, "_points_G", 0)
-        el = np.empty((n_el, G)) if want_host and n_el else None
-        nod = np.empty((n_nod, G)) if want_host and n_nod else None
-        de, dn = C.c_void_p(), C.c_void_p()
-        self._chk(self.L.nxs_dyn_means_points_get(self.h, int(bool(apply_lsm)), _abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None,
-                                                  C.byref(de), C.byref(dn)))
-        return el, nod, de.value, dn.value
+        return self._grid_rows(getattr(self, "_means_n", (0, 0)), getattr(self, "_points_G", 0), want_host,
+                               lambda el, nod, de, dn: self.L.nxs_dyn_means_points_get(self.h, int(bool(apply_lsm)), el, nod, de, dn))
 
     def means_points_reset(self):
         """resetGridMean(): the grid accumulators to zero, on the stream."""
@@ -1786,22 +1801,13 @@ class FiniteElementDynamics:
                 raise ValueError(f"gridLON has {lon.size} entries, the grid {int(ncols) * int(nrows)}")
             p.gridLON = _abi.dptr(lon)
         p.rotation_angle = float(rotation_angle)
-        pairs = list(pairs)
-        p.n_pairs = len(pairs)
-        for k, (first, second) in enumerate(pairs[:_abi.NXS_MEANS_MAX_PAIRS]):
-            p.pair_first[k], p.pair_second[k] = int(first), int(second)
+        self._grid_pairs(p, pairs)
         self._chk(self.L.nxs_dyn_means_regular_set(self.h, C.byref(p)))
         self._regular_G = int(ncols) * int(nrows)
 
     def means_regular_lsm(self, lsm=None) -> np.ndarray:
         """setLSM: computed on the handle's own mesh at rest (1 where any triangle, ghosts included, holds the grid point) or, given, taken over.  Returns it."""
-        G = getattr(self, "_regular_G", 0)
-        out = np.empty(G, np.int32)
-        given = None if lsm is None else np.ascontiguousarray(lsm, np.int32).ravel()
-        if given is not None and given.size != G:
-            raise ValueError(f"lsm has {given.size} entries, the grid {G}")
-        self._chk(self.L.nxs_dyn_means_regular_lsm(self.h, _abi.iptr(given) if given is not None else None, _abi.iptr(out)))
-        return out
+        return self._grid_lsm(self.L.nxs_dyn_means_regular_lsm, getattr(self, "_regular_G", 0), lsm)
 
     def means_regular_update(self):
         """updateGridMean() on the regular grid: two launches on the handle's stream, nothing crosses to the host."""
@@ -1810,14 +1816,8 @@ class FiniteElementDynamics:
     def means_regular_get(self, apply_lsm: bool = False, want_host: bool = True):
         """(elemental [n_el, ncols * nrows] or None, nodal [n_nod, ncols * nrows] or None, device pointer of the elemental rows, of the nodal rows), grid order;
         apply_lsm: applyLSM on the copy."""
-        n_el, n_nod = getattr(self, "_means_n", (0, 0))
-        G = getattr(self, "_regular_G", 0)
-        el = np.empty((n_el, G)) if want_host and n_el else None
-        nod = np.empty((n_nod, G)) if want_host and n_nod else None
-        de, dn = C.c_void_p(), C.c_void_p()
-        self._chk(self.L.nxs_dyn_means_regular_get(self.h, int(bool(apply_lsm)), _abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None,
-                                                   C.byref(de), C.byref(dn)))
-        return el, nod, de.value, dn.value
+        return self._grid_rows(getattr(self, "_means_n", (0, 0)), getattr(self, "_regular_G", 0), want_host,
+                               lambda el, nod, de, dn: self.L.nxs_dyn_means_regular_get(self.h, int(bool(apply_lsm)), el, nod, de, dn))
 
     def means_regular_reset(self):
         """resetGridMean(): the grid accumulators to zero, on the stream."""
@@ -1854,41 +1854,15 @@ class FiniteElementDynamics:
         """The exchange grid of M_cpl_out: `gridmap` is the interp.GridMap of THIS mesh (borrowed: keep it alive; dropped by set_mesh / regrid, attach the new one
         again), the P-points with their rotation and pairs as means_points_set takes them (needed only with nodal variables).  The grid accumulators survive
         set_mesh / regrid and a new attach on a grid of the same size."""
-        p, keep = None, []
-        if gridX is not None and np.size(gridX):
-            x, y = np.ascontiguousarray(gridX, np.float64).ravel(), np.ascontiguousarray(gridY, np.float64).ravel()
-            if x.shape != y.shape:
-                raise ValueError("gridX and gridY differ in length")
-            p = _abi.MeansPoints()
-            p.G, p.rotation = x.size, _abi.MEANS_ROTATION[rotation] if isinstance(rotation, str) else int(rotation)
-            p.gridX, p.gridY = _abi.dptr(x), _abi.dptr(y)
-            keep += [x, y]
-            for name, a in (("gridLON", gridLON), ("gridTheta", gridTheta)):
-                if a is not None:
-                    a = np.ascontiguousarray(a, np.float64).ravel()
-                    if a.shape != x.shape:
-                        raise ValueError(f"{name} has {a.size} entries, the grid {x.size}")
-                    keep.append(a)
-                    setattr(p, name, _abi.dptr(a))
-            p.rotation_angle, p.miss_val = float(rotation_angle), float(miss_val)
-            pairs = list(pairs)
-            p.n_pairs = len(pairs)
-            for k, (first, second) in enumerate(pairs[:_abi.NXS_MEANS_MAX_PAIRS]):
-                p.pair_first[k], p.pair_second[k] = int(first), int(second)
+        p, keep = self._grid_points(gridX, gridY, miss_val, rotation, gridLON, gridTheta, rotation_angle, pairs)
         self._chk(self.L.nxs_dyn_cpl_out_attach_grid(self.h, gridmap.h if gridmap is not None else None, C.byref(p) if p is not None else None))
         self._cpl_map, self._cpl_G = gridmap, gridmap.info()["grid_size"]
 
     def cpl_out_put(self, want_host: bool = True, reset: bool = False):
         """M_cpl_out.updateGridMean() on the handle's stream: (grid_elemental [n_el, G] or None, grid_nodal [n_nod, G] or None, device pointer of the elemental
         grid rows, of the nodal ones).  want_host False: asynchronous, nothing is copied.  reset: resetMeshMean + resetGridMean behind the copies."""
-        n_el, n_nod = getattr(self, "_cpl_n", (0, 0))
-        G = getattr(self, "_cpl_G", 0)
-        el = np.empty((n_el, G)) if want_host and n_el else None
-        nod = np.empty((n_nod, G)) if want_host and n_nod else None
-        de, dn = C.c_void_p(), C.c_void_p()
-        self._chk(self.L.nxs_dyn_cpl_out_put(self.h, _abi.dptr(el) if el is not None else None, _abi.dptr(nod) if nod is not None else None, C.byref(de), C.byref(dn),
-                                             _abi.NXS_CPL_OUT_RESET if reset else 0))
-        return el, nod, de.value, dn.value
+        return self._grid_rows(getattr(self, "_cpl_n", (0, 0)), getattr(self, "_cpl_G", 0), want_host,
+                               lambda el, nod, de, dn: self.L.nxs_dyn_cpl_out_put(self.h, el, nod, de, dn, _abi.NXS_CPL_OUT_RESET if reset else 0))
 
     def cpl_out_reset_grid(self):
         """resetGridMean() of M_cpl_out: the grid accumulators to zero, on the stream."""

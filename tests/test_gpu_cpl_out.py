@@ -285,6 +285,71 @@ def test_moorings_and_coupler_do_not_see_each_other():
         fe.close()
 
 
+def test_the_three_output_grids_of_one_handle_do_not_see_each_other():
+    """A loaded grid of 7 points, a regular grid of 3 x 5 and the exchange grid of the smallest golden case on ONE handle, each accumulated once from seeded mesh
+    rows: other Moorings lists re-make both Moorings grids zeroed and leave the coupler's rows alone, other coupler lists leave both Moorings grids alone.  Bit for bit."""
+    fe, lm, p, f = _handle("toy")
+    c = G.case(min(G.CASES, key=lambda name: G.case(name)["gridX"].size))
+    lists = dict(CO.lists_of(c), nels=lm.num_elements)            # the case's lists read as lists on this mesh: every triangle they name exists here
+    lists["grid_size"] = Gc = lists["G"]
+    assert len({7, 3 * 5, Gc}) == 3 and c["gridP"].size and c["tris"].max() < lm.num_elements
+    gm = interp.GridMap.import_(lists)
+    xm, ym = 0.5 * (lm.coord_x.min() + lm.coord_x.max()), 0.5 * (lm.coord_y.min() + lm.coord_y.max())
+    dx, dy = 0.1 * np.ptp(lm.coord_x), 0.1 * np.ptp(lm.coord_y)   # all three grids lie well inside the mesh
+
+    def raw(ptr, shape):
+        a = np.empty(shape)
+        assert ptr and _hip().hipMemcpy(a.ctypes.data, ptr, a.nbytes, 2) == 0
+        return a
+
+    def seed(get, n_el, n_nod):
+        """both mesh accumulators of a set ([Ne, n_el], [Nn, n_nod]) filled with values in [1, 2): whatever a grid gathers from them inside the mesh is not zero"""
+        fe.synchronize()
+        _, _, de, dn = get(want_host=False)
+        rng = np.random.default_rng(n_el + 10 * n_nod)
+        for ptr, count in ((de, lm.num_elements * n_el), (dn, lm.num_nodes * n_nod)):
+            a = rng.uniform(1., 2., count)
+            assert not count or (ptr and _hip().hipMemcpy(ptr, a.ctypes.data, a.nbytes, 1) == 0)
+
+    def moorings(n_el, n_nod):
+        out = fe.means_points_get()[:2] + fe.means_regular_get()[:2]
+        for a, shape in zip(out, ((n_el, 7), (n_nod, 7), (n_el, 15), (n_nod, 15))):
+            assert (a is None and shape[0] == 0) or a.shape == shape, shape
+        return out
+    try:
+        fe.means_configure(("conc", "thick"), ("VT_x", "VT_y"))
+        fe.cpl_out_configure(("conc", "damage", "thick"), ("VT_x", "VT_y"))
+        fe.means_points_set(xm + dx * np.linspace(-3., 3., 7), ym + dy * np.sin(np.arange(7.)))       # (no pairs: they would not outlive the nodal list)
+        fe.means_regular_set(xm - dx, ym + 2. * dy, dy, ncols=3, nrows=5)
+        fe.cpl_out_attach_grid(gm, xm + dx * np.cos(np.arange(Gc) + 1.), ym + dy * np.sin(np.arange(Gc) + 1.), pairs=((0, 1),))
+        seed(fe.means_get, 2, 2); seed(fe.cpl_out_get, 3, 2)
+        fe.means_points_update(); fe.means_regular_update()
+        ce, cn, de, dn = fe.cpl_out_put()
+        assert ce.shape == (3, Gc) and cn.shape == (2, Gc) and ce.any() and cn.any()
+        assert all(a.any() for a in moorings(2, 2))
+        # (2 elemental, 2 nodal) -> (1, 0): both Moorings grids come back zeroed at the new sizes, the coupler's rows keep their bits
+        fe.means_configure(("conc",), ())
+        pe, pn, re_, rn = moorings(1, 0)
+        assert not pe.any() and not re_.any() and pn is None and rn is None
+        fe.synchronize()
+        assert _same(raw(de, ce.shape), ce) and _same(raw(dn, cn.shape), cn)
+        # ... and accumulated at the new sizes they keep theirs when the coupler's lists change
+        seed(fe.means_get, 1, 0)
+        fe.means_points_update(); fe.means_regular_update()
+        pe, _, re_, _ = moorings(1, 0)
+        assert pe.any() and re_.any()
+        fe.cpl_out_configure(("conc",), ("VT_x", "VT_y", "wind_x"))
+        pe1, _, re1, _ = moorings(1, 0)
+        assert _same(pe1, pe) and _same(re1, re_)
+        fe.cpl_out_attach_grid(gm, xm + dx * np.cos(np.arange(Gc) + 1.), ym + dy * np.sin(np.arange(Gc) + 1.), pairs=((0, 1),))
+        ce, cn, _, _ = fe.cpl_out_put()                            # (its mesh rows were re-made zeroed: the re-made grid rows hold what zeros add up to)
+        assert ce.shape == (1, Gc) and cn.shape == (3, Gc) and not ce.any()
+        pe1, _, re1, _ = moorings(1, 0)
+        assert _same(pe1, pe) and _same(re1, re_)
+    finally:
+        fe.close(); gm.close()
+
+
 # ---- dmax / dmean -------------------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("young", [True, False])
 @pytest.mark.parametrize("nb", [1, 2, 12, 16])
